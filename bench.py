@@ -20,9 +20,16 @@ then predict_mvn on a deep-copied model).  Every item carries its own kernel par
 per-draw HMC-refined parameters of forecast_n_hmc, src/forecasting.jl:63-68): nothing is
 deduplicated.  ``value`` = items / second, whole job, inputs resident in HBM before the timed region.
 
-Also reported (extra keys, never mixed into ``value`` / ``roofline``): the shared-K mode the default
-n_mcmc = n_hmc = 0 path allows, and the end-to-end make_and_fit_model + forecast_with_nowcasts
-wall-clock with a CPU estimate built from the fit's own call trace.
+A plain run sets up, warms up, times the K steps and prints one compact JSON line (``value``,
+``ms_per_step``, the roofline of those steps).  ``--full`` adds the legs beside it (extra keys, never
+mixed into ``value`` / ``roofline``): the shared-K mode the default n_mcmc = n_hmc = 0 path allows,
+the end-to-end make_and_fit_model + forecast_with_nowcasts wall-clock with a CPU estimate built from
+the fit's own call trace, the CPU baseline, C5's fp64 path, the other configurations of the default
+line and, at N > 1, the strong-scaled C4 step.
+
+``--dump-outputs DIR`` writes what the last timed step handed its caller as ``DIR/<name>.npy``
+(float64; at most 64 MB in all, a fixed seeded sample of rows above that).  The inputs depend on the
+arguments only, so two builds can be compared output for output.
 
 Contract: ``python bench.py --gpus N --steps K --warmup W``; for N > 1 launched by torchrun, one
 rank per GPU.  C3 / C5 are weak scaling (every rank owns the whole config); C4 shards its 256
@@ -44,6 +51,30 @@ sys.path.insert(0, ROOT)
 FP64_MFMA_PEAK_TFLOPS = 78.6    # MI355X datasheet, dense fp64 matrix (not in the local guide)
 FP32_MFMA_PEAK_TFLOPS = 157.3   # /opt/skills/guides/MI355X_MICROARCH.md, "Peak FP32 (matrix)"
 PMC_DIRS = [os.path.join(ROOT, "profiles", r) for r in ("r04", "r03", "r02")]   # newest first
+DUMP_BUDGET_BYTES = 64 << 20    # --dump-outputs: all files together
+DUMP_SAMPLE_SEED = 20240601
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every array of ``arrays`` (None skipped) as ``path/<name>.npy`` in float64.
+    Above DUMP_BUDGET_BYTES in all, every array with more than one row keeps the same fixed, seeded
+    sample of its rows and ``<name>_rows.npy`` lists them; the sample leaves room for those lists."""
+    os.makedirs(path, exist_ok=True)
+    arrs = {k: np.asarray(v, dtype=np.float64) for k, v in arrays.items() if v is not None}
+    total = sum(a.nbytes for a in arrs.values())
+    written = {}
+    for name, a in sorted(arrs.items()):
+        rows = None
+        if total > DUMP_BUDGET_BYTES and a.ndim >= 1 and a.shape[0] > 1:
+            keep = max(1, int(a.shape[0] * DUMP_BUDGET_BYTES / (2 * total)))
+            rng = np.random.Generator(np.random.PCG64(DUMP_SAMPLE_SEED))
+            rows = np.sort(rng.choice(a.shape[0], size=keep, replace=False))
+            a = a[rows]
+        np.save(os.path.join(path, f"{name}.npy"), a)
+        written[name] = list(a.shape)
+        if rows is not None:
+            np.save(os.path.join(path, f"{name}_rows.npy"), rows.astype(np.float64))
+    return written
 
 
 def F_logml(n):
@@ -462,14 +493,14 @@ def fit_forecast_wallclock(w, device, rank, args):
 
 def other_configs(args):
     """BASELINE configs C5 and C4 in the driver's record: compact legs run as child processes of
-    the default ``bench.py --gpus 1`` (a few seconds of GPU time each).
+    ``bench.py --gpus 1 --full`` (a few seconds of GPU time each).
     C5: n = 8192, 64 particles, mixed precision, 3 steps, the fp64 path beside it.
     C4: ONE rank's share of the 8-GPU configuration (32 of the 256 particles x 200 scenarios)
     through the product's forecast_with_nowcasts — the per-GPU step an 8-GPU run would take, without
     its collectives' wire time."""
     out = {}
-    legs = {"C5_mixed": ["--config", "C5", "--steps", "3", "--warmup", "1", "--no-cpu-baseline",
-                         "--no-fit"],
+    legs = {"C5_mixed": ["--config", "C5", "--steps", "3", "--warmup", "1", "--full",
+                         "--no-cpu-baseline", "--no-fit"],
             "C4_one_rank_share": ["--config", "C4", "--particles", "32", "--steps", "1", "--warmup",
                                   "1", "--headline-only"],
             # the HMC leapfrog over the headline items (what fit time is made of,
@@ -589,7 +620,7 @@ def main():
     ap.add_argument("--hmc-leapfrog", type=int, default=3,
                     help="leapfrogs per HMC move in the forecast_with_nowcasts_hmc leg")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="skip the compact C5 / C4-share legs of the default run")
+                    help="skip the compact C5 / C4-share legs of a --full run")
     ap.add_argument("--mode", default="predict", choices=["predict", "grad"],
                     help="grad: a step is one logml + gradient call over the items (HMC leapfrog)")
     ap.add_argument("--ensemble", default="prior", choices=["prior", "fitted"],
@@ -603,7 +634,18 @@ def main():
                     help="only the timed steps: no shared-K / resident-factor / fit / CPU legs, so a "
                          "rocprofv3 --stats of this command holds exactly the launches the roofline "
                          "object averages over")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the legs beside the headline (shared-K mode, "
+                         "end-to-end fit + forecast, CPU baseline, C5's fp64 path, other configurations, "
+                         "the strong-scaled C4 step at N > 1); a plain run times the steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (float64, at most "
+                         "64 MB in all: a fixed seeded sample of rows above that)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if not args.full:
+        args.headline_only = True
     precision = args.precision or ("mixed" if args.config == "C5" else "f64")
 
     rank = int(os.environ.get("RANK", "0"))
@@ -702,13 +744,20 @@ def main():
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed = float(tmax.item())
     bad = int((out["info"] != 0).sum())
+    if args.dump_outputs and rank == 0:
+        # the last step's results as its caller receives them (+ the normalised weights and ESS the
+        # predict step's weight update returns)
+        arrays = dict(out)
+        if extra is not None:
+            arrays["weights"], arrays["ess"] = extra
+        dump_outputs(args.dump_outputs, arrays)
 
     # N > 1 on the default line: the C3 figure above is weak scaling of replicas (x N by
     # construction).  The number north_star's ">= 6x at 8 GPUs" is about is the STRONG-scaled
     # C4 step (256 particles x 200 scenarios sharded over the ranks, one all-gather per weight
-    # update): run it here too, after the timed region, so a default scaling run records it.
+    # update): with --full run it here too, after the timed region, so a scaling run records it.
     c4_strong = None
-    if world > 1 and args.config == "C3" and not grad_mode and not args.no_c4_strong:
+    if world > 1 and args.config == "C3" and not grad_mode and args.full and not args.no_c4_strong:
         if job is not None:
             job.close()
             job = None

@@ -1,9 +1,13 @@
 #!/bin/bash
-# microbench detail + bench + rocprof kernel stats.  Usage: gpurun -- bash scripts/gpu_bench.sh [tag]
+# microbench detail + the full bench record + rocprof kernel stats of the headline-only command.
+# Usage (on an MI355X): bash scripts/gpu_bench.sh [tag] [output directory, default bench_out/]
 set -o pipefail
 TAG=${1:-r01}
-mkdir -p gpurun_out
-python - <<'PY' 2>&1 | tee gpurun_out/microbench_${TAG}.log
+R=$(cd "$(dirname "$0")/.." && pwd)
+OUT=${2:-$R/bench_out}
+mkdir -p "$OUT" && OUT=$(cd "$OUT" && pwd)
+cd "$R"
+python - <<'PY' 2>&1 | tee "$OUT/microbench_${TAG}.log"
 import __graft_entry__ as ge
 ge.build()
 from nowcastautogp_amd import _lib
@@ -13,9 +17,9 @@ for bpc in (1, 2, 4):
 w, cp = c.microbench_hbm(1 << 31)
 print(f"hbm write {w:.0f} GB/s  copy {cp:.0f} GB/s")
 PY
-python bench.py --steps 2 --warmup 1 2>gpurun_out/bench_${TAG}.err | tee gpurun_out/bench_${TAG}.json
+python bench.py --full --steps 2 --warmup 1 2>"$OUT/bench_${TAG}.err" | tee "$OUT/bench_${TAG}.json"
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $GRAFT_REPO_ROOT/gpurun_out/prof_${TAG} -- python3 $GRAFT_REPO_ROOT/bench.py --steps 1 --warmup 0 --headline-only > $GRAFT_REPO_ROOT/gpurun_out/prof_${TAG}.log 2>&1
-cd $GRAFT_REPO_ROOT
-find gpurun_out/prof_${TAG} -name "*kernel_stats.csv" | head -1 | xargs -I{} cp {} gpurun_out/kernel_stats_${TAG}.csv
-head -20 gpurun_out/kernel_stats_${TAG}.csv
+rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof_${TAG}" -- python3 "$R/bench.py" --steps 1 --warmup 0 --headline-only > "$OUT/prof_${TAG}.log" 2>&1
+cd "$R"
+find "$OUT/prof_${TAG}" -name "*kernel_stats.csv" | head -1 | xargs -I{} cp {} "$OUT/kernel_stats_${TAG}.csv"
+head -20 "$OUT/kernel_stats_${TAG}.csv"
