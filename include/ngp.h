@@ -140,7 +140,10 @@ ngp_status  ngp_kernel_check(const ngp_kernel *k);
  * therefore COMBINED: the calling thread that finds nobody serving takes every pending request,
  * and requests of the same entry point on bytewise identical dates (same n, same forecast dates
  * and flags) run as ONE launch sequence of sum(B) items with per-item observation rows; every
- * caller gets its own results and status.  A call that arrives alone runs exactly as before;
+ * caller gets its own results and status.  Gradient requests combine only with requests of the
+ * same spec and switches (ngp_set_spec, ngp_set_structured_storage, ngp_set_batch_invariant,
+ * ngp_set_short_series_path), and the group runs under them: a ngp_grad_job_run brings the ones
+ * its job was staged under, a ngp_logml_grad_batch the context's current ones.  A call that arrives alone runs exactly as before;
  * only a caller whose predecessors came in company gives that company at most 200 microseconds to
  * arrive before it serves (tasks woken together by one sequence come back within microseconds of
  * each other), and a wait that was in vain is not repeated.  src/forecasting.jl needs no edit to

@@ -1924,6 +1924,31 @@ struct GradLeaf {
     int last_chunk = 0;                    // items per memory-driven chunk of the last run (ngp_grad_job_info)
 };
 
+// What a gradient evaluation is staged under: the context's spec and the switches that pick its
+// routes.  A job keeps the one it was staged with; a combined group of gradient requests is staged
+// under its members' common one, which need not be the context's current one (ngp_grad_job_run).
+struct GradRoute {
+    ngp_spec spec{};
+    bool toeplitz = true, invariant = false, short_series = true;
+};
+
+static GradRoute grad_route_of(ngp_ctx *c) {   // c->mu held by the caller
+    GradRoute r;
+    r.spec = c->spec;
+    r.toeplitz = c->toeplitz;
+    r.invariant = c->invariant;
+    r.short_series = c->short_series;
+    return r;
+}
+
+static bool grad_route_same(const GradRoute &a, const GradRoute &b) {
+    const ngp_spec &x = a.spec, &y = b.spec;
+    return x.se_form == y.se_form && x.periodic_form == y.periodic_form && x.cp_form == y.cp_form &&
+           x.precision == y.precision && x.jitter == y.jitter && x.mixed_tau == y.mixed_tau &&
+           x.refine_tol == y.refine_tol && x.refine_max == y.refine_max && a.toeplitz == b.toeplitz &&
+           a.invariant == b.invariant && a.short_series == b.short_series;
+}
+
 namespace {
 
 // toep_path: the items are stationary trees on a regular series — aux rows [y' ; e_1'] instead of
@@ -1932,7 +1957,7 @@ namespace {
 // caller's batch, or the rows of several callers' arrays in a combined call
 ngp_status grad_leaf_stage(ngp_ctx *c, int32_t B, const ngp_kernel *kernels, int32_t n,
                            const double *t, const double *y, int64_t ldy, bool toep_path,
-                           GradLeaf **out, const double *const *yrows = nullptr) {
+                           GradLeaf **out, const double *const *yrows, const GradRoute &route) {
     if (!c || !out || !kernels || !t || (!y && !yrows) || B <= 0 || n <= 0) return NGP_ERR_ARG;
     *out = nullptr;
     GradLeaf *j = new (std::nothrow) GradLeaf();
@@ -2030,9 +2055,9 @@ ngp_status grad_leaf_stage(ngp_ctx *c, int32_t B, const ngp_kernel *kernels, int
     }
     std::lock_guard<std::mutex> lk(c->mu);
     HIPCHK(hipSetDevice(c->device));
-    j->spec = c->spec;
-    g.invariant = c->invariant ? 1 : 0;
-    g.short_series = c->short_series ? 1 : 0;
+    j->spec = route.spec;
+    g.invariant = route.invariant ? 1 : 0;
+    g.short_series = route.short_series ? 1 : 0;
     // (gradient jobs store every tile: their tables are per leaf, and on a regular series the
     // stationary trees — the ones structured storage could serve — are on the Toeplitz path)
     void *q = nullptr;
@@ -2400,6 +2425,7 @@ struct ngp_grad_job {
     std::vector<ngp_kernel> h_k;
     int32_t n = 0;
     int64_t h_ldy = 0;
+    GradRoute route;                            // what the job was staged under
 };
 // host copies up to this size (64 particles x 2,049 points = 1 MB; a lockstep job of 12,800 items
 // is 210 MB and has no use for company)
@@ -2408,7 +2434,7 @@ static constexpr size_t GRAD_JOB_HOST_COPY_BYTES = (size_t)16 << 20;
 static ngp_status grad_stage_impl(ngp_ctx *c, int32_t B, const ngp_kernel *kernels, int32_t n,
                                   const double *t, const double *y, int64_t ldy,
                                   const double *const *yrows, ngp_grad_job **out,
-                                  bool keep_host = false) {
+                                  bool keep_host = false, const GradRoute *route_in = nullptr) {
     if (!c || !out || !kernels || !t || (!y && !yrows) || B <= 0 || n <= 0) return NGP_ERR_ARG;
     *out = nullptr;
     for (int i = 0; i < B; ++i) {
@@ -2429,15 +2455,15 @@ static ngp_status grad_stage_impl(ngp_ctx *c, int32_t B, const ngp_kernel *kerne
     // blocks, short enough for the weights kernel's LDS image, and a tree without Linear or
     // ChangePoint nodes
     bool regular = false;
-    bool on, invariant, short_series;
-    double jitter;
-    {
+    GradRoute route;
+    if (route_in) {
+        route = *route_in;
+    } else {
         std::lock_guard<std::mutex> lk(c->mu);
-        on = c->toeplitz;
-        invariant = c->invariant;
-        short_series = c->short_series;
-        jitter = c->spec.jitter;
+        route = grad_route_of(c);
     }
+    const bool on = route.toeplitz, invariant = route.invariant, short_series = route.short_series;
+    const double jitter = route.spec.jitter;
     // (series of up to 256 points: the general leaf factorises them in one launch,
     // ngp_small_kernels.h — shorter than the Toeplitz leaf's chain of sweeps)
     // (batches beyond what the one-launch path takes, SM_MAX_ITEMS, keep the Toeplitz leaf: there it is
@@ -2509,16 +2535,17 @@ static ngp_status grad_stage_impl(ngp_ctx *c, int32_t B, const ngp_kernel *kerne
     auto stage_leaf = [&](const std::vector<int32_t> &idx, bool toep_path, GradLeaf **leaf) -> ngp_status {
         if (idx.empty()) return NGP_OK;
         if ((int)idx.size() == B)   // the whole batch: the caller's arrays as they are
-            return grad_leaf_stage(c, B, kernels, n, t, y, ldy, toep_path, leaf, yrows);
+            return grad_leaf_stage(c, B, kernels, n, t, y, ldy, toep_path, leaf, yrows, route);
         std::vector<ngp_kernel> ks(idx.size());
         for (size_t a = 0; a < idx.size(); ++a) ks[a] = kernels[idx[a]];
         if (!yrows && ldy == 0)
-            return grad_leaf_stage(c, (int32_t)idx.size(), ks.data(), n, t, y, 0, toep_path, leaf);
+            return grad_leaf_stage(c, (int32_t)idx.size(), ks.data(), n, t, y, 0, toep_path, leaf,
+                                   nullptr, route);
         std::vector<const double *> rows(idx.size());   // the leaf's rows where they lie
         for (size_t a = 0; a < idx.size(); ++a)
             rows[a] = yrows ? yrows[idx[a]] : y + (int64_t)idx[a] * ldy;
         return grad_leaf_stage(c, (int32_t)idx.size(), ks.data(), n, t, nullptr, 0, toep_path, leaf,
-                               rows.data());
+                               rows.data(), route);
     };
     ngp_status st = stage_leaf(j->idx_gen, false, &j->gen);
     if (!st) st = stage_leaf(j->idx_toep, true, &j->toep);
@@ -2528,6 +2555,7 @@ static ngp_status grad_stage_impl(ngp_ctx *c, int32_t B, const ngp_kernel *kerne
         return st;
     }
     j->n = n;
+    j->route = route;
     const bool shared = !yrows && ldy == 0;
     if (keep_host && (size_t)(shared ? 1 : B) * (size_t)n * 8 <= GRAD_JOB_HOST_COPY_BYTES) {
         j->h_t.assign(t, t + n);
@@ -2666,13 +2694,14 @@ extern "C" void ngp_grad_job_destroy(ngp_grad_job *j) {
     delete j;
 }
 
+// route: stage under this spec and these switches instead of the context's current ones
 static ngp_status logml_grad_direct(ngp_ctx *c, int32_t B, const ngp_kernel *kernels, int32_t n,
                                     const double *t, const double *y, int64_t ldy,
                                     const double *const *yrows, double *logml, double *grad,
-                                    int32_t *info) {
+                                    int32_t *info, const GradRoute *route = nullptr) {
     if (!grad) return NGP_ERR_ARG;
     ngp_grad_job *j = nullptr;
-    ngp_status st = grad_stage_impl(c, B, kernels, n, t, y, ldy, yrows, &j);
+    ngp_status st = grad_stage_impl(c, B, kernels, n, t, y, ldy, yrows, &j, false, route);
     if (st) return st;
     st = grad_job_run_resident(j, logml, grad, info);
     ngp_grad_job_destroy(j);
@@ -2812,6 +2841,8 @@ struct ngp_comb_req {
     double *logml = nullptr, *grad = nullptr, *mu = nullptr, *sigma = nullptr;
     int32_t *info = nullptr;
     ngp_grad_job *gj = nullptr;   // CK_GRAD from ngp_grad_job_run: alone it runs on its resident inputs
+    GradRoute route;              // CK_GRAD: the job's staged spec and switches, or (one-shot calls) the
+                                  // context's when the batch is served (comb_execute)
     // CK_MIXTURE (one mixture of P components: ngp_mixture_sample with S = 1)
     int32_t P = 0, draws = 0;
     const double *w = nullptr, *cmu = nullptr, *csigma = nullptr;
@@ -2856,6 +2887,7 @@ bool comb_same(const ngp_comb_req &a, const ngp_comb_req &b) {
         a.noise_on_new != b.noise_on_new || a.P != b.P || a.draws != b.draws)
         return false;
     if (a.kind == CK_MIXTURE) return true;
+    if (a.kind == CK_GRAD && !grad_route_same(a.route, b.route)) return false;
     if (std::memcmp(a.t, b.t, 8 * (size_t)a.n) != 0) return false;
     return a.m == 0 || std::memcmp(a.t_new, b.t_new, 8 * (size_t)a.m) == 0;
 }
@@ -2985,8 +3017,11 @@ ngp_status comb_run_group(ngp_ctx *c, const std::vector<ngp_comb_req *> &grp, bo
         size_t ng = 0;
         for (const ngp_kernel &k : ks) ng += (size_t)k.n_params + 1;
         std::vector<double> grad(ng);
+        // under the members' own spec and switches (comb_same), not the context's current ones: a
+        // job keeps what it was staged under whatever ngp_set_spec did since
         const ngp_status st = logml_grad_direct(c, (int32_t)Bt, ks.data(), r0.n, r0.t, nullptr, 0,
-                                                rows.data(), lm.data(), grad.data(), info.data());
+                                                rows.data(), lm.data(), grad.data(), info.data(),
+                                                &r0.route);
         if (st) return st;
         size_t b0 = 0, g0 = 0;
         for (ngp_comb_req *r : grp) {
@@ -3026,6 +3061,14 @@ ngp_status comb_run_group(ngp_ctx *c, const std::vector<ngp_comb_req *> &grp, bo
 
 // everything one server took from `pending`: groups in order of their first member's arrival
 void comb_execute(ngp_ctx *c, const std::vector<ngp_comb_req *> &batch, int64_t stats[6]) {
+    {
+        // one-shot gradient calls run under the context's spec and switches as they are now (as
+        // they would alone); a staged job brought its own (ngp_grad_job_run)
+        std::lock_guard<std::mutex> lk(c->mu);
+        const GradRoute now = grad_route_of(c);
+        for (ngp_comb_req *r : batch)
+            if (r->kind == CK_GRAD && !r->gj) r->route = now;
+    }
     std::vector<char> taken(batch.size(), 0);
     for (size_t i = 0; i < batch.size(); ++i) {
         if (taken[i]) continue;
@@ -3187,6 +3230,7 @@ extern "C" ngp_status ngp_grad_job_run(ngp_grad_job *j, double *logml, double *g
     ngp_comb_req r;
     r.kind = CK_GRAD;
     r.gj = j;
+    r.route = j->route;
     r.B = j->B; r.k = j->h_k.data(); r.n = j->n; r.t = j->h_t.data();
     r.y = j->h_y.data(); r.ldy = j->h_ldy;
     r.logml = logml; r.grad = grad; r.info = info;

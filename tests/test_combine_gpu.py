@@ -356,3 +356,52 @@ def test_default_mode_scenario_tasks_through_the_mirror(ctx):
     assert st["shared_k"] > 0
     # different random streams (per-task clones against one shared stream): same distribution
     assert np.allclose(np.median(a, axis=1), np.median(b, axis=1), rtol=0.05)
+
+
+@pytest.mark.parametrize("staged,later", [("A", "B"), ("B", "A")])
+def test_combined_job_runs_keep_the_spec_they_were_staged_under(ctx, staged, later):
+    """A resident gradient job keeps the spec it was staged under (include/ngp.h ngp_grad_stage).
+    Jobs staged under one spec and run concurrently after ngp_set_spec changed it must still get
+    their staged results when their runs are combined: jitter 1e-5 against 1e-3 and the other
+    periodic form are a different formula, not a rounding difference."""
+    specs = {"A": (0, 1e-5), "B": (1, 1e-3)}
+    default = ctx.get_spec()
+
+    def spec(name):
+        s = ctx.get_spec()
+        s.periodic_form, s.jitter = specs[name]
+        return s
+
+    t, _, tasks = _tasks(256, 8, seed=11)
+    kas = [KernelArray(p) for p, _ in tasks]
+    try:
+        ctx.set_combining(False)
+        ctx.set_spec(spec(staged))
+        jobs = [ctx.stage_grad(kas[i], t, tasks[i][1]) for i in range(T)]
+        solo = [jobs[i].run() for i in range(T)]
+        ctx.set_spec(spec(later))
+        other = [ctx.logml_grad_flat(kas[i], t, tasks[i][1]) for i in range(T)]
+        ctx.set_combining(True)
+        ctx.combine_stats(reset=True)
+        for _ in range(4):              # until a group forms (Python threads may arrive one by one)
+            comb, _ = _burst(lambda i: jobs[i].run(), [(i,) for i in range(T)])
+            st = ctx.combine_stats(reset=True)
+            if st["largest_group"] > 1:
+                break
+        print(f"staged under {staged}, run under {later}:", st)
+        assert st["largest_group"] > 1, st
+        for i in range(T):
+            assert not comb[i][2].any() and not solo[i][2].any()
+            # the spec matters: the other spec's results are far from the staged ones
+            assert nerr(other[i][0], solo[i][0]) > 1e-8, i
+            check("combined job run vs its staged spec: logml", comb[i][0], solo[i][0], TOL_LOGML, ctx=i)
+            off = np.concatenate([[0], np.cumsum(kas[i]._npar + 1)])
+            for b in range(kas[i].n):
+                sl = slice(off[b], off[b + 1])
+                check("combined job run vs its staged spec: gradient", comb[i][1][sl], solo[i][1][sl],
+                      1e-9, ctx=(i, b))
+        for j in jobs:
+            j.close()
+    finally:
+        ctx.set_spec(default)
+        ctx.set_combining(True)

@@ -64,3 +64,26 @@ def summary():
         g["worst_err_over_floor"] = max(g["worst_err_over_floor"], r["err"] / r["floor"])
         g["worst_err_over_tol"] = max(g["worst_err_over_tol"], r["err"] / r["tol"])
     return by
+
+
+def check_components(what, got, ref, scale, floor, cond=1.0, ctx=None, factor=1.0, record=True):
+    """Componentwise judgement: every |got_i - ref_i| <= max(floor, 50 eps cond) * factor * scale_i.
+
+    ``scale`` is each component's own yardstick — a gradient component's s_i from
+    tests/hp_reference.py (the size of the terms it is summed from), sqrt(s_aa) for a predictive
+    mean, sqrt(s_aa s_bb) for a covariance entry (hp_reference.pred_scales) — so a small component
+    next to large ones is judged against its own size, which ``check`` (normwise) does not do.
+    ``factor``: 2 when the reference is fp64 rather than extended precision.  Recorded in RECORDS
+    as the worst max_i |got_i - ref_i| / scale_i against the tolerance, like ``check`` (record=False:
+    not recorded — a check that is meant to fail, in the test of this helper itself)."""
+    got, ref, scale = (np.asarray(a, float) for a in (got, ref, scale))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        r = np.abs(got - ref) / scale
+    r = np.where(got == ref, 0.0, r)            # exact agreement also where the scale is zero
+    e, t = float(np.max(r)), tol(floor, cond) * factor
+    if not np.isfinite(e):
+        e = float("inf")
+    if record:
+        RECORDS.append(dict(what=what, err=e, floor=floor * factor, tol=t, cond=float(cond),
+                            relaxed=t > floor * factor))
+    assert e < t, (what, ctx, e, t, cond, int(np.argmax(r)))
