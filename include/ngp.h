@@ -26,7 +26,9 @@
  *     matrix.
  *   - numerical failure is reported PER ITEM in info[] with LAPACK potrf
  *     semantics (k > 0: leading minor k is not positive definite), which the
- *     shim rethrows as PosDefException(k) (src/make_and_fit_model.jl:6-8).
+ *     shim rethrows as PosDefException(k) (src/make_and_fit_model.jl:6-8).  Every output
+ *     of an item with info > 0 that depends on the failed minor is non-finite (logml of the
+ *     n + d points, mu, sigma; logml_base too unless k > n); other items are not affected.
  *   - re-entrant: may be entered concurrently from many host threads
  *     (Threads.@spawn per scenario, src/forecasting.jl:131-132); device work of one
  *     ctx is serialised by a blocking mutex, never a spin, and concurrent one-shot

@@ -1443,7 +1443,9 @@ __global__ __launch_bounds__(64) void epilogue_kernel(JobGeom g, EpiPtrs p, DevS
         }
     }
     }
-    if (tid == 0 && bad && p.info[item] == 0) p.info[item] = g.n0 + bad;
+    // (info < 0 is NGP_INFO_NOT_REFINED of a mixed-precision job, set before the epilogue ran: a pivot
+    // failure in the tail or the appended points is the stronger statement and replaces it)
+    if (tid == 0 && bad && p.info[item] <= 0) p.info[item] = g.n0 + bad;
 }
 
 // ---------------------------------------------------------------------------------------

@@ -159,19 +159,22 @@ def cov(program, t1, t2, spec=None, add_diag=False, dtype=LD):
 
 
 # ---- factorisation and solves ------------------------------------------------------------------
-def cholesky_ld(A):
+def cholesky_ld(A, pivots=False):
     """lower L with L L' = A, column by column (left-looking); (L, info), info = k > 0 when the
-    k-th leading minor is not positive"""
+    k-th leading minor is not positive.  pivots=True: (L, info, piv) with piv[j] the Schur pivot
+    a_jj - sum_k l_jk^2 of every column reached, the non-positive one (piv[info - 1]) included"""
     n = A.shape[0]
     L = np.zeros_like(A)
+    piv = np.zeros(n, dtype=A.dtype)
     for j in range(n):
         col = A[j:, j] - L[j:, :j] @ L[j, :j]
+        piv[j] = col[0]
         if not (col[0] > 0) or not np.isfinite(col[0]):
-            return None, j + 1
+            return (None, j + 1, piv[:j + 1]) if pivots else (None, j + 1)
         d = np.sqrt(col[0])
         L[j, j] = d
         L[j + 1:, j] = col[1:] / d
-    return L, 0
+    return (L, 0, piv) if pivots else (L, 0)
 
 
 def solve_lower(L, B):
@@ -278,6 +281,84 @@ def _evaluate(program, t, y, spec, want_grad, t_new, noise_on_new):
             m = t_new.size
             sig[np.arange(m), np.arange(m)] += dt(program[2]) + dt(sp[3])
         r.mu, r.sigma = K21 @ alpha, sig
+    return r
+
+
+class NowcastRef:
+    """the nowcast fan-out of one item: logml_base, logml_full [D], mu [D, m], sigma [m, m]"""
+    __slots__ = ("logml_base", "logml_full", "mu", "sigma", "cond", "info", "tol_factor", "n", "d")
+
+
+def _factor_full(program, tt, spec):
+    """(L, info, cond, dtype) of the matrix on the dates tt, cached: the forecast-date sets of one
+    item share it"""
+    key = _key("factor", program[0], program[1], float(program[2]), tt, spec_tuple(spec))
+    if key in _CACHE:
+        return _CACHE[key]
+    hp = tt.size <= HP_MAX_N
+    dt = LD if hp else np.float64
+    K = cov(program, tt, tt, spec, add_diag=True, dtype=dt)
+    ev = np.linalg.eigvalsh(K.astype(np.float64))
+    cond = float(ev[-1] / ev[0]) if ev[0] > 0 else float("inf")
+    if hp:
+        L, info = cholesky_ld(K)
+    else:
+        try:
+            L, info = cholesky(K, lower=True, check_finite=False), 0
+        except np.linalg.LinAlgError as e:
+            msg = str(e)
+            L, info = None, (int(msg.split("-th")[0].split()[-1]) if "-th" in msg else 1)
+    _CACHE[key] = (L, info, cond, dt)
+    return _CACHE[key]
+
+
+def nowcast(program, t, y, t_add, y_add, t_new, spec=None, noise_on_new=True):
+    """The reference of ``ngp_nowcast_batch`` for one item (cached on its inputs).  The matrix on
+    the n + d dates (t, t_add) is factorised ONCE; its leading n-block is the factor of the base
+    matrix, so logml_base comes from the first n rows of the same factor and of the same forward
+    solve.  cond is that of the (n + d) matrix; above HP_MAX_N points fp64 LAPACK, tol_factor 2."""
+    ops = np.asarray(program[0], np.int32)
+    params = np.asarray(program[1], np.float64)
+    program = (ops, params, float(program[2]))
+    t, y = np.asarray(t, np.float64), np.asarray(y, np.float64)
+    t_add = np.asarray(t_add, np.float64).reshape(-1)
+    n, d = t.size, t_add.size
+    y_add = np.asarray(y_add, np.float64).reshape(-1, d) if d else np.zeros((1, 0))
+    t_new = np.asarray(t_new, np.float64).reshape(-1)
+    key = _key("nowcast", ops, params, program[2], t, y, t_add, y_add, t_new, spec_tuple(spec),
+               bool(noise_on_new))
+    if key in _CACHE:
+        return _CACHE[key]
+    sp = spec_tuple(spec)
+    tt = np.concatenate([t, t_add])
+    L, info, cond, dt = _factor_full(program, tt, spec)
+    hp = dt is LD
+    r = NowcastRef()
+    r.n, r.d, r.cond, r.info, r.tol_factor = n, d, cond, info, 1.0 if hp else 2.0
+    D, m = y_add.shape[0], t_new.size
+    if info:
+        r.logml_base = float("nan")
+        r.logml_full = np.full(D, np.nan)
+        r.mu, r.sigma = np.full((D, m), np.nan), np.full((m, m), np.nan)
+        _CACHE[key] = r
+        return r
+    solve = solve_lower if hp else (lambda A, B: solve_triangular(A, B, lower=True, check_finite=False))
+    log2pi = np.log(dt(2 * PI_LD if hp else 2 * np.pi))
+    ldiag = np.log(np.diag(L))
+    # one right-hand side per scenario: they share their first n rows
+    Y = np.concatenate([np.repeat(y.astype(dt)[:, None], D, axis=1), y_add.astype(dt).T], axis=0)
+    Z = solve(L, Y)                                               # [n + d, D]
+    r.logml_base = -(Z[:n, 0] @ Z[:n, 0]) / 2 - np.sum(ldiag[:n]) - dt(n) / 2 * log2pi
+    r.logml_full = -np.sum(Z * Z, axis=0) / 2 - np.sum(ldiag) - dt(n + d) / 2 * log2pi
+    K21 = cov(program, t_new, tt, spec, dtype=dt)
+    K22 = cov(program, t_new, t_new, spec, dtype=dt)
+    V = solve(L, K21.T)                                           # [n + d, m]
+    sig = K22 - V.T @ V
+    sig = (sig + sig.T) / 2
+    if noise_on_new:
+        sig[np.arange(m), np.arange(m)] += dt(program[2]) + dt(sp[3])
+    r.mu, r.sigma = (V.T @ Z).T, sig                              # mu_s = K21 K^-1 y_s = V' z_s
+    _CACHE[key] = r
     return r
 
 

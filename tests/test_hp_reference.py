@@ -229,6 +229,94 @@ def test_componentwise_check_rejects_what_the_normwise_check_accepts():
                          record=False)
 
 
+# ---- the nowcast fan-out ----------------------------------------------------------------------------
+def _nowcast_case(n, seed):
+    t, y = _series(n + 2, seed)
+    rng = np.random.default_rng(seed + 100)
+    y_add = y[n:][None, :] + 0.2 * rng.standard_normal((2, 2))
+    # a date between two training dates, one on an observed date, one beyond the last
+    t_new = np.array([(t[3] + t[4]) / 2, t[6], t[-1] + 1.5])
+    return t[:n], y[:n], t[n:], y_add, t_new
+
+
+@pytest.mark.parametrize("spec", list(SPECS))
+@pytest.mark.parametrize("name", list(PROGRAMS))
+def test_nowcast_reference_matches_mpmath(name, spec):
+    """10 points, d = 2 appended, D = 2 scenarios, against 40 digits"""
+    mp.mp.dps = 40
+    sp = SPECS[spec]
+    ops, params, noise = _prog(name)
+    t, y, t_add, y_add, t_new = _nowcast_case(10, seed=len(name))
+    r = hr.nowcast((ops, params, noise), t, y, t_add, y_add, t_new, sp, noise_on_new=True)
+    assert r.info == 0 and r.tol_factor == 1.0
+    tol = 50 * hr.EPS_LD * r.cond
+    lb, _ = _mp_logml(ops, params, noise, t, y, sp)
+    assert abs(r.logml_base - _ld(lb)) <= tol * max(abs(r.logml_base), 1)
+    tt = np.concatenate([t, t_add])
+    K = _mp_K(ops, params, noise, tt, tt, sp, True)
+    K21 = _mp_K(ops, params, noise, t_new, tt, sp, False)
+    K22 = _mp_K(ops, params, noise, t_new, t_new, sp, False)
+    m = len(t_new)
+    S = K22 - K21 * mp.inverse(K) * K21.T
+    for j in range(m):
+        S[j, j] += mp.mpf(noise) + mp.mpf(sp["jitter"])
+    S_mp = np.array([[_ld(S[a, b]) for b in range(m)] for a in range(m)])
+    d = np.sqrt(np.diag(S_mp))
+    assert np.all(np.abs(r.sigma - S_mp) <= tol * np.outer(d, d))
+    for s in range(2):
+        yy = np.concatenate([y, y_add[s]])
+        lf, _ = _mp_logml(ops, params, noise, tt, yy, sp)
+        assert abs(r.logml_full[s] - _ld(lf)) <= tol * max(abs(r.logml_full[s]), 1)
+        mu = K21 * mp.cholesky_solve(K, mp.matrix([mp.mpf(v) for v in yy]))
+        mu_mp = np.array([_ld(mu[a]) for a in range(m)])
+        assert np.all(np.abs(r.mu[s] - mu_mp) <= tol * d), (s, r.mu[s], mu_mp)
+
+
+@pytest.mark.parametrize("non", [True, False])
+@pytest.mark.parametrize("name", list(PROGRAMS))
+def test_nowcast_reference_matches_the_fp64_oracle_and_evaluate(name, non):
+    ops, params, noise = _prog(name)
+    prog = (ops, params, noise)
+    t, y, t_add, y_add, t_new = _nowcast_case(200, seed=3)
+    r = hr.nowcast(prog, t, y, t_add, y_add, t_new, None, noise_on_new=non)
+    assert r.info == 0
+    assert hr.nowcast(prog, t, y, t_add, y_add, t_new, None, noise_on_new=non) is r      # cached
+    # oracle_np.nowcast: one refactorisation per scenario, in fp64
+    lb, lf, mu, sg, info = oracle_np.nowcast(prog, t, y, t_add, y_add, t_new, non)
+    assert info == 0
+    tol = 50 * EPS * r.cond
+    assert abs(lb - float(r.logml_base)) <= tol * abs(float(r.logml_base))
+    assert np.all(np.abs(lf - r.logml_full.astype(float)) <= tol * np.abs(lf))
+    d, dd = hr.pred_scales(r.sigma)
+    for s in range(2):
+        check_components("hp nowcast vs fp64 oracle: mean", mu[s], r.mu[s], d, 1e-12, r.cond)
+    check_components("hp nowcast vs fp64 oracle: covariance", sg, r.sigma, dd, 1e-12, r.cond)
+    # evaluate on the concatenated series, scenario by scenario, and on the base series: the same
+    # arithmetic in the same precision, so agreement to long-double rounding
+    tol = 50 * hr.EPS_LD * r.cond
+    tt = np.concatenate([t, t_add])
+    e0 = hr.evaluate(prog, t, y, None, grad=False)
+    assert abs(e0.logml - r.logml_base) <= tol * abs(e0.logml)
+    for s in range(2):
+        e = hr.evaluate(prog, tt, np.concatenate([y, y_add[s]]), None, grad=False, t_new=t_new,
+                        noise_on_new=non)
+        assert abs(e.logml - r.logml_full[s]) <= tol * abs(e.logml)
+        assert np.all(np.abs(e.mu - r.mu[s]) <= tol * d)
+        assert np.all(np.abs(e.sigma - r.sigma) <= tol * dd)
+        assert e.cond == r.cond
+
+
+def test_reference_pivots_include_the_non_positive_one():
+    A = np.array([[4.0, 2.0, 2.0], [2.0, 2.0, 1.0], [2.0, 1.0, 0.5]]).astype(LD)
+    L, info, piv = hr.cholesky_ld(A, pivots=True)
+    # pivots 4, 2 - 1 = 1, 0.5 - 1 - 0 = -0.5
+    assert L is None and info == 3 and np.allclose(piv.astype(float), [4.0, 1.0, -0.5])
+    assert hr.cholesky_ld(A)[1] == 3
+    L, info, piv = hr.cholesky_ld(A[:2, :2], pivots=True)
+    assert info == 0 and np.allclose(piv.astype(float), [4.0, 1.0]) and np.allclose(
+        (L @ L.T).astype(float), A[:2, :2].astype(float))
+
+
 def test_reference_reports_an_indefinite_matrix_and_caches():
     t = np.array([0.0, 1.0, 2.0])
     prog = (np.array([1], np.int32), np.array([-5.0]), 0.0)    # a negative constant kernel

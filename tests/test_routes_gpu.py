@@ -22,6 +22,7 @@ from nowcastautogp_amd import _lib
 from nowcastautogp_amd._abi import KernelArray
 from tests import hp_reference as hr
 from tests.util import TOL_LOGML, check, check_components, tol
+from tests.value_cases import ensemble, series, tree
 
 pytestmark = pytest.mark.gpu
 
@@ -40,68 +41,7 @@ def ctx():
     c.close()
 
 
-# ---- items --------------------------------------------------------------------------------------
-def _leaf(rng, stationary=True, small=False):
-    """(op, params) of one leaf, sized for dates in [0, 1] (small: at most two parameters)"""
-    kinds = [1, 3] if small else [1, 3, 4, 5] if stationary else [2, 3, 5]
-    op = int(rng.choice(kinds))
-    if op == 1:
-        return op, [rng.uniform(0.1, 0.5)]
-    if op == 2:
-        return op, [rng.uniform(0.3, 0.7), rng.uniform(0.05, 0.2), rng.uniform(0.2, 0.8)]
-    if op == 3:
-        return op, [rng.uniform(0.05, 0.3), rng.uniform(0.2, 1.0)]
-    if op == 4:
-        return op, [rng.uniform(0.05, 0.3), rng.uniform(1.0, 1.9), rng.uniform(0.2, 1.0)]
-    return op, [rng.uniform(0.8, 2.0), rng.uniform(0.05, 0.3), rng.uniform(0.2, 1.0)]
-
-
-def tree(rng, n_ops, stationary=True, linear=False, cp=False):
-    """an RPN program of exactly n_ops operators (odd): a left fold of leaves by +, x (and one
-    ChangePoint), stack depth 2"""
-    assert n_ops % 2 == 1
-    leaves = (n_ops + 1) // 2
-    small = leaves > 16                    # NGP_MAX_PARAMS = 96
-    op, pr = _leaf(rng, stationary, small)
-    if linear:
-        op, pr = 2, [0.5, 0.1, 0.5]
-    ops, params = [op], list(pr)
-    for k in range(1, leaves):
-        op, pr = _leaf(rng, stationary, small)
-        ops.append(op)
-        params += pr
-        if cp and k == leaves - 1:
-            ops.append(8)
-            params += [rng.uniform(0.3, 0.7), 0.05]
-        else:
-            # products of more than two factors would make K too small to matter: mostly sums
-            ops.append(7 if k % 4 == 1 else 6)
-    return np.array(ops, np.int32), np.array(params, float), float(rng.uniform(0.02, 0.1))
-
-
-def series(n, lattice=True, seed=0):
-    rng = np.random.default_rng(seed)
-    if lattice:
-        t = np.arange(n, dtype=float) / (n - 1)
-    else:
-        t = np.sort(rng.uniform(0.0, 1.0, n))
-        t += np.arange(n) * 1e-4                                   # no two dates within 1e-4
-        t /= t[-1]
-    y = np.sin(2 * np.pi * t * 3) + 0.5 * t + 0.1 * rng.standard_normal(n)
-    return t, y
-
-
-def ensemble(seed, sizes, B, stationary=True, linear_every=0, cp_every=0):
-    """B items whose op counts cycle through ``sizes``"""
-    rng = np.random.default_rng(seed)
-    out = []
-    for i in range(B):
-        lin = bool(linear_every) and i % linear_every == linear_every - 1
-        cpi = bool(cp_every) and i % cp_every == cp_every - 1
-        out.append(tree(rng, sizes[i % len(sizes)], stationary and not lin and not cpi, lin, cpi))
-    return out
-
-
+# ---- items: tests/value_cases.py holds the generators (shared with the value-path tests) -----------
 # ---- the three comparisons ------------------------------------------------------------------------
 def _run(ctx, progs, t, y, profile=False):
     """one staged gradient job over the items (its run gives the one-shot call's bits,
