@@ -381,6 +381,53 @@ ngp_status ngp_mixture_sample_indep(ngp_ctx *ctx, int32_t P, int32_t S, int32_t 
                                     int32_t draws, const uint64_t *seeds,
                                     double *out, int32_t *comp, int32_t *info);
 
+/* ---- exact summaries of the forecast mixture (per-date marginals) ------------------
+ * What the users of the reference compute from the draws — quantile(fc, probs) per forecast date
+ * and the CRPS against what was later observed (docs/vignettes/getting-started.jl:433-746) — in
+ * closed form from the mixture itself, without draws and without the m x m factor of any
+ * covariance.  A mixture is a flat list of C components over m dates; the caller pools scenarios
+ * (component (s, k) of S scenarios gets weight w[s][k] / S):
+ *   w   [C]      weights, >= 0, finite, summing to 1 (as for ngp_mixture_sample; not renormalised)
+ *   mu  [C x m]  marginal means, component-major
+ *   var [C x m]  marginal variances (the diagonal of each component's covariance)
+ * Per date j, with sd^2 = var:
+ *   F_j(x)    = sum_c w_c Phi((x - mu_cj) / sd_cj)
+ *   q_j(p)    : F_j(q) = p                                        (0 < p < 1)
+ *   A(d, v)   = d erf(d / sqrt(2 v)) + sqrt(2 v / pi) exp(-d^2 / (2 v))         ( = E|N(d, v)| )
+ *   CRPS_j(y) = sum_c w_c A(y - mu_cj, var_cj)
+ *               - 1/2 sum_c sum_c' w_c w_c' A(mu_cj - mu_c'j, var_cj + var_c'j)
+ * (E|X - y| - 1/2 E|X - X'| in closed form; Grimit et al. 2006).  ngp_mixture_cdf with x = y is
+ * the PIT value.
+ *   ngp_mixture_cdf       x [m x K] (K points per date)  -> cdf  [m x K]
+ *   ngp_mixture_quantiles probs [Q], each in (0, 1)      -> q    [m x Q]
+ *   ngp_mixture_crps      y [m]                          -> crps [m]
+ * "Exact" means: no sampling error — the result is the formula evaluated in fp64 (CDF to 1e-13
+ * absolute; a quantile q satisfies |F(q) - p| <= 1e-13 + a few ulp of q times the density; CRPS to
+ * 1e-12 of the size of the two sums it is the difference of), judged against a long double
+ * evaluation in tests/.  Quantiles are non-decreasing in p and a level's result does not depend on
+ * Q or on its position in probs.
+ * Malformed calls are NGP_ERR_ARG before anything touches a device: null context or arrays; C, m,
+ * K or Q < 1; a probs entry outside (0, 1); a negative or non-finite weight; weights all zero.
+ * Numerical trouble is per date: info[j] = c + 1 for the first component c with w_c > 0 whose mean
+ * is not finite or whose variance is not finite and positive at date j — that date's outputs are
+ * NaN, other dates are not affected (0: fine).  Components with w_c = 0 are ignored, bad values
+ * included.
+ * Limits (NGP_ERR_TOO_LARGE): C <= 65,536 components, K and Q <= 4,096, m <= 65,535 dates and what
+ * the device memory holds (24 C m bytes and, for the CRPS, 4 m (C / 256)^2) — NOT NGP_MAX_AUX: no
+ * m x m object exists here.
+ * Bitwise reproducible: the same inputs give the same bits on every call, a date's bits do not
+ * depend on the other dates of the call (every sum runs in a fixed order; no floating-point
+ * atomics).  Thread-safe like the other one-shot calls (the context's lock); these calls are not
+ * combined with concurrent callers.                                                            */
+ngp_status ngp_mixture_cdf(ngp_ctx *ctx, int32_t C, int32_t m, const double *w, const double *mu,
+                           const double *var, int32_t K, const double *x, double *cdf,
+                           int32_t *info);
+ngp_status ngp_mixture_quantiles(ngp_ctx *ctx, int32_t C, int32_t m, const double *w,
+                                 const double *mu, const double *var, int32_t Q,
+                                 const double *probs, double *q, int32_t *info);
+ngp_status ngp_mixture_crps(ngp_ctx *ctx, int32_t C, int32_t m, const double *w, const double *mu,
+                            const double *var, const double *y, double *crps, int32_t *info);
+
 /* ---- cached factor ------------------------------
  * A fitted model is queried many times with the same particles and the same
  * training data: forecast() on several date grids, forecast_with_nowcasts()
@@ -479,6 +526,9 @@ ngp_status ngp_selftest_mfma_layout(ngp_ctx *ctx, const double *A, const double 
 /* The same for the fp32 form of the mixed-precision path: D[32x32] = A[32x2] B[2x32] through one
  * v_mfma_f32_32x32x2_f32 (all row-major floats).                                          */
 ngp_status ngp_selftest_mfma_f32_layout(ngp_ctx *ctx, const float *A, const float *B, float *D);
+/* Pair terms A(mu_c - mu_c', var_c + var_c') per second with the operands in registers (no loads):
+ * the ceiling the CRPS cross-term kernel is measured against; `iters` terms per thread.         */
+ngp_status ngp_microbench_mixture_pairs(ngp_ctx *ctx, int32_t iters, double *pairs_per_s);
 /* HBM streaming-write microbenchmark (GB/s) used to anchor the fill roofline. */
 ngp_status ngp_microbench_hbm(ngp_ctx *ctx, int64_t bytes, double *write_gbs, double *copy_gbs);
 

@@ -337,6 +337,57 @@ function mixture_sample_indep(c::Context, w::Matrix{Float64},        # P x S (co
     return out
 end
 
+# ---- exact summaries of a mixture's per-date marginals (include/ngp.h) --------------------------
+# A mixture is C components over m dates: w [C], mu and var m x C (column = component, which is the
+# header's [C x m] row-major).  A date whose info is c > 0 has a component (c, 1-based) with a
+# non-finite mean or a variance that is not finite and positive; its outputs are NaN.
+function _check_marginals(w::Vector{Float64}, mu::Matrix{Float64}, var::Matrix{Float64})
+    size(mu) == size(var) && size(mu, 2) == length(w) ||
+        throw(DimensionMismatch("w [C], mu and var m x C"))
+    return size(mu, 2), size(mu, 1)
+end
+
+"F_j(x) of every date j at K points: x is m x K; returns (cdf m x K, info) (`ngp_mixture_cdf`). With x = y the PIT values."
+function mixture_cdf(c::Context, w::Vector{Float64}, mu::Matrix{Float64}, var::Matrix{Float64},
+                     x::Matrix{Float64})
+    C, m = _check_marginals(w, mu, var)
+    size(x, 1) == m || throw(DimensionMismatch("x is m x K"))
+    K = size(x, 2)
+    xt = permutedims(x)                                         # K x m column-major == [m x K] row-major
+    out = similar(xt); info = zeros(Int32, m)
+    check(ccall((:ngp_mixture_cdf, LIBNGP), Int32,
+                (Ptr{Cvoid}, Int32, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int32,
+                 Ptr{Float64}, Ptr{Float64}, Ptr{Int32}),
+                c.h, C, m, w, mu, var, K, xt, out, info), "ngp_mixture_cdf")
+    return permutedims(out), info
+end
+
+"Exact quantiles per date, `quantile(dist, probs)` without draws: returns (q m x Q, info) (`ngp_mixture_quantiles`)."
+function mixture_quantiles(c::Context, w::Vector{Float64}, mu::Matrix{Float64}, var::Matrix{Float64},
+                           probs::Vector{Float64})
+    C, m = _check_marginals(w, mu, var)
+    Q = length(probs)
+    out = Matrix{Float64}(undef, Q, m); info = zeros(Int32, m)
+    check(ccall((:ngp_mixture_quantiles, LIBNGP), Int32,
+                (Ptr{Cvoid}, Int32, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int32,
+                 Ptr{Float64}, Ptr{Float64}, Ptr{Int32}),
+                c.h, C, m, w, mu, var, Q, probs, out, info), "ngp_mixture_quantiles")
+    return permutedims(out), info
+end
+
+"Closed-form CRPS per date against y [m], on the scale of the mixture: returns (crps, info) (`ngp_mixture_crps`)."
+function mixture_crps(c::Context, w::Vector{Float64}, mu::Matrix{Float64}, var::Matrix{Float64},
+                      y::Vector{Float64})
+    C, m = _check_marginals(w, mu, var)
+    length(y) == m || throw(DimensionMismatch("y has one entry per date"))
+    out = Vector{Float64}(undef, m); info = zeros(Int32, m)
+    check(ccall((:ngp_mixture_crps, LIBNGP), Int32,
+                (Ptr{Cvoid}, Int32, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+                 Ptr{Float64}, Ptr{Int32}),
+                c.h, C, m, w, mu, var, y, out, info), "ngp_mixture_crps")
+    return out, info
+end
+
 """
 The one collective of the path for a multi-GPU Julia host (one process per GPU): RCCL, opened by
 libngp at run time.  Rank 0 calls `comm_unique_id()` and hands the 128 bytes to the other ranks by

@@ -37,6 +37,7 @@ SYMBOLS = (
     "ngp_microbench_mfma_f64", "ngp_microbench_mfma_f64_detail", "ngp_microbench_hbm", "ngp_selftest_mfma_layout",
     "ngp_selftest_mfma_f32_layout", "ngp_set_combining", "ngp_combine_stats",
     "ngp_weights_unpad_normalize", "ngp_grad_job_info", "ngp_set_batch_invariant", "ngp_set_short_series_path",
+    "ngp_mixture_cdf", "ngp_mixture_quantiles", "ngp_mixture_crps", "ngp_microbench_mixture_pairs",
 )
 
 
@@ -117,6 +118,10 @@ def load():
         "ngp_factor_destroy": (None, [vp]),
         "ngp_mixture_sample": (i32, [vp, i32, i32, i32, f64p, f64p, f64p, i32, C.c_uint64, f64p,
                                      i32p, i32p]),
+        "ngp_mixture_cdf": (i32, [vp, i32, i32, f64p, f64p, f64p, i32, f64p, f64p, i32p]),
+        "ngp_mixture_quantiles": (i32, [vp, i32, i32, f64p, f64p, f64p, i32, f64p, f64p, i32p]),
+        "ngp_mixture_crps": (i32, [vp, i32, i32, f64p, f64p, f64p, f64p, f64p, i32p]),
+        "ngp_microbench_mixture_pairs": (i32, [vp, i32, f64p]),
         "ngp_set_structured_storage": (i32, [vp, i32]),
         "ngp_set_combining": (i32, [vp, i32]),
         "ngp_set_batch_invariant": (i32, [vp, i32]),
@@ -521,6 +526,52 @@ class Context:
              "ngp_mixture_sample_indep")
         return out, comp, info
 
+    @staticmethod
+    def _marginals(w, mu, var, who):
+        w, mu, var = as_f64(w), as_f64(mu), as_f64(var)
+        if w.ndim != 1 or mu.ndim != 2 or mu.shape[0] != w.size or var.shape != mu.shape:
+            raise ValueError(f"{who}: w [C], mu [C,m], var [C,m]")
+        return w, mu, var
+
+    def mixture_cdf(self, w, mu, var, x):
+        """F_j(x) of the per-date marginals of a mixture (``ngp_mixture_cdf``): w [C], mu [C,m],
+        var [C,m], x [m,K] -> (cdf [m,K], info [m])."""
+        w, mu, var = self._marginals(w, mu, var, "mixture_cdf")
+        C_, m = mu.shape
+        x = as_f64(x)
+        if x.ndim != 2 or x.shape[0] != m:
+            raise ValueError("mixture_cdf: x [m,K]")
+        out, info = np.empty(x.shape), np.zeros(m, dtype=np.int32)
+        _chk(load().ngp_mixture_cdf(self._h, C_, m, dptr(w), dptr(mu), dptr(var), x.shape[1],
+                                    dptr(x), dptr(out), iptr(info)), "ngp_mixture_cdf")
+        return out, info
+
+    def mixture_quantiles(self, w, mu, var, probs):
+        """Exact quantiles per date (``ngp_mixture_quantiles``): probs [Q] in (0, 1) ->
+        (q [m,Q], info [m])."""
+        w, mu, var = self._marginals(w, mu, var, "mixture_quantiles")
+        C_, m = mu.shape
+        probs = as_f64(probs)
+        if probs.ndim != 1:
+            raise ValueError("mixture_quantiles: probs [Q]")
+        out, info = np.empty((m, probs.size)), np.zeros(m, dtype=np.int32)
+        _chk(load().ngp_mixture_quantiles(self._h, C_, m, dptr(w), dptr(mu), dptr(var), probs.size,
+                                          dptr(probs), dptr(out), iptr(info)),
+             "ngp_mixture_quantiles")
+        return out, info
+
+    def mixture_crps(self, w, mu, var, y):
+        """Closed-form CRPS per date (``ngp_mixture_crps``): y [m] -> (crps [m], info [m])."""
+        w, mu, var = self._marginals(w, mu, var, "mixture_crps")
+        C_, m = mu.shape
+        y = as_f64(y)
+        if y.shape != (m,):
+            raise ValueError("mixture_crps: y [m]")
+        out, info = np.empty(m), np.zeros(m, dtype=np.int32)
+        _chk(load().ngp_mixture_crps(self._h, C_, m, dptr(w), dptr(mu), dptr(var), dptr(y),
+                                     dptr(out), iptr(info)), "ngp_mixture_crps")
+        return out, info
+
     def logml_grad_flat(self, ka: KernelArray, t, y):
         """``ngp_logml_grad_batch`` on a prepared kernel array; the gradients come back as ONE
         vector (per program: d/d params in program order, then d/d noise), no per-program split."""
@@ -631,6 +682,13 @@ class Context:
              "ngp_microbench_mfma_f64_detail")
         return dict(tflops=out[0], cycles_per_mfma=out[1], clock_ghz=out[2],
                     waves_per_simd=int(out[3]))
+
+    def microbench_mixture_pairs(self, iters=4096) -> float:
+        """CRPS pair terms per second on registers only (``ngp_microbench_mixture_pairs``)."""
+        v = C.c_double()
+        _chk(load().ngp_microbench_mixture_pairs(self._h, int(iters), C.byref(v)),
+             "ngp_microbench_mixture_pairs")
+        return float(v.value)
 
     def microbench_hbm(self, nbytes=1 << 30):
         w, c = C.c_double(), C.c_double()

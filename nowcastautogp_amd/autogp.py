@@ -38,7 +38,8 @@ from . import distributed, gp
 from ._lib import PosDefException
 
 __all__ = ["GPModel", "Schedule", "fit_smc", "add_data", "maybe_resample", "num_particles",
-           "mcmc_structure", "mcmc_parameters", "predict_mvn", "MixtureMVN", "HipEngine"]
+           "mcmc_structure", "mcmc_parameters", "predict_mvn", "MixtureMVN", "MixtureMarginals",
+           "HipEngine"]
 
 
 # ---------------------------------------------------------------------------------------------
@@ -85,6 +86,18 @@ class HipEngine:
     def mixture_sample_indep(self, w, mu, sigma, draws, seeds):
         """Draws from S independent mixtures in one device call (``ngp_mixture_sample_indep``)."""
         return self.ctx.mixture_sample_indep(w, mu, sigma, draws, seeds)
+
+    def mixture_cdf(self, w, mu, var, x):
+        """CDF of a mixture's per-date marginals on the device (``ngp_mixture_cdf``)."""
+        return self.ctx.mixture_cdf(w, mu, var, x)
+
+    def mixture_quantiles(self, w, mu, var, probs):
+        """Exact per-date quantiles on the device (``ngp_mixture_quantiles``)."""
+        return self.ctx.mixture_quantiles(w, mu, var, probs)
+
+    def mixture_crps(self, w, mu, var, y):
+        """Closed-form per-date CRPS on the device (``ngp_mixture_crps``)."""
+        return self.ctx.mixture_crps(w, mu, var, y)
 
     def factor(self, programs, t, y):
         """Factorise once, keep L on the device (``ngp_factor``): repeated forecasts of a fitted
@@ -913,6 +926,170 @@ class MixtureMVN:
 
     def mean(self):
         return self.weights @ self.means
+
+    def marginals(self, engine=None) -> "MixtureMarginals":
+        """The per-date marginals (means and the diagonal of every covariance)."""
+        return MixtureMarginals(self.means, np.einsum("kjj->kj", self.covs), self.weights,
+                                engine=engine)
+
+
+_erf = np.frompyfunc(math.erf, 1, 1)
+_erfc = np.frompyfunc(math.erfc, 1, 1)
+
+
+def _abs_moment(d, v):
+    """E|N(d, v)| = d erf(d / sqrt(2 v)) + sqrt(2 v / pi) exp(-d^2 / (2 v))"""
+    s = np.sqrt(2.0 * v)
+    r = d / s
+    return d * _erf(r).astype(np.float64) + s * np.exp(-r * r) / math.sqrt(math.pi)
+
+
+class MixtureMarginals:
+    """The per-date marginals of a Gaussian mixture — ``means`` [C, m], ``variances`` [C, m],
+    ``weights`` [C] — and their exact summaries, each returned date-major ([m], [m, Q]: the
+    orientation of ``forecast``'s [m, draws]):
+
+        cdf(x)        F_j(x) = sum_c w_c Phi((x - mu_cj) / sd_cj)
+        quantile(p)   F_j(q) = p, to the last bits of q; ``inv_transformation`` is applied
+                      elementwise to the exact quantiles — for a monotone non-decreasing map (the
+                      inverses of ``nowcast.get_transformations``, clamp at 0 included) that IS the
+                      quantile on the original scale
+        crps(y)       E|X - y| - E|X - X'| / 2 in closed form, on the MODEL's (transformed) scale,
+                      as the reference's vignette scores it (crps(data_transform(y), ...))
+        pit(y)        F_j(y_j)
+        mean()
+
+    With an engine that has ``mixture_cdf`` / ``mixture_quantiles`` / ``mixture_crps`` (the HIP
+    library, include/ngp.h) those compute; without one the same formulas run on the host with
+    ``math.erf`` / ``math.erfc`` — for small mixtures only (the CRPS is C^2 terms per date)."""
+
+    def __init__(self, means, variances, weights, engine=None):
+        self.means = np.ascontiguousarray(np.asarray(means, dtype=np.float64))
+        self.variances = np.ascontiguousarray(np.asarray(variances, dtype=np.float64))
+        w = np.asarray(weights, dtype=np.float64)
+        if (self.means.ndim != 2 or self.variances.shape != self.means.shape
+                or w.shape != (self.means.shape[0],)):
+            raise ValueError("MixtureMarginals: means [C, m], variances [C, m], weights [C]")
+        self.weights = w / np.sum(w)
+        self.engine = engine
+
+    @classmethod
+    def pool(cls, parts: Sequence["MixtureMarginals"], weights=None) -> "MixtureMarginals":
+        """One mixture of several on the same dates: part d weighs ``weights[d]`` (1 / D each when
+        not given — scenarios that get equal shares of the draws)."""
+        parts = list(parts)
+        D = len(parts)
+        pw = np.full(D, 1.0 / D) if weights is None else np.asarray(weights, dtype=np.float64)
+        if pw.shape != (D,):
+            raise ValueError("MixtureMarginals.pool: one weight per part")
+        return cls(np.concatenate([p.means for p in parts]),
+                   np.concatenate([p.variances for p in parts]),
+                   np.concatenate([a * p.weights for a, p in zip(pw, parts)]),
+                   engine=next((p.engine for p in parts if p.engine is not None), None))
+
+    # ---- plumbing ---------------------------------------------------------------------------
+    def _device(self, name):
+        return getattr(self.engine, name, None) if self.engine is not None else None
+
+    @staticmethod
+    def _check(info):
+        bad = np.flatnonzero(info)
+        if bad.size:      # a variance that is not positive: the covariance it came from is not either
+            raise PosDefException(int(bad[0]) + 1, int(info[bad[0]]) - 1)
+
+    def _host_info(self):
+        act = self.weights > 0
+        ok = np.isfinite(self.means) & np.isfinite(self.variances) & (self.variances > 0)
+        bad = ~ok & act[:, None]
+        return np.where(bad.any(axis=0), bad.argmax(axis=0) + 1, 0)
+
+    def _active(self):
+        act = self.weights > 0
+        return self.weights[act], self.means[act], self.variances[act]
+
+    def _host_cdf(self, x, density=False):
+        """x [m, K] -> F [m, K] (and the density)"""
+        w, mu, var = self._active()
+        inv = 1.0 / np.sqrt(2.0 * var)                                   # [C, m]
+        t = (x[None, :, :] - mu[:, :, None]) * inv[:, :, None]          # [C, m, K]
+        F = np.einsum("c,cmk->mk", w, 0.5 * _erfc(-t).astype(np.float64))
+        if not density:
+            return F
+        f = np.einsum("c,cmk->mk", w, inv[:, :, None] * np.exp(-t * t)) / math.sqrt(math.pi)
+        return F, f
+
+    # ---- summaries --------------------------------------------------------------------------
+    def mean(self):
+        return self.weights @ self.means
+
+    def cdf(self, x):
+        x = np.asarray(x, dtype=np.float64)
+        m = self.means.shape[1]
+        xs = x.reshape(m, -1) if x.ndim <= 1 else x
+        if xs.shape[0] != m or (x.ndim <= 1 and x.size != m):
+            raise ValueError("MixtureMarginals.cdf: x [m] or [m, K]")
+        dev = self._device("mixture_cdf")
+        if dev is not None:
+            F, info = dev(self.weights, self.means, self.variances, np.ascontiguousarray(xs))
+        else:
+            info = self._host_info()
+            self._check(info)
+            F = self._host_cdf(xs)
+        self._check(info)
+        return F[:, 0] if x.ndim <= 1 else F
+
+    def pit(self, y):
+        return self.cdf(np.asarray(y, dtype=np.float64).reshape(-1))
+
+    def quantile(self, probs, inv_transformation=lambda y: y):
+        p = np.atleast_1d(np.asarray(probs, dtype=np.float64))
+        if p.ndim != 1 or not np.all((p > 0) & (p < 1)):
+            raise ValueError("MixtureMarginals.quantile: probs in (0, 1)")
+        dev = self._device("mixture_quantiles")
+        if dev is not None:
+            q, info = dev(self.weights, self.means, self.variances, p)
+            self._check(info)
+        else:
+            self._check(self._host_info())
+            q = self._host_quantile(p)
+        from .nowcast import _apply
+        return _apply(inv_transformation, q)
+
+    def _host_quantile(self, p):
+        """bisection on the host CDF until no number is left between the ends: F(lo) < p <= F(hi)"""
+        w, mu, var = self._active()
+        m = mu.shape[1]
+        sd = np.sqrt(var)
+        lo = np.repeat((mu - 40.0 * sd).min(axis=0)[:, None], p.size, axis=1)
+        hi = np.repeat((mu + 40.0 * sd).max(axis=0)[:, None], p.size, axis=1)
+        for _ in range(1200):
+            mid = 0.5 * lo + 0.5 * hi
+            live = (mid > lo) & (mid < hi)
+            if not live.any():
+                break
+            below = self._host_cdf(mid) < p[None, :]
+            lo = np.where(live & below, mid, lo)
+            hi = np.where(live & ~below, mid, hi)
+        return hi
+
+    def crps(self, y):
+        y = np.asarray(y, dtype=np.float64).reshape(-1)
+        m = self.means.shape[1]
+        if y.size != m:
+            raise ValueError("MixtureMarginals.crps: y [m]")
+        dev = self._device("mixture_crps")
+        if dev is not None:
+            out, info = dev(self.weights, self.means, self.variances, y)
+            self._check(info)
+            return out
+        self._check(self._host_info())
+        w, mu, var = self._active()
+        out = np.empty(m)
+        for j in range(m):
+            t1 = float(w @ _abs_moment(y[j] - mu[:, j], var[:, j]))
+            a = _abs_moment(mu[:, j][:, None] - mu[:, j][None, :], var[:, j][:, None] + var[:, j][None, :])
+            out[j] = t1 - 0.5 * float(w @ a @ w)
+        return out
 
 
 def predict_mvn(model: GPModel, ds, noise_on_new: bool = True) -> MixtureMVN:

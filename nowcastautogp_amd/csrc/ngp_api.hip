@@ -2811,6 +2811,168 @@ extern "C" ngp_status ngp_mixture_sample_indep(ngp_ctx *c, int32_t P, int32_t S,
 }
 
 // ---------------------------------------------------------------------------------------
+// Summaries of a mixture's per-date marginals (ngp_mixture_cdf / _quantiles / _crps)
+//
+// The host pass validates, reports bad dates and restages the mixture for the kernels of
+// ngp_mixture_kernels.h: components of weight zero are dropped (they are to be ignored, bad values
+// included) and the rest goes DATE-MAJOR.  A date with a bad component is computed on harmless
+// stand-in values and comes out as NaN; nothing it holds reaches the arithmetic of another date.
+namespace {
+struct MixStaged {
+    int32_t C = 0;                       // components of positive weight
+    PinVec<double> w, mu, var;           // [C], [m][C], [m][C]
+    std::vector<char> bad;               // [m]
+};
+
+ngp_status mixture_stage(int32_t C, int32_t m, const double *w, const double *mu, const double *var,
+                         int32_t *info, MixStaged *out) {
+    if (!w || !mu || !var || !info || C < 1 || m < 1) return NGP_ERR_ARG;
+    if (C > MIX_MAX_COMPONENTS || m > MIX_MAX_DATES) return NGP_ERR_TOO_LARGE;
+    std::vector<int32_t> keep;
+    keep.reserve(C);
+    for (int32_t c = 0; c < C; ++c) {
+        if (!(w[c] >= 0.0) || !std::isfinite(w[c])) return NGP_ERR_ARG;
+        if (w[c] > 0.0) keep.push_back(c);
+    }
+    if (keep.empty()) return NGP_ERR_ARG;
+    const size_t Cn = keep.size();
+    out->C = (int32_t)Cn;
+    out->w.resize(Cn);
+    out->mu.resize(Cn * m);
+    out->var.resize(Cn * m);
+    out->bad.assign(m, 0);
+    for (int32_t j = 0; j < m; ++j) info[j] = 0;
+    for (size_t k = 0; k < Cn; ++k) {
+        const int32_t c = keep[k];
+        out->w[k] = w[c];
+        const double *mc = mu + (size_t)c * m, *vc = var + (size_t)c * m;
+        for (int32_t j = 0; j < m; ++j) {
+            const bool ok = std::isfinite(mc[j]) && std::isfinite(vc[j]) && vc[j] > 0.0;
+            if (!ok && !info[j]) info[j] = c + 1;      // components come in ascending order
+            out->mu[(size_t)j * Cn + k] = mc[j];
+            out->var[(size_t)j * Cn + k] = vc[j];
+        }
+    }
+    for (int32_t j = 0; j < m; ++j) {
+        if (!info[j]) continue;
+        out->bad[j] = 1;
+        for (size_t k = 0; k < Cn; ++k) {
+            out->mu[(size_t)j * Cn + k] = 0.0;
+            out->var[(size_t)j * Cn + k] = 1.0;
+        }
+    }
+    return NGP_OK;
+}
+
+// device blocks of one call, given back on every exit path
+struct MixBlocks {
+    ngp_ctx *c;
+    std::vector<void *> held;
+    explicit MixBlocks(ngp_ctx *ctx) : c(ctx) {}
+    ~MixBlocks() { for (void *p : held) c->release(p); }
+    ngp_status take(double **p, size_t count) {
+        void *q = nullptr;
+        const ngp_status st = c->alloc(&q, 8 * count);
+        if (st) return st;
+        held.push_back(q);
+        *p = (double *)q;
+        return NGP_OK;
+    }
+};
+
+enum { MIX_CDF = 0, MIX_QUANTILES = 1, MIX_CRPS = 2 };
+
+// pts: x [m x npts] (CDF), probs [npts] (quantiles), y [m] (CRPS, npts = 1); res [m x npts]
+ngp_status mixture_summary(ngp_ctx *c, int kind, int32_t C, int32_t m, const double *w,
+                           const double *mu, const double *var, int32_t npts, const double *pts,
+                           double *res, int32_t *info) {
+    if (!c || !pts || !res || npts < 1) return NGP_ERR_ARG;
+    if (npts > MIX_MAX_POINTS) return NGP_ERR_TOO_LARGE;
+    if (kind == MIX_QUANTILES)
+        for (int32_t k = 0; k < npts; ++k)
+            if (!(pts[k] > 0.0 && pts[k] < 1.0)) return NGP_ERR_ARG;
+    MixStaged h;
+    ngp_status st = mixture_stage(C, m, w, mu, var, info, &h);
+    if (st) return st;
+    const size_t Cn = (size_t)h.C, nres = (size_t)m * npts;
+    const size_t npin = kind == MIX_QUANTILES ? (size_t)npts : nres;
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    MixBlocks blk(c);
+    double *dw = nullptr, *dmu = nullptr, *dvar = nullptr, *daux = nullptr, *dpts = nullptr,
+           *dres = nullptr;
+    // aux: inv [m][C] for the CDF and the quantiles, the slab of tile partials for the CRPS
+    const size_t naux = kind == MIX_CRPS ? (size_t)m * (size_t)mix_tile_pairs(h.C) : Cn * m;
+    if ((st = blk.take(&dw, Cn)) || (st = blk.take(&dmu, Cn * m)) || (st = blk.take(&dvar, Cn * m)) ||
+        (st = blk.take(&daux, naux)) || (st = blk.take(&dpts, npin)) || (st = blk.take(&dres, nres)))
+        return st;
+    hipError_t e = hipMemcpyAsync(dw, h.w.data(), 8 * Cn, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(dmu, h.mu.data(), 8 * Cn * m, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(dvar, h.var.data(), 8 * Cn * m, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(dpts, pts, 8 * npin, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) {
+        if (kind == MIX_CRPS) {
+            launch_mixture_crps(h.C, m, dw, dmu, dvar, dpts, daux, dres, s);
+        } else {
+            launch_mixture_prep(dvar, daux, (int64_t)(Cn * m), s);
+            if (kind == MIX_CDF) launch_mixture_cdf(h.C, m, dw, dmu, daux, npts, dpts, dres, s);
+            else launch_mixture_quantiles(h.C, m, dw, dmu, daux, npts, dpts, dres, s);
+        }
+        e = hipMemcpyAsync(res, dres, 8 * nres, hipMemcpyDeviceToHost, s);
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e == hipSuccess) e = hipGetLastError();
+    if (e != hipSuccess) return (ngp_status)(e > 0 ? e : 999);
+    for (int32_t j = 0; j < m; ++j)
+        if (h.bad[j])
+            for (int32_t k = 0; k < npts; ++k) res[(size_t)j * npts + k] = std::nan("");
+    return NGP_OK;
+}
+}  // namespace
+
+extern "C" ngp_status ngp_mixture_cdf(ngp_ctx *c, int32_t C, int32_t m, const double *w,
+                                      const double *mu, const double *var, int32_t K,
+                                      const double *x, double *cdf, int32_t *info) {
+    return mixture_summary(c, MIX_CDF, C, m, w, mu, var, K, x, cdf, info);
+}
+
+extern "C" ngp_status ngp_mixture_quantiles(ngp_ctx *c, int32_t C, int32_t m, const double *w,
+                                            const double *mu, const double *var, int32_t Q,
+                                            const double *probs, double *q, int32_t *info) {
+    return mixture_summary(c, MIX_QUANTILES, C, m, w, mu, var, Q, probs, q, info);
+}
+
+extern "C" ngp_status ngp_mixture_crps(ngp_ctx *c, int32_t C, int32_t m, const double *w,
+                                       const double *mu, const double *var, const double *y,
+                                       double *crps, int32_t *info) {
+    return mixture_summary(c, MIX_CRPS, C, m, w, mu, var, 1, y, crps, info);
+}
+
+// pair terms of the CRPS cross sum per second with the operands in registers (no loads, no LDS):
+// the ceiling mix_crps_pairs_kernel is measured against (scripts/summary_probe.py)
+extern "C" ngp_status ngp_microbench_mixture_pairs(ngp_ctx *c, int32_t iters, double *pairs_per_s) {
+    if (!c || !pairs_per_s || iters <= 0) return NGP_ERR_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIPCHK(hipSetDevice(c->device));
+    const int blocks = 256 * 8;
+    MixBlocks blk(c);
+    double *out = nullptr;
+    ngp_status st = blk.take(&out, (size_t)blocks * 256);
+    if (st) return st;
+    ScopedEvent a, b;
+    launch_mixture_pair_rate(iters, blocks, out, c->stream);  // warm-up
+    HIPCHK(hipEventRecord(a, c->stream));
+    launch_mixture_pair_rate(iters, blocks, out, c->stream);
+    HIPCHK(hipEventRecord(b, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    float ms = 0.f;
+    HIPCHK(hipEventElapsedTime(&ms, a, b));
+    *pairs_per_s = (double)blocks * 256.0 * (double)iters / ((double)ms * 1e-3);
+    return NGP_OK;
+}
+
+// ---------------------------------------------------------------------------------------
 // Combining concurrent callers (flat combining)
 //
 // The reference enters the boundary from one task per nowcast scenario (Threads.@spawn,

@@ -339,6 +339,22 @@ void launch_cov(const DevProgram *progs, int B, const double *t1, int n1, const 
 void launch_mixture_sample(int P, int S, int m, const double *w, const double *mu, double *chol,
                            int draws, uint64_t seed, const uint64_t *seeds, double *out,
                            int32_t *comp, int32_t *info, hipStream_t s);
+// ---- summaries of a mixture's per-date marginals (ngp_mixture_kernels.h) -------------------
+// w [C], mu / var / inv [m][C] date-major (inv = 1 / sqrt(2 var), launch_mixture_prep); the cross
+// term of the CRPS is cut into MIX_TILE x MIX_TILE tiles of the upper triangle, one partial each
+// in slab [m][mix_tile_pairs(C)]
+constexpr int MIX_TILE = 256;
+constexpr int MIX_MAX_COMPONENTS = 65536, MIX_MAX_POINTS = 4096, MIX_MAX_DATES = 65535;
+inline int mix_tiles(int C) { return (C + MIX_TILE - 1) / MIX_TILE; }
+inline int64_t mix_tile_pairs(int C) { const int64_t nt = mix_tiles(C); return nt * (nt + 1) / 2; }
+void launch_mixture_prep(const double *var, double *inv, int64_t n, hipStream_t s);
+void launch_mixture_cdf(int C, int m, const double *w, const double *mu, const double *inv, int K,
+                        const double *x, double *out, hipStream_t s);
+void launch_mixture_quantiles(int C, int m, const double *w, const double *mu, const double *inv,
+                              int Q, const double *probs, double *q, hipStream_t s);
+void launch_mixture_crps(int C, int m, const double *w, const double *mu, const double *var,
+                         const double *y, double *slab, double *crps, hipStream_t s);
+void launch_mixture_pair_rate(int iters, int blocks, double *out, hipStream_t s);
 void launch_mfma_bench(double *out, int iters, int blocks, hipStream_t s);
 void launch_mfma_bench_detail(unsigned long long *stamps, int iters, int blocks, hipStream_t s);
 void launch_mfma_layout_probe(const double *A, const double *Bm, double *Dout, hipStream_t s);

@@ -36,6 +36,7 @@
 #include "ngp_mfma.h"
 #include "ngp_col_kernels.h"
 #include "ngp_small_kernels.h"
+#include "ngp_mixture_kernels.h"
 
 namespace ngp {
 

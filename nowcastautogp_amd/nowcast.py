@@ -37,7 +37,8 @@ from .autogp import GPModel
 GPConfig = gp.GPConfig
 
 __all__ = ["TData", "GPModel", "GPConfig", "create_transformed_data", "make_and_fit_model",
-           "forecast", "forecast_with_nowcasts", "create_nowcast_data"]
+           "forecast", "forecast_with_nowcasts", "create_nowcast_data", "forecast_mixture",
+           "forecast_mixture_with_nowcasts", "get_transformations"]
 
 
 class TData:
@@ -72,6 +73,127 @@ def create_nowcast_data(nowcasts, dates, *, transformation: Callable = lambda y:
     assert all(len(v) == first for v in nowcasts), \
         "All vectors in nowcasts must have the same length"
     return [create_transformed_data(dates, v, transformation=transformation) for v in nowcasts]
+
+
+def _get_offset(values: np.ndarray) -> float:
+    """Half the smallest positive value when the data touch zero, else 0 (reference
+    src/transformations.jl:51-61)."""
+    assert values.size > 0, "Values array must not be empty"
+    assert np.all(values >= 0), "All values must be non-negative for the selected transformations"
+    return float(values[values > 0].min() / 2) if values.min() == 0 else 0.0
+
+
+def _boxcox(x, lam: float):
+    x = np.asarray(x, dtype=np.float64)
+    return np.log(x) if lam == 0.0 else np.expm1(lam * np.log(x)) / lam
+
+
+def _fit_boxcox_lambda(x: np.ndarray, lo: float = -20.0, hi: float = 20.0) -> float:
+    """Maximum of the Box-Cox profile log-likelihood -(n/2) log var(bc_l(x)) + (l - 1) sum log x
+    over l in [lo, hi]: a grid to find the basin, then golden-section search inside it."""
+    logx = np.log(x)
+    n, slog = x.size, float(np.log(x).sum())
+
+    def nll(lam):
+        with np.errstate(all="ignore"):
+            z = logx if abs(lam) < 1e-12 else np.expm1(lam * logx) / lam
+            v = float(np.var(z))
+        if not np.isfinite(v) or v <= 0.0:
+            return np.inf
+        return 0.5 * n * np.log(v) - (lam - 1.0) * slog
+
+    grid = np.linspace(lo, hi, 161)
+    vals = np.array([nll(l) for l in grid])
+    k = int(np.argmin(vals))
+    a, b = grid[max(k - 1, 0)], grid[min(k + 1, grid.size - 1)]
+    g = (np.sqrt(5.0) - 1.0) / 2.0
+    c, d = b - g * (b - a), a + g * (b - a)
+    fc, fd = nll(c), nll(d)
+    for _ in range(80):
+        if fc < fd:
+            b, d, fd = d, c, fc
+            c = b - g * (b - a)
+            fc = nll(c)
+        else:
+            a, c, fc = c, d, fd
+            d = a + g * (b - a)
+            fd = nll(d)
+    return float(0.5 * (a + b))
+
+
+def _inv_boxcox(lam: float, offset: float, max_value: float) -> Callable:
+    """Inverse Box-Cox that never returns a negative or non-finite value (the edge cases of
+    reference src/transformations.jl:6-44): the base l y + 1 is floored at 1e-10 for l > 0; for
+    l < 0 a base <= 0 is mass at zero and a tiny positive base is clamped at 1000 x the largest
+    observed value."""
+    big = 1000.0 * max_value
+
+    def inv(y):
+        ya = np.asarray(y, dtype=np.float64)
+        base = lam * ya + 1.0
+        with np.errstate(all="ignore"):
+            if lam > 0:
+                res = np.maximum(base, 1.0e-10) ** (1.0 / lam) - offset
+            elif lam < 0:
+                safe = np.where(base > 0, base, 1.0)
+                powd = safe ** (1.0 / lam)
+                res = np.where(base > 1.0e-10, powd - offset,
+                               np.where(base <= 0, 0.0, np.minimum(powd, big) - offset))
+            else:
+                res = np.exp(ya) - offset
+        res = np.maximum(res, 0.0)
+        # (l > 0 and a huge argument: the power overflows — the largest finite number stands for it)
+        res = np.where(np.isfinite(res), res, np.finfo(np.float64).max)
+        return float(res) if np.ndim(y) == 0 else res
+
+    return inv
+
+
+def _elementwise(fn: Callable) -> Callable:
+    def g(y):
+        out = fn(np.asarray(y, dtype=np.float64))
+        return float(out) if np.ndim(y) == 0 else out
+    return g
+
+
+def get_transformations(transform_name: str, values):
+    """``(forward, inverse)`` for ``"percentage"`` (logit of y / 100), ``"positive"`` (log) and
+    ``"boxcox"`` (lambda fitted by maximum likelihood), as reference src/transformations.jl:139-174
+    defines them.  Data that touch zero are shifted by half their smallest positive value; every
+    inverse is monotone non-decreasing (clamp at 0 included) wherever the forward map can land, so
+    applied to an exact quantile of the model's scale it gives the quantile of the original scale (a
+    Box-Cox inverse with lambda < 0 has a pole at y = -1 / lambda; beyond it the reference's rule,
+    kept here, returns 0).  A Box-Cox fit that collapses
+    (transformed values not all finite, or their range <= 1e-2 of the range of log) falls back to
+    ``"positive"`` with a warning.  Both callables take scalars and numpy arrays."""
+    vals = np.asarray(values, dtype=np.float64).ravel()
+    offset = _get_offset(vals)
+    if transform_name == "percentage":
+        def fwd(y):
+            pr = (y + offset) / 100.0
+            with np.errstate(divide="ignore"):
+                return np.log(pr) - np.log1p(-pr)
+        return (_elementwise(fwd),
+                _elementwise(lambda y: np.maximum(100.0 / (1.0 + np.exp(-y)) - offset, 0.0)))
+    if transform_name == "positive":
+        def fwd(y):
+            with np.errstate(divide="ignore"):
+                return np.log(y + offset)
+        return (_elementwise(fwd), _elementwise(lambda y: np.maximum(np.exp(y) - offset, 0.0)))
+    if transform_name == "boxcox":
+        shifted = vals + offset
+        lam = _fit_boxcox_lambda(shifted)
+        with np.errstate(all="ignore"):
+            transformed = _boxcox(shifted, lam)
+        bc_range = float(transformed.max() - transformed.min())
+        log_range = float(np.log(shifted).max() - np.log(shifted).min())
+        if not np.all(np.isfinite(transformed)) or bc_range <= 1.0e-2 * log_range:
+            warnings.warn(f"Box-Cox transformation degenerate (lambda = {lam}, transformed range = "
+                          f"{bc_range}); falling back to log transformation (issue #51).")
+            return get_transformations("positive", values)
+        return (_elementwise(lambda y: _boxcox(y + offset, lam)),
+                _inv_boxcox(lam, offset, float(vals.max())))
+    raise AssertionError(f"Unknown transform_name: {transform_name}")
 
 
 def _stabilize_for_fit(y, *, flat_threshold: float = 1.0e-3, rng=None):
@@ -190,34 +312,18 @@ def forecast_with_nowcasts(base_model: GPModel, nowcasts: Sequence[TData], forec
         return _forecast_with_nowcasts_batched(base_model, nowcasts, dates, draws,
                                                inv_transformation, ess_threshold)
     def clone():
-        # GPModel(deepcopy(Dict(base_model))) of the reference (src/forecasting.jl:128,133).  Every
-        # scenario is its own task with its own randomness there (:131-133); a clone that kept the
-        # snapshot's streams would repeat the first scenario's draws.  Splitting also advances the
-        # base model's shared stream, so a second call differs from the first.
-        return base_model.clone(root=int(base_model.rng_shared.integers(0, 2**62)))
+        return _clone_for_scenario(base_model)
 
     if lockstep and same_dates:
-        # the reference's D tasks as ONE ensemble of P x D items (src/forecasting.jl:131-159)
-        models = [clone() for _ in nowcasts]
-        autogp.add_data_lockstep(models, nowcasts[0].ds, [nc.y for nc in nowcasts],
-                                 base=base_model)
-        autogp.maybe_resample_lockstep(models, ess_threshold * autogp.num_particles(base_model))
-        if n_mcmc > 0 and n_hmc > 0:
-            autogp.mcmc_structure_lockstep(models, n_mcmc, n_hmc, hmc_config)
-        elif n_mcmc == 0 and n_hmc > 0:
-            autogp.mcmc_parameters_lockstep(models, n_hmc, hmc_config)
+        models = _refined_clones_lockstep(base_model, nowcasts, n_mcmc, n_hmc, ess_threshold,
+                                          hmc_config)
         results = forecast_lockstep(models, dates, draws, inv_transformation=inv_transformation,
                                     forecast_n_hmc=forecast_n_hmc, hmc_config=hmc_config)
         if verbose:
             print(f"Nowcast scenarios: {len(results)}/{len(nowcasts)} (lockstep)")
         return np.hstack(results)
     def task(m, nc):      # the body of the reference's per-scenario task (src/forecasting.jl:133-155)
-        autogp.add_data(m, nc.ds, nc.y)
-        autogp.maybe_resample(m, ess_threshold * autogp.num_particles(m))
-        if n_mcmc > 0 and n_hmc > 0:
-            autogp.mcmc_structure(m, n_mcmc, n_hmc, hmc_config)
-        elif n_mcmc == 0 and n_hmc > 0:
-            autogp.mcmc_parameters(m, n_hmc, hmc_config)
+        _refine_scenario(m, nc, n_mcmc, n_hmc, ess_threshold, hmc_config)
         return forecast(m, dates, draws, inv_transformation=inv_transformation,
                         forecast_n_hmc=forecast_n_hmc, hmc_config=hmc_config)
 
@@ -252,10 +358,12 @@ def forecast_with_nowcasts(base_model: GPModel, nowcasts: Sequence[TData], forec
     return np.hstack(results)
 
 
-def _forecast_with_nowcasts_batched(model, nowcasts, dates, draws, inv_transformation,
-                                    ess_threshold):
+def _nowcast_mixtures_batched(model, nowcasts, dates, ess_threshold):
     """All scenarios in one engine call: one factorisation per particle (src/forecasting.jl:133-155
-    with n_mcmc = n_hmc = 0)."""
+    with n_mcmc = n_hmc = 0).  Returns the D scenario mixtures before anything is drawn: weights
+    ``w`` [D, P] (not yet resampled), ``means`` [P, D, m], ``covs`` [P, m, m] shared by the
+    scenarios of a particle, ``low`` [D] (scenarios whose ESS asks for resampling), the stream the
+    draws come from and the device sampler (None: the draws are made on the host)."""
     t, y = model._obs()
     t_add = model.ds_transform.apply(autogp.to_days(list(nowcasts[0].ds)))
     y_add = np.stack([model.y_transform.apply(np.asarray(nc.y, dtype=np.float64))
@@ -301,7 +409,18 @@ def _forecast_with_nowcasts_batched(model, nowcasts, dates, draws, inv_transform
     low = ess < ess_threshold * P
     sampler = getattr(model._eng(), "mixture_sample", None)
     from ._abi import NGP_MAX_AUX
-    if sampler is not None and 0 < m <= NGP_MAX_AUX:   # the device sampler's limit
+    if not 0 < m <= NGP_MAX_AUX:   # the device sampler's limit
+        sampler = None
+    return w, means, covs, low, rng, sampler
+
+
+def _forecast_with_nowcasts_batched(model, nowcasts, dates, draws, inv_transformation,
+                                    ess_threshold):
+    w, means, covs, low, rng, sampler = _nowcast_mixtures_batched(model, nowcasts, dates,
+                                                                  ess_threshold)
+    D, P = w.shape
+    m = len(dates)
+    if sampler is not None:
         # maybe_resample! for every scenario (ancestors ~ w, weights -> ancestor counts / P),
         # then ONE device call that draws from all D mixtures
         if low.any():
@@ -322,3 +441,95 @@ def _forecast_with_nowcasts_batched(model, nowcasts, dates, draws, inv_transform
         mix = autogp.MixtureMVN(means[:, sc, :], covs, wsc, rng)
         res[:, sc * draws:(sc + 1) * draws] = mix.rand(draws)
     return _apply(inv_transformation, res)
+
+
+def forecast_mixture(model: GPModel, forecast_dates) -> "autogp.MixtureMarginals":
+    """The per-date marginals of the mixture ``forecast`` draws from (``predict_mvn`` of reference
+    src/forecasting.jl:46), as an ``autogp.MixtureMarginals``: exact quantiles, CDF / PIT and CRPS
+    instead of draws.  Consumes nothing from the model's random streams."""
+    return autogp.predict_mvn(model, list(forecast_dates)).marginals(engine=model._eng())
+
+
+def forecast_mixture_with_nowcasts(base_model: GPModel, nowcasts: Sequence[TData], forecast_dates, *,
+                                   n_mcmc: int = 0, n_hmc: int = 0, ess_threshold: float = 0.0,
+                                   lockstep: bool = True,
+                                   hmc_config: Optional[dict] = None) -> "autogp.MixtureMarginals":
+    """The mixture ``forecast_with_nowcasts`` draws from, pooled over the scenarios (every scenario
+    weighs 1 / D, as its equal share of the draws does), as an ``autogp.MixtureMarginals``.
+
+    Follows ``forecast_with_nowcasts`` step for step — same asserts, weight update, resampling with
+    the same use of the random streams, refinement moves — up to the point where that function
+    draws, so from the same snapshot and seed the draws of ``forecast_with_nowcasts`` are samples of
+    exactly the mixture returned here.  One exception: on the default path with an engine that has
+    no device sampler (or more forecast dates than it takes), ``forecast_with_nowcasts`` resamples
+    a scenario AFTER it has drawn for the scenarios before it, so with ``ess_threshold > 0`` only
+    the scenarios up to the first resampled one are the same there.  ``forecast_n_hmc`` (a new
+    mixture before every draw) has no single mixture and is not taken."""
+    assert len(nowcasts) > 0, "nowcasts vector must not be empty"
+    assert not (n_mcmc > 0 and n_hmc == 0), \
+        "If n_mcmc > 0, n_hmc must also be > 0 for MCMC refinement"
+    assert 0.0 <= ess_threshold <= 1.0, "ess_threshold must be between 0 and 1"
+    dates = list(forecast_dates)
+    D = len(nowcasts)
+    same_dates = all(list(nc.ds) == list(nowcasts[0].ds) for nc in nowcasts)
+    if n_mcmc == 0 and n_hmc == 0 and same_dates and lockstep:
+        w, means, covs, low, rng, sampler = _nowcast_mixtures_batched(base_model, nowcasts, dates,
+                                                                      ess_threshold)
+        P = w.shape[1]
+        if sampler is not None:
+            if low.any():
+                w[low] = rng.multinomial(P, w[low]) / P
+            rng.integers(0, 2**63 - 1)      # the sampler's seed: leave the stream where the draws would
+        else:
+            for sc in np.flatnonzero(low):
+                w[sc] = np.bincount(rng.choice(P, size=P, p=w[sc]), minlength=P) / P
+        m = len(dates)
+        # the scenarios of a particle share its covariance: [D P, m] from the diagonal, never the
+        # D P full matrices
+        var = np.einsum("pjj->pj", covs) if m else np.zeros((P, 0))
+        return autogp.MixtureMarginals(
+            np.ascontiguousarray(means.transpose(1, 0, 2)).reshape(D * P, m),
+            np.broadcast_to(var[None], (D, P, m)).reshape(D * P, m),
+            (w / D).reshape(D * P), engine=base_model._eng())
+    if lockstep and same_dates:
+        models = _refined_clones_lockstep(base_model, nowcasts, n_mcmc, n_hmc, ess_threshold,
+                                          hmc_config)
+        mixes = autogp.predict_mvn_lockstep(models, dates)
+    else:
+        mixes = []
+        for nc in nowcasts:
+            mdl = _clone_for_scenario(base_model)
+            _refine_scenario(mdl, nc, n_mcmc, n_hmc, ess_threshold, hmc_config)
+            mixes.append(autogp.predict_mvn(mdl, dates))
+    return autogp.MixtureMarginals.pool([mx.marginals(engine=base_model._eng()) for mx in mixes])
+
+
+def _clone_for_scenario(base_model: GPModel) -> GPModel:
+    # GPModel(deepcopy(Dict(base_model))) of the reference (src/forecasting.jl:128,133).  Every
+    # scenario is its own task with its own randomness there (:131-133); a clone that kept the
+    # snapshot's streams would repeat the first scenario's draws.  Splitting also advances the
+    # base model's shared stream, so a second call differs from the first.
+    return base_model.clone(root=int(base_model.rng_shared.integers(0, 2**62)))
+
+
+def _refine_scenario(m: GPModel, nc: TData, n_mcmc, n_hmc, ess_threshold, hmc_config) -> None:
+    """the body of the reference's per-scenario task up to its forecast (src/forecasting.jl:133-149)"""
+    autogp.add_data(m, nc.ds, nc.y)
+    autogp.maybe_resample(m, ess_threshold * autogp.num_particles(m))
+    if n_mcmc > 0 and n_hmc > 0:
+        autogp.mcmc_structure(m, n_mcmc, n_hmc, hmc_config)
+    elif n_mcmc == 0 and n_hmc > 0:
+        autogp.mcmc_parameters(m, n_hmc, hmc_config)
+
+
+def _refined_clones_lockstep(base_model, nowcasts, n_mcmc, n_hmc, ess_threshold, hmc_config):
+    """the reference's D tasks as ONE ensemble of P x D items (src/forecasting.jl:131-149)"""
+    models = [_clone_for_scenario(base_model) for _ in nowcasts]
+    autogp.add_data_lockstep(models, nowcasts[0].ds, [nc.y for nc in nowcasts],
+                             base=base_model)
+    autogp.maybe_resample_lockstep(models, ess_threshold * autogp.num_particles(base_model))
+    if n_mcmc > 0 and n_hmc > 0:
+        autogp.mcmc_structure_lockstep(models, n_mcmc, n_hmc, hmc_config)
+    elif n_mcmc == 0 and n_hmc > 0:
+        autogp.mcmc_parameters_lockstep(models, n_hmc, hmc_config)
+    return models
