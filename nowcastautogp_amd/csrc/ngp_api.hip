@@ -760,6 +760,9 @@ struct EventTimer {  // HIP events on the launch stream, resolved after the job'
         (void)hipEventRecord(r.b, es);
         recs.push_back(r);
     }
+    template <class F> void run(const Cost &c, F &&f, hipStream_t on_stream = nullptr) {
+        run(c.cls, c.flops, c.bytes, std::forward<F>(f), on_stream);
+    }
     void resolve(ngp_profile &p) {
         for (auto &r : recs) {
             float ms = 0.f;
@@ -777,196 +780,115 @@ struct EventTimer {  // HIP events on the launch stream, resolved after the job'
 };
 
 
-// The left-looking factorisation of one chunk (every item's block columns in lock step).
-// Block columns in pairs: a FAT step finishes column jj and pre-accumulates column jj+1 (and,
-// on a side stream, the diagonal tile of jj+2) from the same streamed rows; the THIN step that
-// follows only adds k in [64 (jj-1), 64 jj).  See chol_col_lds_kernel.
+// The left-looking factorisation of one chunk (every item's block columns in lock step): which step
+// runs in which form is ngp_plan.h's (col_step, small_job, two_lane, splitk_eligible, ahead_early),
+// what it is booked as ngp_cost.h's.
 struct Lane {
     hipStream_t main, side;
     hipEvent_t fork, join;
     ngp_ctx *ctx;
 };
 inline Lane lane_of(ngp_ctx *c) { return Lane{c->stream, c->side, c->ev_fork, c->ev_join, c}; }
+inline Lane lane_of(ngp_ctx *c, int i) {
+    return i == 0 ? lane_of(c) : Lane{c->lane_main[i], c->lane_side[i], c->lane_fork[i], c->lane_join[i], c};
+}
+
+// The column kernels address an item's factor storage through a buffer descriptor with 32-bit
+// byte offsets: it must stay below 2 GiB (n <= 16,256 for value jobs, 11,520 for gradient jobs).
+inline bool item_too_large(int64_t item_stride) { return item_stride * 8 > (int64_t)0x7fffffff; }
+
+void factor_chunk_lanes(const Lane &ln, const JobGeom &g, const ChunkPtrs &p0, int bc, EventTimer &tm,
+                        size_t dinv_step, const DevSpec *sp, int32_t *order_buf, unsigned *order_prev);
 
 // dinv_step != 0: block column jj writes / reads its M at p.dinv + jj * dinv_step (cached factor:
 // every M_j is kept); 0: one buffer reused by every step.
 // sp != null and p0.L32 set: mixed-precision job (fat steps on chol_col_glds_kernel<MIXED>, class 9).
-// order_buf / order_prev ([bc] each, mixed jobs): every MIXED_REORDER block columns the items are
-// re-ranked by the fp64 tile products they needed since the last ranking.
-constexpr size_t MAX_CHUNK_ITEMS = 65535;   // gridDim.y
-// The column kernels address an item's factor storage through a buffer descriptor with 32-bit
-// byte offsets: it must stay below 2 GiB (n <= 16,256 for value jobs, 11,520 for gradient jobs).
-inline bool item_too_large(int64_t item_stride) { return item_stride * 8 > (int64_t)0x7fffffff; }
-constexpr int MIXED_REORDER = 16;
-constexpr int AHEAD_EARLY_MAX_ITEMS = 512;
-// Two lanes pay from n ~ 1500 and 64 items on (measured, 64 items: n = 2048 logml 6.78 -> 6.57 ms,
-// logml + gradient 17.07 -> 16.41; n = 1024: 2.00 -> 2.20 and 4.13 -> 4.21, so not there); three and
-// four lanes were slower everywhere (more streams than hardware queues).
-constexpr int TWO_LANE_MIN_ITEMS = 64, TWO_LANE_MIN_NB = 24;
+// order_buf / order_prev ([bc] each, mixed jobs): the ranking of MIXED_REORDER.
 void factor_chunk(const Lane &ln, const JobGeom &g, const ChunkPtrs &p_in, int bc, EventTimer &tm,
                   size_t dinv_step = 0, const DevSpec *sp = nullptr, int32_t *order_buf = nullptr,
                   unsigned *order_prev = nullptr, bool half = false) {
     ChunkPtrs p0 = p_in;
     const bool mixed = sp != nullptr && p0.L32 != nullptr;
     hipStream_t s = ln.main;
-    // Short series: the whole sweep of an item in one launch (ngp_small_kernels.h) — a rule of the
-    // geometry alone, so an item's arithmetic does not depend on its batch.  Resident factors and the
-    // Toeplitz gradient path keep every M_j (dinv_step) and stay on the column sweep; so do chunks
-    // that fill the chip many times over, where the column sweep's matrix-core rate wins.
+    // Short series: the whole sweep of an item in one launch (ngp_small_kernels.h).  Resident factors
+    // and the Toeplitz gradient path keep every M_j (dinv_step) and stay on the column sweep.
     SmallPlan spl;
     if (!mixed && dinv_step == 0 && small_job(g, bc, &spl)) {
-        const double nn = 16.0 * spl.nbe;
-        tm.run(13, bc * small_flops(g, spl), bc * 8.0 * (nn * nn * (spl.ident ? 1.5 : 1.0) + 2.0 * g.naux * nn),
-               [&] { launch_chol_small(g, p0, bc, spl, s); });
+        tm.run(cost_small(g, spl, bc), [&] { launch_chol_small(g, p0, bc, spl, s); });
         return;
     }
-    // small chunks of long series: room for the split-k fat steps (chol_col_glds_kernel<.., SPLITK>);
-    // the buffer stays with the context
-    if (!half && bc <= AHEAD_EARLY_MAX_ITEMS && !mixed && !g.aux_identity && g.nb0 >= 8 && !g.invariant &&
-        ln.ctx->splitk_reserve(bc) == NGP_OK)
+    // room for the split-k fat steps; the buffer stays with the context
+    if (splitk_eligible(g, bc, mixed, half) && ln.ctx->splitk_reserve(bc) == NGP_OK)
         p0.splitk_part = ln.ctx->splitk_part;
-    // Small chunks of long series (the 64-particle calls of a fit) are swept as two half-chunks side
-    // by side, each on its own pair of streams (lanes).  A launch of such a chunk rarely fills the chip or
-    // fills it one and a fraction times (64 items at n = 2048: 576 workgroups on 512 slots at
-    // column 14 — two rounds for the price of 1.1), and chol_diag / the thin step leave it almost
-    // empty: the other half's fat step runs in those gaps.  Every item's arithmetic is what it
-    // would be in a chunk of its half's size.
-    const int nl = ngp_ctx::MAX_LANES;
-    if (!half && !mixed && nl >= 2 && bc >= TWO_LANE_MIN_ITEMS && bc <= AHEAD_EARLY_MAX_ITEMS &&
-        g.nb0 >= TWO_LANE_MIN_NB && ln.main == ln.ctx->stream && ln.ctx->make_lanes(nl)) {
-        ngp_ctx *c = ln.ctx;
-        (void)hipEventRecord(c->ev_lane_go, s);
-        std::vector<EventTimer> tms;
-        tms.reserve((size_t)nl);
-        int h0 = 0;
-        for (int i = 0; i < nl; ++i) {
-            const int h1 = (int)((long)bc * (i + 1) / nl);
-            ChunkPtrs pi = p0;
-            pi.L += (size_t)h0 * g.item_stride;
-            pi.dinv += (size_t)h0 * NB * NB;
-            pi.progs += h0;
-            pi.logdet += h0;
-            pi.info += h0;
-            if (pi.tab) pi.tab += (size_t)h0 * g.maxstat * g.R;   // read by the column kernels (toep)
-            pi.n_fill_single = (int32_t)((long)p0.n_fill_single * (h1 - h0) / bc);   // byte accounting only
-            if (pi.splitk_part) pi.splitk_part += (size_t)h0 * SPLITK_SLOTS * 4 * 64 * 64;
-            if (i == 0) {
-                factor_chunk(ln, g, pi, h1 - h0, tm, dinv_step, sp, order_buf, order_prev, true);
-            } else {
-                const Lane li{c->lane_main[i], c->lane_side[i], c->lane_fork[i], c->lane_join[i], c};
-                tms.emplace_back(tm.on, li.main);
-                (void)hipStreamWaitEvent(li.main, c->ev_lane_go, 0);
-                factor_chunk(li, g, pi, h1 - h0, tms.back(), dinv_step, sp, order_buf, order_prev, true);
-                (void)hipEventRecord(c->lane_done[i], li.main);
-            }
-            h0 = h1;
-        }
-        for (int i = 1; i < nl; ++i) (void)hipStreamWaitEvent(s, c->lane_done[i], 0);
-        for (auto &t : tms) {
-            tm.recs.insert(tm.recs.end(), t.recs.begin(), t.recs.end());
-            t.recs.clear();
-        }
-        return;
-    }
-    const double nrows_aux = (double)g.naux;
-    const double lazy_frac =
-        (g.toep && p0.n_fill_single > 0 && !mixed) ? std::min(1.0, (double)p0.n_fill_single / bc) : 0.0;
-    bool ahead_pending = false;
-    // An odd number of block columns: column 0 goes alone (a FULL step without a k-loop: only the
-    // solve) and the pairs start at column 1.  Pairing from column 0 leaves the LAST column alone,
-    // whose FULL step carries the longest k-loop of the sweep on the direct-load kernel (gradient
-    // jobs at n = 2049, 33 block columns: 62 MB of reads per item and 3.7 % of the call).
-    const int o = (g.nb0 >= 3 && (g.nb0 & 1)) ? 1 : 0;
+    if (two_lane(g, bc, mixed, half) && ln.main == ln.ctx->stream && ln.ctx->make_lanes(ngp_ctx::MAX_LANES))
+        return factor_chunk_lanes(ln, g, p0, bc, tm, dinv_step, sp, order_buf, order_prev);
+    const double lazy_frac = lazy_fraction(g, p0.n_fill_single, bc, mixed);
     for (int jj = 0; jj < g.nb0; ++jj) {
-        const bool fat = jj >= o && ((jj - o) % 2 == 0) && (jj + 1 < g.nb0);
-        const bool thin = jj >= o && ((jj - o) % 2 == 1);
-        const int mode = fat ? COL_FAT : (thin ? COL_THIN : COL_FULL);
-        const int ahead = (fat && jj + 2 < g.nb0) ? 1 : 0;
-        const int k0_col = thin ? (jj - 1) * NB : 0;
-        // diag tile (jj,jj): second column of a pair: pre-accumulated over k < 64 (jj-1) by the fat
-        // step jj-1; first column of the second pair on: over k < 64 (jj-2) by its diag-ahead tile
-        const int k0_diag = thin ? (jj - 1) * NB : (jj - o >= 2 ? (jj - 2) * NB : 0);
-        const double k = (double)jj * NB;
-        const double kd = k - k0_diag;
+        const ColStepPlan st = col_step(g, jj);
         ChunkPtrs p = p0;
         p.dinv = p0.dinv + (size_t)jj * dinv_step;
-        // the diag-ahead tile (jj, jj) was launched on the side stream at step jj-2, beside
-        // diag(jj-1) / col(jj-1); chol_diag(jj) is its only consumer
-        if (ahead_pending && ((jj - o) % 2 == 0)) {
-            (void)hipStreamWaitEvent(s, ln.join, 0);
-            ahead_pending = false;
-        }
-        // Small chunks (the 64-particle calls of a fit): the diag-ahead tile of this pair goes to
-        // the side stream BEFORE chol_diag / the fat step — everything it reads (rows of block
-        // jj + 2, columns < 64 jj) is final once column jj - 1 is.  Beside the fat step it has
-        // several hundred microseconds to hide in; launched after it (the large-batch order below)
-        // its single-wave k-loop outlasts chol_diag + the thin step from n ~ 1500 on and
-        // chol_diag(jj + 2) waits for it.  The order of launches does not change any result.
-        const bool ahead_early = bc <= AHEAD_EARLY_MAX_ITEMS;
+        if (st.join) (void)hipStreamWaitEvent(s, ln.join, 0);   // chol_diag(jj) is the tile's only consumer
         auto launch_ahead = [&] {
             (void)hipEventRecord(ln.fork, s);
             (void)hipStreamWaitEvent(ln.side, ln.fork, 0);
-            // class 8: on the side stream
-            tm.run(8, bc * (double)NB * NB * k, bc * 8.0 * NB * k,
-                   [&] { launch_diag_ahead(g, p0, bc, jj, ln.side); }, ln.side);
+            tm.run(cost_ahead(bc, jj), [&] { launch_diag_ahead(g, p0, bc, jj, ln.side); }, ln.side);
             (void)hipEventRecord(ln.join, ln.side);
-            ahead_pending = true;
         };
-        if (ahead && jj > 0 && ahead_early) launch_ahead();
-        tm.run(1, bc * ((double)NB * NB * kd + (double)NB * NB * NB / 3.0),
-               bc * 8.0 * (NB * kd + 2.0 * NB * NB),
-               [&] { launch_chol_diag(g, p, bc, jj, k0_diag, s); });
-        // rows that take part and the k-products they carry.  Gradient jobs (aux rows [I ; y']):
-        // identity tile a joins from block column a on and its k-loop starts at 64 a — the kernels
-        // skip the rest, so it is not counted either
-        double rows = (double)(g.n0 - (jj + 1) * NB) + nrows_aux;
-        const double kc = k - k0_col;
-        double rows_kc = rows * kc;
-        if (g.aux_identity) {
-            rows = (double)(g.n0 - (jj + 1) * NB) + (double)(g.naux - g.n0);   // main rows + y'
-            rows_kc = rows * kc;
-            for (int a = 0; a <= jj && a < g.nb0; ++a) {
-                rows += NB;
-                rows_kc += NB * std::max(0.0, k - std::max((double)k0_col, (double)a * NB));
-            }
-        }
-        double fl = 2.0 * NB * rows_kc + rows * (double)NB * NB;
-        double by = 8.0 * (rows_kc + NB * kc + 2.0 * rows * NB);
-        if (fat) {  // + column jj+1 partial sums from the same rows
-            fl += 2.0 * NB * rows_kc;
-            by += 8.0 * (NB * k + 2.0 * rows * NB);
-        }
-        // Toeplitz jobs: the first step that touches a main tile of a single-table item reads 127
-        // table entries instead of the stored tile (the sibling wave of the first row tile works
-        // on the stored diagonal tile)
-        if (lazy_frac > 0.0 && (fat || (mode == COL_FULL && jj == 0))) {
-            const double rm = (double)(g.n0 - (jj + 1) * NB);
-            by -= lazy_frac * 8.0 * NB * (rm + (fat ? std::max(0.0, rm - NB) : 0.0));
-        }
-        // class 0: the LDS-DMA kernel of the fat steps (the dominant kernel, the roofline figure);
-        // class 12: its gradient-geometry instantiation (aux rows [I ; y'], <.., IDENT>: another
-        // kernel with its own flops, bytes and rate); class 6: the direct-load kernel of the thin /
-        // full steps
-        tm.run(fat ? (mixed ? 9 : (g.aux_identity ? 12 : 0)) : 6, bc * fl, bc * by,
-               [&] { launch_chol_col(g, p, bc, jj, mode, k0_col, s, sp); });
-        if (mixed && fat && order_buf && jj >= 8 && jj % MIXED_REORDER == 8) {
+        if (st.ahead && ahead_early(bc)) launch_ahead();
+        tm.run(cost_diag(bc, jj, st.k0_diag), [&] { launch_chol_diag(g, p, bc, jj, st.k0_diag, s); });
+        tm.run(cost_col(g, bc, jj, st.mode, st.k0_col, mixed, lazy_frac),
+               [&] { launch_chol_col(g, p, bc, jj, st.mode, st.k0_col, s, sp); });
+        if (mixed && st.mode == COL_FAT && order_buf && jj >= 8 && jj % MIXED_REORDER == 8) {
             // p0.order stays null (dispatch order) unless the ranking was really launched:
             // order_buf comes from the caching allocator uninitialised
             if (launch_mixed_order(p0, order_prev, order_buf, bc, s)) p0.order = order_buf;
         }
-        // large chunks: beside chol_diag(jj+1) / the thin step of jj+1 (beside the fat step it
-        // cost more: profiles/r02/README.md)
-        if (ahead && jj > 0 && !ahead_early) launch_ahead();
-    }
-    if (ahead_pending) {
-        (void)hipStreamWaitEvent(s, ln.join, 0);
-        ahead_pending = false;
+        if (st.ahead && !ahead_early(bc)) launch_ahead();
     }
 }
 
-// stage_general keeps a staging buffer up to this size with the job instead of waiting for the copy;
-// ngp_job_fetch brings a result region up to FETCH_PACKED_BYTES back in one copy
-constexpr size_t STAGE_KEEP_BYTES = (size_t)4 << 20, FETCH_PACKED_BYTES = (size_t)1 << 20;
+// Small chunks of long series (the 64-particle calls of a fit) are swept as two half-chunks side
+// by side, each on its own pair of streams (lanes).  A launch of such a chunk rarely fills the chip or
+// fills it one and a fraction times (64 items at n = 2048: 576 workgroups on 512 slots at
+// column 14 — two rounds for the price of 1.1), and chol_diag / the thin step leave it almost
+// empty: the other half's fat step runs in those gaps.  Every item's arithmetic is what it
+// would be in a chunk of its half's size.
+void factor_chunk_lanes(const Lane &ln, const JobGeom &g, const ChunkPtrs &p0, int bc, EventTimer &tm,
+                        size_t dinv_step, const DevSpec *sp, int32_t *order_buf, unsigned *order_prev) {
+    ngp_ctx *c = ln.ctx;
+    const int nl = ngp_ctx::MAX_LANES;
+    (void)hipEventRecord(c->ev_lane_go, ln.main);
+    std::vector<EventTimer> tms;
+    tms.reserve((size_t)nl);
+    int h0 = 0;
+    for (int i = 0; i < nl; ++i) {
+        const int h1 = (int)((long)bc * (i + 1) / nl);
+        ChunkPtrs pi = p0;
+        pi.L += (size_t)h0 * g.item_stride;
+        pi.dinv += (size_t)h0 * NB * NB;
+        pi.progs += h0;
+        pi.logdet += h0;
+        pi.info += h0;
+        if (pi.tab) pi.tab += (size_t)h0 * g.maxstat * g.R;   // read by the column kernels (toep)
+        pi.n_fill_single = (int32_t)((long)p0.n_fill_single * (h1 - h0) / bc);   // byte accounting only
+        if (pi.splitk_part) pi.splitk_part += (size_t)h0 * SPLITK_SLOTS * 4 * 64 * 64;
+        if (i == 0) {
+            factor_chunk(ln, g, pi, h1 - h0, tm, dinv_step, sp, order_buf, order_prev, true);
+        } else {
+            const Lane li = lane_of(c, i);
+            tms.emplace_back(tm.on, li.main);
+            (void)hipStreamWaitEvent(li.main, c->ev_lane_go, 0);
+            factor_chunk(li, g, pi, h1 - h0, tms.back(), dinv_step, sp, order_buf, order_prev, true);
+            (void)hipEventRecord(c->lane_done[i], li.main);
+        }
+        h0 = h1;
+    }
+    for (int i = 1; i < nl; ++i) (void)hipStreamWaitEvent(ln.main, c->lane_done[i], 0);
+    for (auto &t : tms) {
+        tm.recs.insert(tm.recs.end(), t.recs.begin(), t.recs.end());
+        t.recs.clear();
+    }
+}
 
 template <class T> ngp_status job_alloc(ngp_job *j, T **p, size_t count) {
     void *v = nullptr;
@@ -1054,10 +976,7 @@ ngp_status stage_general(ngp_ctx *c, int P, const ngp_kernel *kernels, int n, co
     HIPCHK(hipSetDevice(c->device));
     g.invariant = c->invariant ? 1 : 0;
     g.short_series = c->short_series ? 1 : 0;
-    // (short series are factorised from registers in one launch and store every tile)
-    if (c->toeplitz && c->spec.precision != NGP_PREC_MIXED &&
-        !(g.short_series && g.nb0 <= 4 && (P <= SM_MAX_ITEMS || g.invariant)))
-        g.toep = toep_stride;
+    if (stores_structured(g, P, c->toeplitz, c->spec.precision)) g.toep = toep_stride;
     ngp_job *j = new (std::nothrow) ngp_job();
     if (!j) return NGP_ERR_TOO_LARGE;
     j->ctx = c;
@@ -1180,6 +1099,54 @@ ngp_status stage_general(ngp_ctx *c, int P, const ngp_kernel *kernels, int n, co
 
 namespace {
 
+// what the epilogue reads and writes, from a staged job (tab / sig / qpts: the caller's, when resident)
+EpiPtrs epi_ptrs_of(const ngp_job &j) {
+    EpiPtrs e{};
+    e.progs = j.progs;
+    e.taux = j.taux;
+    e.G = j.G;
+    e.ya = j.ya;
+    e.logdet = j.logdet;
+    e.info = j.info;
+    e.work = j.work;
+    e.zbuf = j.zbuf;
+    e.logml_base = j.logml_base;
+    e.logml_full = j.logml_full;
+    e.mu = j.mu;
+    e.sigma = j.sigma;
+    e.work_stride = j.work_stride;
+    return e;
+}
+
+// the share of chunk [b0, b0 + bc) in one of a job's fill lists (ascending job-wide indices; dev: its
+// device copy)
+void fill_share(const std::vector<int32_t> &v, const int32_t *dev, int b0, int bc, const int32_t **ptr,
+                int32_t *cnt) {
+    const auto lo = std::lower_bound(v.begin(), v.end(), b0);
+    const auto hi = std::lower_bound(v.begin(), v.end(), b0 + bc);
+    *ptr = dev + (lo - v.begin());
+    *cnt = (int32_t)(hi - lo);
+}
+template <class Job>
+void fill_shares(const Job &j, const int32_t *single_d, const int32_t *chain_d, const int32_t *other_d,
+                 int b0, int bc, ChunkPtrs *p) {
+    fill_share(j.fill_single, single_d, b0, bc, &p->fill_single, &p->n_fill_single);
+    fill_share(j.fill_chain, chain_d, b0, bc, &p->fill_chain, &p->n_fill_chain);
+    fill_share(j.fill_other, other_d, b0, bc, &p->fill_other, &p->n_fill_other);
+    p->fill_base = b0;
+}
+
+// One attempt at a run's working storage: `layout` is walked twice through the same sequence of
+// requests (WsPlan), once to add the sizes up and reserve the workspace in one piece, once to take
+// the pieces.  NGP_ERR_TOO_LARGE: the caller cuts its chunk (each by its own policy) and tries again.
+template <class Layout> ngp_status ws_layout(ngp_ctx *c, Layout &&layout) {
+    WsPlan measure{c, true}, take{c, false};
+    (void)layout(measure);
+    ngp_status st = c->ws_reserve(measure.total);
+    if (!st) st = layout(take);
+    return st;
+}
+
 // Device buffers of the Gram refinement of one chunk (NGP_PREC_MIXED).
 struct RefineBufs {
     double *X = nullptr, *A = nullptr, *R = nullptr;   // [Bc][naux_pad][n0]
@@ -1285,11 +1252,7 @@ extern "C" ngp_status ngp_job_run(ngp_job *j) {
         HIPCHK(hipMemsetAsync(j->info, 0, sizeof(int32_t) * (size_t)g.B, s));
     }
     j->zeroed = false;
-    // mixed precision needs at least one fat step (two block columns); shorter series run fp64, and
-    // so do series of more than 129 block columns (n > 8,319): a fat step classifies its k-tiles
-    // in two 64-bit masks
-    const bool mixed = j->spec.precision == NGP_PREC_MIXED && g.nb0 >= 2 && g.nb0 <= 129 &&
-                       !g.aux_identity;
+    const bool mixed = mixed_eligible(g, j->spec.precision);
     const bool refine = mixed && j->spec.refine_max > 0;
     j->refine_steps.assign((size_t)g.B, 0);
     j->refine_delta.assign((size_t)g.B, 0.0);
@@ -1352,16 +1315,12 @@ extern "C" ngp_status ngp_job_run(ngp_job *j) {
             Bc = (int)(((size_t)g.B + nchunks - 1) / nchunks);
             // refinement sweeps need every block inverse M_j, not only the current one
             mstep = refine ? (size_t)Bc * NB * NB : 0;
-            WsPlan measure{c, true}, take{c, false};
-            (void)take_all(measure);
-            st = c->ws_reserve(measure.total);
-            if (!st) st = take_all(take);
+            st = ws_layout(c, take_all);
             if (st != NGP_ERR_TOO_LARGE || Bc <= 1) break;
         }
         single_chunk = Bc >= g.B;
         if (st) return st;
         const Lane ln = lane_of(c);
-        const double nrows_aux = (double)g.naux;
         for (int b0 = 0; b0 < g.B; b0 += Bc) {
             const int bc = std::min(Bc, g.B - b0);
             ChunkPtrs p{};
@@ -1376,19 +1335,8 @@ extern "C" ngp_status ngp_job_run(ngp_job *j) {
             p.tab = (double *)tab;
             p.sig = (double *)sig;
             p.qpts = j->qpts;
-            if (j->fill_other_d) {   // the chunk's share of the two item lists
-                auto range = [&](const std::vector<int32_t> &v, const int32_t *dev,
-                                 const int32_t **ptr, int32_t *cnt) {
-                    const auto lo = std::lower_bound(v.begin(), v.end(), b0);
-                    const auto hi = std::lower_bound(v.begin(), v.end(), b0 + bc);
-                    *ptr = dev + (lo - v.begin());
-                    *cnt = (int32_t)(hi - lo);
-                };
-                range(j->fill_chain, j->fill_chain_d, &p.fill_chain, &p.n_fill_chain);
-                range(j->fill_other, j->fill_other_d, &p.fill_other, &p.n_fill_other);
-                range(j->fill_single, j->fill_single_d, &p.fill_single, &p.n_fill_single);
-                p.fill_base = b0;
-            }
+            if (j->fill_other_d)
+                fill_shares(*j, j->fill_single_d, j->fill_chain_d, j->fill_other_d, b0, bc, &p);
             if (mixed) {
                 p.L32 = (float *)L32;
                 p.tmax = (float *)tmx;
@@ -1398,11 +1346,7 @@ extern "C" ngp_status ngp_job_run(ngp_job *j) {
             }
             if (g.lattice)
                 tm.run(4, 0.0, 0.0, [&] { launch_tables(g, p, bc, sp, s); });
-            // Toeplitz jobs: single-table items store their diagonal tiles and aux rows only
-            const double fill_elems =
-                (double)bc * ((double)g.n0 * (g.n0 + NB) / 2.0 + nrows_aux * g.n0) -
-                (g.toep ? (double)p.n_fill_single * ((double)g.n0 * (g.n0 - NB) / 2.0) : 0.0);
-            tm.run(4, 0.0, 8.0 * fill_elems, [&] { launch_fill(g, p, bc, sp, s); });
+            tm.run(cost_fill(g, bc, p.n_fill_single), [&] { launch_fill(g, p, bc, sp, s); });
             if (mixed) HIPCHK(hipMemsetAsync(order_prev, 0, 4 * (size_t)bc, s));
             double *Gchunk = j->G + (int64_t)b0 * g.naux * g.naux;
             // short jobs: the one launch of the factorisation leaves G too
@@ -1411,8 +1355,7 @@ extern "C" ngp_status ngp_job_run(ngp_job *j) {
             factor_chunk(ln, g, p, bc, tm, mstep, mixed ? &sp : nullptr, (int32_t *)order_buf,
                          (unsigned *)order_prev);
             if (!gram_inside)
-                tm.run(2, bc * nrows_aux * nrows_aux * g.n0, bc * 8.0 * nrows_aux * g.n0,
-                       [&] { launch_gram(g, (const double *)Lbuf, Gchunk, bc, s); });
+                tm.run(cost_gram(g, bc), [&] { launch_gram(g, (const double *)Lbuf, Gchunk, bc, s); });
             if (mixed) {
                 std::vector<unsigned> hc(2 * (size_t)bc);
                 HIPCHK(hipMemcpyAsync(hc.data(), cnt, 8 * (size_t)bc, hipMemcpyDeviceToHost, s));
@@ -1439,20 +1382,7 @@ extern "C" ngp_status ngp_job_run(ngp_job *j) {
             }
         }
     }
-    EpiPtrs e{};
-    e.progs = j->progs;
-    e.taux = j->taux;
-    e.G = j->G;
-    e.ya = j->ya;
-    e.logdet = j->logdet;
-    e.info = j->info;
-    e.work = j->work;
-    e.zbuf = j->zbuf;
-    e.logml_base = j->logml_base;
-    e.logml_full = j->logml_full;
-    e.mu = j->mu;
-    e.sigma = j->sigma;
-    e.work_stride = j->work_stride;
+    EpiPtrs e = epi_ptrs_of(*j);
     // (batch-invariant jobs evaluate the small Schur blocks directly, whatever the number of chunks)
     if (g.lattice && single_chunk && !g.invariant) {   // the tables of the only chunk are still in place
         e.tab = (const double *)tab;
@@ -1679,14 +1609,12 @@ ngp_status factor_run(ngp_factor *f, ngp_job *j, bool create) {
         p.tab = (double *)tab;
         p.sig = (double *)sig;
         p.qpts = j->qpts;
-        const double nrows_aux = (double)g.naux;
         const size_t mstep = (size_t)P * NB * NB;
         if (g.lattice) tm.run(4, 0.0, 0.0, [&] { launch_tables(g, p, P, sp, s); });
         if (create) {
             HIPCHK(hipMemsetAsync(j->logdet, 0, sizeof(double) * (size_t)P, s));
             HIPCHK(hipMemsetAsync(j->info, 0, sizeof(int32_t) * (size_t)P, s));
-            tm.run(4, 0.0, 8.0 * P * ((double)g.n0 * (g.n0 + NB) / 2.0 + nrows_aux * g.n0),
-                   [&] { launch_fill(g, p, P, sp, s); });
+            tm.run(cost_fill(g, P, 0), [&] { launch_fill(g, p, P, sp, s); });
             factor_chunk(lane_of(c), g, p, P, tm, mstep);
             HIPCHK(hipMemcpyAsync(f->logdet, j->logdet, sizeof(double) * (size_t)P,
                                   hipMemcpyDeviceToDevice, s));
@@ -1697,39 +1625,21 @@ ngp_status factor_run(ngp_factor *f, ngp_job *j, bool create) {
                                   hipMemcpyDeviceToDevice, s));
             HIPCHK(hipMemcpyAsync(j->info, f->info, sizeof(int32_t) * (size_t)P,
                                   hipMemcpyDeviceToDevice, s));
-            tm.run(4, 0.0, 8.0 * P * nrows_aux * g.n0,
-                   [&] { launch_fill(g, p, P, sp, s, /*aux_only=*/true); });
+            tm.run(cost_fill_aux(g, P), [&] { launch_fill(g, p, P, sp, s, /*aux_only=*/true); });
             // right-looking sweep of the aux rows through the resident factor
             for (int jj = 0; jj < g.nb0; ++jj) {
                 ChunkPtrs pj = p;
                 pj.dinv = f->dinv + (size_t)jj * mstep;
-                tm.run(6, P * nrows_aux * (double)NB * NB, P * 8.0 * 3.0 * nrows_aux * NB,
-                       [&] { launch_chol_col(g, pj, P, jj, COL_AUX, jj * NB, s); });
-                tm.run(7, P * nrows_aux * 2.0 * NB * (double)(g.n0 - (jj + 1) * NB),
-                       P * 8.0 * (g.n0 - (jj + 1) * NB) * (2.0 * nrows_aux + NB),
-                       [&] { launch_aux_update(g, pj, P, jj, s); });
+                tm.run(cost_aux_solve(g, P), [&] { launch_chol_col(g, pj, P, jj, COL_AUX, jj * NB, s); });
+                tm.run(cost_aux_update(g, P, jj), [&] { launch_aux_update(g, pj, P, jj, s); });
             }
         }
-        tm.run(2, P * nrows_aux * nrows_aux * g.n0, P * 8.0 * nrows_aux * g.n0,
-               [&] { launch_gram(g, f->L, j->G, P, s); });
+        tm.run(cost_gram(g, P), [&] { launch_gram(g, f->L, j->G, P, s); });
     } else {
         HIPCHK(hipMemsetAsync(j->logdet, 0, sizeof(double) * (size_t)P, s));
         HIPCHK(hipMemsetAsync(j->info, 0, sizeof(int32_t) * (size_t)P, s));
     }
-    EpiPtrs e{};
-    e.progs = j->progs;
-    e.taux = j->taux;
-    e.G = j->G;
-    e.ya = j->ya;
-    e.logdet = j->logdet;
-    e.info = j->info;
-    e.work = j->work;
-    e.zbuf = j->zbuf;
-    e.logml_base = j->logml_base;
-    e.logml_full = j->logml_full;
-    e.mu = j->mu;
-    e.sigma = j->sigma;
-    e.work_stride = j->work_stride;
+    EpiPtrs e = epi_ptrs_of(*j);
     if (g.lattice && g.n0 > 0) {
         e.tab = (const double *)tab;
         e.sig = (const double *)sig;
@@ -2161,7 +2071,7 @@ struct LeafRun {
         const JobGeom &g = j->g;
         const int B = j->B;
         const bool tp = j->toep_path;
-        const int GP = NGP_MAX_PARAMS + 1, ntri = g.nb0 * (g.nb0 + 1) / 2, nd = (g.n_real + 255) / 256;
+        const int GP = NGP_MAX_PARAMS + 1;
         hipStream_t s = ln.main;
         const DevSpec sp = dev_spec(j->spec);
         h_items.assign((size_t)B, 0);
@@ -2203,43 +2113,25 @@ struct LeafRun {
             p.qpts = (const int32_t *)d_q;
             p.dtab = (double *)d_dtab;
             p.splitk_part = splitk;
-            if (g.lattice) {   // the chunk's share of the three fill lists
-                auto range = [&](const std::vector<int32_t> &v, size_t off, const int32_t **ptr, int32_t *cnt) {
-                    const auto lo = std::lower_bound(v.begin(), v.end(), b0);
-                    const auto hi = std::lower_bound(v.begin(), v.end(), b0 + bc);
-                    *ptr = (const int32_t *)(io + off) + (lo - v.begin());
-                    *cnt = (int32_t)(hi - lo);
-                };
-                range(j->fill_single, j->o_fs, &p.fill_single, &p.n_fill_single);
-                range(j->fill_chain, j->o_fc, &p.fill_chain, &p.n_fill_chain);
-                range(j->fill_other, j->o_fo, &p.fill_other, &p.n_fill_other);
-                p.fill_base = b0;
-            }
+            if (g.lattice)
+                fill_shares(*j, (const int32_t *)(io + j->o_fs), (const int32_t *)(io + j->o_fc),
+                            (const int32_t *)(io + j->o_fo), b0, bc, &p);
             if (g.lattice) tm.run(4, 0.0, 0.0, [&] { launch_tables(g, p, bc, sp, s); });
-            // K's lower blocks, the y' tile row and the zero blocks (a, a-1): the identity block of
-            // the aux rows is synthesised by the column kernels, not written
-            tm.run(4, 0.0,
-                   8.0 * bc * ((double)g.n0 * (g.n0 + NB) / 2.0 + (tp ? 1.0 : 2.0) * NB * (double)g.n0),
-                   [&] { launch_fill(g, p, bc, sp, s); });
+            tm.run(cost_fill_grad(g, bc, tp), [&] { launch_fill(g, p, bc, sp, s); });
             const size_t mstep = tp ? (size_t)bc * NB * NB : 0;
             factor_chunk(ln, g, p, bc, tm, mstep, nullptr, nullptr, nullptr, no_lane_split);
-            const double n3 = (double)g.n0 * g.n0 * g.n0;
             if (tp) {
-                // z'z, then A = X K^-1 by one backward sweep of the two aux rows (class 10 with the
-                // other backward sweeps of the library)
-                tm.run(10, 0.0, bc * 8.0 * g.n0,
+                // z'z, then A = X K^-1 by one backward sweep of the two aux rows
+                tm.run(cost_toep_quad(g, bc),
                        [&] { launch_toep_quad(g, (const double *)d_L, (double *)d_quad, bc, s); });
                 for (int cc = g.nb0 - 1; cc >= 0; --cc)
-                    tm.run(10, bc * 2.0 * 2.0 * NB * (double)(cc + 1) * NB,
-                           bc * 8.0 * ((double)NB * NB * (cc + 1) + 2.0 * 2.0 * NB * (cc + 1)), [&] {
-                               launch_aux_back(g, p, p.dinv, mstep, (double *)d_kinv, 0, bc, cc, s);
-                           });
+                    tm.run(cost_toep_back(bc, cc), [&] {
+                        launch_aux_back(g, p, p.dinv, mstep, (double *)d_kinv, 0, bc, cc, s);
+                    });
             } else {
-                // short jobs (factor_chunk's rule), and small chunks of series up to 448 points on the
-                // column sweep: its W_I has the same entries where the 16 x 16-block kernel reads them
-                const bool short_job = small_job(g, bc) || (g.nb0 < 8 && bc <= AHEAD_EARLY_MAX_ITEMS && !g.invariant);
-                tm.run(5, bc * n3 / 3.0, bc * 8.0 * 1.5 * (double)g.n0 * g.n0, [&] {
-                    if (short_job)
+                const bool kinv_small = kinv_route(g, bc) == KINV_SMALL;
+                tm.run(cost_kinv(g, bc), [&] {
+                    if (kinv_small)
                         launch_grad_kinv_small(g, (const double *)d_L, (double *)d_kinv, (double *)d_alpha,
                                                (double *)d_quad, bc, s);
                     else
@@ -2249,12 +2141,7 @@ struct LeafRun {
             }
             // the chunk's items sorted by tree size: every size class runs on the contraction kernel
             // sized for it
-            // (small launches — the 24- or 64-particle calls of a fit on short series — stay ONE launch
-            // sized by the largest tree: up to five dependent launches of a few microseconds each cost
-            // more there than the occupancy of the smaller instantiations gains)
-            // (batch-invariant jobs: always — an item then runs on the instantiation of ITS tree size,
-            // not on the one the largest tree of its batch picks)
-            const bool by_size = g.lattice && (g.invariant || (tp ? (long)nd * bc > 512 : (long)ntri * bc > 4096));
+            const bool by_size = contract_by_size(g, tp, bc);
             int32_t counts[GRAD_BUCKETS] = {};
             if (by_size) {
                 for (int i = 0; i < bc; ++i) ++counts[grad_bucket(j->n_ops[(size_t)(b0 + i)])];
@@ -2267,14 +2154,14 @@ struct LeafRun {
                 if (ce != hipSuccess) return (ngp_status)ce;
             }
             if (tp) {
-                tm.run(11, 0.0, bc * 8.0 * 3.0 * (double)g.n0, [&] {
+                tm.run(cost_toep_grad(g, bc), [&] {
                     launch_toep_grad(g, p, (const double *)d_kinv, (double *)d_alpha,
                                      (const double *)d_quad, (double *)d_part,
                                      (double *)d_grad + (int64_t)b0 * GP, (double *)d_logml + b0, bc, sp,
                                      s, by_size ? (const int32_t *)d_items + b0 : nullptr, counts);
                 });
             } else {
-                tm.run(11, 0.0, bc * 8.0 * 0.5 * (double)g.n0 * g.n0, [&] {
+                tm.run(cost_contract(g, bc), [&] {
                     launch_grad_contract(g, p, (const double *)d_kinv, (const double *)d_alpha,
                                          (const double *)d_quad, (double *)d_part,
                                          (double *)d_grad + (int64_t)b0 * GP, (double *)d_logml + b0,
@@ -2320,10 +2207,7 @@ ngp_status grad_leaf_run(GradLeaf *j, double *logml, double *grad, int32_t *info
                                  std::max<size_t>(1, c->mem_cap / item_bytes));
     // the chunk is halved when the device cannot hold it after all (other handles, rounding)
     for (;; r.Bc = (r.Bc + 1) / 2) {
-        WsPlan measure{c, true}, take{c, false};
-        (void)r.layout(measure);
-        ngp_status st = c->ws_reserve(measure.total);
-        if (!st) st = r.layout(take);
+        const ngp_status st = ws_layout(c, [&](WsPlan &w) { return r.layout(w); });
         if (!st) break;
         if (st != NGP_ERR_TOO_LARGE || r.Bc <= 1) return st;
     }
@@ -2364,11 +2248,10 @@ ngp_status grad_pair_run(GradLeaf *a, double *lm_a, double *g_a, int32_t *info_a
     if ((st = ra.layout(take)) || (st = rb.layout(take))) return st;
     // the Toeplitz leaf runs on the value kernels: their split-k fat steps of late columns (small
     // chunks) need the context's buffer, which factor_chunk only reserves for a chunk it owns whole
-    if (b->toep_path && b->g.nb0 >= 8 && b->B <= AHEAD_EARLY_MAX_ITEMS && !b->g.invariant &&
-        c->splitk_reserve(b->B) == NGP_OK)
+    if (b->toep_path && splitk_eligible(b->g, b->B, false, false) && c->splitk_reserve(b->B) == NGP_OK)
         rb.splitk = c->splitk_part;
     const Lane l0 = lane_of(c);
-    const Lane l1{c->lane_main[1], c->lane_side[1], c->lane_fork[1], c->lane_join[1], c};
+    const Lane l1 = lane_of(c, 1);
     // what the context's stream holds (the staging copies of both leaves) comes first on lane 1 too
     (void)hipEventRecord(c->ev_lane_go, c->stream);
     (void)hipStreamWaitEvent(l1.main, c->ev_lane_go, 0);
@@ -2464,12 +2347,7 @@ static ngp_status grad_stage_impl(ngp_ctx *c, int32_t B, const ngp_kernel *kerne
     }
     const bool on = route.toeplitz, invariant = route.invariant, short_series = route.short_series;
     const double jitter = route.spec.jitter;
-    // (series of up to 256 points: the general leaf factorises them in one launch,
-    // ngp_small_kernels.h — shorter than the Toeplitz leaf's chain of sweeps)
-    // (batches beyond what the one-launch path takes, SM_MAX_ITEMS, keep the Toeplitz leaf: there it is
-    // the faster one — 8,192 stationary items at n = 208: 14.8 against 21.3 ms; batch-invariant contexts
-    // route by the series alone)
-    if (on && n >= 2 * NB && n <= 8192 && !(short_series && n <= 4 * NB && (B <= SM_MAX_ITEMS || invariant))) {
+    if (toep_grad_series(n, B, on, short_series, invariant)) {
         std::vector<double> real(t, t + n);
         std::vector<int32_t> q;
         double hh = 0.0;
@@ -2509,24 +2387,12 @@ static ngp_status grad_stage_impl(ngp_ctx *c, int32_t B, const ngp_kernel *kerne
         }
         (stationary ? j->idx_toep : j->idx_gen).push_back(i);
     }
-    // A batch that is split runs its two leaves one after the other: two chains of dependent launches
-    // instead of one.  That pays when the leaves are throughput-bound (12,800 items at n = 2049:
-    // 2,615 -> 1,794 ms) and costs when they are latency-bound (24 items at n = 208: 615 -> 790 us; 64 at
-    // n = 2048: 15.9 -> 16.3 ms), so a mixed batch is split only from SPLIT_MIN_ITEMS on; a batch
-    // of stationary trees only is never split and always takes the Toeplitz path.
-    // Just below that (PAIR_MIN_ITEMS .. SPLIT_MIN_ITEMS, long series) the two leaves run SIDE BY SIDE
-    // on two stream pairs (grad_pair_run); smaller mixed batches are not split at all.  Measured on
-    // the prior ensemble at n = 2048, general job -> split: 64 items 15.1 -> 17.2 ms side by side
-    // (each leaf's chain is as long as the whole batch's, and they compete for the chip), 128 items
-    // 26.8 -> 25.0 side by side, 256 items 50.2 -> 40.0 and 512 items 98.8 -> 72.0 in turn
-    // (scripts/mixed_grad_probe.py).
-    constexpr int SPLIT_MIN_ITEMS = 256, PAIR_MIN_ITEMS = 128, PAIR_MIN_N = 1024;
-    // (batch-invariant contexts route by the item alone: a stationary tree on a regular series
-    // always takes the Toeplitz leaf, whatever travels with it)
-    if (!j->idx_gen.empty() && !j->idx_toep.empty() && B < SPLIT_MIN_ITEMS) {
-        if (invariant || (n >= PAIR_MIN_N && B >= PAIR_MIN_ITEMS)) {
+    // a mixed batch: both leaves in turn, side by side, or everything on the general leaf
+    if (!j->idx_gen.empty() && !j->idx_toep.empty()) {
+        const GradBatchRoute br = grad_batch_route(B, n, invariant);
+        if (br == GRAD_PAIR) {
             j->side_by_side = true;
-        } else {
+        } else if (br == GRAD_UNSPLIT) {
             j->idx_toep.clear();
             j->idx_gen.resize((size_t)B);
             for (int i = 0; i < B; ++i) j->idx_gen[(size_t)i] = i;

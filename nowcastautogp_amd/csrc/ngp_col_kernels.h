@@ -1498,16 +1498,9 @@ void launch_chol_col_t(const JobGeom &g, const ChunkPtrs &p, int Bc, int j, int 
         st.groups = (st.ntiles + 1) / 2;
         const dim3 grid(st.groups * bpad);
         // small batches: late columns (few tile pairs, long k-loops) are cut along k so that the
-        // launch fills the chip; every piece keeps at least 8 staged chunks
+        // launch fills the chip (splitk_count, ngp_plan.h)
         int splits = 1;
-        if (!mixed && !g.aux_identity && p.splitk_part) {
-            const int nchunks = j * NB / LDS_KC;
-            // 384, not the 512 workgroups the chip holds: chol_diag's successor tile (diag_ahead,
-            // 4 waves of 224 VGPRs) is resident beside this launch and a second round costs more
-            // than the split saves (measured at 64 items, n = 2048)
-            splits = std::min(std::min(8, SPLITK_SLOTS / std::max(st.groups, 1)),
-                              std::min(nchunks / 8, 384 / std::max(st.groups * Bc, 1)));
-        }
+        if (!mixed && !g.aux_identity && p.splitk_part) splits = splitk_count(st.groups, j * NB / LDS_KC, Bc);
         st.splits = std::max(splits, 1);
         if (splits >= 2) {
             hipLaunchKernelGGL((chol_col_glds_kernel<false, Probe, false, 1>),

@@ -179,7 +179,6 @@ constexpr int SM_NSLOT = 20;           // register blocks per wave (8 VGPRs each
 constexpr int SM_DSTR = 17;            // row stride of a diagonal block in LDS (doubles)
 constexpr int SM_MAX_PANEL = 34;       // panel blocks of one step: main rows + the sweep's aux row-blocks
 constexpr int SM_MAX_SWEEPS = 4;
-constexpr int SM_MAX_ITEMS = 4096;      // larger chunks fill the chip on the column sweep (measured: 24 x n = 208 scenarios x particles up to 4,096 items win here, 8,192 gradient items lose)
 
 // One sweep over the block columns.  Aux row-blocks taken along: identity rows [i0, i1) (gradient
 // jobs: row-block a is e_(16a..16a+15)', it joins at column a and stays upper triangular) and dense
@@ -202,74 +201,14 @@ struct SmallPlan {
 constexpr int SM_LDS_FIXED = 8 * (16 * 256 + 16 * 16 * SM_DSTR + 256 + 32);   // M_j | diagonal blocks | pivots | flags
 inline int small_lds_bytes(const SmallPlan &pl) { return SM_LDS_FIXED + pl.npanel * 2048; }
 
-// The plan of a geometry, or false when the column sweep has to do it (n0 > 256, structured
-// storage, the Toeplitz gradient path, more aux rows than four sweeps hold).
-inline bool small_plan(const JobGeom &g, SmallPlan *pl) {
-    if (g.n0 <= 0 || g.nb0 > 4 || g.aux_e1 || g.toep) return false;
-    const int nb16 = g.n0 / 16, nbe = (g.n_real + 15) / 16;
-    if (nbe < 1 || nbe > nb16) return false;
-    const int cap_main = (SM_WAVES - 1) * SM_NSLOT, cap_aux = SM_WAVES * SM_NSLOT;
-    SmallPlan p{};
-    p.nbe = nbe;
-    p.ident = g.aux_identity ? 1 : 0;
-    int used = nbe * (nbe - 1) / 2;
-    if (used > cap_main) return false;
-    int ns = 0, npanel = nbe;
-    if (g.aux_identity) {
-        const int ytile = nb16;                           // slab rows 2 n0 ...: y'
-        if (used + nbe > cap_main) return false;          // (120 + 16 <= 140)
-        p.sw[ns++] = SmallSweep{1, 0, 0, ytile, ytile + 1};
-        p.sw[ns++] = SmallSweep{2, 0, nbe, 0, 0};
-        npanel = std::max(npanel, nbe + 1);
-        // Block column j of L^-1 costs (nbe - j)(nbe - j - 1) / 2 block products, all on one wave.
-        // Longest first, each to the wave whose SIMD (waves w and w + 4 share one) carries least;
-        // of that SIMD's two waves the less loaded one.
-        int load[SM_WAVES] = {};
-        for (int j = 0; j < nbe; ++j) {
-            int best = 0;
-            for (int w = 1; w < SM_WAVES; ++w) {
-                const int sb = load[best % 4] + load[best % 4 + 4], sw_ = load[w % 4] + load[w % 4 + 4];
-                if (sw_ < sb || (sw_ == sb && load[w] < load[best])) best = w;
-            }
-            load[best] += (nbe - j) * (nbe - j - 1) / 2 + 1;
-            p.colwave |= (uint64_t)best << (4 * j);
-        }
-    } else {
-        const int nba = (g.naux + 15) / 16;
-        int a = std::min(nba, (cap_main - used) / nbe);
-        a = std::min(a, SM_MAX_PANEL - nbe);
-        p.sw[ns++] = SmallSweep{1, 0, 0, 0, a};
-        npanel = std::max(npanel, nbe + a);
-        while (a < nba) {
-            if (ns == SM_MAX_SWEEPS) return false;
-            const int b = std::min(nba, a + std::min(cap_aux / nbe, SM_MAX_PANEL - nbe));
-            p.sw[ns++] = SmallSweep{0, 0, 0, a, b};
-            npanel = std::max(npanel, nbe + b - a);
-            a = b;
-        }
-    }
-    if (npanel > SM_MAX_PANEL) return false;
-    p.nsweeps = ns;
-    p.npanel = std::max(npanel, 9);     // (the waves' 16 x 18 staging corners of the prologue: 8 x 2,304 B)
-    *pl = p;
-    return true;
-}
+enum { COL_FULL = 0, COL_FAT = 1, COL_THIN = 2, COL_AUX = 3 };   // launch_chol_col's mode
 
-// the rule every caller shares: the geometry qualifies and the chunk is not one that fills the chip
-// many times over (batch-invariant jobs: the geometry alone decides)
-inline bool small_job(const JobGeom &g, int Bc, SmallPlan *pl = nullptr) {
-    SmallPlan tmp;
-    return g.short_series && small_plan(g, pl ? pl : &tmp) && (Bc <= SM_MAX_ITEMS || g.invariant);
-}
-
-// flops the launch executes per item (factor + the aux rows' solves and updates), for the profile
-inline double small_flops(const JobGeom &g, const SmallPlan &pl) {
-    const double n = 16.0 * pl.nbe;
-    double f = n * n * n / 3.0;
-    if (pl.ident) f += n * n * n / 3.0 + n * n;
-    else f += (double)g.naux * n * n;
-    return f;
-}
+}  // namespace ngp
+// the route rules (small_plan, small_job, the column schedule, every threshold) and the roofline
+// accounting of the launches: host-only headers over the structs above
+#include "ngp_plan.h"
+#include "ngp_cost.h"
+namespace ngp {
 
 void launch_chol_small(const JobGeom &g, const ChunkPtrs &p, int Bc, const SmallPlan &pl, hipStream_t s);
 // K^-1 = W_I W_I', alpha = W_I z and z'z of a short gradient job in one launch (16 x 16 blocks)
@@ -281,7 +220,6 @@ void launch_tables(const JobGeom &g, const ChunkPtrs &p, int Bc, const DevSpec &
 void launch_fill(const JobGeom &g, const ChunkPtrs &p, int Bc, const DevSpec &sp, hipStream_t s,
                  bool aux_only = false);
 void launch_chol_diag(const JobGeom &g, const ChunkPtrs &p, int Bc, int j, int k0, hipStream_t s);
-enum { COL_FULL = 0, COL_FAT = 1, COL_THIN = 2, COL_AUX = 3 };
 // sp: only mixed_tau / jitter are read, and only when p.L32 is set (mixed-precision job)
 void launch_chol_col(const JobGeom &g, const ChunkPtrs &p, int Bc, int j, int mode, int k0,
                      hipStream_t s, const DevSpec *sp = nullptr);
@@ -308,25 +246,14 @@ void launch_grad_kinv(const JobGeom &g, const double *L, double *Kinv, double *a
                       int Bc, hipStream_t s, hipStream_t side = nullptr, hipEvent_t fork = nullptr,
                       hipEvent_t join = nullptr);
 // items / bucket_counts: the chunk's items (chunk-local indices) sorted by tree size into
-// GRAD_BUCKETS groups — at most 1, 2, 4, 8, 16 leaves, larger — and the size of every group;
+// GRAD_BUCKETS groups (grad_bucket, ngp_plan.h) — at most 1, 2, 4, 8, 16 leaves, larger — and the size of every group;
 // null: one launch for the whole chunk, sized by g.maxops
-constexpr int GRAD_BUCKETS = 6;
-inline int grad_bucket(int n_ops) {
-    return n_ops <= 1 ? 0 : n_ops <= 3 ? 1 : n_ops <= 7 ? 2 : n_ops <= 15 ? 3 : n_ops <= 31 ? 4 : 5;
-}
 void launch_grad_contract(const JobGeom &g, const ChunkPtrs &p, const double *Kinv,
                           const double *alpha, const double *quad, double *partials, double *grad,
                           double *logml, int Bc, const DevSpec &sp, hipStream_t s,
                           const int32_t *items = nullptr, const int32_t *bucket_counts = nullptr,
                           hipStream_t side = nullptr, hipEvent_t fork = nullptr,
                           hipEvent_t join = nullptr);
-// workgroups per 64x64 tile of the gradient contraction: small launches are cut finer
-// (batch-invariant jobs: by the geometry alone — the split decides how a thread groups its rows,
-// i.e. the order of a partial sum)
-inline int grad_contract_split(long ntri, long Bc, bool invariant = false) {
-    if (invariant) return ntri <= 36 ? 4 : 1;
-    return ntri * Bc <= 1024 ? 4 : (ntri * Bc <= 2048 ? 2 : 1);
-}
 void launch_toep_grad(const JobGeom &g, const ChunkPtrs &p, const double *A, double *wbuf,
                       const double *quad, double *partials, double *grad, double *logml, int Bc,
                       const DevSpec &sp, hipStream_t s, const int32_t *items = nullptr,

@@ -2712,81 +2712,63 @@ void launch_fill(const JobGeom &g, const ChunkPtrs &p, int Bc, const DevSpec &sp
     // which the k-loops of a tile pair and of K^-1 = W W' read as part of their shared k-range.
     const int ntiles = ntri + (g.aux_identity ? g.nb0 + (g.nb0 - 1) : (g.naux_pad / NB) * g.nb0);
     const int off = aux_only ? ntri : 0;
-    if (g.lattice) {
-        const long nwg = (long)(ntiles - off) * Bc;
-        const int split = nwg <= 1024 ? 4 : (nwg <= 2048 ? 2 : 1);
-        // Short jobs are chains of launches a few microseconds long: ONE fill launch on the general
-        // kernel (reduced / full programs; the chain and single-table kernels compute the same
-        // values, operation for operation) instead of up to three per program shape plus the aux one
-        const bool one_launch = small_job(g, Bc);
-        if (one_launch && p.dtab && !aux_only) {
-            ChunkPtrs q = p;   // gradient job: main tiles only (y' comes from the observations)
-            q.fill_other = nullptr;
-            const long nwg_m = (long)ntri * Bc;
-            const int split_m = nwg_m <= 1024 ? 4 : (nwg_m <= 2048 ? 2 : 1);
-            hipLaunchKernelGGL(fill_lattice_kernel<true>, dim3(ntri * split_m, Bc), dim3(256), 0, s, g, q,
-                               ntri, 0, split_m, sp);
-        } else if (p.dtab && p.fill_other && !aux_only) {
-            // Gradient jobs: the main tiles through the kernels of the value jobs — one lookup for a
-            // stationary tree, chain programs decoded once per thread for sixteen elements, the
-            // rest on the reduced program — reading the subtree tables behind the per-leaf ones;
-            // the values are those of the full program, operation for operation (keval_stat).  The
-            // full-program interpreter decodes every node for every element from LDS: 8 us per item
-            // at n = 2049 against 4.  The aux tiles (y', the zero blocks, e_1') hold no covariance.
-            ChunkPtrs q = p;
-            q.tab = p.tab + (size_t)g.tab_sub * g.R;
-            q.dtab = nullptr;
-            const long nwg_o = (long)ntri * p.n_fill_other;
-            const int split_o = nwg_o <= 1024 ? 4 : (nwg_o <= 2048 ? 2 : 1);
-            if (p.n_fill_other > 0)
-                hipLaunchKernelGGL(fill_lattice_kernel<false>, dim3(ntri * split_o, p.n_fill_other),
-                                   dim3(256), 0, s, g, q, ntri, 0, split_o, sp);
-            if (p.n_fill_chain > 0) {
-                const int tpw = (long)ntri * p.n_fill_chain >= 65536 ? 4 : 1;
-                hipLaunchKernelGGL(fill_chain_kernel, dim3((ntri + tpw - 1) / tpw, p.n_fill_chain), dim3(256),
-                                   0, s, g, q, ntri, sp, ntri, tpw);
-            }
-            if (p.n_fill_single > 0)
-                hipLaunchKernelGGL(fill_single_kernel, dim3(ntri, p.n_fill_single), dim3(256), 0, s, g,
-                                   q, ntri, sp);
-            // (short jobs: chol_small_kernel takes y' from the observations and neither it nor
-            // grad_kinv_small_kernel reads the zero blocks — one launch less in their chain)
-            if (!small_job(g, Bc)) {
-                ChunkPtrs a = p;
-                a.fill_other = nullptr;
-                const long nwg_a = (long)(ntiles - ntri) * Bc;
-                const int split_a = nwg_a <= 1024 ? 4 : (nwg_a <= 2048 ? 2 : 1);
-                hipLaunchKernelGGL(fill_lattice_kernel<true>, dim3((ntiles - ntri) * split_a, Bc), dim3(256),
-                                   0, s, g, a, ntri, ntri, split_a, sp);
-            }
-        } else if (p.dtab) {
-            ChunkPtrs q = p;
-            q.fill_other = nullptr;
-            hipLaunchKernelGGL(fill_lattice_kernel<true>, dim3((ntiles - off) * split, Bc), dim3(256),
-                               0, s, g, q, ntri, off, split, sp);
-        } else if (p.fill_other && !aux_only && !one_launch) {
-            // staged value jobs: chain programs on their own kernel, the rest element by element
-            if (p.n_fill_other > 0)
-                hipLaunchKernelGGL(fill_lattice_kernel<false>, dim3(ntiles * split, p.n_fill_other),
-                                   dim3(256), 0, s, g, p, ntri, 0, split, sp);
-            if (p.n_fill_chain > 0) {
-                const int tpw = (long)ntiles * p.n_fill_chain >= 65536 ? 4 : 1;
-                hipLaunchKernelGGL(fill_chain_kernel, dim3((ntiles + tpw - 1) / tpw, p.n_fill_chain),
-                                   dim3(256), 0, s, g, p, ntri, sp, ntiles, tpw);
-            }
-            if (p.n_fill_single > 0)
-                hipLaunchKernelGGL(fill_single_kernel,
-                                   dim3(g.toep ? ntiles - ntri + g.nb0 : ntiles, p.n_fill_single),
-                                   dim3(256), 0, s, g, p, ntri, sp);
-        } else {
-            ChunkPtrs q = p;
-            q.fill_other = nullptr;
-            hipLaunchKernelGGL(fill_lattice_kernel<false>, dim3((ntiles - off) * split, Bc),
-                               dim3(256), 0, s, g, q, ntri, off, split, sp);
+    const dim3 blk(256);
+    // other / chain / single-table items of a chunk, each on its own kernel, over tiles [0, nt)
+    auto by_shape = [&](int nt, int nt_single, int split) {
+        // gradient jobs: the value kernels read the subtree tables behind the per-leaf ones
+        ChunkPtrs lists = p;
+        if (p.dtab) {
+            lists.tab = p.tab + (size_t)g.tab_sub * g.R;
+            lists.dtab = nullptr;
         }
+        if (p.n_fill_other > 0)
+            hipLaunchKernelGGL(fill_lattice_kernel<false>, dim3(nt * split, p.n_fill_other), blk, 0, s, g,
+                               lists, ntri, 0, split, sp);
+        if (p.n_fill_chain > 0) {
+            const int tpw = tiles_per_wg((long)nt * p.n_fill_chain);
+            hipLaunchKernelGGL(fill_chain_kernel, dim3((nt + tpw - 1) / tpw, p.n_fill_chain), blk, 0, s, g,
+                               lists, ntri, sp, nt, tpw);
+        }
+        if (p.n_fill_single > 0)
+            hipLaunchKernelGGL(fill_single_kernel, dim3(nt_single, p.n_fill_single), blk, 0, s, g, lists,
+                               ntri, sp);
+    };
+    // tiles [first, first + nt) of every item on the general kernel (FULL: the gradient job's program)
+    auto general = [&](auto kernel, int first, int nt) {
+        ChunkPtrs whole = p;   // one kernel for every item of the chunk
+        whole.fill_other = nullptr;
+        const int split = launch_split((long)nt * Bc);
+        hipLaunchKernelGGL(kernel, dim3(nt * split, Bc), blk, 0, s, g, whole, ntri, first, split, sp);
+    };
+    switch (fill_route(g, p.dtab != nullptr, p.fill_other != nullptr, Bc, aux_only)) {
+    case FILL_DIRECT:
+        hipLaunchKernelGGL(fill_kernel, dim3(ntiles - off, Bc), blk, 0, s, g, p, ntri, off, sp);
+        break;
+    case FILL_GRAD_SMALL:   // main tiles only (y' comes from the observations)
+        general(fill_lattice_kernel<true>, 0, ntri);
+        break;
+    case FILL_GRAD_LISTS:
+        // The main tiles through the kernels of the value jobs — one lookup for a stationary tree,
+        // chain programs decoded once per thread for sixteen elements, the rest on the reduced
+        // program; the values are those of the full program, operation for operation (keval_stat).
+        // The full-program interpreter decodes every node for every element from LDS: 8 us per item
+        // at n = 2049 against 4.  The aux tiles (y', the zero blocks, e_1') hold no covariance.
+        by_shape(ntri, ntri, launch_split((long)ntri * p.n_fill_other));
+        // (short jobs: chol_small_kernel takes y' from the observations and neither it nor
+        // grad_kinv_small_kernel reads the zero blocks — one launch less in their chain)
+        if (!small_job(g, Bc)) general(fill_lattice_kernel<true>, ntri, ntiles - ntri);
+        break;
+    case FILL_GRAD_FULL:
+        general(fill_lattice_kernel<true>, off, ntiles - off);
+        break;
+    case FILL_VALUE_LISTS:   // Toeplitz jobs: single-table items store their diagonal tiles and aux rows
+        // (the general kernel's split follows the chunk, not its share of it)
+        by_shape(ntiles, g.toep ? ntiles - ntri + g.nb0 : ntiles, launch_split((long)ntiles * Bc));
+        break;
+    case FILL_VALUE_ONE:
+        general(fill_lattice_kernel<false>, off, ntiles - off);
+        break;
     }
-    else
-        hipLaunchKernelGGL(fill_kernel, dim3(ntiles - off, Bc), dim3(256), 0, s, g, p, ntri, off, sp);
 }
 
 // The product instantiation of the column sweep: NoProbe.  Weak, so that the diagnostic build
@@ -2795,17 +2777,11 @@ void launch_fill(const JobGeom &g, const ChunkPtrs &p, int Bc, const DevSpec &sp
 // 1: chol_diag_wave_kernel (ngp_small_kernels.h), 0: chol_diag_kernel — a process-wide switch for
 // same-box A/B runs (scripts/diag_form_ab.py), not part of the C-ABI
 static std::atomic<int> g_diag_form{1};
-constexpr int DIAG_WAVE_MAX_ITEMS = 512;
 extern "C" void ngp_debug_set_diag_form(int form) { g_diag_form.store(form); }
 
 __attribute__((weak)) void launch_chol_diag(const JobGeom &g, const ChunkPtrs &p, int Bc, int j,
                                             int k0, hipStream_t s) {
-    // Small chunks (the 24- and 64-particle calls of a fit), where the launch is on the critical path
-    // of the sweep: 42 -> 34 us at 64 items.  Large chunks keep chol_diag_kernel: there every
-    // workgroup competes for its CU with three others and what counts is its total work, of which the
-    // wave form — one wave factoring while three wait — has more (6,400 items: 376 -> 455 us per
-    // launch).  Batch-invariant jobs never switch (the two forms differ in the last bits).
-    if (g_diag_form.load(std::memory_order_relaxed) && !g.invariant && Bc <= DIAG_WAVE_MAX_ITEMS)
+    if (g_diag_form.load(std::memory_order_relaxed) && diag_wave(g, Bc))
         launch_chol_diag_wave(g, p, Bc, j, k0, s);
     else
         launch_chol_diag_t<NoProbe>(g, p, Bc, j, k0, s);
@@ -2877,11 +2853,8 @@ bool launch_mixed_order(const ChunkPtrs &p, unsigned *prev, int32_t *order, int 
     return hipGetLastError() == hipSuccess;
 }
 
-constexpr int DIAG_AHEAD_SPLIT_K = 512;
 void launch_diag_ahead(const JobGeom &g, const ChunkPtrs &p, int Bc, int j, hipStream_t s) {
-    // the split depends on the geometry only (not on the batch), so a given matrix is always
-    // summed in the same order
-    if (j * NB >= DIAG_AHEAD_SPLIT_K)
+    if (diag_ahead_waves(j) == 4)
         hipLaunchKernelGGL(diag_ahead_kernel<4>, dim3(Bc), dim3(256), 0, s, g, p, j);
     else
         hipLaunchKernelGGL(diag_ahead_kernel<1>, dim3(Bc), dim3(64), 0, s, g, p, j);
@@ -2893,7 +2866,7 @@ void launch_grad_kinv(const JobGeom &g, const double *L, double *Kinv, double *a
     // itself, from the rows it stages; the alpha kernel is left with the quadratic form z'z (one
     // wave per item).  Shorter series: alpha reads every row of W once and does not depend on K^-1:
     // it runs beside it on the side stream.
-    const bool lds = g.nb0 >= 8;
+    const bool lds = kinv_lds(g);
     const int a_first = lds ? g.n0 : 0;
     const dim3 agrid(lds ? 1 : (g.n0 + 1 + 3) / 4, Bc);
     const bool beside = side && fork && join;
@@ -2925,9 +2898,7 @@ void launch_grad_contract(const JobGeom &g, const ChunkPtrs &p, const double *Ki
                           hipEvent_t fork, hipEvent_t join) {
     const int ntri = g.nb0 * (g.nb0 + 1) / 2;
     int nparts = ntri;
-    // size classes of a SMALL chunk alternate between the main and the side stream: each is a few
-    // rounds of the chip with a ragged last one, and they touch different items
-    const bool two = side && fork && join && items && Bc <= 512;
+    const bool two = side && fork && join && items && contract_two_streams(Bc);
     int nlaunched = 0;
     hipStream_t s = s0;
     if (two) {
@@ -2936,17 +2907,13 @@ void launch_grad_contract(const JobGeom &g, const ChunkPtrs &p, const double *Ki
     }
     if (g.lattice && p.dtab) {
         const int split = grad_contract_split(ntri, Bc, g.invariant != 0);
-        // large launches: four tiles per workgroup (not under ngp_set_batch_invariant: the grouping of
-        // a thread's partial sums would follow the batch size)
         // items sorted by tree size (grad_bucket): 1, 2, 4, 8 leaves on the register-accumulator
         // kernel, up to 16 leaves in two passes of it, larger trees on the general kernel
         const int32_t *it = items;
         int32_t whole[GRAD_BUCKETS] = {};
         whole[grad_bucket(g.maxops)] = Bc;
         const int32_t *cnt = items ? bucket_counts : whole;
-        // (... and only when every item of the chunk runs on the lists kernel: the kernel of the
-        // largest trees keeps one tile per workgroup, and a chunk has ONE partial-sum layout)
-        const int tpw = (!g.invariant && split == 1 && (long)ntri * Bc >= 65536 && cnt[GRAD_BUCKETS - 1] == 0) ? 4 : 1;
+        const int tpw = contract_tiles_per_wg(g, split, ntri, Bc, cnt[GRAD_BUCKETS - 1] != 0);
         const int ngrp = (ntri + tpw - 1) / tpw;
         nparts = ngrp * split;
         for (int bk = 0; bk < GRAD_BUCKETS; ++bk) {

@@ -1,8 +1,11 @@
-// The planner of the short-series launch (small_plan, csrc/ngp_internal.h) over every geometry it can
+// The planner of the short-series launch (small_plan, csrc/ngp_plan.h) over every geometry it can
 // be asked about: whatever it accepts must fit the kernel's fixed resources — twenty register blocks
 // per wave (seven workers in a main sweep, eight waves otherwise), SM_MAX_PANEL panel blocks in LDS,
 // at most SM_MAX_SWEEPS sweeps — and must carry every aux row-block exactly once; the inverse phase of
-// a gradient job must give every block column to one wave.  Host code only (hipcc --cuda-host-only).
+// a gradient job must give every block column to one wave.  Then the other route rules of
+// csrc/ngp_plan.h over their whole domain, for the relations the host layer relies on
+// (check_routes).  Host code only (hipcc --cuda-host-only).
+#include <cstddef>
 #include <cstdio>
 #include <vector>
 
@@ -19,7 +22,123 @@ static int col_count(const SmallSweep &sw, int nbe, int k) {
     return cm + ci + (sw.a1 - sw.a0);
 }
 
+// tests/sanitize/mock_hip.cpp checksums the geometry argument of a launch as 128 raw bytes.  That is
+// deterministic because the struct has no implicit padding (26 x int32, a double, two int64: the odd
+// int32 is the explicit pad_) and every JobGeom of the host layer starts as JobGeom g{}.
+static_assert(offsetof(ChunkPtrs, n_fill_chain) == 168 && offsetof(ChunkPtrs, fill_base) == 180,
+              "mock_hip.cpp trace_args reads the fill counts and fill_base of a ChunkPtrs at 168 .. 184");
+static_assert(sizeof(JobGeom) == 128, "mock_hip.cpp trace_args reads 128 bytes of a JobGeom");
+
+static JobGeom value_geom(int nb0, int naux) {
+    JobGeom g{};
+    g.n0 = nb0 * NB;
+    g.nb0 = nb0;
+    g.n_real = g.n0;
+    g.naux = naux;
+    g.naux_pad = (naux + NB - 1) / NB * NB;
+    g.short_series = 1;
+    return g;
+}
+
+static void check_routes() {
+    // stage_general sets JobGeom::toep from stores_structured: a job that small_job takes stores every
+    // tile, and every value geometry of up to SM_MAX_NB block columns has a plan (the rule is the
+    // block count's alone)
+    for (int nb0 = 0; nb0 <= 8; ++nb0)
+        for (int naux = 1; naux <= NGP_MAX_AUX; naux += (nb0 ? 1 : 191))
+            for (int P : {1, SM_MAX_ITEMS, SM_MAX_ITEMS + 1})
+                for (int flags = 0; flags < 8; ++flags) {
+                    JobGeom g = value_geom(nb0, naux);
+                    g.short_series = flags & 1;
+                    g.invariant = (flags >> 1) & 1;
+                    const int prec = (flags & 4) ? NGP_PREC_MIXED : NGP_PREC_F64;
+                    const bool st = stores_structured(g, P, true, prec);
+                    CHECK(!(st && small_job(g, P)), "nb0 %d naux %d P %d: structured and one launch", nb0, naux, P);
+                    CHECK(!stores_structured(g, P, false, prec), "structured with the option off");
+                    const bool by_count = g.short_series && nb0 <= SM_MAX_NB && (P <= SM_MAX_ITEMS || g.invariant);
+                    if (nb0 >= 1) CHECK(small_job(g, P) == by_count, "nb0 %d naux %d P %d flags %d: small_job is not the block count's rule", nb0, naux, P, flags);
+                    CHECK(st == (prec != NGP_PREC_MIXED && !(nb0 >= 1 && by_count)), "nb0 %d P %d flags %d: stores_structured", nb0, P, flags);
+                }
+    for (int nb0 = 1; nb0 <= 254; ++nb0)
+        for (int bc : {1, 63, 64, 512, 513, 4096, 4097})
+            for (int flags = 0; flags < 16; ++flags) {
+                JobGeom g = value_geom(nb0, 7);
+                g.invariant = flags & 1;
+                g.aux_identity = (flags >> 1) & 1;
+                const bool mixed = flags & 4, half = flags & 8;
+                if (splitk_eligible(g, bc, mixed, half))
+                    CHECK(!g.invariant && !mixed && !half && !g.aux_identity && bc <= SPLITK_MAX_ITEMS, "split-k of nb0 %d bc %d flags %d", nb0, bc, flags);
+                if (two_lane(g, bc, mixed, half))
+                    CHECK(bc <= AHEAD_EARLY_MAX_ITEMS && ahead_early(bc) && bc / 2 >= 1 && !mixed && !half, "two lanes of nb0 %d bc %d flags %d", nb0, bc, flags);
+                if (diag_wave(g, bc)) CHECK(!g.invariant, "wave diagonal form in an invariant job");
+                const KinvRoute kr = kinv_route(g, bc);
+                CHECK((kr == KINV_LDS) == (nb0 >= KINV_LDS_MIN_NB && !small_job(g, bc)), "K^-1 route of nb0 %d bc %d", nb0, bc);
+                if (g.invariant && kr == KINV_SMALL) CHECK(small_job(g, bc), "an invariant job's K^-1 route follows the chunk");
+                CHECK(mixed_eligible(g, NGP_PREC_MIXED) == (nb0 >= 2 && nb0 <= 129 && !g.aux_identity), "mixed range at nb0 %d", nb0);
+                CHECK(!mixed_eligible(g, NGP_PREC_F64), "fp64 job taken for mixed");
+            }
+    // The column schedule: every block column once and in order (by construction of the loop), THIN
+    // only behind a FAT step whose pre-accumulation it continues, a FULL step first when the count is
+    // odd, every diag-ahead tile joined exactly where chol_diag consumes it with the k-range it covered.
+    for (int nb0 = 1; nb0 <= 254; ++nb0) {
+        const JobGeom g = value_geom(nb0, 7);
+        int prev = -1, forked = -1, n_full = 0;
+        std::vector<int> fork_at((size_t)nb0 + 2, -1);
+        for (int jj = 0; jj < nb0; ++jj) {
+            const ColStepPlan st = col_step(g, jj);
+            CHECK(st.mode == COL_FAT || st.mode == COL_THIN || st.mode == COL_FULL, "mode");
+            if (st.mode == COL_THIN) {
+                CHECK(prev == COL_FAT, "nb0 %d: THIN step %d without a FAT step before it", nb0, jj);
+                CHECK(st.k0_col == (jj - 1) * NB && st.k0_diag == (jj - 1) * NB, "nb0 %d: THIN step %d starts at %d / %d", nb0, jj, st.k0_col, st.k0_diag);
+            } else {
+                CHECK(st.k0_col == 0, "nb0 %d: step %d accumulates from %d", nb0, jj, st.k0_col);
+            }
+            if (st.mode == COL_FAT) CHECK(jj + 1 < nb0, "nb0 %d: FAT step %d has no second column", nb0, jj);
+            if (st.mode == COL_FULL) { ++n_full; CHECK(jj == 0 || jj == nb0 - 1, "nb0 %d: FULL step at %d", nb0, jj); }
+            if (st.join) {
+                CHECK(forked == jj, "nb0 %d: step %d joins a tile nobody forked", nb0, jj);
+                CHECK(st.k0_diag == fork_at[(size_t)jj] * NB, "nb0 %d: diag %d starts at %d, its tile covered %d", nb0, jj, st.k0_diag, fork_at[(size_t)jj] * NB);
+                forked = -1;
+            } else if (st.mode != COL_THIN) {
+                CHECK(st.k0_diag == 0, "nb0 %d: diag %d starts at %d without a diag-ahead tile", nb0, jj, st.k0_diag);
+            }
+            if (st.ahead) {
+                CHECK(st.mode == COL_FAT && forked < 0 && jj + 2 < nb0, "nb0 %d: fork at %d", nb0, jj);
+                forked = jj + 2;
+                fork_at[(size_t)jj + 2] = jj;
+            }
+            prev = st.mode;
+        }
+        CHECK(forked < 0, "nb0 %d: a diag-ahead tile is never joined", nb0);
+        CHECK(n_full == ((nb0 & 1) ? 1 : 0), "nb0 %d: %d FULL steps", nb0, n_full);
+    }
+    // launch sizes and gradient routes
+    for (long nwg = 1; nwg <= 70000; ++nwg) {
+        const int sp = launch_split(nwg);
+        CHECK(sp == 4 || sp == 2 || sp == 1, "split");
+        CHECK(launch_split(nwg + 1) <= sp, "split grows with the launch");
+        CHECK(tiles_per_wg(nwg) == 1 || sp == 1, "four tiles per workgroup in a launch that is cut finer");
+    }
+    for (int B = 1; B <= 600; ++B)
+        for (int n : {128, 1023, 1024, 8192})
+            for (int inv = 0; inv < 2; ++inv) {
+                const GradBatchRoute r = grad_batch_route(B, n, inv != 0);
+                CHECK((r == GRAD_SPLIT) == (B >= SPLIT_MIN_ITEMS), "split of B %d", B);
+                if (inv) CHECK(r != GRAD_UNSPLIT, "an invariant batch routed by its size");
+            }
+    for (int ops = 1; ops <= NGP_MAX_OPS; ++ops) {
+        CHECK(grad_bucket(ops) >= 0 && grad_bucket(ops) < GRAD_BUCKETS, "bucket of %d", ops);
+        CHECK(ops == 1 || grad_bucket(ops) >= grad_bucket(ops - 1), "buckets in order");
+    }
+    for (int groups = 1; groups <= 130; ++groups)
+        for (int bc : {1, 64, 512})
+            for (int nchunks = 0; nchunks <= 512; nchunks += 8)
+                CHECK(splitk_count(groups, nchunks, bc) * groups <= SPLITK_SLOTS || splitk_count(groups, nchunks, bc) <= 1,
+                      "split-k pieces of %d groups exceed the slots", groups);
+}
+
 int main() {
+    check_routes();
     int accepted = 0, refused = 0;
     for (int grad = 0; grad < 2; ++grad)
         for (int n0 = 64; n0 <= 320; n0 += 64)

@@ -1,4 +1,4 @@
-// The sweeps small_plan (csrc/ngp_internal.h) gives every value-job geometry, printed for
+// The sweeps small_plan (csrc/ngp_plan.h, through ngp_internal.h) gives every value-job geometry, printed for
 // tests/test_value_cases_cpu.py: one line "n0 naux nsweeps" (0: refused, the column sweep takes it).
 // Host code only (hipcc --cuda-host-only), the geometry set up as in plan_check.cpp.
 #include <cstdio>

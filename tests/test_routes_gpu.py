@@ -11,7 +11,7 @@ on both sides
 and, with ngp_set_batch_invariant on, the two sides give the same bits.
 
 Tree sizes: a tree of L leaves has 2L - 1 operators, so the bucket edges (1, 3, 7, 15, 31 operators,
-grad_bucket in ngp_internal.h) are straddled with 1|3, 3|5, 7|9, 15|17, 31|33 and 63 operators.
+grad_bucket in ngp_plan.h) are straddled with 1|3, 3|5, 7|9, 15|17, 31|33 and 63 operators.
 """
 import contextlib
 

@@ -1,4 +1,4 @@
-"""The planner of the short-series launch (``small_plan``, csrc/ngp_internal.h) checked on the host
+"""The planner of the short-series launch (``small_plan``, csrc/ngp_plan.h) checked on the host
 over every geometry it can be asked about (tests/sanitize/plan_check.cpp): what it accepts fits the
 kernel's registers, LDS and sweep count and carries every aux row-block exactly once.  No GPU."""
 import os

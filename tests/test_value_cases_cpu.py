@@ -86,7 +86,7 @@ def test_the_table_reaches_every_noise_level_tree_kind_and_sweep_count():
 @pytest.mark.skipif(HIPCC is None, reason="no hipcc")
 def test_the_restated_planner_is_the_planner(tmp_path):
     """value_cases.small_plan_sweeps against small_plan itself (tests/sanitize/plan_sweeps.cpp
-    compiles csrc/ngp_internal.h on the host) over every value geometry, and the sweeps rows:
+    compiles csrc/ngp_plan.h, through ngp_internal.h, on the host) over every value geometry, and the sweeps rows:
     one, two and three sweeps.  With NGP_MAX_AUX = 192 aux rows (12 row-blocks of 16) and at least
     160 // 16 = 10 row-blocks per further sweep, a value job never needs the fourth sweep and never
     falls back for want of one: the planner itself says so here."""

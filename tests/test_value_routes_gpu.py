@@ -11,7 +11,7 @@ noise_on_new), and on each side
   2. sampled items agree with the item in a call of its own (FLOOR_RT on the same scales);
   3. where both sides hold the same data, the two sides agree with each other (FLOOR_RT);
   4. on lattice dates, structured storage on and off give the same bits.  The switch only acts on
-     jobs that reach the column sweep with nb0 >= 2 (stage_general, ngp_api.hip:1058-1060): the
+     jobs that reach the column sweep with nb0 >= 2 (stores_structured, csrc/ngp_plan.h): the
      4,097-item side, the diagonal-block, split-k, two-lane, aux-tile and fill-kernel rows, nb0 = 5
      and every side run with the short path off at nb0 >= 2; on the one-launch sides and at
      nb0 = 1 the comparison is of two identical jobs (and between_off dates leave no lattice);
@@ -200,7 +200,7 @@ def test_one_launch_aux_sweeps(ctx, name, sweeps):
 
 # ---- the column sweep ----------------------------------------------------------------------------------
 def test_diagonal_blocks_512_vs_513_items(ctx):
-    """DIAG_WAVE_MAX_ITEMS / AHEAD_EARLY_MAX_ITEMS (csrc/ngp_kernels.hip:2795, ngp_api.hip:801): up to
+    """DIAG_WAVE_MAX_ITEMS / AHEAD_EARLY_MAX_ITEMS (diag_wave / ahead_early, csrc/ngp_plan.h): up to
     512 items in the chunk chol_diag_wave_kernel and the early diag-ahead launch, above them
     chol_diag_kernel and the late one.  Both diagonal kernels are class 1 and the launch counts are
     the same, so the profile cannot tell them apart; it does show one chunk on the sweep."""
@@ -212,7 +212,7 @@ def test_diagonal_blocks_512_vs_513_items(ctx):
 
 
 def test_split_k_fat_steps(ctx):
-    """split-k fat steps (ngp_api.hip:825): chunks of at most 512 items from nb0 = 8 on — nb0 = 7 | 8
+    """split-k fat steps (splitk_eligible, csrc/ngp_plan.h): chunks of at most 512 items from nb0 = 8 on — nb0 = 7 | 8
     at 40 items, 512 | 513 items at nb0 = 8.  chol_col_glds_kernel<.., SPLITK> shares class 0 with
     the plain fat step: the profile cannot tell.  Batch-invariant jobs never split."""
     for name in ("splitk_nb7", "splitk_nb8"):
@@ -227,7 +227,7 @@ def test_split_k_fat_steps(ctx):
 
 
 def test_two_lanes(ctx):
-    """TWO_LANE_MIN_NB / TWO_LANE_MIN_ITEMS (ngp_api.hip:805): from 24 block columns and 64 items on
+    """TWO_LANE_MIN_NB / TWO_LANE_MIN_ITEMS (two_lane, csrc/ngp_plan.h): from 24 block columns and 64 items on
     the chunk is swept as two half-chunks side by side — every launch of the sweep twice.  Items 31
     and 32 sit on either side of the half-chunk seam.  n > HP_MAX_N: the reference is fp64
     (tol_factor 2)."""
@@ -247,7 +247,7 @@ def test_two_lanes(ctx):
 @pytest.mark.parametrize("nb0", [1, 2, 3, 4, 5])
 def test_column_pairing(ctx, nb0, tail):
     """block columns go in pairs (fat step, class 0, then thin step, class 6); an odd count of three
-    or more sends column 0 alone (o = 1, ngp_api.hip:879), a count of one is a single full step.
+    or more sends column 0 alone (col_pair_offset / col_step, csrc/ngp_plan.h), a count of one is a single full step.
     Up to nb0 = 4 the one-launch kernel is the other side."""
     c = CASES[f"pairs_nb{nb0}_tail{tail}"]
     fat = (nb0 - (1 if nb0 >= 3 and nb0 % 2 else 0)) // 2
@@ -306,7 +306,7 @@ def _d9_first_8(b, i):
 
 def test_scenario_solve_8_vs_9_scenarios(ctx):
     """the epilogue solves up to 8 scenarios one after the other with every row's dot product spread
-    over the wave, more than 8 with one lane per scenario (csrc/ngp_kernels.hip:1381, g.D <= 8): the
+    over the wave, more than 8 with one lane per scenario (launch_epilogue in csrc/ngp_kernels.hip, g.D <= 8): the
     same kernel, so nothing in the profile.  Scenarios 0..7 are the same on both sides.  Here y is
     shared by the items (ngp_nowcast_batch takes one y); the next test gives every item its own."""
     c8, c9 = CASES["scen8"], CASES["scen9"]
@@ -359,7 +359,7 @@ def test_scenario_solve_with_per_item_observation_rows(ctx):
 @pytest.mark.parametrize("name", ["epi_lat", "epi_irr"])
 def test_epilogue_schur_blocks_tables_vs_direct_evaluation(ctx, name):
     """a single-chunk job on lattice dates reads the small Schur blocks' covariances from the resident
-    tables; a batch-invariant job (ngp_api.hip:1457) and any job on irregular dates (or with one
+    tables; a batch-invariant job (ngp_job_run: the epilogue's resident tables) and any job on irregular dates (or with one
     forecast date off the lattice: the between_off set) evaluates them directly.  Both are class 3;
     each is judged against the reference, and the two against each other."""
     c = CASES[name]
@@ -369,7 +369,7 @@ def test_epilogue_schur_blocks_tables_vs_direct_evaluation(ctx, name):
 
 
 def test_fill_kernels_single_table_chain_and_other_items(ctx):
-    """fill_single / fill_chain / fill_other (stage_general, ngp_api.hip:1076-1080) in one batch, three
+    """fill_single / fill_chain / fill_other (the fill lists of stage_general; fill_route, csrc/ngp_plan.h) in one batch, three
     items of each by compile_program's rule (value_cases.fill_kind restates it): pure stationary trees
     (one table), trees in which one operand of every general node is a table or a Linear leaf (chain),
     and trees with a general node between two general subtrees (other); every item is sampled.  The

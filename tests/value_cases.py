@@ -289,7 +289,7 @@ for _nb in (1, 2, 3, 4, 5):
                                                  sizes=(1, 3, 5), per_size=False)
 
 
-# ---- the planner of the one-launch kernel, restated (csrc/ngp_internal.h small_plan, value jobs) -----
+# ---- the planner of the one-launch kernel, restated (csrc/ngp_plan.h small_plan, value jobs) -----
 SM_WAVES, SM_NSLOT, SM_MAX_PANEL, SM_MAX_SWEEPS, NGP_MAX_AUX = 8, 20, 34, 4, 192
 
 
