@@ -702,6 +702,49 @@ extern "C" ngp_status ngp_profile_get(ngp_ctx *c, ngp_profile *out) {
 // ---------------------------------------------------------------------------------------
 // jobs
 // ---------------------------------------------------------------------------------------
+// The fill-list section of a staging arena.  A lattice job's items by the shape of their reduced
+// program — one table for the whole tree (fill_single_kernel; in a Toeplitz job the structured
+// items, prog_structure) / chain programs (fill_chain_kernel) / the rest (the general fill) — as
+// ascending job-wide indices, and where the three lists sit in the arena.  launch_fill reads a
+// chunk's share of each list (share_of).
+struct FillLists {
+    std::vector<int32_t> single, chain, other;
+    size_t o_single = 0, o_chain = 0, o_other = 0;   // byte offsets in the arena
+
+    void sort_items(const DevProgram *hp, int n) {
+        for (int i = 0; i < n; ++i)
+            (prog_single_table(&hp[i]) ? single : hp[i].rchain ? chain : other).push_back(i);
+    }
+    // take(bytes) -> offset: the arena's own allocator, so the section sits where it always did
+    template <class Take>
+    void layout(Take &&take) {
+        o_single = take(4 * single.size());
+        o_chain = take(4 * chain.size());
+        o_other = take(4 * other.size());
+    }
+    void copy_to(unsigned char *h) const {
+        auto put = [&](const std::vector<int32_t> &v, size_t o) {
+            if (!v.empty()) std::memcpy(h + o, v.data(), 4 * v.size());
+        };
+        put(single, o_single);
+        put(chain, o_chain);
+        put(other, o_other);
+    }
+    // the share of chunk [b0, b0 + bc) in each list; io: the arena on the device
+    void share_of(const unsigned char *io, int b0, int bc, ChunkPtrs *p) const {
+        auto share = [&](const std::vector<int32_t> &v, size_t o, const int32_t **ptr, int32_t *cnt) {
+            const auto lo = std::lower_bound(v.begin(), v.end(), b0);
+            const auto hi = std::lower_bound(v.begin(), v.end(), b0 + bc);
+            *ptr = (const int32_t *)(io + o) + (lo - v.begin());
+            *cnt = (int32_t)(hi - lo);
+        };
+        share(single, o_single, &p->fill_single, &p->n_fill_single);
+        share(chain, o_chain, &p->fill_chain, &p->n_fill_chain);
+        share(other, o_other, &p->fill_other, &p->n_fill_other);
+        p->fill_base = b0;
+    }
+};
+
 struct ngp_job {
     ngp_ctx *ctx = nullptr;
     JobGeom g{};
@@ -724,10 +767,10 @@ struct ngp_job {
     bool out_fetched = false;   // h_out holds the result region of the last run
     // the spec the job was staged under: a later ngp_set_spec does not reach a staged job
     ngp_spec spec{};
-    // lattice jobs: items whose reduced program is a chain of more than one instruction / the other
-    // items (ascending job-wide indices; device copies fill_chain_d / fill_other_d)
-    std::vector<int32_t> fill_chain, fill_other, fill_single;   // single: the whole tree is ONE table
-    int32_t *fill_chain_d = nullptr, *fill_other_d = nullptr, *fill_single_d = nullptr;
+    // lattice jobs with a main block: the items by their fill kernel; fill_io: the arena once the
+    // lists are on the device (null: every item goes through the general fill)
+    FillLists fill;
+    const unsigned char *fill_io = nullptr;
     // NGP_PREC_MIXED: per item, filled by ngp_job_run
     std::vector<int32_t> refine_steps;
     std::vector<double> refine_delta, frac32;
@@ -990,13 +1033,7 @@ ngp_status stage_general(ngp_ctx *c, int P, const ngp_kernel *kernels, int n, co
         return s;
     };
     const int ny = g.y_shared ? 1 : P;
-    // the fill kernel of every item: one table for the whole tree (in a Toeplitz job the
-    // structured items, prog_structure) / chain programs / the rest
-    if (g.lattice && g.n0 > 0)
-        for (int i = 0; i < P; ++i)
-            (prog_single_table(&hp[(size_t)i]) ? j->fill_single
-                                                : hp[(size_t)i].rchain ? j->fill_chain : j->fill_other)
-                .push_back(i);
+    if (g.lattice && g.n0 > 0) j->fill.sort_items(hp.data(), P);
     // ONE device arena for everything that crosses the bus, inputs first, outputs last:
     //   [programs | t0 | taux | y0 | ya | lattice indices | fill lists | logdet | info |
     //    logml_base | logml_full | mu | sigma]
@@ -1012,10 +1049,9 @@ ngp_status stage_general(ngp_ctx *c, int P, const ngp_kernel *kernels, int n, co
                  n_ya = (size_t)std::max((int64_t)ny * D * g.da, (int64_t)1);
     const size_t o_progs = take(sizeof(DevProgram) * (size_t)P), o_t0 = take(8 * n_t0),
                  o_taux = take(8 * n_taux), o_y0 = take(8 * n_y0), o_ya = take(8 * n_ya),
-                 o_q = take(g.lattice ? 4 * (size_t)g.npts : 0),
-                 o_fs = take(4 * j->fill_single.size()), o_fc = take(4 * j->fill_chain.size()),
-                 o_fo = take(4 * j->fill_other.size()), o_logdet = take(8 * (size_t)P),
-                 o_info = take(4 * (size_t)P);
+                 o_q = take(g.lattice ? 4 * (size_t)g.npts : 0);
+    j->fill.layout(take);
+    const size_t o_logdet = take(8 * (size_t)P), o_info = take(4 * (size_t)P);
     const size_t in_bytes = off;
     const size_t o_lb = take(8 * (size_t)P), o_lf = take(8 * (size_t)P * D),
                  o_mu = take(m > 0 ? 8 * (size_t)P * D * m : 0),
@@ -1040,12 +1076,7 @@ ngp_status stage_general(ngp_ctx *c, int P, const ngp_kernel *kernels, int n, co
                     dst[g.tail + a] = y_add[(int64_t)b * ld_yadd_item + (int64_t)sc * d + a];
             }
         if (g.lattice) std::memcpy(h + o_q, h_q.data(), 4 * (size_t)g.npts);
-        if (!j->fill_single.empty())
-            std::memcpy(h + o_fs, j->fill_single.data(), 4 * j->fill_single.size());
-        if (!j->fill_chain.empty())
-            std::memcpy(h + o_fc, j->fill_chain.data(), 4 * j->fill_chain.size());
-        if (!j->fill_other.empty())
-            std::memcpy(h + o_fo, j->fill_other.data(), 4 * j->fill_other.size());
+        j->fill.copy_to(h);
     }
     unsigned char *io = nullptr;
     if ((st = job_alloc(j, &io, off))) return fail(st);
@@ -1055,11 +1086,7 @@ ngp_status stage_general(ngp_ctx *c, int P, const ngp_kernel *kernels, int n, co
     j->y0 = (double *)(io + o_y0);
     j->ya = (double *)(io + o_ya);
     if (g.lattice) j->qpts = (int32_t *)(io + o_q);
-    if (g.lattice && g.n0 > 0) {
-        j->fill_single_d = (int32_t *)(io + o_fs);
-        j->fill_chain_d = (int32_t *)(io + o_fc);
-        j->fill_other_d = (int32_t *)(io + o_fo);
-    }
+    if (g.lattice && g.n0 > 0) j->fill_io = io;
     j->logdet = (double *)(io + o_logdet);
     j->info = (int32_t *)(io + o_info);
     j->logml_base = (double *)(io + o_lb);
@@ -1116,24 +1143,6 @@ EpiPtrs epi_ptrs_of(const ngp_job &j) {
     e.sigma = j.sigma;
     e.work_stride = j.work_stride;
     return e;
-}
-
-// the share of chunk [b0, b0 + bc) in one of a job's fill lists (ascending job-wide indices; dev: its
-// device copy)
-void fill_share(const std::vector<int32_t> &v, const int32_t *dev, int b0, int bc, const int32_t **ptr,
-                int32_t *cnt) {
-    const auto lo = std::lower_bound(v.begin(), v.end(), b0);
-    const auto hi = std::lower_bound(v.begin(), v.end(), b0 + bc);
-    *ptr = dev + (lo - v.begin());
-    *cnt = (int32_t)(hi - lo);
-}
-template <class Job>
-void fill_shares(const Job &j, const int32_t *single_d, const int32_t *chain_d, const int32_t *other_d,
-                 int b0, int bc, ChunkPtrs *p) {
-    fill_share(j.fill_single, single_d, b0, bc, &p->fill_single, &p->n_fill_single);
-    fill_share(j.fill_chain, chain_d, b0, bc, &p->fill_chain, &p->n_fill_chain);
-    fill_share(j.fill_other, other_d, b0, bc, &p->fill_other, &p->n_fill_other);
-    p->fill_base = b0;
 }
 
 // One attempt at a run's working storage: `layout` is walked twice through the same sequence of
@@ -1335,8 +1344,7 @@ extern "C" ngp_status ngp_job_run(ngp_job *j) {
             p.tab = (double *)tab;
             p.sig = (double *)sig;
             p.qpts = j->qpts;
-            if (j->fill_other_d)
-                fill_shares(*j, j->fill_single_d, j->fill_chain_d, j->fill_other_d, b0, bc, &p);
+            if (j->fill_io) j->fill.share_of(j->fill_io, b0, bc, &p);
             if (mixed) {
                 p.L32 = (float *)L32;
                 p.tmax = (float *)tmx;
@@ -1825,8 +1833,7 @@ struct GradLeaf {
     size_t o_t = 0, o_y = 0, o_q = 0, o_info = 0, o_logdet = 0, o_grad = 0, o_logml = 0, io_bytes = 0;
     // lattice jobs: the items by the shape of their reduced program, as in a staged value job
     // (ascending leaf indices; the fill of the main tiles runs on the value jobs' kernels)
-    std::vector<int32_t> fill_single, fill_chain, fill_other;
-    size_t o_fs = 0, o_fc = 0, o_fo = 0;
+    FillLists fill;
     PinVec<unsigned char> h_in, h_out;        // staging copy of a small job's inputs; results
     bool fresh = false;                    // info / logdet still hold the zeros they were staged with
     bool progs_dirty = false;              // set_params since the last upload
@@ -1927,10 +1934,7 @@ ngp_status grad_leaf_stage(ngp_ctx *c, int32_t B, const ngp_kernel *kernels, int
             // and the items sorted by the kernel that fills their main tiles (launch_fill)
             g.tab_sub = g.maxstat;
             g.maxstat += maxtab;
-            for (int i = 0; i < B; ++i)
-                (prog_single_table(&j->hp[(size_t)i]) ? j->fill_single
-                                                       : j->hp[(size_t)i].rchain ? j->fill_chain : j->fill_other)
-                    .push_back(i);
+            j->fill.sort_items(j->hp.data(), B);
         }
     }
     const int ny = g.y_shared ? 1 : B;
@@ -1939,10 +1943,9 @@ ngp_status grad_leaf_stage(ngp_ctx *c, int32_t B, const ngp_kernel *kernels, int
     j->o_t = al(sizeof(DevProgram) * (size_t)B);
     j->o_y = j->o_t + al(8 * (size_t)g.n0);
     j->o_q = j->o_y + al(8 * (size_t)ny * g.n0);
-    j->o_fs = j->o_q + (g.lattice ? al(4 * (size_t)g.n0) : 0);
-    j->o_fc = j->o_fs + al(4 * j->fill_single.size());
-    j->o_fo = j->o_fc + al(4 * j->fill_chain.size());
-    j->o_info = j->o_fo + al(4 * j->fill_other.size());
+    size_t off = j->o_q + (g.lattice ? al(4 * (size_t)g.n0) : 0);
+    j->fill.layout([&](size_t bytes) { const size_t o = off; off += al(bytes); return o; });
+    j->o_info = off;
     j->o_logdet = j->o_info + al(4 * (size_t)B);
     j->o_grad = j->o_logdet + al(8 * (size_t)B);
     j->o_logml = j->o_grad + al(8 * (size_t)B * GP);
@@ -1956,12 +1959,7 @@ ngp_status grad_leaf_stage(ngp_ctx *c, int32_t B, const ngp_kernel *kernels, int
         for (int b = 0; b < ny; ++b)
             std::memcpy(hy + (size_t)b * g.n0, yrows ? yrows[b] : y + (int64_t)b * ldy, 8 * (size_t)n);
         if (g.lattice) std::memcpy(j->h_in.data() + j->o_q, h_q.data(), 4 * (size_t)g.n0);
-        if (!j->fill_single.empty())
-            std::memcpy(j->h_in.data() + j->o_fs, j->fill_single.data(), 4 * j->fill_single.size());
-        if (!j->fill_chain.empty())
-            std::memcpy(j->h_in.data() + j->o_fc, j->fill_chain.data(), 4 * j->fill_chain.size());
-        if (!j->fill_other.empty())
-            std::memcpy(j->h_in.data() + j->o_fo, j->fill_other.data(), 4 * j->fill_other.size());
+        j->fill.copy_to(j->h_in.data());
     }
     std::lock_guard<std::mutex> lk(c->mu);
     HIPCHK(hipSetDevice(c->device));
@@ -2113,9 +2111,7 @@ struct LeafRun {
             p.qpts = (const int32_t *)d_q;
             p.dtab = (double *)d_dtab;
             p.splitk_part = splitk;
-            if (g.lattice)
-                fill_shares(*j, (const int32_t *)(io + j->o_fs), (const int32_t *)(io + j->o_fc),
-                            (const int32_t *)(io + j->o_fo), b0, bc, &p);
+            if (g.lattice) j->fill.share_of(io, b0, bc, &p);
             if (g.lattice) tm.run(4, 0.0, 0.0, [&] { launch_tables(g, p, bc, sp, s); });
             tm.run(cost_fill_grad(g, bc, tp), [&] { launch_fill(g, p, bc, sp, s); });
             const size_t mstep = tp ? (size_t)bc * NB * NB : 0;

@@ -7,6 +7,15 @@ namespace ngp {
 typedef double f64x4 __attribute__((ext_vector_type(4)));
 typedef double f64x2 __attribute__((ext_vector_type(2)));
 
+// Index t = r (r + 1) / 2 + c of an element of the lower triangle (r >= c) -> (r, c): the tile and
+// pair numbering of every launch that walks a triangle
+__device__ __forceinline__ void tri_decode(int t, int &r, int &c) {
+    r = (int)((sqrt(8.0 * t + 1.0) - 1.0) * 0.5);
+    while ((r + 1) * (r + 2) / 2 <= t) ++r;
+    while (r * (r + 1) / 2 > t) --r;
+    c = t - r * (r + 1) / 2;
+}
+
 __device__ __forceinline__ f64x4 mfma64(double a, double b, f64x4 c) {
     return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0);
 }

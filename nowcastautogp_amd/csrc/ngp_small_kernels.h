@@ -602,10 +602,8 @@ __global__ __launch_bounds__(256) void grad_kinv_small_kernel(JobGeom g, const d
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int pr = blockIdx.x * 4 + wave;
     if (pr >= nbe * (nbe + 1) / 2) return;
-    int a = (int)((sqrt(8.0 * pr + 1.0) - 1.0) * 0.5);
-    while ((a + 1) * (a + 2) / 2 <= pr) ++a;
-    while (a * (a + 1) / 2 > pr) --a;
-    const int b = pr - a * (a + 1) / 2;   // a >= b
+    int a, b;   // a >= b
+    tri_decode(pr, a, b);
     const long ld = g.ld;
     const int r16 = lane & 15, q = lane >> 4;
     const double *W = L + (long)item * g.item_stride + (long)g.n0 * ld;

@@ -27,7 +27,7 @@ def build_stamps_lib():
     csrc = os.path.join(ROOT, "nowcastautogp_amd", "csrc")
     srcs = [os.path.join(csrc, "ngp_kernels.hip"), os.path.join(csrc, "ngp_api.hip"),
             os.path.join(ROOT, "scripts", "stamps", "ngp_stamps.hip")]
-    deps = srcs + [os.path.join(csrc, h) for h in ("ngp_col_kernels.h", "ngp_mfma.h", "ngp_internal.h")]
+    deps = srcs + [os.path.join(csrc, h) for h in os.listdir(csrc) if h.endswith(".h")]
     if os.path.exists(STAMPS_LIB) and all(os.path.getmtime(d) <= os.path.getmtime(STAMPS_LIB)
                                           for d in deps):
         return
