@@ -11,10 +11,14 @@
 // of a roofline formula shows as a diff.  The table puts at least one job on each side of every
 // rule in csrc/ngp_plan.h; the geometries are those of tests/test_value_routes_gpu.py and
 // tests/test_routes_gpu.py.
+// `route_trace --grammar FILE` runs the grammar zoo instead (below, before main).
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <fstream>
 #include <initializer_list>
+#include <sstream>
 #include <string>
 #include <vector>
 
@@ -216,10 +220,119 @@ static void precision(int prec, int refine_max) {
     OK(ngp_set_spec(ctx, &sp));
 }
 
+// ---- route_trace --grammar FILE: the grammar zoo (tests/grammar_cases.py writes the file: one item per
+// line, "name | operators | parameters | noise") through the batches of tests/test_grammar_gpu.py whose
+// contraction instantiation the kernel-class profile cannot show.  tests/test_route_trace.py compares
+// the output with tests/golden/route_trace_grammar_v1.txt.
+struct Zoo {
+    std::vector<std::string> names;
+    std::vector<std::vector<int32_t>> ops;
+    std::vector<std::vector<double>> par;
+    std::vector<double> noise;
+    explicit Zoo(const char *path) {
+        std::ifstream in(path);
+        std::string line;
+        while (std::getline(in, line)) {
+            if (line.empty()) continue;
+            std::vector<std::string> f;
+            size_t a = 0;
+            for (size_t b; (b = line.find('|', a)) != std::string::npos; a = b + 1) f.push_back(line.substr(a, b - a));
+            f.push_back(line.substr(a));
+            if (f.size() != 4) { say("FAIL zoo line: %s", line.c_str()); std::exit(2); }
+            std::istringstream nm(f[0]), so(f[1]), sp(f[2]);
+            std::string name;
+            nm >> name;
+            names.push_back(name);
+            ops.emplace_back();
+            par.emplace_back();
+            for (int v; so >> v;) ops.back().push_back(v);
+            for (double v; sp >> v;) par.back().push_back(v);
+            noise.push_back(std::stod(f[3]));
+        }
+    }
+    // the items idx as kernels (the vectors above outlive them)
+    std::vector<ngp_kernel> kernels(const std::vector<int> &idx) const {
+        std::vector<ngp_kernel> ks;
+        for (int i : idx)
+            ks.push_back(ngp_kernel{(int32_t)ops[(size_t)i].size(), (int32_t)par[(size_t)i].size(), ops[(size_t)i].data(),
+                                    par[(size_t)i].data(), noise[(size_t)i]});
+        return ks;
+    }
+    bool toeplitz_eligible(int i) const {
+        for (int32_t o : ops[(size_t)i]) if (o == NGP_OP_LINEAR || o == NGP_OP_CHANGEPOINT) return false;
+        return ops[(size_t)i].size() <= 31;
+    }
+};
+
+static void zoo_grad(const Zoo &z, const char *row, const std::vector<int> &idx, int n) {
+    int maxops = 0;
+    for (int i : idx) maxops = std::max(maxops, (int)z.ops[(size_t)i].size());
+    say("== %s n=%d B=%d largest tree %d operators", row, n, (int)idx.size(), maxops);
+    std::vector<ngp_kernel> ks = z.kernels(idx);
+    Series s(n, true, 0, 1, 0);
+    room(idx.size() * (NGP_MAX_PARAMS + 1) + 16);
+    ngp_grad_job *j = nullptr;
+    OK(ngp_grad_stage(ctx, (int32_t)ks.size(), ks.data(), n, s.t.data(), s.y.data(), 0, &j));
+    if (!j) return;
+    OK(ngp_grad_job_run(j, out_a.data(), out_b.data(), out_i.data()));
+    int32_t how[5] = {};
+    OK(ngp_grad_job_info(j, how));
+    say("-- leaves: general %d, toeplitz %d", how[0], how[2]);
+    ngp_grad_job_destroy(j);
+    done();
+}
+
+static int grammar(const char *path) {
+    Zoo z(path);
+    const int B = (int)z.names.size();
+    say("grammar zoo: %d items", B);
+    std::vector<int> by_size((size_t)B);
+    for (int i = 0; i < B; ++i) by_size[(size_t)i] = i;
+    std::stable_sort(by_size.begin(), by_size.end(),
+                     [&](int a, int b) { return z.ops[(size_t)a].size() < z.ops[(size_t)b].size(); });
+    auto prefixes = [&](const std::vector<int> &idx) {
+        std::vector<std::vector<int>> out;
+        for (size_t cap : {1, 3, 7, 15, 31, 63}) {
+            std::vector<int> p;
+            for (int i : idx) if (z.ops[(size_t)i].size() <= cap) p.push_back(i);
+            if (!p.empty() && (out.empty() || p.size() > out.back().size())) out.push_back(p);
+        }
+        return out;
+    };
+    for (const auto &p : prefixes(by_size)) zoo_grad(z, "G-sized", p, 130);
+    OK(ngp_set_batch_invariant(ctx, 1));
+    zoo_grad(z, "G-own", by_size, 130);
+    OK(ngp_set_batch_invariant(ctx, 0));
+    std::vector<int> toep;
+    int stat17 = -1;
+    for (int i : by_size) {
+        if (z.toeplitz_eligible(i)) toep.push_back(i);
+        if (z.names[(size_t)i] == "stat17") stat17 = i;
+    }
+    for (const auto &p : prefixes(toep)) zoo_grad(z, "G-toep", p, 321);
+    toep.push_back(stat17);
+    zoo_grad(z, "G-toep with the 17-leaf tree", toep, 321);
+    {
+        say("== V-lists n=321 B=%d", B);
+        std::vector<ngp_kernel> ks = z.kernels(by_size);
+        const int d = 2, D = 2, m = 5;
+        Series s(321, true, d, D, m);
+        room((size_t)B * (size_t)(D * m + m * m) + 16);
+        OK(ngp_nowcast_batch(ctx, B, ks.data(), 321, s.t.data(), s.y.data(), d, s.t_add.data(), D, s.y_add.data(),
+                             m, s.t_new.data(), 1, out_a.data(), out_b.data(), out_c.data(), out_d.data(), out_i.data()));
+        done();
+    }
+    ngp_ctx_destroy(ctx);
+    if (mock_hip_errors()) { ++fails; say("FAIL the mock runtime saw a bad free or an out-of-bounds copy"); }
+    say("route_trace --grammar: %d failures", fails);
+    return fails ? 1 : 0;
+}
+
 int main(int argc, char **argv) {
     full = argc > 1 && std::string(argv[1]) == "--full";
     mock_hip_trace(full ? 1 : 2);
     fresh_context();
+    if (argc > 2 && std::string(argv[1]) == "--grammar") return grammar(argv[2]);
     const std::initializer_list<int> MIX = {STAT, CHAIN, OTHER};
 
     // ---- value jobs: short series (one launch | column sweep), the three fill kernels -------------
