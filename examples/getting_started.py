@@ -84,6 +84,18 @@ def main():
                                        inv_transformation=inv_transformation, n_hmc=1, **kw)
         print(f"forecast_with_nowcasts(n_hmc=1), {label}: {time.perf_counter() - t0:.2f} s, "
               f"median of week 1 {np.median(fr[0]):.1f}")
+    # which part of the forecast is trend, which is season (AutoGP's decompose): the additive parts
+    # of every particle's kernel, conditioned on the same data through the model's resident factor,
+    # grouped by kind across the particles — 95 % bands on the scale the model was fitted on
+    from nowcastautogp_amd import autogp
+    fc = autogp.predict_components(model, dates[n:n + horizon])
+    bands = {kind: g.quantile([0.025, 0.5, 0.975]) for kind, g in fc.grouped().items()}
+    print(f"additive parts of the forecast (constant of the y-transform: {fc.offset:.3f}; "
+          f"part kinds of particle 0: {fc.kinds[0]})")
+    print("  date        " + "".join(f"{kind + ' 2.5%':>16s}{'50%':>8s}{'97.5%':>8s}" for kind in bands))
+    for k in range(horizon):
+        print(f"  {dates[n + k]}  " + "".join(f"{b[k, 0]:16.3f}{b[k, 1]:8.3f}{b[k, 2]:8.3f}"
+                                              for b in bands.values()))
 
 
 if __name__ == "__main__":

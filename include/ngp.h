@@ -454,6 +454,53 @@ ngp_status ngp_factor_nowcast(ngp_factor *f, int32_t d, const double *t_add,
                               double *mu, double *sigma, int32_t *info);
 void       ngp_factor_destroy(ngp_factor *f);
 
+/* ---- additive decomposition of a fitted model's forecast ------------------------
+ * What AutoGP offers as `decompose`: which part of a forecast is trend, which is season.  A fitted
+ * tree is almost always a sum.  Its COMPONENTS are the maximal non-Plus subtrees reached from the
+ * root through Plus nodes only; in postfix order each is a contiguous slice of ops and of params,
+ * so a component is itself a valid ngp_kernel.  A tree whose root is not Plus has one component,
+ * itself.  (A ChangePoint is additive too, but its two summands are not expressible in the
+ * grammar: it is never split, and neither is a Plus below a Times or a ChangePoint.)
+ *
+ * For particle p with components c = 1..C, k = sum_c k_c, training times t,
+ * K = k(t,t) + (noise + jitter) I, query dates t* (m of them) and X_c = k_c(t*, t):
+ *     mu_c       = X_c K^-1 y                                         [m]
+ *     Sigma_c,c' = delta_cc' k_c(t*, t*) - X_c K^-1 X_c'^T            [m x m]
+ * the joint posterior of the independent latent parts g_c ~ GP(0, k_c) given y.  No noise term
+ * appears: noise is a part of its own, the remainder y - sum_c g_c.  Against the noise-free
+ * predict of the same factor (ngp_factor_nowcast with d = 0, noise_on_new = 0):
+ *     sum_c mu_c = mu,   sum_c,c' Sigma_c,c' = Sigma,   every Sigma_c,c is positive semi-definite,
+ * and the variance of any sum of components ("all seasonal parts") is the sum of its blocks.
+ *
+ * ngp_kernel_components (host only) does the slicing: component i of k is
+ * ops[op_first[i] .. + op_len[i]), params[par_first[i] .. + par_len[i]), left to right.  The four
+ * arrays hold up to NGP_MAX_OPS / 2 + 1 entries each and may be NULL (count alone).
+ *
+ * ngp_factor_components is ONE query of the resident factor: the C_p m component rows of a
+ * particle share its aux block with the tail observations and the y row and are swept through the
+ * resident L once; no m x n matrix crosses the bus.
+ *   comp_count [P]       C_p >= 1
+ *   comps      [sum C_p] component programs, particle-major.  The library does NOT check that
+ *                        they sum to the particle's kernel: the formulas above are what it returns
+ *                        for ANY k_c (K stays the factor's).  A component's `noise` is ignored.
+ *   mu    [sum C_p][m]
+ *   sigma per particle [C_p m][C_p m] row-major (row = c m + j), packed back to back; may be NULL
+ *   var   [sum C_p][m]  the diagonals of sigma, bit for bit; may be NULL
+ *   info  [P] as ngp_factor_logml, plus a pivot failure among the tail observations; may be NULL.
+ *         An item with info > 0 returns NaN in all its outputs; other items are not affected.
+ * Limit: (n mod 64) + 1 + C_p m <= NGP_MAX_AUX for every particle, else NGP_ERR_TOO_LARGE (longer
+ * horizons: several calls on blocks of dates — covariances across blocks are then not formed).
+ * Null arguments, m < 1 and C_p < 1 are NGP_ERR_ARG, a malformed component NGP_ERR_PROGRAM, all
+ * before anything touches a device.  Runs under the factor's spec; thread-safe through the
+ * context's lock like the other factor queries; not combined with concurrent callers.  Bitwise
+ * reproducible from call to call (fixed summation order, no floating-point atomics).
+ * Profile classes: the component fill is booked under 4, the component epilogue under 3.      */
+ngp_status ngp_kernel_components(const ngp_kernel *k, int32_t *count, int32_t *op_first,
+                                 int32_t *op_len, int32_t *par_first, int32_t *par_len);
+ngp_status ngp_factor_components(ngp_factor *f, const int32_t *comp_count, const ngp_kernel *comps,
+                                 int32_t m, const double *t_new, double *mu, double *sigma,
+                                 double *var, int32_t *info);
+
 /* ---- measurement hooks -----------------------------------------------------
  * HIP-event timing of the kernels a job launches, on the stream they are
  * launched on.  Classes: 0 = chol_col_glds_kernel (fat steps: trailing-update

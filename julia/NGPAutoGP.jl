@@ -285,6 +285,53 @@ function nowcast(f::Factor, t_add::Vector{Float64}, y_add::Matrix{Float64}, t_ne
     return (logml_base = lb, logml_full = lf, mu = mu, sigma = sigma, info = info)
 end
 
+"""
+The additive components of a program (include/ngp.h `ngp_kernel_components`): the maximal non-Plus
+subtrees under the root's Plus nodes, left to right, each a `Program` of its own.
+"""
+function kernel_components(p::Program)
+    cap = length(p.ops) ÷ 2 + 1
+    cnt = Ref{Int32}(0)
+    of, ol, pf, pl = zeros(Int32, cap), zeros(Int32, cap), zeros(Int32, cap), zeros(Int32, cap)
+    GC.@preserve p begin
+        k = Ref(NgpKernel(length(p.ops), length(p.params), pointer(p.ops), pointer(p.params), p.noise))
+        check(ccall((:ngp_kernel_components, LIBNGP), Int32,
+                    (Ref{NgpKernel}, Ref{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}),
+                    k, cnt, of, ol, pf, pl), "ngp_kernel_components")
+    end
+    return [Program(p.ops[of[i]+1:of[i]+ol[i]], p.params[pf[i]+1:pf[i]+pl[i]], p.noise) for i in 1:cnt[]]
+end
+
+"""
+Joint posterior of every particle's additive parts on the dates `t_new` (include/ngp.h
+`ngp_factor_components`): `comps[p]` are particle p's component programs.  Returns per particle
+`mu` (m x C_p), `var` (m x C_p) and `sigma` (C_p m x C_p m, index = (c - 1) m + j); the C_p m rows
+share the aux block: (n mod 64) + 1 + C_p m <= NGP_MAX_AUX.
+"""
+function components(f::Factor, comps::Vector{Vector{Program}}, t_new::Vector{Float64})
+    length(comps) == f.P || throw(ArgumentError("one vector of component programs per particle"))
+    m = length(t_new)
+    counts = Int32[length(c) for c in comps]
+    flat = reduce(vcat, comps)
+    tot = length(flat)
+    mu, var = Matrix{Float64}(undef, m, tot), Matrix{Float64}(undef, m, tot)
+    sizes = [(Int(c) * m)^2 for c in counts]
+    sg = Vector{Float64}(undef, sum(sizes))
+    info = zeros(Int32, f.P)
+    GC.@preserve flat begin
+        ks = kernels(flat)
+        check(ccall((:ngp_factor_components, LIBNGP), Int32,
+                    (Ptr{Cvoid}, Ptr{Int32}, Ptr{NgpKernel}, Int32, Ptr{Float64}, Ptr{Float64},
+                     Ptr{Float64}, Ptr{Float64}, Ptr{Int32}),
+                    f.h, counts, ks, m, t_new, mu, sg, var, info), "ngp_factor_components")
+    end
+    first = cumsum(vcat(0, Int.(counts))); soff = cumsum(vcat(0, sizes))
+    return (mu = [mu[:, first[p]+1:first[p+1]] for p in 1:f.P],
+            var = [var[:, first[p]+1:first[p+1]] for p in 1:f.P],
+            sigma = [reshape(sg[soff[p]+1:soff[p+1]], Int(counts[p]) * m, Int(counts[p]) * m) for p in 1:f.P],
+            info = info)
+end
+
 "Draws from S mixtures over the same components on the device (include/ngp.h `ngp_mixture_sample`)."
 function mixture_sample(c::Context, w::Matrix{Float64},        # P x S  (column = scenario)
                         mu::Array{Float64,3},                   # m x S x P
@@ -943,6 +990,52 @@ function predict_mvn_lockstep(ms::Vector{GPModel}, dates::AbstractVector{<:Dates
         off += length(m.particles)
     end
     return out
+end
+
+"One additive part of a particle's kernel: `kind` is :trend (a Linear inside), :seasonal (a Periodic and no Linear) or :other."
+struct Component
+    tree::Node
+    label::String
+    kind::Symbol
+end
+component_kind(p::Program) = 2 in p.ops ? :trend : (5 in p.ops ? :seasonal : :other)
+const NODE_NAMES = ("Constant", "Linear", "SquaredExponential", "GammaExponential", "Periodic", "Plus",
+                    "Times", "ChangePoint")
+function label(n::Node)
+    ps = join(string.(n.params), ", ")
+    isleaf(n) && return "$(NODE_NAMES[n.op])($ps)"
+    return "$(NODE_NAMES[n.op])($(label(n.left)), $(label(n.right))$(isempty(ps) ? "" : ", " * ps))"
+end
+
+"AutoGP.decompose: per particle the additive parts of its kernel (a ChangePoint is one part)."
+function decompose(m::GPModel)
+    return [[Component(from_program(c), label(from_program(c)), component_kind(c))
+             for c in kernel_components(p)] for p in m.particles]
+end
+
+"""
+The additive decomposition of the forecast on `dates`, original scale of y: per particle `means`
+(m x C_p), `var` (m x C_p) and the joint `sigma` of its parts, the particle `weights`, the parts'
+`kinds`, and `offset` — the constant of the y-transform, which belongs to no part (forecast without
+noise = offset + sum of the parts).  One query of a resident factor (`ngp_factor_components`); the
+horizon is limited as stated by `components` (the Python mirror serves longer ones in date blocks).
+"""
+function predict_components(m::GPModel, dates::AbstractVector{<:Dates.TimeType})
+    parts = decompose(m)
+    t, y = _obs(m)
+    cmax = maximum(length.(parts))
+    cmax * length(dates) <= horizon_room(length(t)) || throw(ArgumentError(
+        "predict_components: $(length(dates)) dates x $cmax parts, but one call carries at most " *
+        "$(horizon_room(length(t))) rows beside $(length(t)) observations (NGP_MAX_AUX = $NGP_MAX_AUX)"))
+    f = Factor(m.ctx, m.particles, t, y)
+    comps = [[Program(c.ops, c.params, 0.0) for c in kernel_components(p)] for p in m.particles]
+    o = components(f, comps, _model_time(m, dates))
+    raise_if_not_posdef(o.info)
+    w, _, _ = weights_normalize(m.log_weights)
+    s = 1 / m.y_slope
+    return (means = [a .* s for a in o.mu], var = [a .* s^2 for a in o.var],
+            sigma = [a .* s^2 for a in o.sigma], weights = w,
+            kinds = [[c.kind for c in ps] for ps in parts], offset = -m.y_intercept * s)
 end
 
 """

@@ -38,6 +38,7 @@ SYMBOLS = (
     "ngp_selftest_mfma_f32_layout", "ngp_set_combining", "ngp_combine_stats",
     "ngp_weights_unpad_normalize", "ngp_grad_job_info", "ngp_set_batch_invariant", "ngp_set_short_series_path",
     "ngp_mixture_cdf", "ngp_mixture_quantiles", "ngp_mixture_crps", "ngp_microbench_mixture_pairs",
+    "ngp_kernel_components", "ngp_factor_components",
 )
 
 
@@ -116,6 +117,8 @@ def load():
         "ngp_factor_nowcast": (i32, [vp, i32, f64p, i32, f64p, i32, f64p, i32, f64p, f64p, f64p,
                                      f64p, i32p]),
         "ngp_factor_destroy": (None, [vp]),
+        "ngp_kernel_components": (i32, [KP, i32p, i32p, i32p, i32p, i32p]),
+        "ngp_factor_components": (i32, [vp, i32p, KP, i32, f64p, f64p, f64p, f64p, i32p]),
         "ngp_mixture_sample": (i32, [vp, i32, i32, i32, f64p, f64p, f64p, i32, C.c_uint64, f64p,
                                      i32p, i32p]),
         "ngp_mixture_cdf": (i32, [vp, i32, i32, f64p, f64p, f64p, i32, f64p, f64p, i32p]),
@@ -159,6 +162,23 @@ def _chk(st: int, where: str):
 def kernel_check(program) -> int:
     ka = KernelArray([program])
     return int(load().ngp_kernel_check(C.byref(ka.arr[0])))
+
+
+def kernel_components(program):
+    """The additive components of a program (``ngp_kernel_components``): the maximal non-Plus
+    subtrees under the root's Plus nodes, left to right, each a program of its own —
+    ``[(ops, params, noise), ...]`` with the slices of the caller's arrays."""
+    from ._abi import NGP_MAX_OPS
+    ka = KernelArray([program])
+    cap = NGP_MAX_OPS // 2 + 1
+    cnt = C.c_int32()
+    of, ol, pf, pl = (np.zeros(cap, dtype=np.int32) for _ in range(4))
+    _chk(load().ngp_kernel_components(C.byref(ka.arr[0]), C.byref(cnt), iptr(of), iptr(ol), iptr(pf),
+                                      iptr(pl)), "ngp_kernel_components")
+    ops = np.asarray(program[0], dtype=np.int32).reshape(-1)
+    params = np.asarray(program[1], dtype=np.float64).reshape(-1)
+    return [(ops[of[i]:of[i] + ol[i]].copy(), params[pf[i]:pf[i] + pl[i]].copy(), float(program[2]))
+            for i in range(int(cnt.value))]
 
 
 def weights_normalize(logw):
@@ -368,6 +388,35 @@ class Factor:
                                        dptr(lf), _nullable(mu), _nullable(sg), iptr(info)),
              "ngp_factor_nowcast")
         return dict(logml_base=lb, logml_full=lf, mu=mu, sigma=sg, info=info)
+
+    def components(self, comps, t_new, want_sigma=True):
+        """The joint posterior of every particle's additive parts (``ngp_factor_components``).
+        ``comps``: per particle the list of its component programs (any kernels: the library does
+        not check that they sum to the particle's).  Returns ``mu`` and ``var`` as lists of
+        [C_p, m] arrays, ``sigma`` as a list of [C_p m, C_p m] arrays (row = c m + j; None without
+        ``want_sigma``) and ``info`` [P]; the outputs of a particle with info > 0 are NaN."""
+        if len(comps) != self.P:
+            raise ValueError("one list of component programs per particle")
+        t_new = as_f64(t_new)
+        m = t_new.size
+        counts = np.array([len(c) for c in comps], dtype=np.int32)
+        ka = KernelArray([prog for c in comps for prog in c])
+        tot = int(counts.sum())
+        mu, var = np.empty((tot, m)), np.empty((tot, m))
+        sizes = (counts.astype(np.int64) * m) ** 2
+        sg = np.empty(int(sizes.sum())) if want_sigma else None
+        info = np.zeros(self.P, dtype=np.int32)
+        _chk(load().ngp_factor_components(self._h, iptr(counts), ka.arr, m, dptr(t_new) if m else None,
+                                          dptr(mu), _nullable(sg), dptr(var), iptr(info)),
+             "ngp_factor_components")
+        first = np.concatenate([[0], np.cumsum(counts)])
+        soff = np.concatenate([[0], np.cumsum(sizes)])
+        return dict(
+            mu=[mu[first[p]:first[p + 1]] for p in range(self.P)],
+            var=[var[first[p]:first[p + 1]] for p in range(self.P)],
+            sigma=([sg[soff[p]:soff[p + 1]].reshape(int(counts[p]) * m, int(counts[p]) * m)
+                    for p in range(self.P)] if want_sigma else None),
+            info=info)
 
     def predict(self, t_new, noise_on_new=True):
         r = self.nowcast(np.zeros(0), np.zeros((1, 0)), t_new, noise_on_new)

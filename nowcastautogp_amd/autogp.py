@@ -39,7 +39,7 @@ from ._lib import PosDefException
 
 __all__ = ["GPModel", "Schedule", "fit_smc", "add_data", "maybe_resample", "num_particles",
            "mcmc_structure", "mcmc_parameters", "predict_mvn", "MixtureMVN", "MixtureMarginals",
-           "HipEngine"]
+           "HipEngine", "decompose", "predict_components", "Component", "ComponentForecast"]
 
 
 # ---------------------------------------------------------------------------------------------
@@ -1177,3 +1177,206 @@ def rand_lockstep(mixes: Sequence[MixtureMVN], draws: int, engine=None) -> List[
     if bad.size:
         raise PosDefException(int(info[tuple(bad[0])]), int(bad[0][1]))
     return [np.ascontiguousarray(out[j].T) for j in range(len(mixes))]
+
+
+# ---------------------------------------------------------------------------------------------
+# additive decomposition (AutoGP's ``decompose``; include/ngp.h "additive decomposition")
+# ---------------------------------------------------------------------------------------------
+@dataclass
+class Component:
+    """One additive part of a particle's kernel: a maximal non-Plus subtree under the root's Plus
+    nodes.  ``kind``: "trend" if the subtree contains a Linear, "seasonal" if it contains a Periodic
+    and no Linear, "other" otherwise."""
+    tree: gp.Node
+    label: str
+    kind: str
+
+
+def component_kind(ops) -> str:
+    ops = [int(o) for o in ops]
+    if gp.LINEAR in ops:
+        return "trend"
+    return "seasonal" if gp.PERIODIC in ops else "other"
+
+
+def decompose(model: GPModel) -> List[List[Component]]:
+    """Per particle, the additive parts of its kernel, left to right (``ngp_kernel_components``
+    does the slicing).  A ChangePoint is one part (its summands are not kernels of the grammar); a
+    Plus below a Times or a ChangePoint is not split."""
+    from . import _lib
+    out = []
+    for ops, params, noise in model.programs():
+        parts = []
+        for c_ops, c_par, _ in _lib.kernel_components((ops, params, noise)):
+            tree = gp.from_program(c_ops, c_par)
+            parts.append(Component(tree, str(tree), component_kind(c_ops)))
+        out.append(parts)
+    return out
+
+
+class AtomMixtureMarginals(MixtureMarginals):
+    """A mixture whose share ``atom`` sits in a point mass at 0 (particles that have no component
+    of a group contribute exactly 0 to that group); ``means`` / ``variances`` / ``weights`` are the
+    continuous components, the weights summing to 1 among themselves.  The point mass is handled
+    here, on the host; the continuous rest is a ``MixtureMarginals`` like any other."""
+
+    def __init__(self, means, variances, weights, atom: float, engine=None):
+        super().__init__(means, variances, weights, engine=engine)
+        if not 0.0 < atom < 1.0:
+            raise ValueError("AtomMixtureMarginals: 0 < atom < 1")
+        self.atom = float(atom)
+
+    def _rest(self):
+        return MixtureMarginals(self.means, self.variances, self.weights, engine=self.engine)
+
+    def mean(self):
+        return (1.0 - self.atom) * super().mean()
+
+    def cdf(self, x):
+        x = np.asarray(x, dtype=np.float64)
+        m = self.means.shape[1]
+        F = self._rest().cdf(x)
+        step = (x.reshape(m, -1) >= 0.0).astype(np.float64).reshape(F.shape)
+        return (1.0 - self.atom) * F + self.atom * step
+
+    def quantile(self, probs, inv_transformation=lambda y: y):
+        p = np.atleast_1d(np.asarray(probs, dtype=np.float64))
+        if p.ndim != 1 or not np.all((p > 0) & (p < 1)):
+            raise ValueError("MixtureMarginals.quantile: probs in (0, 1)")
+        a, rest = self.atom, self._rest()
+        m = self.means.shape[1]
+        F0 = (1.0 - a) * rest.cdf(np.zeros(m))                    # mass strictly below the atom
+        below, above = p / (1.0 - a), (p - a) / (1.0 - a)         # levels of the rest on either side
+        q = np.zeros((m, p.size))
+        for levels, pick in ((below, p[None, :] < F0[:, None]), (above, p[None, :] > F0[:, None] + a)):
+            ok = (levels > 0) & (levels < 1)
+            if ok.any() and pick[:, ok].any():
+                q[:, ok] = np.where(pick[:, ok], rest.quantile(levels[ok]), q[:, ok])
+        from .nowcast import _apply
+        return _apply(inv_transformation, q)
+
+    def crps(self, y):
+        y = np.asarray(y, dtype=np.float64).reshape(-1)
+        a, rest = self.atom, self._rest()
+        c_rest = rest.crps(y)                                     # E|X - y| - E|X - X'| / 2 of the rest
+        w, mu, var = rest._active()
+        e_y = w @ _abs_moment(y[None, :] - mu, var)
+        e_0 = w @ _abs_moment(mu, var)
+        e_xx = 2.0 * (e_y - c_rest)
+        return ((1.0 - a) * e_y + a * np.abs(y)
+                - 0.5 * ((1.0 - a) ** 2 * e_xx + 2.0 * a * (1.0 - a) * e_0))
+
+
+class ComponentForecast:
+    """The joint posterior of every particle's additive parts on the forecast dates, on the
+    ORIGINAL scale of y (what ``predict_components`` returns):
+
+        means[p]  [C_p, m]          posterior mean of part c
+        sigma[p]  [C_p m, C_p m]    joint covariance of the parts, row = c m + j
+        var[p]    [C_p, m]          its diagonal (always there)
+        weights   [P]               particle weights
+        kinds[p], labels[p]         per part: "trend" / "seasonal" / "other", the printed sub-kernel
+        offset                      the constant of the y-transform: it belongs to no part, the
+                                    forecast without noise is  offset + sum_c part_c
+        date_blocks                 None, or the (lo, hi) blocks of dates a long horizon was served
+                                    in: covariances ACROSS blocks are then not formed and ``sigma`` is
+                                    block-diagonal in dates (zeros elsewhere)
+
+    The parts are the latent functions; observation noise is a part of its own (the remainder) and
+    appears nowhere here."""
+
+    def __init__(self, means, sigma, var, weights, kinds, labels, offset, date_blocks=None, engine=None):
+        self.means, self.sigma, self.var = means, sigma, var
+        self.weights = np.asarray(weights, dtype=np.float64)
+        self.kinds, self.labels, self.offset = kinds, labels, float(offset)
+        self.date_blocks, self.engine = date_blocks, engine
+
+    def grouped(self, by: str = "kind"):
+        """Per group, the weighted mixture over particles of the SUM of that group's parts: mean
+        sum_{c in g} mu_c, variance per date sum_{c, c' in g} Sigma_cc'[j, j].  ``by``: "kind" or
+        "label".  A particle without a part in a group contributes a point mass at 0 (an
+        ``AtomMixtureMarginals``); groups are the ones at least one particle has."""
+        keys = {"kind": self.kinds, "label": self.labels}.get(by)
+        if keys is None:
+            raise ValueError('ComponentForecast.grouped: by = "kind" or "label"')
+        names = []
+        for ks in keys:
+            for k in ks:
+                if k not in names:
+                    names.append(k)
+        out = {}
+        for name in names:
+            mus, vs, ws, atom = [], [], [], 0.0
+            for p, ks in enumerate(keys):
+                idx = [c for c, k in enumerate(ks) if k == name]
+                if not idx:
+                    atom += self.weights[p]
+                    continue
+                C, m = self.means[p].shape
+                blocks = np.einsum("ajbj->abj", self.sigma[p].reshape(C, m, C, m))   # same-date entries
+                mus.append(self.means[p][idx].sum(axis=0))
+                vs.append(blocks[np.ix_(idx, idx)].sum(axis=(0, 1)))
+                ws.append(self.weights[p])
+            atom /= float(np.sum(self.weights))
+            if atom > 0.0:
+                out[name] = AtomMixtureMarginals(np.stack(mus), np.stack(vs), np.asarray(ws), atom,
+                                                 engine=self.engine)
+            else:
+                out[name] = MixtureMarginals(np.stack(mus), np.stack(vs), np.asarray(ws),
+                                             engine=self.engine)
+        return out
+
+
+def component_blocks(n_obs: int, c_max: int, m: int):
+    """The C m component rows of a particle share the aux block with the tail observations and the
+    y row: (n mod 64) + 1 + C m <= NGP_MAX_AUX (include/ngp.h).  None when the m dates fit one
+    call, else the (lo, hi) blocks of dates to query one by one."""
+    from ._abi import NGP_MAX_AUX
+    per = (NGP_MAX_AUX - (n_obs % 64) - 1) // max(c_max, 1)
+    if m <= per:
+        return None
+    if per < 1:
+        raise ValueError(f"predict_components: a kernel of {c_max} additive parts leaves no room "
+                         f"for a forecast date beside the factor (NGP_MAX_AUX = {NGP_MAX_AUX} rows)")
+    return [(lo, min(lo + per, m)) for lo in range(0, m, per)]
+
+
+def predict_components(model: GPModel, ds) -> ComponentForecast:
+    """The additive decomposition of the model's forecast on the dates ``ds``: ONE query of the
+    model's resident factor (``ngp_factor_components``) per block of dates — no refit on a
+    sub-kernel, which would not be conditioned on the same K.  Needs an engine with resident
+    factors (there is no host path).  In a sharded run every rank gets its own particles' parts,
+    with their globally normalised weights."""
+    fac = model._factor()
+    if fac is None or not hasattr(fac, "components"):
+        raise RuntimeError("predict_components needs the engine's resident factor (ngp_factor_components)")
+    parts = decompose(model)
+    comps = [[gp.to_program(c.tree) + (0.0,) for c in ps] for ps in parts]
+    t, _ = model._obs()
+    t_new = model.ds_transform.apply(to_days(list(ds)))
+    m = t_new.size
+    blocks = component_blocks(t.size, max(len(ps) for ps in parts), m)
+    P = len(parts)
+    means = [np.empty((len(ps), m)) for ps in parts]
+    var = [np.empty((len(ps), m)) for ps in parts]
+    sigma = [np.zeros((len(ps) * m, len(ps) * m)) for ps in parts]
+    for lo, hi in (blocks or [(0, m)]):
+        o = fac.components(comps, t_new[lo:hi])
+        bad = np.flatnonzero(o["info"])
+        if bad.size:
+            raise PosDefException(int(o["info"][bad[0]]), int(bad[0]))
+        k = hi - lo
+        for p in range(P):
+            C = len(parts[p])
+            means[p][:, lo:hi] = o["mu"][p]
+            var[p][:, lo:hi] = o["var"][p]
+            sigma[p].reshape(C, m, C, m)[:, lo:hi, :, lo:hi] = o["sigma"][p].reshape(C, k, C, k)
+    inv = 1.0 / model.y_transform.slope           # y = (y_model - intercept) / slope
+    means = [a * inv for a in means]
+    var = [a * (inv * inv) for a in var]
+    sigma = [a * (inv * inv) for a in sigma]
+    w, _ = distributed.normalize_log_weights(model.log_weights[:, None],
+                                             P_total=model.n_particles_total)
+    return ComponentForecast(means, sigma, var, w[:, 0], [[c.kind for c in ps] for ps in parts],
+                             [[c.label for c in ps] for ps in parts],
+                             -model.y_transform.intercept * inv, blocks, engine=model._eng())

@@ -1583,7 +1583,10 @@ struct ngp_factor {
 namespace {
 
 // run the job of a cached-factor query: only the aux rows are filled and swept
-ngp_status factor_run(ngp_factor *f, ngp_job *j, bool create) {
+// comp (ngp_factor_components): the job's forecast rows are component rows — filled a second time
+// under their own programs, and read by the component epilogue (comp_work: its [B][stride] buffer)
+ngp_status factor_run(ngp_factor *f, ngp_job *j, bool create, const CompPtrs *comp = nullptr,
+                      double *comp_work = nullptr, int64_t comp_work_stride = 0) {
     ngp_ctx *c = f->ctx;
     std::lock_guard<std::mutex> lk(c->mu);
     HIPCHK(hipSetDevice(c->device));
@@ -1634,6 +1637,8 @@ ngp_status factor_run(ngp_factor *f, ngp_job *j, bool create) {
             HIPCHK(hipMemcpyAsync(j->info, f->info, sizeof(int32_t) * (size_t)P,
                                   hipMemcpyDeviceToDevice, s));
             tm.run(cost_fill_aux(g, P), [&] { launch_fill(g, p, P, sp, s, /*aux_only=*/true); });
+            if (comp)
+                tm.run(4, 0.0, 8.0 * P * (double)g.m * g.n0, [&] { launch_component_fill(g, p, *comp, P, sp, s); });
             // right-looking sweep of the aux rows through the resident factor
             for (int jj = 0; jj < g.nb0; ++jj) {
                 ChunkPtrs pj = p;
@@ -1653,7 +1658,13 @@ ngp_status factor_run(ngp_factor *f, ngp_job *j, bool create) {
         e.sig = (const double *)sig;
         e.qpts = j->qpts;
     }
-    tm.run(3, 0.0, 0.0, [&] { launch_epilogue(g, e, sp, s); });
+    if (comp) {
+        e.work = comp_work;
+        e.work_stride = comp_work_stride;
+        tm.run(3, 0.0, 0.0, [&] { launch_component_epilogue(g, e, *comp, sp, s); });
+    } else {
+        tm.run(3, 0.0, 0.0, [&] { launch_epilogue(g, e, sp, s); });
+    }
     hipError_t err = hipStreamSynchronize(s);
     if (err == hipSuccess) err = hipGetLastError();
     tm.resolve(c->prof);
@@ -1758,6 +1769,140 @@ extern "C" ngp_status ngp_factor_nowcast(ngp_factor *f, int32_t d, const double 
     if (st) return st;
     st = factor_run(f, job, /*create=*/false);
     if (!st) st = ngp_job_fetch(job, logml_base, logml_full, mu, sigma, info);
+    ngp_job_destroy(job);
+    return st;
+}
+
+// ---- additive decomposition ---------------------------------------
+// The components of a tree: its maximal non-Plus subtrees reached from the root through Plus nodes
+// only, left to right.  In postfix order a subtree is a contiguous slice of ops and of params.
+extern "C" ngp_status ngp_kernel_components(const ngp_kernel *k, int32_t *count, int32_t *op_first,
+                                            int32_t *op_len, int32_t *par_first, int32_t *par_len) {
+    if (!k || !count) return NGP_ERR_ARG;
+    ngp_status st = check_program(k);
+    if (st) return st;
+    struct Sub { int left, right, op0, par0, par1; };   // children, first op, params [par0, par1)
+    std::vector<Sub> nodes;
+    std::vector<int> stack;
+    int pi = 0;
+    for (int i = 0; i < k->n_ops; ++i) {
+        const int op = k->ops[i];
+        Sub nd{-1, -1, i, pi, 0};
+        if (op >= NGP_OP_PLUS) {
+            nd.right = stack.back(); stack.pop_back();
+            nd.left = stack.back(); stack.pop_back();
+            nd.op0 = nodes[(size_t)nd.left].op0;
+            nd.par0 = nodes[(size_t)nd.left].par0;
+        }
+        pi += k_nparams[op];
+        nd.par1 = pi;
+        nodes.push_back(nd);
+        stack.push_back(i);
+    }
+    int nc = 0;
+    std::vector<int> todo{stack.back()};
+    while (!todo.empty()) {
+        const int i = todo.back();
+        todo.pop_back();
+        const Sub &nd = nodes[(size_t)i];
+        if (k->ops[i] == NGP_OP_PLUS) {
+            todo.push_back(nd.right);   // the left summand comes out first
+            todo.push_back(nd.left);
+            continue;
+        }
+        if (op_first) op_first[nc] = nd.op0;
+        if (op_len) op_len[nc] = i - nd.op0 + 1;
+        if (par_first) par_first[nc] = nd.par0;
+        if (par_len) par_len[nc] = nd.par1 - nd.par0;
+        ++nc;
+    }
+    *count = nc;
+    return NGP_OK;
+}
+
+extern "C" ngp_status ngp_factor_components(ngp_factor *f, const int32_t *comp_count,
+                                            const ngp_kernel *comps, int32_t m, const double *t_new,
+                                            double *mu, double *sigma, double *var, int32_t *info) {
+    if (!f || !comp_count || !comps || !t_new || !mu || m < 1) return NGP_ERR_ARG;
+    const int P = f->P;
+    std::vector<int32_t> first((size_t)P + 1, 0);
+    std::vector<int64_t> sig_off((size_t)P, 0);
+    int cmax = 0;
+    int64_t sig_total = 0;
+    for (int b = 0; b < P; ++b) {
+        const int cb = comp_count[b];
+        if (cb < 1) return NGP_ERR_ARG;
+        if ((int64_t)(f->n % NB) + 1 + (int64_t)cb * m > NGP_MAX_AUX) return NGP_ERR_TOO_LARGE;
+        first[(size_t)b + 1] = first[(size_t)b] + cb;
+        sig_off[(size_t)b] = sig_total;
+        sig_total += (int64_t)cb * m * cb * m;
+        cmax = std::max(cmax, cb);
+    }
+    const size_t ncomp = (size_t)first[(size_t)P];
+    std::vector<DevProgram> hp(ncomp);
+    for (size_t i = 0; i < ncomp; ++i) {
+        ngp_status st = compile_program(&comps[i], &hp[i], nullptr);
+        if (st) return st;
+    }
+    // the query's geometry: cmax groups of the m dates (an item with fewer components leaves its
+    // last groups zero); no appended points, one scenario, no noise on the new points
+    std::vector<double> t_rep((size_t)cmax * m);
+    for (int c = 0; c < cmax; ++c) std::copy(t_new, t_new + m, t_rep.begin() + (size_t)c * m);
+    ngp_ctx *c = f->ctx;
+    static const double dummy = 0.0;
+    ngp_job *job = nullptr;
+    ngp_status st = stage_general(c, P, f->kernels.data(), f->n, f->t.data(), f->y.data(), f->ldy, 0,
+                                  &dummy, 1, &dummy, 0, cmax * m, t_rep.data(), 0, &job);
+    if (st) return st;
+    const size_t n_out = ncomp * (size_t)m;
+    const int64_t work_stride = (int64_t)cmax * m * (job->g.da + 1);
+    const size_t o_first = sizeof(DevProgram) * ncomp, o_sig = (o_first + 4 * first.size() + 7) & ~(size_t)7,
+                 in_bytes = o_sig + 8 * sig_off.size();
+    std::vector<unsigned char> h_in(in_bytes);
+    std::memcpy(h_in.data(), hp.data(), o_first);
+    std::memcpy(h_in.data() + o_first, first.data(), 4 * first.size());
+    std::memcpy(h_in.data() + o_sig, sig_off.data(), 8 * sig_off.size());
+    void *d_in = nullptr, *d_mu = nullptr, *d_sigma = nullptr, *d_var = nullptr, *d_work = nullptr;
+    {
+        std::lock_guard<std::mutex> lk(c->mu);
+        if (hipSetDevice(c->device) != hipSuccess) st = NGP_ERR_NO_DEVICE;
+        if (!st) st = c->alloc(&d_in, in_bytes);
+        if (!st) st = c->alloc(&d_mu, 8 * n_out);
+        if (!st && sigma) st = c->alloc(&d_sigma, 8 * (size_t)sig_total);
+        if (!st && var) st = c->alloc(&d_var, 8 * n_out);
+        if (!st) st = c->alloc(&d_work, 8 * (size_t)P * (size_t)work_stride);
+        if (!st && hipMemcpyAsync(d_in, h_in.data(), in_bytes, hipMemcpyHostToDevice, c->stream) != hipSuccess)
+            st = NGP_ERR_STATE;
+    }
+    if (!st) {
+        CompPtrs cp{};
+        cp.progs = (const DevProgram *)d_in;
+        cp.first = (const int32_t *)((unsigned char *)d_in + o_first);
+        cp.sig_off = (const int64_t *)((unsigned char *)d_in + o_sig);
+        cp.mu = (double *)d_mu;
+        cp.sigma = (double *)d_sigma;
+        cp.var = (double *)d_var;
+        cp.m = m;
+        cp.cmax = cmax;
+        st = factor_run(f, job, /*create=*/false, &cp, (double *)d_work, work_stride);
+    }
+    if (!st) st = ngp_job_fetch(job, nullptr, nullptr, nullptr, nullptr, info);
+    {
+        std::lock_guard<std::mutex> lk(c->mu);
+        hipStream_t s = c->stream;
+        hipError_t e = hipSuccess;
+        if (!st && hipSetDevice(c->device) != hipSuccess) st = NGP_ERR_NO_DEVICE;
+        if (!st) {
+            e = hipMemcpyAsync(mu, d_mu, 8 * n_out, hipMemcpyDeviceToHost, s);
+            if (e == hipSuccess && sigma)
+                e = hipMemcpyAsync(sigma, d_sigma, 8 * (size_t)sig_total, hipMemcpyDeviceToHost, s);
+            if (e == hipSuccess && var) e = hipMemcpyAsync(var, d_var, 8 * n_out, hipMemcpyDeviceToHost, s);
+        }
+        // (also on an error path: the staging copy may still be reading h_in)
+        const hipError_t es = hipStreamSynchronize(s);
+        if (!st && (e != hipSuccess || es != hipSuccess)) st = (ngp_status)(e != hipSuccess ? e : es);
+        c->release(d_in); c->release(d_mu); c->release(d_sigma); c->release(d_var); c->release(d_work);
+    }
     ngp_job_destroy(job);
     return st;
 }

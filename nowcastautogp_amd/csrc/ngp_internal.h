@@ -173,6 +173,19 @@ struct EpiPtrs {
     const int32_t *qpts;      // [npts]
 };
 
+// ngp_factor_components (ngp_component_kernels.h): the forecast rows of the query are Cmax groups of
+// m dates, group c of an item evaluated under the item's c-th component program
+struct CompPtrs {
+    const DevProgram *progs;  // [sum C_b] component programs, item-major
+    const int32_t *first;     // [B + 1] an item's first component (running sum of C_b)
+    const int64_t *sig_off;   // [B] where the item's [C_b m][C_b m] block starts in sigma
+    double       *mu;         // [sum C_b][m]
+    double       *sigma;      // the items' blocks back to back, or null
+    double       *var;        // [sum C_b][m], or null
+    int32_t       m;          // dates per component
+    int32_t       cmax;       // max C_b: the geometry's m is cmax * m
+};
+
 // ---- short series in one launch (ngp_small_kernels.h) ------------------------------------
 constexpr int SM_WAVES = 8, SM_THREADS = 64 * SM_WAVES;   // two waves per SIMD: 256 VGPRs each
 constexpr int SM_NSLOT = 20;           // register blocks per wave (8 VGPRs each)
@@ -261,6 +274,12 @@ void launch_toep_grad(const JobGeom &g, const ChunkPtrs &p, const double *A, dou
 void launch_toep_quad(const JobGeom &g, const double *L, double *quad, int Bc, hipStream_t s);
 void launch_gram(const JobGeom &g, const double *L, double *G, int Bc, hipStream_t s);
 void launch_epilogue(const JobGeom &g, const EpiPtrs &p, const DevSpec &sp, hipStream_t s);
+// component rows of a resident factor's query: their fill (behind launch_fill(.., aux_only), which
+// leaves the tail and y' rows) and the epilogue that stands in for launch_epilogue
+void launch_component_fill(const JobGeom &g, const ChunkPtrs &p, const CompPtrs &cp, int Bc,
+                           const DevSpec &sp, hipStream_t s);
+void launch_component_epilogue(const JobGeom &g, const EpiPtrs &p, const CompPtrs &cp,
+                               const DevSpec &sp, hipStream_t s);
 void launch_cov(const DevProgram *progs, int B, const double *t1, int n1, const double *t2,
                 int n2, int add_diag, double *out, const DevSpec &sp, hipStream_t s);
 void launch_mixture_sample(int P, int S, int m, const double *w, const double *mu, double *chol,

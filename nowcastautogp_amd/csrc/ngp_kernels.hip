@@ -14,7 +14,8 @@
 //                         helpers, cov_kernel, tables_kernel, the four fill kernels, kapply_kernel
 //   ngp_grad_kernels.h    grad_kinv*, grad_alpha, the three grad_contract* kernels, toep_*, grad_reduce
 //   ngp_col_kernels.h     chol_diag_kernel and the column kernels; ngp_small_kernels.h: short series
-//                         in one launch; ngp_mixture_kernels.h: mixture summaries
+//                         in one launch; ngp_mixture_kernels.h: mixture summaries;
+//                         ngp_component_kernels.h: fill and epilogue of ngp_factor_components
 //   this file             aux_update / aux_back_* / refine_gram_* (resident factor, Gram refinement),
 //                         diag_ahead, gram, epilogue, mixture sampling, the probe and stream kernels,
 //                         and every launcher
@@ -47,6 +48,7 @@
 #include "ngp_small_kernels.h"
 #include "ngp_mixture_kernels.h"
 #include "ngp_tree_kernels.h"
+#include "ngp_component_kernels.h"
 #include "ngp_grad_kernels.h"
 
 namespace ngp {
@@ -1088,6 +1090,19 @@ void launch_epilogue(const JobGeom &g, const EpiPtrs &p, const DevSpec &sp, hipS
     const int lds_work = bytes > 0 && bytes <= 60 * 1024;
     hipLaunchKernelGGL(epilogue_kernel, dim3(g.B), dim3(64), lds_work ? bytes : 0, s, g, p, sp,
                        lds_work);
+}
+
+void launch_component_fill(const JobGeom &g, const ChunkPtrs &p, const CompPtrs &cp, int Bc,
+                           const DevSpec &sp, hipStream_t s) {
+    if (g.n0 == 0) return;
+    const int mt = (cp.m + NB - 1) / NB;
+    hipLaunchKernelGGL(component_fill_kernel, dim3(g.nb0 * mt, Bc, cp.cmax), dim3(256), 0, s, g, p, cp,
+                       sp);
+}
+
+void launch_component_epilogue(const JobGeom &g, const EpiPtrs &p, const CompPtrs &cp,
+                               const DevSpec &sp, hipStream_t s) {
+    hipLaunchKernelGGL(component_epilogue_kernel, dim3(g.B), dim3(64), 0, s, g, p, cp, sp);
 }
 
 void launch_cov(const DevProgram *progs, int B, const double *t1, int n1, const double *t2, int n2,
