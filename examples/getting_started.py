@@ -96,6 +96,12 @@ def main():
     for k in range(horizon):
         print(f"  {dates[n + k]}  " + "".join(f"{b[k, 0]:16.3f}{b[k, 1]:8.3f}{b[k, 2]:8.3f}"
                                               for b in bands.values()))
+    # the same question for the nowcast-conditioned forecast: a ChangePoint root is split into its
+    # two windows, and every scenario of the nowcasts weighs 1 / D
+    fn = nc.forecast_components_with_nowcasts(model, nowcasts, dates[n:n + horizon], split="changepoint")
+    print(f"with nowcasts: {len(fn.means)} (scenario, particle) entries; parts of particle 0: {fn.labels[0]}")
+    for kind, g in fn.grouped().items():
+        print(f"  {kind:>9s}, week 1: median {g.quantile([0.5])[0, 0]:.3f}")
 
 
 if __name__ == "__main__":

@@ -459,8 +459,9 @@ void       ngp_factor_destroy(ngp_factor *f);
  * tree is almost always a sum.  Its COMPONENTS are the maximal non-Plus subtrees reached from the
  * root through Plus nodes only; in postfix order each is a contiguous slice of ops and of params,
  * so a component is itself a valid ngp_kernel.  A tree whose root is not Plus has one component,
- * itself.  (A ChangePoint is additive too, but its two summands are not expressible in the
- * grammar: it is never split, and neither is a Plus below a Times or a ChangePoint.)
+ * itself.  ngp_kernel_components never splits a ChangePoint, nor a Plus below a Times or a
+ * ChangePoint; ngp_kernel_terms below does (a ChangePoint's two summands ARE expressible in the
+ * grammar: ChangePoint(k1, Constant(0)) and ChangePoint(Constant(0), k2)).
  *
  * For particle p with components c = 1..C, k = sum_c k_c, training times t,
  * K = k(t,t) + (noise + jitter) I, query dates t* (m of them) and X_c = k_c(t*, t):
@@ -500,6 +501,60 @@ ngp_status ngp_kernel_components(const ngp_kernel *k, int32_t *count, int32_t *o
 ngp_status ngp_factor_components(ngp_factor *f, const int32_t *comp_count, const ngp_kernel *comps,
                                  int32_t m, const double *t_new, double *mu, double *sigma,
                                  double *var, int32_t *info);
+
+/* ---- sum-of-products terms; the decomposition conditioned on nowcasts -------------
+ * The trees real fits end in are ChangePoint / Times trees, whose root is no Plus.  The device
+ * blend of a ChangePoint is  s(t1) a s(t2) + (1 - s(t1)) b (1 - s(t2))  in its operand values a, b
+ * under BOTH cp_form values (the form only picks the sigmoid s), i.e. linear in a and in b, and a
+ * Times distributes over a Plus.  The TERMS of a tree T are therefore kernels that sum to T:
+ *     leaf                              {T}
+ *     Plus(l, r)                        terms(l) then terms(r)
+ *     ChangePoint(l, r; th)             {CP(x, Constant(0); th) : x in terms(l)} then
+ *       with NGP_SPLIT_CHANGEPOINT      {CP(Constant(0), y; th) : y in terms(r)}
+ *     Times(l, r) with NGP_SPLIT_TIMES  {Times(x, y)}, x in terms(l) outer, y in terms(r) inner
+ * A ChangePoint / Times without its flag is one term, verbatim (a Plus below it is not split).
+ * The transition of a ChangePoint itself is not split: each windowed term carries it.
+ *
+ * ngp_kernel_terms (host only) writes the terms as NEW programs back to back into ops_out /
+ * params_out; term i is ops_out[op_first[i] .. + op_len[i]), params_out[par_first[i] .. +
+ * par_len[i]).  *count is always the true number of terms.  NGP_ERR_TOO_LARGE (with *count set)
+ * when count > max_terms, when a term does not pass ngp_kernel_check, or when ops_cap / par_cap /
+ * a missing buffer cannot take the terms.  The number of terms, the longest term and the size of
+ * all terms together are known from the tree's structure, so every one of these returns comes
+ * before a term is built: what the call allocates is bounded by ops_cap and par_cap, however many
+ * terms a product of sums asks for.  All six output arrays NULL: the count alone (no term is
+ * built; a term longer than NGP_MAX_OPS / NGP_MAX_PARAMS is still reported).  A term never has
+ * more ops or parameters than the tree.  split = 0 gives
+ * exactly the programs ngp_kernel_components slices.  The tree may be longer than NGP_MAX_OPS
+ * (up to 64 NGP_MAX_OPS) as long as its terms are not.
+ *
+ * ngp_factor_components_nowcast is ngp_factor_components conditioned on d appended points and D
+ * scenarios of their values (ngp_factor_nowcast's t_add, y_add [D x d]): with t+ = [t; t_add],
+ * y+_s = [y; y_add_s], K+ = k(t+, t+) + (noise + jitter) I, X_c = k_c(t*, t+)
+ *     mu_c,s     = X_c (K+)^-1 y+_s                                    [m]
+ *     Sigma_c,c' = delta_cc' k_c(t*, t*) - X_c (K+)^-1 X_c'^T          (the same for every scenario)
+ * One query of the resident factor and one code path with ngp_factor_components: d = 0, D = 1
+ * returns its bits.  Against ngp_factor_nowcast of the same arguments with noise_on_new = 0 the
+ * means of a scenario add up to its mean, the blocks to sigma, and logml_full agrees.
+ *   logml_full [P][D]           as ngp_factor_nowcast; may be NULL
+ *   mu         [sum C_p][D][m]
+ *   sigma, var, info            as ngp_factor_components; a pivot failure among the tail and the
+ *                               appended points reports n0 + k (n0 = 64 floor(n / 64)), the item
+ *                               is NaN in every output, logml_full included
+ * Limit: (n mod 64) + d + 1 + C_p m <= NGP_MAX_AUX for every particle, else NGP_ERR_TOO_LARGE.
+ * NGP_ERR_ARG as ngp_factor_components, and for d < 0, D < 1, null t_add / y_add with d > 0; all
+ * before anything touches a device.  A scenario's outputs depend neither on D nor on its place
+ * among the scenarios (fixed summation order, no floating-point atomics).  Runs under the factor's
+ * spec and the context's lock; not combined with concurrent callers.  Profile classes 4 and 3.  */
+enum { NGP_SPLIT_PLUS = 0, NGP_SPLIT_CHANGEPOINT = 1, NGP_SPLIT_TIMES = 2 };   /* flags, or-ed */
+ngp_status ngp_kernel_terms(const ngp_kernel *k, int32_t split, int32_t max_terms, int32_t *count,
+                            int32_t *op_first, int32_t *op_len, int32_t *par_first, int32_t *par_len,
+                            int32_t *ops_out, int32_t ops_cap, double *params_out, int32_t par_cap);
+ngp_status ngp_factor_components_nowcast(ngp_factor *f, int32_t d, const double *t_add, int32_t D,
+                                         const double *y_add, const int32_t *comp_count,
+                                         const ngp_kernel *comps, int32_t m, const double *t_new,
+                                         double *logml_full, double *mu, double *sigma, double *var,
+                                         int32_t *info);
 
 /* ---- measurement hooks -----------------------------------------------------
  * HIP-event timing of the kernels a job launches, on the stream they are

@@ -332,6 +332,68 @@ function components(f::Factor, comps::Vector{Vector{Program}}, t_new::Vector{Flo
             info = info)
 end
 
+const NGP_SPLIT_PLUS, NGP_SPLIT_CHANGEPOINT, NGP_SPLIT_TIMES = Int32(0), Int32(1), Int32(2)
+
+"""
+The sum-of-products terms of a program (include/ngp.h `ngp_kernel_terms`): new `Program`s that sum
+to it.  `split`: NGP_SPLIT_* flags or-ed (0: the programs of `kernel_components`); a ChangePoint is
+split into its two windows, each blended against Constant(0), a Times distributed over the sums
+below it.  More than `max_terms` terms is an error (NGP_ERR_TOO_LARGE).
+"""
+function kernel_terms(p::Program, split::Integer; max_terms::Integer = typemax(Int32))
+    cnt = Ref{Int32}(0)
+    GC.@preserve p begin
+        k = Ref(NgpKernel(length(p.ops), length(p.params), pointer(p.ops), pointer(p.params), p.noise))
+        check(ccall((:ngp_kernel_terms, LIBNGP), Int32,
+                    (Ref{NgpKernel}, Int32, Int32, Ref{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32},
+                     Ptr{Int32}, Int32, Ptr{Float64}, Int32),
+                    k, split, max_terms, cnt, C_NULL, C_NULL, C_NULL, C_NULL, C_NULL, 0, C_NULL, 0),
+              "ngp_kernel_terms")
+        n = Int(cnt[])
+        of, ol, pf, pl = zeros(Int32, n), zeros(Int32, n), zeros(Int32, n), zeros(Int32, n)
+        ops, par = zeros(Int32, n * length(p.ops)), zeros(Float64, n * length(p.params))
+        check(ccall((:ngp_kernel_terms, LIBNGP), Int32,
+                    (Ref{NgpKernel}, Int32, Int32, Ref{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32},
+                     Ptr{Int32}, Int32, Ptr{Float64}, Int32),
+                    k, split, n, cnt, of, ol, pf, pl, ops, length(ops), par, length(par)),
+              "ngp_kernel_terms")
+        return [Program(ops[of[i]+1:of[i]+ol[i]], par[pf[i]+1:pf[i]+pl[i]], p.noise) for i in 1:n]
+    end
+end
+
+"""
+`components` conditioned on the appended points `t_add` (d) and the scenarios `y_add` (d x D)
+(include/ngp.h `ngp_factor_components_nowcast`).  Returns per particle `mu` (m x D x C_p), `var`
+(m x C_p) and `sigma` (C_p m x C_p m), shared by the scenarios, and `logml_full` (D x P);
+(n mod 64) + d + 1 + C_p m <= NGP_MAX_AUX.
+"""
+function components_nowcast(f::Factor, comps::Vector{Vector{Program}}, t_add::Vector{Float64},
+                            y_add::Matrix{Float64}, t_new::Vector{Float64})
+    length(comps) == f.P || throw(ArgumentError("one vector of component programs per particle"))
+    d, D, m = length(t_add), max(size(y_add, 2), 1), length(t_new)
+    counts = Int32[length(c) for c in comps]
+    flat = reduce(vcat, comps)
+    tot = length(flat)
+    mu, var = Array{Float64}(undef, m, D, tot), Matrix{Float64}(undef, m, tot)
+    sizes = [(Int(c) * m)^2 for c in counts]
+    sg = Vector{Float64}(undef, sum(sizes))
+    lf = Matrix{Float64}(undef, D, f.P)
+    info = zeros(Int32, f.P)
+    GC.@preserve flat begin
+        ks = kernels(flat)
+        check(ccall((:ngp_factor_components_nowcast, LIBNGP), Int32,
+                    (Ptr{Cvoid}, Int32, Ptr{Float64}, Int32, Ptr{Float64}, Ptr{Int32}, Ptr{NgpKernel}, Int32,
+                     Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}),
+                    f.h, d, t_add, D, y_add, counts, ks, m, t_new, lf, mu, sg, var, info),
+              "ngp_factor_components_nowcast")
+    end
+    first = cumsum(vcat(0, Int.(counts))); soff = cumsum(vcat(0, sizes))
+    return (mu = [mu[:, :, first[p]+1:first[p+1]] for p in 1:f.P],
+            var = [var[:, first[p]+1:first[p+1]] for p in 1:f.P],
+            sigma = [reshape(sg[soff[p]+1:soff[p+1]], Int(counts[p]) * m, Int(counts[p]) * m) for p in 1:f.P],
+            logml_full = lf, info = info)
+end
+
 "Draws from S mixtures over the same components on the device (include/ngp.h `ngp_mixture_sample`)."
 function mixture_sample(c::Context, w::Matrix{Float64},        # P x S  (column = scenario)
                         mu::Array{Float64,3},                   # m x S x P

@@ -39,6 +39,7 @@ SYMBOLS = (
     "ngp_weights_unpad_normalize", "ngp_grad_job_info", "ngp_set_batch_invariant", "ngp_set_short_series_path",
     "ngp_mixture_cdf", "ngp_mixture_quantiles", "ngp_mixture_crps", "ngp_microbench_mixture_pairs",
     "ngp_kernel_components", "ngp_factor_components",
+    "ngp_kernel_terms", "ngp_factor_components_nowcast",
 )
 
 
@@ -119,6 +120,9 @@ def load():
         "ngp_factor_destroy": (None, [vp]),
         "ngp_kernel_components": (i32, [KP, i32p, i32p, i32p, i32p, i32p]),
         "ngp_factor_components": (i32, [vp, i32p, KP, i32, f64p, f64p, f64p, f64p, i32p]),
+        "ngp_kernel_terms": (i32, [KP, i32, i32, i32p, i32p, i32p, i32p, i32p, i32p, i32, f64p, i32]),
+        "ngp_factor_components_nowcast": (i32, [vp, i32, f64p, i32, f64p, i32p, KP, i32, f64p, f64p,
+                                                f64p, f64p, f64p, i32p]),
         "ngp_mixture_sample": (i32, [vp, i32, i32, i32, f64p, f64p, f64p, i32, C.c_uint64, f64p,
                                      i32p, i32p]),
         "ngp_mixture_cdf": (i32, [vp, i32, i32, f64p, f64p, f64p, i32, f64p, f64p, i32p]),
@@ -179,6 +183,35 @@ def kernel_components(program):
     params = np.asarray(program[1], dtype=np.float64).reshape(-1)
     return [(ops[of[i]:of[i] + ol[i]].copy(), params[pf[i]:pf[i] + pl[i]].copy(), float(program[2]))
             for i in range(int(cnt.value))]
+
+
+def kernel_terms(program, split, max_terms=None):
+    """The sum-of-products terms of a program (``ngp_kernel_terms``): new programs that sum to it,
+    ``[(ops, params, noise), ...]``.  ``split``: NGP_SPLIT_* flags or-ed (0: the components of
+    ``kernel_components``).  More than ``max_terms`` terms (None: no limit), or a term that is no
+    valid program: ``NgpError`` with status NGP_ERR_TOO_LARGE, its ``count`` the number of terms."""
+    ka = KernelArray([program])
+    cnt = C.c_int32()
+    L = load()
+    st = L.ngp_kernel_terms(C.byref(ka.arr[0]), int(split), 2**31 - 1 if max_terms is None else int(max_terms),
+                            C.byref(cnt), None, None, None, None, None, 0, None, 0)
+    if st != 0:
+        err = NgpError(int(st), "ngp_kernel_terms")
+        err.count = int(cnt.value)
+        raise err
+    n = int(cnt.value)
+    n_ops = np.asarray(program[0]).size
+    n_par = np.asarray(program[1]).size
+    of, ol, pf, pl = (np.zeros(n, dtype=np.int32) for _ in range(4))
+    ops, par = np.zeros(n * n_ops, dtype=np.int32), np.zeros(max(n * n_par, 1))   # a term is no longer than the tree
+    st = L.ngp_kernel_terms(C.byref(ka.arr[0]), int(split), n, C.byref(cnt), iptr(of), iptr(ol), iptr(pf),
+                            iptr(pl), iptr(ops), ops.size, dptr(par), n * n_par)
+    if st != 0:
+        err = NgpError(int(st), "ngp_kernel_terms")
+        err.count = int(cnt.value)
+        raise err
+    return [(ops[of[i]:of[i] + ol[i]].copy(), par[pf[i]:pf[i] + pl[i]].copy(), float(program[2]))
+            for i in range(n)]
 
 
 def weights_normalize(logw):
@@ -417,6 +450,38 @@ class Factor:
             sigma=([sg[soff[p]:soff[p + 1]].reshape(int(counts[p]) * m, int(counts[p]) * m)
                     for p in range(self.P)] if want_sigma else None),
             info=info)
+
+    def components_nowcast(self, comps, t_add, y_add, t_new, want_sigma=True):
+        """``components`` conditioned on the appended points ``t_add`` [d] and the scenarios
+        ``y_add`` [D, d] (``ngp_factor_components_nowcast``).  As ``components``, with ``mu`` a list
+        of [C_p, D, m] arrays and ``logml_full`` [P, D]; ``sigma`` / ``var`` are shared by the
+        scenarios of a particle."""
+        if len(comps) != self.P:
+            raise ValueError("one list of component programs per particle")
+        t_add, t_new = as_f64(t_add), as_f64(t_new)
+        d, m = t_add.size, t_new.size
+        y_add = as_f64(y_add).reshape(-1, d) if d else np.zeros((1, 0))
+        D = y_add.shape[0]
+        counts = np.array([len(c) for c in comps], dtype=np.int32)
+        ka = KernelArray([prog for c in comps for prog in c])
+        tot = int(counts.sum())
+        mu, var = np.empty((tot, D, m)), np.empty((tot, m))
+        sizes = (counts.astype(np.int64) * m) ** 2
+        sg = np.empty(int(sizes.sum())) if want_sigma else None
+        lf = np.empty((self.P, D))
+        info = np.zeros(self.P, dtype=np.int32)
+        _chk(load().ngp_factor_components_nowcast(
+            self._h, d, dptr(t_add) if d else None, D, dptr(y_add) if d else None, iptr(counts), ka.arr,
+            m, dptr(t_new) if m else None, dptr(lf), dptr(mu), _nullable(sg), dptr(var), iptr(info)),
+            "ngp_factor_components_nowcast")
+        first = np.concatenate([[0], np.cumsum(counts)])
+        soff = np.concatenate([[0], np.cumsum(sizes)])
+        return dict(
+            mu=[mu[first[p]:first[p + 1]] for p in range(self.P)],
+            var=[var[first[p]:first[p + 1]] for p in range(self.P)],
+            sigma=([sg[soff[p]:soff[p + 1]].reshape(int(counts[p]) * m, int(counts[p]) * m)
+                    for p in range(self.P)] if want_sigma else None),
+            logml_full=lf, info=info)
 
     def predict(self, t_new, noise_on_new=True):
         r = self.nowcast(np.zeros(0), np.zeros((1, 0)), t_new, noise_on_new)

@@ -1184,12 +1184,15 @@ def rand_lockstep(mixes: Sequence[MixtureMVN], draws: int, engine=None) -> List[
 # ---------------------------------------------------------------------------------------------
 @dataclass
 class Component:
-    """One additive part of a particle's kernel: a maximal non-Plus subtree under the root's Plus
-    nodes.  ``kind``: "trend" if the subtree contains a Linear, "seasonal" if it contains a Periodic
-    and no Linear, "other" otherwise."""
+    """One additive part of a particle's kernel.  With ``split="plus"`` a maximal non-Plus subtree
+    under the root's Plus nodes, else a sum-of-products term (``ngp_kernel_terms``).  ``kind``:
+    "trend" if the part contains a Linear, "seasonal" if it contains a Periodic and no Linear,
+    "other" otherwise.  ``split``: the split that was used for this particle (the one asked for, or
+    a weaker one it fell back to)."""
     tree: gp.Node
     label: str
     kind: str
+    split: str = "plus"
 
 
 def component_kind(ops) -> str:
@@ -1199,17 +1202,63 @@ def component_kind(ops) -> str:
     return "seasonal" if gp.PERIODIC in ops else "other"
 
 
-def decompose(model: GPModel) -> List[List[Component]]:
-    """Per particle, the additive parts of its kernel, left to right (``ngp_kernel_components``
-    does the slicing).  A ChangePoint is one part (its summands are not kernels of the grammar); a
-    Plus below a Times or a ChangePoint is not split."""
+SPLITS = ("plus", "changepoint", "products")      # weakest first; flags of ngp_kernel_terms: 0, 1, 1 | 2
+_SPLIT_FLAGS = {"plus": 0, "changepoint": 1, "products": 3}
+
+
+def _zero(nd: gp.Node) -> bool:
+    return nd.op == gp.CONSTANT and nd.params[0] == 0.0
+
+
+def term_label(tree: gp.Node) -> str:
+    """The printed sub-kernel; a windowed term (one side of a ChangePoint, the other side
+    Constant(0)) names its side and the change point's location instead of printing the zero."""
+    if tree.op == gp.CHANGE_POINT and _zero(tree.right) != _zero(tree.left):
+        side, inner = ("before", tree.left) if _zero(tree.right) else ("after", tree.right)
+        return f"{term_label(inner)} [{side} {tree.params[0]:.4g}]"
+    if tree.op == gp.TIMES:
+        return f"Times({term_label(tree.left)}, {term_label(tree.right)})"
+    return str(tree)
+
+
+def decompose(model: GPModel, split: str = "plus", max_terms: Optional[int] = None) -> List[List[Component]]:
+    """Per particle, the additive parts of its kernel, left to right.
+
+    ``split="plus"``: the maximal non-Plus subtrees under the root's Plus nodes
+    (``ngp_kernel_components``); a ChangePoint or a Times is one part.  ``"changepoint"`` also
+    splits a ChangePoint into its two windows (each side's terms blended against Constant(0): the
+    device blend is linear in its operands), ``"products"`` in addition distributes a Times over
+    the sums below it (``ngp_kernel_terms``).  A particle with more than ``max_terms`` terms
+    (default: what leaves room for one forecast date beside the factor, NGP_MAX_AUX - (n mod 64) -
+    2) falls back to the next weaker split; ``Component.split`` records the one used."""
     from . import _lib
+    from ._abi import NGP_MAX_AUX
+    if split not in _SPLIT_FLAGS:
+        raise ValueError(f'decompose: split is one of {", ".join(SPLITS)}')
+    if split == "plus":
+        out = []
+        for ops, params, noise in model.programs():
+            parts = []
+            for c_ops, c_par, _ in _lib.kernel_components((ops, params, noise)):
+                tree = gp.from_program(c_ops, c_par)
+                parts.append(Component(tree, str(tree), component_kind(c_ops)))
+            out.append(parts)
+        return out
+    if max_terms is None:
+        max_terms = NGP_MAX_AUX - (model._obs()[0].size % 64) - 2
     out = []
-    for ops, params, noise in model.programs():
+    for prog in model.programs():
+        for used in reversed(SPLITS[:SPLITS.index(split) + 1]):
+            try:
+                terms = _lib.kernel_terms(prog, _SPLIT_FLAGS[used], max_terms if used != "plus" else None)
+                break
+            except _lib.NgpError as e:
+                if e.status != -3 or used == "plus":      # NGP_ERR_TOO_LARGE: the next weaker split
+                    raise
         parts = []
-        for c_ops, c_par, _ in _lib.kernel_components((ops, params, noise)):
+        for c_ops, c_par, _ in terms:
             tree = gp.from_program(c_ops, c_par)
-            parts.append(Component(tree, str(tree), component_kind(c_ops)))
+            parts.append(Component(tree, term_label(tree), component_kind(c_ops), used))
         out.append(parts)
     return out
 
@@ -1327,12 +1376,12 @@ class ComponentForecast:
         return out
 
 
-def component_blocks(n_obs: int, c_max: int, m: int):
-    """The C m component rows of a particle share the aux block with the tail observations and the
-    y row: (n mod 64) + 1 + C m <= NGP_MAX_AUX (include/ngp.h).  None when the m dates fit one
-    call, else the (lo, hi) blocks of dates to query one by one."""
+def component_blocks(n_obs: int, c_max: int, m: int, d: int = 0):
+    """The C m component rows of a particle share the aux block with the tail observations, the d
+    appended points and the y row: (n mod 64) + d + 1 + C m <= NGP_MAX_AUX (include/ngp.h).  None
+    when the m dates fit one call, else the (lo, hi) blocks of dates to query one by one."""
     from ._abi import NGP_MAX_AUX
-    per = (NGP_MAX_AUX - (n_obs % 64) - 1) // max(c_max, 1)
+    per = (NGP_MAX_AUX - (n_obs % 64) - d - 1) // max(c_max, 1)
     if m <= per:
         return None
     if per < 1:
@@ -1341,16 +1390,16 @@ def component_blocks(n_obs: int, c_max: int, m: int):
     return [(lo, min(lo + per, m)) for lo in range(0, m, per)]
 
 
-def predict_components(model: GPModel, ds) -> ComponentForecast:
+def predict_components(model: GPModel, ds, split: str = "plus") -> ComponentForecast:
     """The additive decomposition of the model's forecast on the dates ``ds``: ONE query of the
     model's resident factor (``ngp_factor_components``) per block of dates — no refit on a
     sub-kernel, which would not be conditioned on the same K.  Needs an engine with resident
     factors (there is no host path).  In a sharded run every rank gets its own particles' parts,
-    with their globally normalised weights."""
+    with their globally normalised weights.  ``split``: as ``decompose``."""
     fac = model._factor()
     if fac is None or not hasattr(fac, "components"):
         raise RuntimeError("predict_components needs the engine's resident factor (ngp_factor_components)")
-    parts = decompose(model)
+    parts = decompose(model, split)
     comps = [[gp.to_program(c.tree) + (0.0,) for c in ps] for ps in parts]
     t, _ = model._obs()
     t_new = model.ds_transform.apply(to_days(list(ds)))

@@ -7,6 +7,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <dlfcn.h>
+#include <functional>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -1820,10 +1821,161 @@ extern "C" ngp_status ngp_kernel_components(const ngp_kernel *k, int32_t *count,
     return NGP_OK;
 }
 
-extern "C" ngp_status ngp_factor_components(ngp_factor *f, const int32_t *comp_count,
-                                            const ngp_kernel *comps, int32_t m, const double *t_new,
-                                            double *mu, double *sigma, double *var, int32_t *info) {
-    if (!f || !comp_count || !comps || !t_new || !mu || m < 1) return NGP_ERR_ARG;
+// ---- sum-of-products terms of a tree ------------------------------
+// terms(leaf) = {leaf}; terms(Plus(l, r)) = terms(l) then terms(r); with NGP_SPLIT_CHANGEPOINT
+// terms(CP(l, r)) = {CP(x, Constant(0))} then {CP(Constant(0), y)}; with NGP_SPLIT_TIMES
+// terms(Times(l, r)) = {Times(x, y)}, x outer.  A node that is not split is one term, verbatim.
+// The device blend of a ChangePoint is g1 a g2 + (1 - g1) b (1 - g2) (cp_blend, ngp_tree_kernels.h)
+// under both cp_form values — the form only picks the sigmoid — so it is linear in its operand
+// values and the terms sum to the tree; an operand that is Constant(0) contributes an exact zero.
+extern "C" ngp_status ngp_kernel_terms(const ngp_kernel *k, int32_t split, int32_t max_terms,
+                                       int32_t *count, int32_t *op_first, int32_t *op_len,
+                                       int32_t *par_first, int32_t *par_len, int32_t *ops_out,
+                                       int32_t ops_cap, double *params_out, int32_t par_cap) {
+    if (!k || !count || split < 0 || split > (NGP_SPLIT_CHANGEPOINT | NGP_SPLIT_TIMES) ||
+        max_terms < 0 || ops_cap < 0 || par_cap < 0)
+        return NGP_ERR_ARG;
+    *count = 0;
+    // the structure alone: a tree longer than NGP_MAX_OPS may still have terms that fit
+    if (!k->ops || k->n_ops <= 0) return NGP_ERR_PROGRAM;
+    constexpr int MAX_IN = 64 * NGP_MAX_OPS;      // bounds the recursion below
+    if (k->n_ops > MAX_IN) return NGP_ERR_TOO_LARGE;
+    // cnt: the number of terms below the node; lo / lp: the longest term's ops / parameters;
+    // to / tp: the ops / parameters of all its terms together (all saturating)
+    struct Sub { int op, left, right, op0, par0, own; int64_t cnt, lo, lp, to, tp; };
+    constexpr int64_t SAT = (int64_t)1 << 40;
+    auto sat = [&](int64_t v) { return std::min(SAT, v); };
+    auto mul = [&](int64_t a, int64_t b) { return a >= SAT || b >= SAT || a * b >= SAT ? SAT : a * b; };
+    std::vector<Sub> nodes;
+    std::vector<int> stack;
+    int pi = 0;
+    auto splits = [&](int op) {
+        return op == NGP_OP_PLUS || (op == NGP_OP_CHANGEPOINT && (split & NGP_SPLIT_CHANGEPOINT)) ||
+               (op == NGP_OP_TIMES && (split & NGP_SPLIT_TIMES));
+    };
+    for (int i = 0; i < k->n_ops; ++i) {
+        const int op = k->ops[i];
+        if (op < 1 || op > 8) return NGP_ERR_PROGRAM;
+        Sub nd{op, -1, -1, i, pi, pi, 1, 0, 0, 0, 0};
+        if (op >= NGP_OP_PLUS) {
+            if (stack.size() < 2) return NGP_ERR_PROGRAM;
+            nd.right = stack.back(); stack.pop_back();
+            nd.left = stack.back(); stack.pop_back();
+            nd.op0 = nodes[(size_t)nd.left].op0;
+            nd.par0 = nodes[(size_t)nd.left].par0;
+            // the count of a node reached through split nodes only (its operands then are, too)
+            const Sub &l = nodes[(size_t)nd.left], &r = nodes[(size_t)nd.right];
+            const int64_t a = l.cnt, b = r.cnt;
+            if (op == NGP_OP_PLUS) {
+                nd.cnt = sat(a + b);
+                nd.lo = std::max(l.lo, r.lo); nd.lp = std::max(l.lp, r.lp);
+                nd.to = sat(l.to + r.to); nd.tp = sat(l.tp + r.tp);
+            } else if (op == NGP_OP_CHANGEPOINT && splits(op)) {     // + Constant(0) and the node
+                nd.cnt = sat(a + b);
+                nd.lo = std::max(l.lo, r.lo) + 2; nd.lp = std::max(l.lp, r.lp) + 3;
+                nd.to = sat(l.to + r.to + mul(2, nd.cnt)); nd.tp = sat(l.tp + r.tp + mul(3, nd.cnt));
+            } else if (splits(op)) {                                 // Times: x y and the node
+                nd.cnt = mul(a, b);
+                nd.lo = l.lo + r.lo + 1; nd.lp = l.lp + r.lp;
+                nd.to = sat(mul(l.to, b) + mul(r.to, a) + nd.cnt);
+                nd.tp = sat(mul(l.tp, b) + mul(r.tp, a));
+            }
+        }
+        pi += k_nparams[op];
+        if (op < NGP_OP_PLUS || !splits(op)) {                       // one term, verbatim
+            nd.lo = nd.to = i - nd.op0 + 1;
+            nd.lp = nd.tp = pi - nd.par0;
+        }
+        nodes.push_back(nd);
+        stack.push_back(i);
+    }
+    if (stack.size() != 1 || pi != k->n_params || (pi > 0 && !k->params)) return NGP_ERR_PROGRAM;
+    const int root = stack.back();
+    const int64_t total = nodes[(size_t)root].cnt;
+    *count = (int32_t)std::min<int64_t>(total, INT32_MAX);
+    if (total > max_terms) return NGP_ERR_TOO_LARGE;
+    const bool want = op_first || op_len || par_first || par_len || ops_out || params_out;
+    const Sub &rt = nodes[(size_t)root];
+    // a term that is no valid program, or more than the buffers hold: known before a term is
+    // built, so what is built below is bounded by the caller's own buffers
+    if (rt.lo > NGP_MAX_OPS || rt.lp > NGP_MAX_PARAMS) return NGP_ERR_TOO_LARGE;
+    if (!want) return NGP_OK;                     // the count alone: no term is built
+    if (!ops_out || !params_out || rt.to > ops_cap || rt.tp > par_cap) return NGP_ERR_TOO_LARGE;
+    struct Term { std::vector<int32_t> ops; std::vector<double> par; };
+    auto terms = [&](auto &&self, int i) -> std::vector<Term> {
+        const Sub &nd = nodes[(size_t)i];
+        std::vector<Term> out;
+        const double *th = k->params + nd.own;    // the node's own parameters
+        if (nd.op < NGP_OP_PLUS || !splits(nd.op)) {
+            Term t;
+            t.ops.assign(k->ops + nd.op0, k->ops + i + 1);
+            t.par.assign(k->params + nd.par0, k->params + nd.own + k_nparams[nd.op]);
+            out.push_back(std::move(t));
+            return out;
+        }
+        std::vector<Term> L = self(self, nd.left), R = self(self, nd.right);
+        if (nd.op == NGP_OP_PLUS) {
+            out = std::move(L);
+            for (Term &t : R) out.push_back(std::move(t));
+        } else if (nd.op == NGP_OP_CHANGEPOINT) {
+            for (Term &x : L) {                   // the window before the change point
+                x.ops.push_back(NGP_OP_CONSTANT); x.ops.push_back(NGP_OP_CHANGEPOINT);
+                x.par.push_back(0.0); x.par.push_back(th[0]); x.par.push_back(th[1]);
+                out.push_back(std::move(x));
+            }
+            for (Term &y : R) {                   // the window after it
+                Term t;
+                t.ops.push_back(NGP_OP_CONSTANT);
+                t.ops.insert(t.ops.end(), y.ops.begin(), y.ops.end());
+                t.ops.push_back(NGP_OP_CHANGEPOINT);
+                t.par.push_back(0.0);
+                t.par.insert(t.par.end(), y.par.begin(), y.par.end());
+                t.par.push_back(th[0]); t.par.push_back(th[1]);
+                out.push_back(std::move(t));
+            }
+        } else {
+            for (const Term &x : L)
+                for (const Term &y : R) {
+                    Term t = x;
+                    t.ops.insert(t.ops.end(), y.ops.begin(), y.ops.end());
+                    t.ops.push_back(NGP_OP_TIMES);
+                    t.par.insert(t.par.end(), y.par.begin(), y.par.end());
+                    out.push_back(std::move(t));
+                }
+        }
+        return out;
+    };
+    const std::vector<Term> all = terms(terms, root);
+    bool fits = true;
+    int64_t no = 0, np = 0;
+    for (size_t c = 0; c < all.size(); ++c) {
+        const Term &t = all[c];
+        const ngp_kernel tk{(int32_t)t.ops.size(), (int32_t)t.par.size(), t.ops.data(), t.par.data(), k->noise};
+        if (ngp_kernel_check(&tk) != NGP_OK) fits = false;
+        if (!ops_out || !params_out || no + (int64_t)t.ops.size() > ops_cap ||
+            np + (int64_t)t.par.size() > par_cap)
+            fits = false;
+        if (fits) {
+            std::copy(t.ops.begin(), t.ops.end(), ops_out + no);
+            std::copy(t.par.begin(), t.par.end(), params_out + np);
+            if (op_first) op_first[c] = (int32_t)no;
+            if (op_len) op_len[c] = (int32_t)t.ops.size();
+            if (par_first) par_first[c] = (int32_t)np;
+            if (par_len) par_len[c] = (int32_t)t.par.size();
+        }
+        no += (int64_t)t.ops.size();
+        np += (int64_t)t.par.size();
+    }
+    return fits ? NGP_OK : NGP_ERR_TOO_LARGE;
+}
+
+namespace {
+
+// ngp_factor_components (d = 0, D = 1, no logml) and ngp_factor_components_nowcast: one body
+ngp_status components_query(ngp_factor *f, int32_t d, const double *t_add, int32_t D,
+                            const double *y_add, const int32_t *comp_count, const ngp_kernel *comps,
+                            int32_t m, const double *t_new, double *logml_full, double *mu,
+                            double *sigma, double *var, int32_t *info) {
     const int P = f->P;
     std::vector<int32_t> first((size_t)P + 1, 0);
     std::vector<int64_t> sig_off((size_t)P, 0);
@@ -1832,7 +1984,7 @@ extern "C" ngp_status ngp_factor_components(ngp_factor *f, const int32_t *comp_c
     for (int b = 0; b < P; ++b) {
         const int cb = comp_count[b];
         if (cb < 1) return NGP_ERR_ARG;
-        if ((int64_t)(f->n % NB) + 1 + (int64_t)cb * m > NGP_MAX_AUX) return NGP_ERR_TOO_LARGE;
+        if ((int64_t)(f->n % NB) + d + 1 + (int64_t)cb * m > NGP_MAX_AUX) return NGP_ERR_TOO_LARGE;
         first[(size_t)b + 1] = first[(size_t)b] + cb;
         sig_off[(size_t)b] = sig_total;
         sig_total += (int64_t)cb * m * cb * m;
@@ -1845,17 +1997,19 @@ extern "C" ngp_status ngp_factor_components(ngp_factor *f, const int32_t *comp_c
         if (st) return st;
     }
     // the query's geometry: cmax groups of the m dates (an item with fewer components leaves its
-    // last groups zero); no appended points, one scenario, no noise on the new points
+    // last groups zero); no noise on the new points
     std::vector<double> t_rep((size_t)cmax * m);
     for (int c = 0; c < cmax; ++c) std::copy(t_new, t_new + m, t_rep.begin() + (size_t)c * m);
     ngp_ctx *c = f->ctx;
     static const double dummy = 0.0;
+    if (d == 0) { t_add = &dummy; y_add = &dummy; }
     ngp_job *job = nullptr;
-    ngp_status st = stage_general(c, P, f->kernels.data(), f->n, f->t.data(), f->y.data(), f->ldy, 0,
-                                  &dummy, 1, &dummy, 0, cmax * m, t_rep.data(), 0, &job);
+    ngp_status st = stage_general(c, P, f->kernels.data(), f->n, f->t.data(), f->y.data(), f->ldy, d,
+                                  t_add, D, y_add, 0, cmax * m, t_rep.data(), 0, &job);
     if (st) return st;
-    const size_t n_out = ncomp * (size_t)m;
-    const int64_t work_stride = (int64_t)cmax * m * (job->g.da + 1);
+    const size_t n_out = ncomp * (size_t)m, n_mu = n_out * (size_t)D;
+    // V and the prior's diagonal, then room for L_A and its three vectors when LDS does not hold them
+    const int64_t work_stride = (int64_t)cmax * m * (job->g.da + 1) + comp_epi_small(job->g.da);
     const size_t o_first = sizeof(DevProgram) * ncomp, o_sig = (o_first + 4 * first.size() + 7) & ~(size_t)7,
                  in_bytes = o_sig + 8 * sig_off.size();
     std::vector<unsigned char> h_in(in_bytes);
@@ -1867,7 +2021,7 @@ extern "C" ngp_status ngp_factor_components(ngp_factor *f, const int32_t *comp_c
         std::lock_guard<std::mutex> lk(c->mu);
         if (hipSetDevice(c->device) != hipSuccess) st = NGP_ERR_NO_DEVICE;
         if (!st) st = c->alloc(&d_in, in_bytes);
-        if (!st) st = c->alloc(&d_mu, 8 * n_out);
+        if (!st) st = c->alloc(&d_mu, 8 * n_mu);
         if (!st && sigma) st = c->alloc(&d_sigma, 8 * (size_t)sig_total);
         if (!st && var) st = c->alloc(&d_var, 8 * n_out);
         if (!st) st = c->alloc(&d_work, 8 * (size_t)P * (size_t)work_stride);
@@ -1886,14 +2040,14 @@ extern "C" ngp_status ngp_factor_components(ngp_factor *f, const int32_t *comp_c
         cp.cmax = cmax;
         st = factor_run(f, job, /*create=*/false, &cp, (double *)d_work, work_stride);
     }
-    if (!st) st = ngp_job_fetch(job, nullptr, nullptr, nullptr, nullptr, info);
+    if (!st) st = ngp_job_fetch(job, nullptr, logml_full, nullptr, nullptr, info);
     {
         std::lock_guard<std::mutex> lk(c->mu);
         hipStream_t s = c->stream;
         hipError_t e = hipSuccess;
         if (!st && hipSetDevice(c->device) != hipSuccess) st = NGP_ERR_NO_DEVICE;
         if (!st) {
-            e = hipMemcpyAsync(mu, d_mu, 8 * n_out, hipMemcpyDeviceToHost, s);
+            e = hipMemcpyAsync(mu, d_mu, 8 * n_mu, hipMemcpyDeviceToHost, s);
             if (e == hipSuccess && sigma)
                 e = hipMemcpyAsync(sigma, d_sigma, 8 * (size_t)sig_total, hipMemcpyDeviceToHost, s);
             if (e == hipSuccess && var) e = hipMemcpyAsync(var, d_var, 8 * n_out, hipMemcpyDeviceToHost, s);
@@ -1905,6 +2059,28 @@ extern "C" ngp_status ngp_factor_components(ngp_factor *f, const int32_t *comp_c
     }
     ngp_job_destroy(job);
     return st;
+}
+
+}  // namespace
+
+extern "C" ngp_status ngp_factor_components(ngp_factor *f, const int32_t *comp_count,
+                                            const ngp_kernel *comps, int32_t m, const double *t_new,
+                                            double *mu, double *sigma, double *var, int32_t *info) {
+    if (!f || !comp_count || !comps || !t_new || !mu || m < 1) return NGP_ERR_ARG;
+    return components_query(f, 0, nullptr, 1, nullptr, comp_count, comps, m, t_new, nullptr, mu, sigma,
+                            var, info);
+}
+
+extern "C" ngp_status ngp_factor_components_nowcast(ngp_factor *f, int32_t d, const double *t_add,
+                                                    int32_t D, const double *y_add,
+                                                    const int32_t *comp_count, const ngp_kernel *comps,
+                                                    int32_t m, const double *t_new, double *logml_full,
+                                                    double *mu, double *sigma, double *var,
+                                                    int32_t *info) {
+    if (!f || !comp_count || !comps || !t_new || !mu || m < 1) return NGP_ERR_ARG;
+    if (d < 0 || D < 1 || (d > 0 && (!t_add || !y_add))) return NGP_ERR_ARG;
+    return components_query(f, d, t_add, D, y_add, comp_count, comps, m, t_new, logml_full, mu, sigma,
+                            var, info);
 }
 
 extern "C" void ngp_factor_destroy(ngp_factor *f) {

@@ -179,7 +179,7 @@ struct CompPtrs {
     const DevProgram *progs;  // [sum C_b] component programs, item-major
     const int32_t *first;     // [B + 1] an item's first component (running sum of C_b)
     const int64_t *sig_off;   // [B] where the item's [C_b m][C_b m] block starts in sigma
-    double       *mu;         // [sum C_b][m]
+    double       *mu;         // [sum C_b][D][m]
     double       *sigma;      // the items' blocks back to back, or null
     double       *var;        // [sum C_b][m], or null
     int32_t       m;          // dates per component
@@ -276,6 +276,10 @@ void launch_gram(const JobGeom &g, const double *L, double *G, int Bc, hipStream
 void launch_epilogue(const JobGeom &g, const EpiPtrs &p, const DevSpec &sp, hipStream_t s);
 // component rows of a resident factor's query: their fill (behind launch_fill(.., aux_only), which
 // leaves the tail and y' rows) and the epilogue that stands in for launch_epilogue
+// component_epilogue_kernel keeps L_A [da x da] and four vectors of da in dynamic LDS while they
+// fit COMP_EPI_LDS_BYTES (da <= 76), else behind V in the per-item work buffer
+constexpr int COMP_EPI_LDS_BYTES = 48 * 1024;
+inline int64_t comp_epi_small(int da) { return (int64_t)da * da + 4 * (int64_t)da; }   // doubles
 void launch_component_fill(const JobGeom &g, const ChunkPtrs &p, const CompPtrs &cp, int Bc,
                            const DevSpec &sp, hipStream_t s);
 void launch_component_epilogue(const JobGeom &g, const EpiPtrs &p, const CompPtrs &cp,

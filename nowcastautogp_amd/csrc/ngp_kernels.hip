@@ -1102,7 +1102,10 @@ void launch_component_fill(const JobGeom &g, const ChunkPtrs &p, const CompPtrs 
 
 void launch_component_epilogue(const JobGeom &g, const EpiPtrs &p, const CompPtrs &cp,
                                const DevSpec &sp, hipStream_t s) {
-    hipLaunchKernelGGL(component_epilogue_kernel, dim3(g.B), dim3(64), 0, s, g, p, cp, sp);
+    const size_t bytes = sizeof(double) * (size_t)comp_epi_small(g.da);
+    const int lds_work = bytes <= (size_t)COMP_EPI_LDS_BYTES;
+    hipLaunchKernelGGL(component_epilogue_kernel, dim3(g.B), dim3(64), lds_work ? bytes : 0, s, g, p,
+                       cp, sp, lds_work);
 }
 
 void launch_cov(const DevProgram *progs, int B, const double *t1, int n1, const double *t2, int n2,

@@ -504,6 +504,90 @@ def forecast_mixture_with_nowcasts(base_model: GPModel, nowcasts: Sequence[TData
     return autogp.MixtureMarginals.pool([mx.marginals(engine=base_model._eng()) for mx in mixes])
 
 
+def forecast_components_with_nowcasts(base_model: GPModel, nowcasts: Sequence[TData], forecast_dates, *,
+                                      split: str = "changepoint",
+                                      ess_threshold: float = 0.0) -> "autogp.ComponentForecast":
+    """Which part of the nowcast-conditioned forecast is trend, which is season: the additive
+    decomposition (``autogp.predict_components``) of the mixture ``forecast_mixture_with_nowcasts``
+    returns on its default path.  The parts come from ONE query of the resident factor per block
+    of dates (``ngp_factor_components_nowcast``); the weights come from a second one, the default
+    path's own ``ngp_factor_nowcast`` query over all the forecast dates (its means and covariances
+    are not used): a log evidence moves in its last bits with the number of rows swept beside the
+    factor, and only that query gives the weights of ``forecast_mixture_with_nowcasts`` bit for bit.
+    So a call costs about two sweeps through the factor.
+
+    Default mode only: the scenarios share their dates and no refinement moves are made (refined
+    clones no longer share particles — call ``autogp.predict_components`` per clone for those).
+    Single-rank runs only (``NotImplementedError`` in a sharded run, where ``predict_components``
+    per rank still works).  Weights and resampling are those of
+    ``forecast_mixture_with_nowcasts``' default path, with the same use of the random streams: from
+    the same snapshot and seed the two describe one mixture.
+
+    The entries of the returned ``ComponentForecast`` are the pairs (s, p), scenario-major, with
+    weight w[s][p] / D; ``sigma`` / ``var`` of (s, p) are the same array objects as particle p's
+    (the scenarios of a particle share its covariance).  Original scale of y; ``split`` as
+    ``autogp.decompose``."""
+    assert len(nowcasts) > 0, "nowcasts vector must not be empty"
+    assert 0.0 <= ess_threshold <= 1.0, "ess_threshold must be between 0 and 1"
+    if not all(list(nc.ds) == list(nowcasts[0].ds) for nc in nowcasts):
+        raise ValueError("forecast_components_with_nowcasts: the scenarios must share their dates")
+    model = base_model
+    fac = model._factor()
+    if fac is None or not hasattr(fac, "components_nowcast"):
+        raise RuntimeError("forecast_components_with_nowcasts needs the engine's resident factor "
+                           "(ngp_factor_components_nowcast)")
+    dist_ = autogp.distributed
+    if dist_.world()[1] > 1:
+        raise NotImplementedError("forecast_components_with_nowcasts: single-rank runs only")
+    dates = list(forecast_dates)
+    t, _ = model._obs()
+    t_add = model.ds_transform.apply(autogp.to_days(list(nowcasts[0].ds)))
+    # the appended points take rows beside the factor too: a particle whose terms fit without them
+    # but not with them goes to the weaker split
+    from ._abi import NGP_MAX_AUX
+    parts = autogp.decompose(model, split, max_terms=NGP_MAX_AUX - t.size % 64 - t_add.size - 2)
+    comps = [[gp.to_program(c.tree) + (0.0,) for c in ps] for ps in parts]
+    y_add = np.stack([model.y_transform.apply(np.asarray(nc.y, dtype=np.float64)) for nc in nowcasts])
+    t_new = model.ds_transform.apply(autogp.to_days(dates))
+    D, m, P = len(nowcasts), t_new.size, len(parts)
+    # weights, the scenarios to resample and the stream: the default path's own routine, so the
+    # log evidences are the bits of the very query it makes (they move in the last place with the
+    # number of forecast rows beside the factor)
+    w, _, _, low, rng, sampler = _nowcast_mixtures_batched(model, nowcasts, dates, ess_threshold)
+    blocks = autogp.component_blocks(t.size, max(len(ps) for ps in parts), m, t_add.size)
+    means = [np.empty((len(ps), D, m)) for ps in parts]
+    var = [np.empty((len(ps), m)) for ps in parts]
+    sigma = [np.zeros((len(ps) * m, len(ps) * m)) for ps in parts]
+    for lo, hi in (blocks or [(0, m)]):
+        o = fac.components_nowcast(comps, t_add, y_add, t_new[lo:hi])
+        bad = np.flatnonzero(o["info"])
+        if bad.size:
+            raise autogp.PosDefException(int(o["info"][bad[0]]), int(bad[0]))
+        k = hi - lo
+        for p in range(P):
+            C = len(parts[p])
+            means[p][:, :, lo:hi] = o["mu"][p]
+            var[p][:, lo:hi] = o["var"][p]
+            sigma[p].reshape(C, m, C, m)[:, lo:hi, :, lo:hi] = o["sigma"][p].reshape(C, k, C, k)
+    if sampler is not None:
+        if low.any():
+            w[low] = rng.multinomial(P, w[low]) / P
+        rng.integers(0, 2**63 - 1)      # the sampler's seed: leave the stream where the draws would
+    else:
+        for sc in np.flatnonzero(low):
+            w[sc] = np.bincount(rng.choice(P, size=P, p=w[sc]), minlength=P) / P
+    inv = 1.0 / model.y_transform.slope           # y = (y_model - intercept) / slope
+    var = [a * (inv * inv) for a in var]
+    sigma = [a * (inv * inv) for a in sigma]
+    return autogp.ComponentForecast(
+        [np.ascontiguousarray(means[p][:, sc, :]) * inv for sc in range(D) for p in range(P)],
+        [sigma[p] for _ in range(D) for p in range(P)], [var[p] for _ in range(D) for p in range(P)],
+        (w / D).reshape(D * P),
+        [[c.kind for c in parts[p]] for _ in range(D) for p in range(P)],
+        [[c.label for c in parts[p]] for _ in range(D) for p in range(P)],
+        -model.y_transform.intercept * inv, blocks, engine=model._eng())
+
+
 def _clone_for_scenario(base_model: GPModel) -> GPModel:
     # GPModel(deepcopy(Dict(base_model))) of the reference (src/forecasting.jl:128,133).  Every
     # scenario is its own task with its own randomness there (:131-133); a clone that kept the
