@@ -72,6 +72,20 @@ def main():
         print(f"  {dates[n + k]}  " + "".join(f"{v:10.1f}" for v in qt[k])
               + f"  {crps[k]:8.4f}  {pit[k]:6.3f}")
     print(f"  mean CRPS (log scale) over the {horizon} held-out weeks: {crps.mean():.4f}")
+    # what no per-date summary gives: the total of the next four weeks and the peak week.  These are
+    # functionals of whole paths — 5,000 per scenario are drawn, mapped back to counts, reduced and
+    # ranked on the device; the paths themselves never come to the host.
+    t0 = time.perf_counter()
+    tg = nc.forecast_targets_with_nowcasts(
+        model, nowcasts, dates[n:n + horizon],
+        [("sum", 0, 3), ("argmax", 0, horizon - 1), ("exceed", 0, horizon - 1, 1.5 * counts[n - 1])],
+        5000, probs=levels, inv_transformation=inv_transformation)
+    print(f"trajectory targets of {tg.N} paths in {(time.perf_counter() - t0) * 1e3:.1f} ms")
+    print("  four-week total  " + "".join(f"{v:10.1f}" for v in tg.quantile(0))
+          + f"   truth {counts[n:n + 4].sum():.1f}")
+    peak = tg.peak_distribution(1)
+    print(f"  peak week: {dates[n + int(np.argmax(peak))]} (P = {peak.max():.2f}); "
+          f"P(any week above 1.5 x the last count) = {tg.prob_above(2):.3f}")
     # "Approach 5" of the reference's vignette (docs/vignettes/getting-started.jl:631-634): HMC
     # refinement of every scenario's particles after its nowcast.  Three ways to run the same thing:
     # the lockstep ensemble (one call of P x D items per leapfrog), the reference's own form — one

@@ -428,6 +428,83 @@ ngp_status ngp_mixture_quantiles(ngp_ctx *ctx, int32_t C, int32_t m, const doubl
 ngp_status ngp_mixture_crps(ngp_ctx *ctx, int32_t C, int32_t m, const double *w, const double *mu,
                             const double *var, const double *y, double *crps, int32_t *info);
 
+/* ---- trajectory targets: functionals of whole sample paths on the original scale -------------
+ * What the per-date summaries above cannot give — the total over the next k dates, the peak value,
+ * the peak date, the probability that any date exceeds a threshold, the probability that date j1 is
+ * above date j0 — has no closed form under a mixture of Gaussians followed by a Box-Cox, log or
+ * logit inverse (reference src/transformations.jl:139-174): it needs paths.  These calls draw the
+ * paths, transform them, reduce them and rank them on the device; only the summaries come back.
+ *
+ * Paths.  w, mu, sigma, draws, seed / seeds and their layouts are those of ngp_mixture_sample /
+ * ngp_mixture_sample_indep; path (s, d) is the path that call draws for the same arguments (same
+ * Philox counters, component pick and Box-Muller pairing), equal to it to rounding — bit equality
+ * is not promised.  The N = S draws paths are pooled, as the reference's hcat pools them.
+ * Inverse transformation.  Every path value is v = g(x), g as nowcast.get_transformations builds
+ * its inverses, edge rules included:
+ *   NGP_INV_IDENTITY     x
+ *   NGP_INV_EXP          max(exp(x) - offset, 0)
+ *   NGP_INV_LOGISTIC100  max(100 / (1 + exp(-x)) - offset, 0)
+ *   NGP_INV_BOXCOX       with base = lam x + 1:
+ *                          lam > 0:  max(base, 1e-10)^(1 / lam) - offset
+ *                          lam < 0:  base^(1 / lam) - offset            where base > 1e-10,
+ *                                    0                                  where base <= 0 (the pole),
+ *                                    min(base^(1 / lam), cap) - offset  in between
+ *                          lam = 0:  exp(x) - offset
+ *                        then max(., 0), and a non-finite result becomes the largest finite double
+ * -0.0 is stored as +0.0.
+ * Targets, per path, over the inclusive window j0 .. j1 (0 <= j0 <= j1 < m):
+ *   NGP_TARGET_SUM     sum of v_j, j ascending        NGP_TARGET_MAX     the window's maximum
+ *   NGP_TARGET_DIFF    v[j1] - v[j0]                  NGP_TARGET_ARGMAX  first date j of the maximum
+ *   NGP_TARGET_EXCEED  1 if any v_j > thr, else 0
+ * Summaries over the N paths of target t:
+ *   q [T x Q]     real-valued kinds (SUM, MAX, DIFF): the order statistic x_(k), k =
+ *                 clamp((int64) ceil(probs[i] N), 1, N) — an exact selection, nothing interpolated
+ *                 or approximated; a level's result does not depend on Q or on its position in
+ *                 probs.  NaN for ARGMAX and EXCEED.
+ *   mean [T]      the sum over the paths in a fixed order, over N (EXCEED: the probability; ARGMAX:
+ *                 the mean date index)
+ *   count [T]     paths with value > thr (DIFF with thr = 0: N P(increase)); EXCEED: the exceeding
+ *                 paths; ARGMAX: 0
+ *   hist [T x m]  ARGMAX: paths whose peak is at date j; zero outside the window and for other kinds
+ *   values [T x N] (may be NULL) every path's target value, path (s, d) at s draws + d
+ *   info          as ngp_mixture_sample: [P] ([S x P] for _indep), may be NULL; 0 or the first
+ *                 non-positive pivot of chol(sigma[k]).  A failed component of positive weight makes
+ *                 EVERY output of the call NaN (count and hist: 0) — its paths are pooled with the
+ *                 others, so no summary is left that it has not touched.
+ * Bitwise reproducible: the same inputs give the same bits on every call (fixed-order sums, no
+ * floating-point atomics; integer atomics only where the order cannot matter).
+ * NGP_ERR_ARG, before anything touches a device: null context or arrays (values and info may be
+ * NULL; seeds may not); P, S, m, draws, T or Q < 1; a window outside [0, m) or with j0 > j1; an
+ * unknown kind; a probs entry outside (0, 1); a non-finite thr, lam, offset or cap; NGP_INV_BOXCOX
+ * with cap <= 0.  Limits (NGP_ERR_TOO_LARGE): m <= NGP_MAX_AUX, T <= 64, Q <= 64, N <= 2^31 - 1,
+ * S P <= 2^31 - 1, and the 8 T N bytes of target values (kept on the device whether or not values
+ * is asked for) must fit in device memory.
+ * Thread-safe like the other one-shot calls (the context's lock); not combined with concurrent
+ * callers; not counted in ngp_profile.
+ * inv points to ONE ngp_inv_transform and targets to T ngp_path_target; the two parameters are
+ * declared const void * because every other parameter type of this header is a scalar, an array of
+ * scalars or an opaque handle, and the bindings that are checked against it (julia/NGPAutoGP.jl)
+ * know only those.                                                                              */
+enum { NGP_INV_IDENTITY = 0, NGP_INV_EXP = 1, NGP_INV_LOGISTIC100 = 2, NGP_INV_BOXCOX = 3 };
+typedef struct ngp_inv_transform { int32_t kind; double lam, offset, cap; } ngp_inv_transform;
+enum { NGP_TARGET_SUM = 0, NGP_TARGET_MAX = 1, NGP_TARGET_DIFF = 2,   /* real-valued */
+       NGP_TARGET_ARGMAX = 3, NGP_TARGET_EXCEED = 4 };
+typedef struct ngp_path_target { int32_t kind, j0, j1; double thr; } ngp_path_target;
+ngp_status ngp_mixture_path_targets(ngp_ctx *ctx, int32_t P, int32_t S, int32_t m,
+                                    const double *w, const double *mu, const double *sigma,
+                                    int32_t draws, uint64_t seed, const void *inv,
+                                    int32_t T, const void *targets, int32_t Q,
+                                    const double *probs, double *q, double *mean, int64_t *count,
+                                    int64_t *hist, double *values, int32_t *info);
+ngp_status ngp_mixture_path_targets_indep(ngp_ctx *ctx, int32_t P, int32_t S, int32_t m,
+                                          const double *w, const double *mu, const double *sigma,
+                                          int32_t draws, const uint64_t *seeds,
+                                          const void *inv, int32_t T,
+                                          const void *targets, int32_t Q,
+                                          const double *probs, double *q, double *mean,
+                                          int64_t *count, int64_t *hist, double *values,
+                                          int32_t *info);
+
 /* ---- cached factor ------------------------------
  * A fitted model is queried many times with the same particles and the same
  * training data: forecast() on several date grids, forecast_with_nowcasts()

@@ -497,6 +497,63 @@ function mixture_crps(c::Context, w::Vector{Float64}, mu::Matrix{Float64}, var::
     return out, info
 end
 
+# ---- trajectory targets: functionals of whole sample paths (include/ngp.h) ----------------------
+# Mirrors of ngp_inv_transform / ngp_path_target (C layout: Int32 then 8-byte aligned doubles).
+struct InvTransform
+    kind::Int32
+    lam::Float64
+    offset::Float64
+    cap::Float64
+end
+struct PathTarget
+    kind::Int32
+    j0::Int32        # 0-based, as the header: the window j0 .. j1 is inclusive
+    j1::Int32
+    thr::Float64
+end
+const INV_IDENTITY, INV_EXP, INV_LOGISTIC100, INV_BOXCOX = Int32(0), Int32(1), Int32(2), Int32(3)
+const TARGET_SUM, TARGET_MAX, TARGET_DIFF, TARGET_ARGMAX, TARGET_EXCEED =
+    Int32(0), Int32(1), Int32(2), Int32(3), Int32(4)
+
+"""
+Summaries of functionals of the paths `mixture_sample` (one `seed`) / `mixture_sample_indep` (a
+vector of S seeds) draws for the same arguments, on the scale `inv` maps to: returns
+`(q Q x T, mean, count, hist m x T, values)` — `values` (N x T) only with `want_values = true`.
+`w`, `mu`, `sigma` in the layouts of the two samplers (`ngp_mixture_path_targets[_indep]`).
+"""
+function mixture_path_targets(c::Context, w::Array{Float64}, mu::Array{Float64}, sigma::Array{Float64},
+                              draws::Integer, seed::Union{Integer,Vector{UInt64}}, inv::InvTransform,
+                              targets::Vector{PathTarget}, probs::Vector{Float64};
+                              want_values::Bool = false)
+    P, S, m = size(w, 1), size(w, 2), size(mu, 1)              # column-major views of [S x P], [.. x m]
+    T, Q, N = length(targets), length(probs), S * Int(draws)
+    q = Matrix{Float64}(undef, Q, T); mean = Vector{Float64}(undef, T)
+    count = zeros(Int64, T); hist = zeros(Int64, m, T)
+    values = want_values ? Matrix{Float64}(undef, N, T) : nothing
+    vptr = want_values ? pointer(values) : Ptr{Float64}(C_NULL)
+    rinv = Ref(inv)
+    if seed isa Integer
+        info = zeros(Int32, P)
+        GC.@preserve values check(ccall((:ngp_mixture_path_targets, LIBNGP), Int32,
+                    (Ptr{Cvoid}, Int32, Int32, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int32,
+                     UInt64, Ptr{Cvoid}, Int32, Ptr{Cvoid}, Int32, Ptr{Float64},
+                     Ptr{Float64}, Ptr{Float64}, Ptr{Int64}, Ptr{Int64}, Ptr{Float64}, Ptr{Int32}),
+                    c.h, P, S, m, w, mu, sigma, draws, UInt64(seed), rinv, T, targets, Q, probs,
+                    q, mean, count, hist, vptr, info), "ngp_mixture_path_targets")
+    else
+        length(seed) == S || throw(DimensionMismatch("one seed per mixture"))
+        info = zeros(Int32, P * S)
+        GC.@preserve values check(ccall((:ngp_mixture_path_targets_indep, LIBNGP), Int32,
+                    (Ptr{Cvoid}, Int32, Int32, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int32,
+                     Ptr{UInt64}, Ptr{Cvoid}, Int32, Ptr{Cvoid}, Int32, Ptr{Float64},
+                     Ptr{Float64}, Ptr{Float64}, Ptr{Int64}, Ptr{Int64}, Ptr{Float64}, Ptr{Int32}),
+                    c.h, P, S, m, w, mu, sigma, draws, seed, rinv, T, targets, Q, probs,
+                    q, mean, count, hist, vptr, info), "ngp_mixture_path_targets_indep")
+    end
+    raise_if_not_posdef(vec(info))
+    return q, mean, count, hist, values
+end
+
 """
 The one collective of the path for a multi-GPU Julia host (one process per GPU): RCCL, opened by
 libngp at run time.  Rank 0 calls `comm_unique_id()` and hands the 128 bytes to the other ranks by

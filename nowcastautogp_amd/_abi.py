@@ -50,6 +50,19 @@ class NgpKernel(C.Structure):
     ]
 
 
+class NgpInvTransform(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("lam", C.c_double), ("offset", C.c_double), ("cap", C.c_double)]
+
+
+class NgpPathTarget(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("j0", C.c_int32), ("j1", C.c_int32), ("thr", C.c_double)]
+
+
+NGP_INV_IDENTITY, NGP_INV_EXP, NGP_INV_LOGISTIC100, NGP_INV_BOXCOX = 0, 1, 2, 3
+NGP_TARGET_SUM, NGP_TARGET_MAX, NGP_TARGET_DIFF, NGP_TARGET_ARGMAX, NGP_TARGET_EXCEED = 0, 1, 2, 3, 4
+PATH_MAX_TARGETS = PATH_MAX_LEVELS = 64
+
+
 class NgpProfile(C.Structure):
     _fields_ = [
         ("ms", C.c_double * NGP_NUM_KERNEL_CLASSES),

@@ -13,8 +13,8 @@ from typing import Optional, Sequence
 
 import numpy as np
 
-from ._abi import (KernelArray, NgpKernel, NgpProfile, NgpSpec, as_f64, c_double_p, c_int32_p,
-                   dptr, iptr)
+from ._abi import (KernelArray, NgpInvTransform, NgpKernel, NgpPathTarget, NgpProfile, NgpSpec,
+                   as_f64, c_double_p, c_int32_p, dptr, iptr)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("NGP_LIB") or os.path.join(_HERE, "libngp.so")  # NGP_LIB: A/B builds
@@ -40,6 +40,7 @@ SYMBOLS = (
     "ngp_mixture_cdf", "ngp_mixture_quantiles", "ngp_mixture_crps", "ngp_microbench_mixture_pairs",
     "ngp_kernel_components", "ngp_factor_components",
     "ngp_kernel_terms", "ngp_factor_components_nowcast",
+    "ngp_mixture_path_targets", "ngp_mixture_path_targets_indep",
 )
 
 
@@ -129,6 +130,14 @@ def load():
         "ngp_mixture_quantiles": (i32, [vp, i32, i32, f64p, f64p, f64p, i32, f64p, f64p, i32p]),
         "ngp_mixture_crps": (i32, [vp, i32, i32, f64p, f64p, f64p, f64p, f64p, i32p]),
         "ngp_microbench_mixture_pairs": (i32, [vp, i32, f64p]),
+        "ngp_mixture_path_targets": (i32, [vp, i32, i32, i32, f64p, f64p, f64p, i32, C.c_uint64,
+                                           C.POINTER(NgpInvTransform), i32, C.POINTER(NgpPathTarget),
+                                           i32, f64p, f64p, f64p, C.POINTER(i64), C.POINTER(i64),
+                                           f64p, i32p]),
+        "ngp_mixture_path_targets_indep": (i32, [vp, i32, i32, i32, f64p, f64p, f64p, i32,
+                                                 C.POINTER(C.c_uint64), C.POINTER(NgpInvTransform),
+                                                 i32, C.POINTER(NgpPathTarget), i32, f64p, f64p,
+                                                 f64p, C.POINTER(i64), C.POINTER(i64), f64p, i32p]),
         "ngp_set_structured_storage": (i32, [vp, i32]),
         "ngp_set_combining": (i32, [vp, i32]),
         "ngp_set_batch_invariant": (i32, [vp, i32]),
@@ -639,6 +648,47 @@ class Context:
                                              dptr(out), iptr(comp), iptr(info)),
              "ngp_mixture_sample_indep")
         return out, comp, info
+
+    def mixture_path_targets(self, w, mu, sigma, draws: int, seed, inv, targets, probs,
+                             want_values: bool = False):
+        """Functionals of whole sample paths (``ngp_mixture_path_targets``; with ``seed`` a
+        sequence of S seeds ``ngp_mixture_path_targets_indep``): w, mu, sigma as ``mixture_sample``
+        / ``mixture_sample_indep``; ``inv`` = (kind, lam, offset, cap); ``targets`` a sequence of
+        (kind, j0, j1, thr); ``probs`` [Q] ->  dict(q [T,Q], mean [T], count [T], hist [T,m],
+        values [T,N] or None, info)."""
+        w, mu, sigma = as_f64(w), as_f64(mu), as_f64(sigma)
+        indep = not np.isscalar(seed)
+        if w.ndim != 2 or mu.ndim != 3:
+            raise ValueError("mixture_path_targets: w [S,P], mu [P,S,m] ([S,P,m] with S seeds)")
+        S, P = w.shape
+        m = mu.shape[2]
+        if indep:
+            if mu.shape != (S, P, m) or sigma.shape != (S, P, m, m) or len(seed) != S:
+                raise ValueError("mixture_path_targets: w [S,P], mu [S,P,m], sigma [S,P,m,m], seeds [S]")
+        elif mu.shape != (P, S, m) or sigma.shape != (P, m, m):
+            raise ValueError("mixture_path_targets: w [S,P], mu [P,S,m], sigma [P,m,m]")
+        probs = as_f64(probs).reshape(-1)
+        T, Q, N = len(targets), probs.size, S * int(draws)
+        tg = (NgpPathTarget * max(T, 1))(*[NgpPathTarget(int(k), int(j0), int(j1), float(thr))
+                                           for k, j0, j1, thr in targets])
+        iv = NgpInvTransform(int(inv[0]), float(inv[1]), float(inv[2]), float(inv[3]))
+        q, mean = np.empty((T, Q)), np.empty(T)
+        count, hist = np.zeros(T, dtype=np.int64), np.zeros((T, m), dtype=np.int64)
+        values = np.empty((T, N)) if want_values else None
+        info = np.zeros((S, P) if indep else P, dtype=np.int32)
+        i64p = C.POINTER(C.c_int64)
+        tail = (C.byref(iv), T, tg, Q, dptr(probs), dptr(q), dptr(mean), count.ctypes.data_as(i64p),
+                hist.ctypes.data_as(i64p), dptr(values) if want_values else None, iptr(info))
+        if indep:
+            sd = np.array([int(v) & (2**64 - 1) for v in seed], dtype=np.uint64)
+            _chk(load().ngp_mixture_path_targets_indep(
+                self._h, P, S, m, dptr(w), dptr(mu), dptr(sigma), int(draws),
+                sd.ctypes.data_as(C.POINTER(C.c_uint64)), *tail), "ngp_mixture_path_targets_indep")
+        else:
+            _chk(load().ngp_mixture_path_targets(
+                self._h, P, S, m, dptr(w), dptr(mu), dptr(sigma), int(draws),
+                C.c_uint64(int(seed) & (2**64 - 1)), *tail), "ngp_mixture_path_targets")
+        return dict(q=q, mean=mean, count=count, hist=hist, values=values, info=info)
 
     @staticmethod
     def _marginals(w, mu, var, who):

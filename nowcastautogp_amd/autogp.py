@@ -87,6 +87,12 @@ class HipEngine:
         """Draws from S independent mixtures in one device call (``ngp_mixture_sample_indep``)."""
         return self.ctx.mixture_sample_indep(w, mu, sigma, draws, seeds)
 
+    def mixture_path_targets(self, w, mu, sigma, draws, seed, inv, targets, probs, want_values=False):
+        """Functionals of whole sample paths on the device (``ngp_mixture_path_targets``; S seeds:
+        ``ngp_mixture_path_targets_indep``)."""
+        return self.ctx.mixture_path_targets(w, mu, sigma, draws, seed, inv, targets, probs,
+                                             want_values)
+
     def mixture_cdf(self, w, mu, var, x):
         """CDF of a mixture's per-date marginals on the device (``ngp_mixture_cdf``)."""
         return self.ctx.mixture_cdf(w, mu, var, x)
@@ -1429,3 +1435,197 @@ def predict_components(model: GPModel, ds, split: str = "plus") -> ComponentFore
     return ComponentForecast(means, sigma, var, w[:, 0], [[c.kind for c in ps] for ps in parts],
                              [[c.label for c in ps] for ps in parts],
                              -model.y_transform.intercept * inv, blocks, engine=model._eng())
+
+
+# ---------------------------------------------------------------------------------------------
+# trajectory targets (include/ngp.h "trajectory targets")
+# ---------------------------------------------------------------------------------------------
+TARGET_KINDS = {"sum": 0, "max": 1, "diff": 2, "argmax": 3, "exceed": 4}
+REAL_TARGETS = (0, 1, 2)
+
+
+def _target_tuples(targets, m: int):
+    """(kind, j0, j1[, thr]) with kind a name of TARGET_KINDS or its code -> [(code, j0, j1, thr)]"""
+    out = []
+    for tg in targets:
+        kind, j0, j1 = tg[0], int(tg[1]), int(tg[2])
+        thr = float(tg[3]) if len(tg) > 3 else 0.0
+        code = TARGET_KINDS[kind] if isinstance(kind, str) else int(kind)
+        if code not in TARGET_KINDS.values() or not 0 <= j0 <= j1 < m or not np.isfinite(thr):
+            raise ValueError(f"path target {tg!r}: kind in {sorted(TARGET_KINDS)}, 0 <= j0 <= j1 < {m}, "
+                             "finite threshold")
+        out.append((code, j0, j1, thr))
+    if not out:
+        raise ValueError("path_targets: at least one target")
+    return out
+
+
+def quantile_rank(p: float, N: int) -> int:
+    """1-based rank of the order statistic that stands for level p among N paths:
+    clamp(ceil(p N), 1, N), the product taken in float64 as the library takes it."""
+    return int(min(max(int(math.ceil(float(p) * float(N))), 1), N))
+
+
+def path_functionals(v: np.ndarray, targets) -> np.ndarray:
+    """v [N, m] paths on the original scale, targets [(code, j0, j1, thr)] -> values [T, N], with
+    the definitions of include/ngp.h (sum in ascending date order; first index of the maximum)."""
+    out = np.empty((len(targets), v.shape[0]))
+    for t, (code, j0, j1, thr) in enumerate(targets):
+        win = v[:, j0:j1 + 1]
+        if code == 0:
+            acc = np.zeros(v.shape[0])
+            for j in range(win.shape[1]):
+                acc = acc + win[:, j]
+            out[t] = acc
+        elif code == 1:
+            out[t] = win.max(axis=1)
+        elif code == 2:
+            out[t] = v[:, j1] - v[:, j0]
+        elif code == 3:
+            out[t] = j0 + np.argmax(win, axis=1)
+        else:
+            out[t] = (win.max(axis=1) > thr).astype(np.float64)
+    return out + 0.0
+
+
+def summarize_path_values(values: np.ndarray, targets, probs, m: int):
+    """The summaries of include/ngp.h from values [T, N]: q [T, Q] (order statistics), mean, count,
+    hist [T, m]."""
+    T, N = values.shape
+    probs = np.asarray(probs, dtype=np.float64).reshape(-1)
+    q = np.full((T, probs.size), np.nan)
+    count, hist = np.zeros(T, dtype=np.int64), np.zeros((T, m), dtype=np.int64)
+    ks = np.array([quantile_rank(p, N) for p in probs], dtype=np.int64) - 1
+    for t, (code, j0, j1, thr) in enumerate(targets):
+        if code in REAL_TARGETS:
+            q[t] = np.sort(values[t])[ks]
+            count[t] = int(np.sum(values[t] > thr))
+        elif code == 3:
+            hist[t] = np.bincount(values[t].astype(np.int64), minlength=m)
+        else:
+            count[t] = int(np.sum(values[t] > 0.5))
+    return q, values.mean(axis=1), count, hist
+
+
+class PathTargets:
+    """Summaries of functionals of whole forecast paths (``path_targets``): per target t
+
+        quantile(t)            the levels' order statistics among the N paths (real-valued kinds)
+        mean(t)                mean over the paths (``exceed``: the probability; ``argmax``: mean index)
+        prob_above(t)          share of paths above the target's threshold (``exceed``: of paths
+                               that exceed it anywhere in the window)
+        peak_distribution(t)   ``argmax``: share of paths whose peak is at each date, [m]
+        values(t)              every path's value, if they were asked for
+    """
+
+    def __init__(self, targets, probs, q, mean, count, hist, N, values=None, device=False):
+        self.targets, self.probs = list(targets), np.asarray(probs, dtype=np.float64)
+        self.q, self._mean, self.count, self.hist = q, mean, count, hist
+        self.N, self._values, self.device = int(N), values, bool(device)
+
+    def quantile(self, t: int = 0):
+        if self.targets[t][0] not in REAL_TARGETS:
+            raise ValueError("quantile: a sum, max or diff target")
+        return self.q[t].copy()
+
+    def mean(self, t: int = 0) -> float:
+        return float(self._mean[t])
+
+    def prob_above(self, t: int = 0) -> float:
+        if self.targets[t][0] == 3:
+            raise ValueError("prob_above: not for an argmax target")
+        return float(self.count[t]) / self.N
+
+    def peak_distribution(self, t: int = 0):
+        if self.targets[t][0] != 3:
+            raise ValueError("peak_distribution: an argmax target")
+        return self.hist[t] / float(self.N)
+
+    def values(self, t: int = 0):
+        if self._values is None:
+            raise ValueError("values: call path_targets(..., want_values=True)")
+        return self._values[t]
+
+
+def path_targets(mixes_or_arrays, targets, probs, draws: int, seed=None, inv_transformation=None, *,
+                 engine=None, want_values: bool = False) -> PathTargets:
+    """Functionals of whole sample paths of forecast mixtures on the original scale: totals over a
+    window, peak value and date, exceedance, change between two dates (include/ngp.h "trajectory
+    targets").
+
+    ``mixes_or_arrays``: one ``MixtureMVN`` or a sequence of them on the same dates (their paths
+    are pooled; mixture j is keyed by ``seed[j]``, taken from its own stream when ``seed`` is None,
+    as ``rand_lockstep`` takes it), or arrays ``(w [S,P], mu [P,S,m], sigma [P,m,m])`` with one
+    seed — S mixtures over shared components, the layout of ``ngp_mixture_sample`` — or
+    ``(w [S,P], mu [S,P,m], sigma [S,P,m,m])`` with S seeds.  The paths are those the sampler draws
+    for the same arguments.  ``targets``: ``(kind, j0, j1[, thr])``, kind one of "sum", "max",
+    "diff", "argmax", "exceed", window inclusive.
+
+    ``inv_transformation`` None (identity) or a callable that carries ``ngp_inv`` (the inverses of
+    ``nowcast.get_transformations``) runs wholly on the device when the engine has
+    ``mixture_path_targets``; any other callable, or an engine without that entry, takes the host
+    path — the engine's sampler (numpy without one), then numpy with the same definitions."""
+    if isinstance(mixes_or_arrays, MixtureMVN):
+        mixes_or_arrays = [mixes_or_arrays]
+    if isinstance(mixes_or_arrays[0], MixtureMVN):
+        mixes = list(mixes_or_arrays)
+        if seed is None:
+            seed = [int(mx.rng.integers(0, 2**63 - 1)) for mx in mixes]
+        elif np.isscalar(seed):
+            seed = [int(seed)] if len(mixes) == 1 else None
+        if seed is None or len(seed) != len(mixes):
+            raise ValueError("path_targets: one seed per mixture")
+        w = np.stack([mx.weights for mx in mixes])
+        mu = np.stack([mx.means for mx in mixes])
+        sigma = np.stack([mx.covs for mx in mixes])
+        seed = [int(v) for v in seed]
+    else:
+        w, mu, sigma = (np.asarray(a, dtype=np.float64) for a in mixes_or_arrays)
+        if seed is None:
+            raise ValueError("path_targets: arrays need a seed")
+        seed = int(seed) if np.isscalar(seed) else [int(v) for v in seed]
+    indep = not np.isscalar(seed)
+    S, m, N = w.shape[0], mu.shape[2], w.shape[0] * int(draws)
+    tgs = _target_tuples(targets, m)
+    probs = np.asarray(probs, dtype=np.float64).reshape(-1)
+    if probs.size < 1 or not np.all((probs > 0.0) & (probs < 1.0)):
+        raise ValueError("path_targets: levels in (0, 1)")
+    inv = (0, 0.0, 0.0, 0.0) if inv_transformation is None else getattr(inv_transformation, "ngp_inv", None)
+    device = getattr(engine, "mixture_path_targets", None) if engine is not None else None
+    if device is not None and inv is not None:
+        o = device(w, mu, sigma, int(draws), seed, inv, tgs, probs, want_values)
+        bad = np.argwhere(np.atleast_1d(o["info"]) != 0)
+        if bad.size:
+            raise PosDefException(int(o["info"][tuple(bad[0])]), int(bad[0][-1]))
+        return PathTargets(tgs, probs, o["q"], o["mean"], o["count"], o["hist"], N, o["values"], True)
+    # host path: the sampler's draws, numpy for the rest
+    sampler = getattr(engine, "mixture_sample_indep" if indep else "mixture_sample", None)
+    if sampler is not None:
+        x, _, info = sampler(w, mu, sigma, int(draws), seed)
+        bad = np.argwhere(np.atleast_1d(info) != 0)
+        if bad.size:
+            raise PosDefException(int(info[tuple(bad[0])]), int(bad[0][-1]))
+    elif indep and getattr(engine, "mixture_sample", None) is not None:
+        # mixture s of the independent form IS a one-mixture call keyed by seeds[s]
+        x = []
+        for s in range(S):
+            xs, _, info = engine.mixture_sample(w[s:s + 1], np.ascontiguousarray(mu[s][:, None, :]),
+                                                sigma[s], int(draws), seed[s])
+            if np.any(info):
+                k = int(np.flatnonzero(info)[0])
+                raise PosDefException(int(info[k]), k)
+            x.append(xs[0])
+        x = np.stack(x)
+    elif indep:
+        x = np.stack([MixtureMVN(mu[s], sigma[s], w[s], np.random.default_rng(seed[s])).rand(int(draws)).T
+                      for s in range(S)])
+    else:
+        rng = np.random.default_rng(seed)
+        x = np.stack([MixtureMVN(mu[:, s], sigma, w[s], rng).rand(int(draws)).T for s in range(S)])
+    x = np.ascontiguousarray(x.reshape(N, m))
+    if inv_transformation is not None:
+        from .nowcast import _apply
+        x = _apply(inv_transformation, x)
+    values = path_functionals(x, tgs)
+    q, mean, count, hist = summarize_path_values(values, tgs, probs, m)
+    return PathTargets(tgs, probs, q, mean, count, hist, N, values if want_values else None, False)

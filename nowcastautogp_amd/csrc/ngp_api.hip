@@ -3156,6 +3156,169 @@ extern "C" ngp_status ngp_microbench_mixture_pairs(ngp_ctx *c, int32_t iters, do
 }
 
 // ---------------------------------------------------------------------------------------
+// Trajectory targets (ngp_mixture_path_targets / _indep; kernels: ngp_path_kernels.h)
+//
+// The host validates, turns the levels into ranks (ascending, distinct: the select passes work
+// on those; q is filled per level from them), stages, launches and scatters the few results.
+namespace {
+ngp_status path_targets_impl(ngp_ctx *c, int32_t P, int32_t S, int32_t m, const double *w,
+                             const double *mu, const double *sigma, int32_t draws, uint64_t seed,
+                             const uint64_t *seeds, const ngp_inv_transform *inv, int32_t T,
+                             const ngp_path_target *targets, int32_t Q, const double *probs,
+                             double *q, double *mean, int64_t *count, int64_t *hist,
+                             double *values, int32_t *info) {
+    if (!c || !w || !mu || !sigma || !inv || !targets || !probs || !q || !mean || !count || !hist ||
+        P <= 0 || S <= 0 || m <= 0 || draws < 1 || T < 1 || Q < 1)
+        return NGP_ERR_ARG;
+    if (inv->kind < NGP_INV_IDENTITY || inv->kind > NGP_INV_BOXCOX || !std::isfinite(inv->lam) ||
+        !std::isfinite(inv->offset) || !std::isfinite(inv->cap) ||
+        (inv->kind == NGP_INV_BOXCOX && !(inv->cap > 0.0)))
+        return NGP_ERR_ARG;
+    if (T > PATH_MAX_TARGETS || Q > PATH_MAX_LEVELS) return NGP_ERR_TOO_LARGE;   // bounds the loops below
+    for (int32_t t = 0; t < T; ++t) {
+        const ngp_path_target &tg = targets[t];
+        if (tg.kind < NGP_TARGET_SUM || tg.kind > NGP_TARGET_EXCEED || tg.j0 < 0 || tg.j1 >= m ||
+            tg.j0 > tg.j1 || !std::isfinite(tg.thr))
+            return NGP_ERR_ARG;
+    }
+    for (int32_t i = 0; i < Q; ++i)
+        if (!(probs[i] > 0.0 && probs[i] < 1.0)) return NGP_ERR_ARG;
+    const int64_t N = (int64_t)S * draws, Bn = seeds ? (int64_t)S * P : (int64_t)P;
+    if (m > NGP_MAX_AUX || N > INT32_MAX || (int64_t)S * P > INT32_MAX) return NGP_ERR_TOO_LARGE;
+
+    // levels -> ranks, ascending and distinct; lvl[i]: where level i's rank sits among them
+    std::vector<int64_t> rank_of(Q), ranks;
+    for (int32_t i = 0; i < Q; ++i)
+        rank_of[i] = std::min<int64_t>(std::max<int64_t>((int64_t)std::ceil(probs[i] * (double)N), 1), N);
+    ranks = rank_of;
+    std::sort(ranks.begin(), ranks.end());
+    ranks.erase(std::unique(ranks.begin(), ranks.end()), ranks.end());
+    std::vector<int32_t> real;
+    for (int32_t t = 0; t < T; ++t)
+        if (targets[t].kind <= NGP_TARGET_DIFF) real.push_back(t);
+
+    PathGeom g{};
+    g.P = P; g.S = S; g.m = m; g.draws = draws;
+    g.B = (int32_t)Bn;
+    g.indep = seeds ? 1 : 0;
+    g.PW = path_pw(m);
+    g.T = T; g.Tr = (int32_t)real.size(); g.R = (int32_t)ranks.size();
+    g.N = N;
+    const size_t Nn = (size_t)N, B = (size_t)Bn, Tn = (size_t)T, R = ranks.size(),
+                 Tr = std::max<size_t>(real.size(), 1), slices = (size_t)path_slices(N);
+    const size_t nw = (size_t)S * P, nmu = (size_t)P * S * m, nsg = B * m * m;
+
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIPCHK(hipSetDevice(c->device));
+    c->refresh_mem_cap();
+    if ((double)(8 * Tn + 12) * (double)Nn + 8.0 * (double)(nw + nmu + nsg) > (double)c->mem_cap)
+        return NGP_ERR_TOO_LARGE;
+    hipStream_t s = c->stream;
+    MixBlocks blk(c);
+    auto take = [&](auto **p, size_t bytes) {
+        double *d = nullptr;
+        const ngp_status st = blk.take(&d, (bytes + 7) / 8);
+        *p = reinterpret_cast<std::remove_reference_t<decltype(*p)>>(d);
+        return st;
+    };
+    double *dw = nullptr, *dmu = nullptr;
+    uint64_t *dseeds = nullptr;
+    int64_t *dranks = nullptr;
+    int32_t *dreal = nullptr;
+    ngp_path_target *dtargets = nullptr;
+    PathBufs b{};
+    ngp_status st;
+    if ((st = take(&dw, 8 * nw)) || (st = take(&dmu, 8 * nmu)) || (st = take(&b.chol, 8 * nsg)) ||
+        (seeds && (st = take(&dseeds, 8 * (size_t)S))) || (st = take(&b.info, 4 * B)) ||
+        (st = take(&b.bkt, 4 * Nn)) || (st = take(&b.order, 4 * Nn)) || (st = take(&b.rank, 4 * Nn)) ||
+        (st = take(&b.cnt, 4 * B)) || (st = take(&b.off, 4 * (B + 1))) ||
+        (st = take(&b.wgoff, 4 * (B + 1))) || (st = take(&dtargets, sizeof(ngp_path_target) * Tn)) ||
+        (st = take(&dreal, 4 * Tr)) || (st = take(&dranks, 8 * R)) ||
+        (st = take(&b.values, 8 * Tn * Nn)) || (st = take(&b.partial, 8 * Tn * slices)) ||
+        (st = take(&b.mean, 8 * Tn)) || (st = take(&b.count, 8 * Tn)) ||
+        (st = take(&b.hist, 8 * Tn * m)) || (st = take(&b.prefix, 8 * Tr * R)) ||
+        (st = take(&b.gpre, 8 * Tr * R)) || (st = take(&b.krem, 8 * Tr * R)) ||
+        (st = take(&b.grp, 4 * Tr * R)) || (st = take(&b.ng, 4 * Tr)) ||
+        (st = take(&b.ghist, 4 * Tr * R * 256)) || (st = take(&b.q, 8 * Tr * R)))
+        return st;
+    b.w = dw; b.mu = dmu; b.seeds = dseeds; b.targets = dtargets; b.real = dreal; b.ranks = dranks;
+
+    std::vector<int32_t> hinfo(B, 0);
+    std::vector<double> hq(Tr * R, 0.0);
+    hipError_t e = hipMemcpyAsync(dw, w, 8 * nw, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(dmu, mu, 8 * nmu, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(b.chol, sigma, 8 * nsg, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess && seeds) e = hipMemcpyAsync(dseeds, seeds, 8 * (size_t)S, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(dtargets, targets, sizeof(ngp_path_target) * Tn, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess && !real.empty())
+        e = hipMemcpyAsync(dreal, real.data(), 4 * real.size(), hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(dranks, ranks.data(), 8 * R, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = launch_path_targets(g, b, *inv, seed, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(mean, b.mean, 8 * Tn, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(count, b.count, 8 * Tn, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(hist, b.hist, 8 * Tn * m, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess && !real.empty())
+        e = hipMemcpyAsync(hq.data(), b.q, 8 * real.size() * R, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess && values) e = hipMemcpyAsync(values, b.values, 8 * Tn * Nn, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(hinfo.data(), b.info, 4 * B, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e == hipSuccess) e = hipGetLastError();
+    if (e != hipSuccess) return (ngp_status)(e > 0 ? e : 999);
+
+    if (info) std::copy(hinfo.begin(), hinfo.end(), info);
+    const double nan = std::nan("");
+    for (size_t i = 0; i < Tn * (size_t)Q; ++i) q[i] = nan;
+    for (size_t y = 0; y < real.size(); ++y)
+        for (int32_t i = 0; i < Q; ++i) {
+            const size_t r = std::lower_bound(ranks.begin(), ranks.end(), rank_of[i]) - ranks.begin();
+            q[(size_t)real[y] * Q + i] = hq[y * R + r];
+        }
+    // a failed component that paths can come from: nothing the call returns is free of it
+    bool failed = false;
+    for (size_t k = 0; k < B && !failed; ++k) {
+        if (!hinfo[k]) continue;
+        if (seeds) failed = w[k] > 0.0;
+        else for (int32_t sc = 0; sc < S && !failed; ++sc) failed = w[(size_t)sc * P + k] > 0.0;
+    }
+    if (failed) {
+        for (size_t i = 0; i < Tn * (size_t)Q; ++i) q[i] = nan;
+        for (size_t t = 0; t < Tn; ++t) { mean[t] = nan; count[t] = 0; }
+        for (size_t i = 0; i < Tn * (size_t)m; ++i) hist[i] = 0;
+        if (values) for (size_t i = 0; i < Tn * Nn; ++i) values[i] = nan;
+    }
+    return NGP_OK;
+}
+}  // namespace
+
+extern "C" ngp_status ngp_mixture_path_targets(ngp_ctx *c, int32_t P, int32_t S, int32_t m,
+                                               const double *w, const double *mu,
+                                               const double *sigma, int32_t draws, uint64_t seed,
+                                               const void *inv, int32_t T, const void *targets,
+                                               int32_t Q, const double *probs, double *q,
+                                               double *mean, int64_t *count, int64_t *hist,
+                                               double *values, int32_t *info) {
+    return path_targets_impl(c, P, S, m, w, mu, sigma, draws, seed, nullptr,
+                             (const ngp_inv_transform *)inv, T, (const ngp_path_target *)targets, Q,
+                             probs, q, mean, count, hist, values, info);
+}
+
+extern "C" ngp_status ngp_mixture_path_targets_indep(ngp_ctx *c, int32_t P, int32_t S, int32_t m,
+                                                     const double *w, const double *mu,
+                                                     const double *sigma, int32_t draws,
+                                                     const uint64_t *seeds,
+                                                     const void *inv, int32_t T,
+                                                     const void *targets, int32_t Q,
+                                                     const double *probs, double *q, double *mean,
+                                                     int64_t *count, int64_t *hist, double *values,
+                                                     int32_t *info) {
+    if (!seeds) return NGP_ERR_ARG;
+    return path_targets_impl(c, P, S, m, w, mu, sigma, draws, 0, seeds,
+                             (const ngp_inv_transform *)inv, T, (const ngp_path_target *)targets, Q,
+                             probs, q, mean, count, hist, values, info);
+}
+
+// ---------------------------------------------------------------------------------------
 // Combining concurrent callers (flat combining)
 //
 // The reference enters the boundary from one task per nowcast scenario (Threads.@spawn,

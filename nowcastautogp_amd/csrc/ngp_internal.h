@@ -305,6 +305,47 @@ void launch_mixture_quantiles(int C, int m, const double *w, const double *mu, c
 void launch_mixture_crps(int C, int m, const double *w, const double *mu, const double *var,
                          const double *y, double *slab, double *crps, hipStream_t s);
 void launch_mixture_pair_rate(int iters, int blocks, double *out, hipStream_t s);
+// ---- functionals of whole sample paths (ngp_path_kernels.h) ---------------------------------
+constexpr int PATH_LCHUNK = 2048;      // doubles of L staged in LDS at a time (whole rows)
+constexpr int PATH_SLICE = 4096;       // values per workgroup in the reduce and select passes
+constexpr int PATH_MAX_TARGETS = 64, PATH_MAX_LEVELS = 64;
+// paths per workgroup of path_values_kernel: L's chunk plus the state [m][PW] stay within 80 KiB
+// (two workgroups per CU) up to m = 64; beyond, one wave's worth of paths (114,688 B at m = 192)
+inline int path_pw(int m) { return m <= 32 ? 256 : m <= 64 ? 128 : 64; }
+inline size_t path_lds_bytes(int m, int PW) { return 8 * ((size_t)PATH_LCHUNK + (size_t)m * PW); }
+constexpr int PATH_LDS_MAX = 8 * (PATH_LCHUNK + NGP_MAX_AUX * 64);
+static_assert(PATH_LCHUNK >= NGP_MAX_AUX, "a chunk holds at least one row of L");
+static_assert(PATH_LDS_MAX <= 160 * 1024, "the state of 64 paths at NGP_MAX_AUX dates fits the LDS");
+inline int64_t path_slices(int64_t N) { return (N + PATH_SLICE - 1) / PATH_SLICE; }
+// an upper bound of sum_b ceil(cnt_b / PW) over B buckets that hold N paths
+inline int64_t path_values_grid(int64_t N, int64_t B, int PW) { return N / PW + std::min(N, B) + 1; }
+struct PathGeom {
+    int32_t P, S, m, draws;
+    int32_t B;         // buckets: P (shared components) or S P (independent mixtures)
+    int32_t indep, PW;
+    int32_t T, Tr, R;  // targets, the real-valued ones among them, distinct ranks asked for
+    int64_t N;         // S draws
+};
+struct PathBufs {
+    const double *w, *mu;          // as ngp_mixture_sample(_indep) takes them
+    double *chol;                  // sigma in, L out
+    const uint64_t *seeds;         // [S] or null
+    int32_t *info;                 // [B]
+    int32_t *bkt, *order;          // [N]
+    uint32_t *rank, *cnt, *off, *wgoff;   // [N], [B], [B + 1], [B + 1]
+    const ngp_path_target *targets;       // [T]
+    const int32_t *real;           // [Tr] the real-valued targets
+    const int64_t *ranks;          // [R] ascending, distinct, 1-based
+    double *values, *partial, *mean;      // [T][N], [T][path_slices(N)], [T]
+    unsigned long long *count, *hist;     // [T], [T][m]
+    unsigned long long *prefix, *gpre;    // [Tr][R]
+    long long *krem;               // [Tr][R]
+    int32_t *grp, *ng;             // [Tr][R], [Tr]
+    uint32_t *ghist;               // [Tr][R][256]
+    double *q;                     // [Tr][R]
+};
+hipError_t launch_path_targets(const PathGeom &g, const PathBufs &p, const ngp_inv_transform &inv,
+                               uint64_t seed, hipStream_t s);
 void launch_mfma_bench(double *out, int iters, int blocks, hipStream_t s);
 void launch_mfma_bench_detail(unsigned long long *stamps, int iters, int blocks, hipStream_t s);
 void launch_mfma_layout_probe(const double *A, const double *Bm, double *Dout, hipStream_t s);

@@ -15,7 +15,8 @@
 //   ngp_grad_kernels.h    grad_kinv*, grad_alpha, the three grad_contract* kernels, toep_*, grad_reduce
 //   ngp_col_kernels.h     chol_diag_kernel and the column kernels; ngp_small_kernels.h: short series
 //                         in one launch; ngp_mixture_kernels.h: mixture summaries;
-//                         ngp_component_kernels.h: fill and epilogue of ngp_factor_components
+//                         ngp_component_kernels.h: fill and epilogue of ngp_factor_components;
+//                         ngp_path_kernels.h: functionals of whole sample paths
 //   this file             aux_update / aux_back_* / refine_gram_* (resident factor, Gram refinement),
 //                         diag_ahead, gram, epilogue, mixture sampling, the probe and stream kernels,
 //                         and every launcher
@@ -691,6 +692,10 @@ void launch_mixture_sample(int P, int S, int m, const double *w, const double *m
                        S, m, w, mu, (const double *)chol, draws, (unsigned)seed,
                        (unsigned)(seed >> 32), (const unsigned long long *)seeds, out, comp);
 }
+
+}  // namespace ngp
+#include "ngp_path_kernels.h"   // uses philox4x32_10, u01 and small_chol_kernel above
+namespace ngp {
 
 // ---------------------------------------------------------------------------------------
 // microbenchmarks / self tests

@@ -31,14 +31,15 @@ from typing import Callable, List, Optional, Sequence
 
 import numpy as np
 
-from . import autogp, gp
+from . import _abi, autogp, gp
 from .autogp import GPModel
 
 GPConfig = gp.GPConfig
 
 __all__ = ["TData", "GPModel", "GPConfig", "create_transformed_data", "make_and_fit_model",
            "forecast", "forecast_with_nowcasts", "create_nowcast_data", "forecast_mixture",
-           "forecast_mixture_with_nowcasts", "get_transformations"]
+           "forecast_mixture_with_nowcasts", "get_transformations", "forecast_targets",
+           "forecast_targets_with_nowcasts"]
 
 
 class TData:
@@ -146,13 +147,18 @@ def _inv_boxcox(lam: float, offset: float, max_value: float) -> Callable:
         res = np.where(np.isfinite(res), res, np.finfo(np.float64).max)
         return float(res) if np.ndim(y) == 0 else res
 
+    inv.ngp_inv = (_abi.NGP_INV_BOXCOX, float(lam), float(offset), float(big))
     return inv
 
 
-def _elementwise(fn: Callable) -> Callable:
+def _elementwise(fn: Callable, ngp_inv=None) -> Callable:
+    """``ngp_inv``: (kind, lam, offset, cap) — how include/ngp.h ``ngp_inv_transform`` states an
+    inverse, for the calls that apply it on the device (``autogp.path_targets``)."""
     def g(y):
         out = fn(np.asarray(y, dtype=np.float64))
         return float(out) if np.ndim(y) == 0 else out
+    if ngp_inv is not None:
+        g.ngp_inv = ngp_inv
     return g
 
 
@@ -174,12 +180,14 @@ def get_transformations(transform_name: str, values):
             with np.errstate(divide="ignore"):
                 return np.log(pr) - np.log1p(-pr)
         return (_elementwise(fwd),
-                _elementwise(lambda y: np.maximum(100.0 / (1.0 + np.exp(-y)) - offset, 0.0)))
+                _elementwise(lambda y: np.maximum(100.0 / (1.0 + np.exp(-y)) - offset, 0.0),
+                             (_abi.NGP_INV_LOGISTIC100, 0.0, offset, 0.0)))
     if transform_name == "positive":
         def fwd(y):
             with np.errstate(divide="ignore"):
                 return np.log(y + offset)
-        return (_elementwise(fwd), _elementwise(lambda y: np.maximum(np.exp(y) - offset, 0.0)))
+        return (_elementwise(fwd), _elementwise(lambda y: np.maximum(np.exp(y) - offset, 0.0),
+                                                (_abi.NGP_INV_EXP, 0.0, offset, 0.0)))
     if transform_name == "boxcox":
         shifted = vals + offset
         lam = _fit_boxcox_lambda(shifted)
@@ -586,6 +594,99 @@ def forecast_components_with_nowcasts(base_model: GPModel, nowcasts: Sequence[TD
         [[c.kind for c in parts[p]] for _ in range(D) for p in range(P)],
         [[c.label for c in parts[p]] for _ in range(D) for p in range(P)],
         -model.y_transform.intercept * inv, blocks, engine=model._eng())
+
+
+def forecast_targets(model: GPModel, forecast_dates, targets, forecast_draws: int, *,
+                     probs=(0.025, 0.25, 0.5, 0.75, 0.975), inv_transformation: Optional[Callable] = None,
+                     want_values: bool = False) -> "autogp.PathTargets":
+    """Summaries of functionals of the paths ``forecast`` returns — totals over a window, the peak
+    and its date, exceedance, change between two dates (``autogp.path_targets``) — from the same
+    snapshot and seed exactly those paths, without bringing them to the host when the engine has
+    ``mixture_path_targets`` and the inverse is one of ``get_transformations``'."""
+    mix = autogp.predict_mvn(model, list(forecast_dates))
+    eng = model._eng()
+    if mix.sampler is None or int(forecast_draws) <= 1:    # the draws forecast() makes on the host
+        x = mix.rand(int(forecast_draws)).T
+        return _targets_of_paths(x if inv_transformation is None else _apply(inv_transformation, np.ascontiguousarray(x)),
+                                 targets, probs, want_values)
+    return autogp.path_targets(mix, targets, probs, int(forecast_draws), None, inv_transformation,
+                               engine=eng, want_values=want_values)
+
+
+def _targets_of_paths(v, targets, probs, want_values):
+    """numpy summaries of paths v [N, m] that were drawn on the host"""
+    tgs = autogp._target_tuples(targets, v.shape[1])
+    values = autogp.path_functionals(np.ascontiguousarray(v), tgs)
+    q, mean, count, hist = autogp.summarize_path_values(values, tgs, probs, v.shape[1])
+    return autogp.PathTargets(tgs, probs, q, mean, count, hist, v.shape[0],
+                              values if want_values else None, False)
+
+
+def forecast_targets_with_nowcasts(base_model: GPModel, nowcasts: Sequence[TData], forecast_dates,
+                                   targets, forecast_draws_per_nowcast: int, *,
+                                   probs=(0.025, 0.25, 0.5, 0.75, 0.975),
+                                   inv_transformation: Optional[Callable] = None, n_mcmc: int = 0,
+                                   n_hmc: int = 0, ess_threshold: float = 0.0, lockstep: bool = True,
+                                   hmc_config: Optional[dict] = None,
+                                   want_values: bool = False) -> "autogp.PathTargets":
+    """``autogp.path_targets`` of the paths ``forecast_with_nowcasts`` returns.
+
+    Follows ``forecast_with_nowcasts`` step for step — same asserts, weight update, resampling, use
+    of the random streams and sampler seed — so from one snapshot and seed it summarises exactly
+    the matrix that function would return (column (s, d) is path s draws + d).  The default mode
+    (``n_mcmc = n_hmc = 0``) is one call over the shared components; lockstep-refined clones no
+    longer share particles and go through the independent form.  ``forecast_n_hmc`` (a new mixture
+    before every draw) is not taken; sharded runs raise ``NotImplementedError``."""
+    assert len(nowcasts) > 0, "nowcasts vector must not be empty"
+    assert not (n_mcmc > 0 and n_hmc == 0), \
+        "If n_mcmc > 0, n_hmc must also be > 0 for MCMC refinement"
+    assert 0.0 <= ess_threshold <= 1.0, "ess_threshold must be between 0 and 1"
+    if autogp.distributed.world()[1] > 1:
+        raise NotImplementedError("forecast_targets_with_nowcasts: single-rank runs only")
+    dates = list(forecast_dates)
+    draws = int(forecast_draws_per_nowcast)
+    eng = base_model._eng()
+    same_dates = all(list(nc.ds) == list(nowcasts[0].ds) for nc in nowcasts)
+    if n_mcmc == 0 and n_hmc == 0 and same_dates and lockstep:
+        w, means, covs, low, rng, sampler = _nowcast_mixtures_batched(base_model, nowcasts, dates,
+                                                                      ess_threshold)
+        P = w.shape[1]
+        if sampler is None:       # forecast_with_nowcasts draws these on the host, scenario by scenario
+            res = np.empty((len(dates), len(nowcasts) * draws))
+            for sc in range(len(nowcasts)):
+                wsc = w[sc]
+                if low[sc]:
+                    wsc = np.bincount(rng.choice(P, size=P, p=wsc), minlength=P) / P
+                res[:, sc * draws:(sc + 1) * draws] = autogp.MixtureMVN(means[:, sc, :], covs, wsc,
+                                                                        rng).rand(draws)
+            x = np.ascontiguousarray(res.T)
+            return _targets_of_paths(x if inv_transformation is None else _apply(inv_transformation, x),
+                                     targets, probs, want_values)
+        if low.any():
+            w[low] = rng.multinomial(P, w[low]) / P
+        seed = int(rng.integers(0, 2**63 - 1))
+        return autogp.path_targets((w, means, covs), targets, probs, draws, seed, inv_transformation,
+                                   engine=eng, want_values=want_values)
+    if lockstep and same_dates:
+        models = _refined_clones_lockstep(base_model, nowcasts, n_mcmc, n_hmc, ess_threshold,
+                                          hmc_config)
+        mixes = autogp.predict_mvn_lockstep(models, dates)
+        m, P = mixes[0].means.shape[1], mixes[0].means.shape[0]
+        if (getattr(eng, "mixture_sample_indep", None) is not None and len(mixes) >= 2 and draws > 1
+                and m > 0 and all(mx.sampler is not None and mx.means.shape == (P, m) for mx in mixes)):
+            return autogp.path_targets(mixes, targets, probs, draws, None, inv_transformation,
+                                       engine=eng, want_values=want_values)
+        x = np.hstack(autogp.rand_lockstep(mixes, draws, eng)).T
+    else:
+        cols = []
+        for nc in nowcasts:
+            mdl = _clone_for_scenario(base_model)
+            _refine_scenario(mdl, nc, n_mcmc, n_hmc, ess_threshold, hmc_config)
+            cols.append(autogp.predict_mvn(mdl, dates).rand(draws))
+        x = np.hstack(cols).T
+    x = np.ascontiguousarray(x)
+    return _targets_of_paths(x if inv_transformation is None else _apply(inv_transformation, x),
+                             targets, probs, want_values)
 
 
 def _clone_for_scenario(base_model: GPModel) -> GPModel:
