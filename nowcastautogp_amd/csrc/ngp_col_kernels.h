@@ -334,8 +334,8 @@ __global__ __launch_bounds__(256, 4) void chol_diag_kernel(JobGeom g, ChunkPtrs 
 // (measured: the kernel turned bandwidth-bound).  So block columns are processed in pairs:
 //   FAT  step (j even):  chol_col_glds_kernel — column j is accumulated over k < 64 j and finished
 //                        (solve + store) by one wave, while its sibling wave pre-accumulates
-//                        column j+1 over the same k from the same LDS-staged rows and subtracts
-//                        the partial sum from K in place;
+//                        column j+1 over the same k from the same LDS-staged rows, subtracts
+//                        the partial sum from K in place and runs the last quarter of the solve;
 //   THIN step (j odd):   chol_col_kernel — only k in [64 (j-1), 64 j) is left;
 //   FULL step:           chol_col_kernel — single column over all k (last column of an odd count).
 // Beside the fat launch, diag_ahead_kernel pre-accumulates the diagonal tile (j+2, j+2) over
@@ -426,13 +426,26 @@ __device__ __forceinline__ void stage_mstrips(double *lds_m, const double *mstri
 // ksl (JobGeom::toep, structured items, a tile no step has touched yet): the tile was never
 // written — K[i][jj] = ksl[63 + i - jj], the 127 table entries of the tile's lattice distances,
 // staged in LDS by the caller (struct_slice); null: read the stored tile.
-template <bool SHADOW = false, bool SYNTH = false, class Probe = NoProbe, bool KROWS = false>
-__device__ __forceinline__ void solve_and_store_lds(const double (*acc4)[4][4], double *Lr,
-                                                    const double *lds_m, long ld, int kmax,
-                                                    int lane, double *buf, Probe &probe,
-                                                    float *Lr32 = nullptr,
-                                                    float *tmax_out = nullptr, int synth = 0,
-                                                    const double *ksl = nullptr, int nit = 4) {
+// HAND (the fat steps' sibling wave): the passes are independent of each other — pass `it` reads
+// the 16 tile rows 16 it .. of K' and S' and writes the same rows of X' — so the last pass of a full
+// tile (EPI_HAND_PASS) is run by the tile's other wave, which has no solve of its own.  S' of that
+// pass is not in this wave's accumulators: the owner left it at hand[16 x 64] (element 4 jt + r of
+// lane l at hand[(4 jt + r) 64 + l]), which may be the tile `buf` — every value is read before the
+// first result is written.  Same operands, same instruction sequence per element as in the owner's
+// passes: bit-identical to the owner running all four.
+// Returns the largest magnitude stored (SHADOW; otherwise 0), the same value in every lane.
+constexpr int EPI_HAND_PASS = 3;
+template <bool SHADOW = false, bool SYNTH = false, class Probe = NoProbe, bool KROWS = false,
+          bool HAND = false>
+__device__ __forceinline__ double solve_and_store_lds(const double (*acc4)[4][4], double *Lr,
+                                                      const double *lds_m, long ld, int kmax,
+                                                      int lane, double *buf, Probe &probe,
+                                                      float *Lr32 = nullptr,
+                                                      float *tmax_out = nullptr, int synth = 0,
+                                                      const double *ksl = nullptr, int nit = 4,
+                                                      const double *hand = nullptr) {
+    static_assert(!(HAND && KROWS), "the row form of K' goes through the tile the hand-over is in");
+    constexpr int IT0 = HAND ? EPI_HAND_PASS : 0;
     double amax = 0.0;
     const int n16 = lane & 15, isub = lane >> 4;
     const int jj0 = 4 * (n16 >> 2) + isub;          // row of S' inside a 16-tile
@@ -516,16 +529,19 @@ __device__ __forceinline__ void solve_and_store_lds(const double (*acc4)[4][4], 
                 for (int r = 0; r < 4; ++r) kv[jt][r] = kvp[jt][r];
         }
     };
-    load_k(0);
+    load_k(IT0);
 #pragma unroll
-    for (int it = 0; it < 4; ++it) {                // 16 tile rows per pass
+    for (int it = IT0; it < 4; ++it) {              // 16 tile rows per pass
         if (it >= nit) break;                       // an aux tile's zero rows: nothing to solve or store
         double c4[4][4];   // C' = K' - S' for this 16-row group of the tile
         take_k(it, c4);
 #pragma unroll
         for (int jt = 0; jt < 4; ++jt)
 #pragma unroll
-            for (int r = 0; r < 4; ++r) c4[jt][r] = c4[jt][r] - acc4[jt][it][r];
+            for (int r = 0; r < 4; ++r) {
+                if constexpr (HAND) c4[jt][r] = c4[jt][r] - hand[(4 * jt + r) * 64 + lane];
+                else c4[jt][r] = c4[jt][r] - acc4[jt][it][r];
+            }
         probe.mark_after(12 + 3 * it, c4[3][3] + c4[0][0] + c4[1][2] + c4[2][1]);
         if (it + 1 < nit) load_k(it + 1);
         // 16 strip groups cb4 = 4 ct + cq (output rows 4 cb4 ..: C' tiles jt <= ct).  The M strips of
@@ -580,8 +596,9 @@ __device__ __forceinline__ void solve_and_store_lds(const double (*acc4)[4][4], 
 #pragma unroll
         for (int off = 32; off > 0; off >>= 1) amax = fmax(amax, __shfl_xor(amax, off, 64));
         // rounded UP to fp32: the decision must never see a maximum smaller than the true one
-        if (lane == 0) *tmax_out = __double2float_ru(amax);
+        if (tmax_out && lane == 0) *tmax_out = __double2float_ru(amax);
     }
+    return amax;
 }
 
 // tile[i][c0 + jj] -= S'[jj][i], straight from the 4x4x4 register layout.  The 16 elements a lane
@@ -1038,10 +1055,14 @@ __global__ __launch_bounds__(256, 2) void chol_col_glds_kernel(JobGeom g, ChunkP
     // JobGeom::toep: the main tiles of a single-table item below the block diagonal were never
     // written; a fat step is the first to touch its two columns' tiles (the sibling wave of the
     // first row tile works on the diagonal tile (j+1, j+1), which IS stored: it carries the noise)
-    bool structured = false;
+    // (sib_structured: the same for the column-j tile of this wave's row tile — the sibling wave
+    // runs one pass of that tile's solve, see the epilogue)
+    bool structured = false, sib_structured = false;
     if constexpr (!MIXED && !IDENT) {
-        if (g.toep && st.first_touch && valid && tile < st.nmain && !(col && tile == 0))
-            structured = prog_structure(p.progs + item) != 0;
+        if (g.toep && st.first_touch && valid && tile < st.nmain) {
+            sib_structured = prog_structure(p.progs + item) != 0;
+            structured = sib_structured && !(col && tile == 0);
+        }
     }
     // gradient jobs (aux rows [I ; y']): identity tile a is zero left of block column a.  The two
     // tiles of a workgroup share the staged k-range, so it starts at the smaller of their starts;
@@ -1431,37 +1452,82 @@ __global__ __launch_bounds__(256, 2) void chol_col_glds_kernel(JobGeom g, ChunkP
     }
     // the staging buffers are free (every wave passed the k-loop's last barrier): M strips go to
     // LDS for both tiles of the workgroup
-    static_assert(EPI_LDS_BYTES + TOEP_LDS_BYTES <= 2 * STAGE,
+    //
+    // Who computes what.  The column-j wave of a row tile has the long job — the solve X' = M C',
+    // 640 mfma4 and the tile read and written — its sibling only K - S' in place, after which its
+    // SIMD slot would hold nothing until the kernel ends.  The solve's four passes (16 tile rows
+    // each) are independent, so the sibling runs the last one (EPI_HAND_PASS) of every full tile:
+    // the column-j wave leaves S' of those 16 rows in the SIBLING's LDS tile ahead of the barrier
+    // that publishes the M strips (no further synchronisation: the two waves write disjoint rows of
+    // the tile in HBM), and the sibling reads K' of those rows itself.  Each element of X' is still
+    // formed by one wave with solve_and_store_lds's instruction sequence: bit-identical.  (Two
+    // passes would balance the waves better where the in-place update is short, but S' of a
+    // second pass — 8 KiB per tile — has no room beside the M strips in the 72 KiB of staging.)
+    static_assert(EPI_LDS_BYTES + TOEP_LDS_BYTES + 2 * 8 <= 2 * STAGE,
                   "epilogue LDS must fit the stage buffers");
+    static_assert(16 * 64 * 8 <= EPI_WAVE_BYTES, "S' of one pass must fit a wave's LDS tile");
     probe.mark(3);
-    const double *ksl = nullptr;
+    double *wtile = reinterpret_cast<double *>(smem + EPI_M_BYTES + wave * EPI_WAVE_BYTES);
+    const bool hand_over = valid && nit == 4;    // the same in both waves of a row tile
+    const double *ksl = nullptr, *sib_ksl = nullptr;
     if (structured) {
         double *sl = reinterpret_cast<double *>(smem + EPI_LDS_BYTES) + wave * 128;
         struct_slice(sl, g, p, item, (int)tile_row0(tile), col ? kmax + NB : kmax, lane);
         ksl = sl;
     }
+    if (col && sib_structured) sib_ksl = reinterpret_cast<double *>(smem + EPI_LDS_BYTES) + (wave - 1) * 128;
+    if (!col && hand_over) {
+        double *hand = reinterpret_cast<double *>(smem + EPI_M_BYTES + (wave + 1) * EPI_WAVE_BYTES);
+#pragma unroll
+        for (int jt = 0; jt < 4; ++jt)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) hand[(4 * jt + r) * 64 + lane] = acc4[jt][EPI_HAND_PASS][r];
+    }
     stage_mstrips(reinterpret_cast<double *>(smem), p.dinv + (long)item * (NB * NB), tid);
     __syncthreads();
     probe.mark(4);
-    if (!valid) return;
+    if constexpr (!MIXED) {
+        if (!valid) return;
+    }
 
     double *Lr = Lit + tile_row0(tile) * ld;
-    if (col) {
-        subtract_in_place_rows(Lr, ld, (j + 1) * NB, acc4, lane,
-                               reinterpret_cast<double *>(smem + EPI_M_BYTES + wave * EPI_WAVE_BYTES),
-                               IDENT && synth != 0, ksl, nit);
-    } else if constexpr (MIXED) {
-        const int rt = (tile < st.nmain) ? j + 1 + tile : g.nb0 + (tile - st.nmain);
-        solve_and_store_lds<true>(
-            acc4, Lr, reinterpret_cast<const double *>(smem), ld, kmax, lane,
-            reinterpret_cast<double *>(smem + EPI_M_BYTES + wave * EPI_WAVE_BYTES), probe,
-            p.L32 + (long)item * g.item_stride + tile_row0(tile) * ld,
-            p.tmax + (long)item * (g.nb0 + g.naux_pad / NB) * g.nb0 + tmax_index(g, rt, j));
+    const double *lds_m = reinterpret_cast<const double *>(smem);
+    const int nown = hand_over ? EPI_HAND_PASS : nit;   // passes the column-j wave runs itself
+    // pair 0 (no k-range): S' = 0 and K - S' is K — a stored tile is neither read nor written; a
+    // tile that exists only as a table slice or as the identity's zeros is still materialised
+    const bool no_sum = SPLITK == 0 && (MIXED ? j == 0 : kmax <= kbeg);
+    if constexpr (MIXED) {
+        // the tile's largest magnitude is the larger of the two waves' (fmax: exact, any order);
+        // the sibling's goes through LDS, behind a barrier that every wave reaches
+        double *xch = reinterpret_cast<double *>(smem + EPI_LDS_BYTES + TOEP_LDS_BYTES);
+        float *Lr32 = p.L32 + (long)item * g.item_stride + tile_row0(tile) * ld;
+        double amax = 0.0;
+        if (valid && col) {
+            if (hand_over)
+                amax = solve_and_store_lds<true, false, Probe, false, true>(
+                    acc4, Lr, lds_m, ld, kmax, lane, wtile, probe, Lr32, nullptr, 0, nullptr, 4, wtile);
+            if (lane == 0) xch[ltile] = amax;
+            if (!no_sum) subtract_in_place_rows(Lr, ld, (j + 1) * NB, acc4, lane, wtile, false, nullptr, nit);
+        } else if (valid) {
+            amax = solve_and_store_lds<true, false, Probe>(acc4, Lr, lds_m, ld, kmax, lane, wtile,
+                                                           probe, Lr32, nullptr, 0, nullptr, nown);
+        }
+        __syncthreads();
+        if (valid && !col && lane == 0) {
+            const int rt = (tile < st.nmain) ? j + 1 + tile : g.nb0 + (tile - st.nmain);
+            p.tmax[(long)item * (g.nb0 + g.naux_pad / NB) * g.nb0 + tmax_index(g, rt, j)] =
+                __double2float_ru(fmax(amax, xch[ltile]));
+        }
+    } else if (col) {
+        if (hand_over)
+            solve_and_store_lds<false, IDENT, Probe, false, true>(
+                acc4, Lr, lds_m, ld, kmax, lane, wtile, probe, nullptr, nullptr, synth, sib_ksl, 4, wtile);
+        const bool fresh = IDENT && synth != 0;
+        if (!(no_sum && !fresh && ksl == nullptr))
+            subtract_in_place_rows(Lr, ld, (j + 1) * NB, acc4, lane, wtile, fresh, ksl, nit);
     } else {
-        solve_and_store_lds<false, IDENT>(
-            acc4, Lr, reinterpret_cast<const double *>(smem), ld, kmax, lane,
-            reinterpret_cast<double *>(smem + EPI_M_BYTES + wave * EPI_WAVE_BYTES), probe, nullptr,
-            nullptr, synth, ksl, nit);
+        solve_and_store_lds<false, IDENT, Probe>(acc4, Lr, lds_m, ld, kmax, lane, wtile, probe, nullptr,
+                                                 nullptr, synth, ksl, nown);
     }
     probe.mark(5);
     probe.drain();       // stores retired (vmcnt(0))
