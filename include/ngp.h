@@ -78,12 +78,14 @@ typedef struct ngp_spec {
     double  jitter;        /* added to the diagonal next to the noise variance */
     /* ---- NGP_PREC_MIXED only (BASELINE config C5: long histories) ---------------------
      * The trailing updates of the blocked Cholesky run on the fp32 matrix cores wherever
-     * that is provably harmless and in fp64 elsewhere: the product of two 64x64 tiles of L
-     * goes through v_mfma_f32_32x32x2_f32 (operands rounded to fp32) iff
-     *     64 * 2^-24 * max|tile A| * max|tile B|  <=  mixed_tau * (noise + jitter),
-     * i.e. iff its rounding error is below mixed_tau of the smallest pivot the matrix can
-     * have; everything else (the diagonal blocks, the panel solves, the accumulators and
-     * the stored factor) stays fp64.  The Gram matrix X K^-1 X' of the appended / forecast
+     * that is provably harmless and in fp64 elsewhere: a workgroup multiplies two tiles of
+     * the column pair (A) with two row tiles (B), 64x64 tiles of L each, and a k-tile of
+     * those four products goes through v_mfma_f32_32x32x2_f32 (operands rounded to fp32) iff
+     *     64 * 2^-24 * max|A tiles| * max|B tiles|  <=  mixed_tau * (noise + jitter),
+     * the maxima taken over BOTH tiles of each pair (stricter than a rule per single
+     * product), i.e. iff the rounding error of each is below mixed_tau of the smallest
+     * pivot the matrix can have; everything else (the diagonal blocks, the panel solves,
+     * the accumulators and the stored factor) stays fp64.  The Gram matrix X K^-1 X' of the appended / forecast
      * / data rows is then refined against the fp64 covariance (G <- A X' + (X - A K) A',
      * A += (X - A K) (L L')^-1) until the predicted remaining relative error is below
      * refine_tol or refine_max steps were taken; an item that does not get there is

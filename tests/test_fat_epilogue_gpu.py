@@ -118,3 +118,19 @@ def test_mixed_precision_tile_maxima_across_the_two_waves(ctx):
         assert nerr(lm[b], rlm) < TOL_MIXED, (b, cond)
         assert nerr(mu[b], rmu) < TOL_MIXED, (b, cond)
         assert nerr(np.diag(sg[b]), np.diag(rsg)) < TOL_MIXED, (b, cond)
+    # the merged maxima decide which tile products run in fp32: the share the device reports against
+    # the host model's counts (tests/mixed_model.py; the allowance is tests/mixed_cases.count_error's)
+    from tests import mixed_cases, mixed_model
+    sp = default_spec(NGP_PREC_MIXED)
+    ctx.set_spec(sp)
+    try:
+        job = ctx.stage_predict(progs, t, y, t_new)
+        frac = job.run().mixed_stats()["frac_f32"]
+        job.close()
+    finally:
+        ctx.set_spec(default_spec())
+    for b, p in enumerate(progs):
+        m = mixed_model.item_counts(p, t, y, t_new, sp.mixed_tau, sp.jitter)
+        err, allowed = mixed_cases.count_error(frac[b], m)
+        assert m["n32"] + m["n64"] == 8 and m["borderline"] == 0
+        assert err <= allowed, (b, frac[b], m["n32"], m["n64"])
