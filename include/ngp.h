@@ -657,6 +657,19 @@ typedef struct ngp_profile {
     double   flops[NGP_NUM_KERNEL_CLASSES];    /* algorithmic flops executed   */
     double   bytes[NGP_NUM_KERNEL_CLASSES];    /* algorithmic HBM bytes        */
 } ngp_profile;
+/* Lattice dates.  Dates that sit on a lattice t = tmin + q h (whole-day dates, before or after a
+ * rescale to [0, 1]) let every job replace the transcendentals of stationary subtrees by tables of
+ * k(q h); structured storage and the Toeplitz gradient path below build on the same decision.  It is
+ * made per call from all dates of the call (t, t_add, t_new) and accepts a series only if
+ *     max_ij |(t_i - t_j) - (q_i - q_j) h| <= 2.5 eps (tmax - tmin),
+ * i.e. the table arguments are the date differences to rounding at the scale of the differences;
+ * a lattice of more than 16 (dates) + 4096 steps is refused for the size of its tables.  Correctly
+ * rounded lattice dates qualify when their origin lies within their span (max |t| <= tmax - tmin):
+ * k / (n - 1), slope * (days - origin), whole-day numbers (exact).  Dates far from their origin —
+ * decimal years 2020 + k / 52, 1e4 + u — carry eps |t| / 2 of representation noise each, many eps
+ * of the span: they are NOT taken for a lattice and every covariance entry is evaluated from the
+ * dates as given, which is correct to rounding for any dates, but slower.  A caller who wants the
+ * table route subtracts the origin before the call. */
 /* Storage option of staged fp64 value jobs (on by default).  On a regular series (the main
  * block's dates at a constant lattice stride) the covariance matrix of a stationary kernel tree is
  * Toeplitz, K_ik = f(|i - k|): 127 numbers describe a 64 x 64 tile exactly.  Such an item's tiles

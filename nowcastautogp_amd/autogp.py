@@ -172,8 +172,8 @@ class DateTransform(LinearTransform):
     """The affine map days -> model time, applied as ``slope * (days - origin)``: the subtraction
     of two day numbers is exact, so dates that are whole days apart land on an exact lattice
     ``q * slope`` — which is what lets the library replace every transcendental of the kernel
-    grammar by table lookups (``detect_lattice`` in csrc/ngp_api.hip accepts a few ulp of
-    deviation).  ``slope * days + intercept`` on day numbers of ~7e5 loses eleven digits to
+    grammar by table lookups (``detect_lattice`` in csrc/ngp_plan.h accepts 2.5 eps of
+    the span between the dates and their lattice, so the origin has to lie within the data's span).  ``slope * days + intercept`` on day numbers of ~7e5 loses eleven digits to
     cancellation and every job of a fitted model took the direct-evaluation kernels."""
     origin: float = 0.0
 

@@ -294,52 +294,6 @@ ngp_status compile_program(const ngp_kernel *k, DevProgram *out, std::vector<int
     return NGP_OK;
 }
 
-// Do all times sit on a lattice t = tmin + q h (true for integer-day dates after the [0,1]
-// rescale)?  Floating-point Euclid over the gaps; accepted only if every point is reproduced to a
-// few ulp, so a table value at distance k h equals the direct evaluation to rounding.
-bool detect_lattice(const std::vector<double> &t, double *h_out, std::vector<int32_t> *q,
-                    int *R_out) {
-    const size_t n = t.size();
-    if (n < 2) return false;
-    double tmin = t[0], tmax = t[0];
-    for (double v : t) { tmin = std::min(tmin, v); tmax = std::max(tmax, v); }
-    if (!(tmax > tmin) || !std::isfinite(tmax) || !std::isfinite(tmin)) return false;
-    const double span = tmax - tmin;
-    const double tol = 1e-9 * span;
-    double g = 0.0;
-    for (double v : t) {
-        double a = v - tmin;
-        if (a <= tol) continue;
-        if (g == 0.0) { g = a; continue; }
-        double x = g, y = a;          // Euclid with snapping
-        for (int it = 0; it < 64 && y > tol; ++it) {
-            double r = std::fmod(x, y);
-            if (y - r <= tol) r = 0.0;
-            x = y;
-            y = r;
-        }
-        g = x;
-        if (g < span / (double)(1 << 20)) return false;
-    }
-    if (g <= 0.0) return false;
-    const double qmaxd = std::round(span / g);
-    if (qmaxd < 1.0 || qmaxd > (double)(1 << 20)) return false;
-    // a lattice far sparser than the data (a few points on a very fine grid) would cost more in
-    // tables (R entries per stationary subtree and item) than direct evaluation costs in the fill
-    if (qmaxd > 16.0 * (double)n + 4096.0) return false;
-    const double h = span / qmaxd;
-    const double scale = std::max(std::max(std::fabs(tmin), std::fabs(tmax)), 1.0);
-    q->resize(n);
-    for (size_t i = 0; i < n; ++i) {
-        const double qi = std::round((t[i] - tmin) / h);
-        if (std::fabs((t[i] - tmin) - qi * h) > 16.0 * 2.220446049250313e-16 * scale) return false;
-        (*q)[i] = (int32_t)qi;
-    }
-    *h_out = h;
-    *R_out = (int)qmaxd + 1;
-    return true;
-}
-
 }  // namespace
 
 // ---------------------------------------------------------------------------------------

@@ -6,6 +6,10 @@
 // Two thresholds that are equal today keep two names where they guard different things.
 #pragma once
 
+#include <cmath>
+#include <cstdint>
+#include <vector>
+
 namespace ngp {
 
 // ---- thresholds ------------------------------------------------------------------------------------
@@ -202,6 +206,73 @@ inline bool ahead_early(int bc) { return bc <= AHEAD_EARLY_MAX_ITEMS; }
 // workgroups per 64 x 64 tile of a fill or contraction launch of nwg tiles
 inline int launch_split(long nwg) { return nwg <= SPLIT4_MAX_WGS ? 4 : (nwg <= SPLIT2_MAX_WGS ? 2 : 1); }
 inline int tiles_per_wg(long nwg) { return nwg >= TILES4_MIN_WGS ? 4 : 1; }
+
+// ---- lattice dates -----------------------------------------------------------------------------------
+// Do all dates sit on a lattice t = tmin + q h (integer-day dates, before or after a rescale)?  Every
+// consumer of "lattice" dates trusts this one decision: once a series is accepted, a stationary
+// subtree is no longer evaluated at t_i - t_j but read from a table at |q_i - q_j| h.
+// Floating-point Euclid over the gaps gives h; then the residuals e_i = (t_i - tmin) - q_i h, formed
+// without rounding error (two-sum and fma), must all lie within LATTICE_FIT_ACCEPT eps span of each
+// other: max_ij |(t_i - t_j) - (q_i - q_j) h| <= 2.5 eps (tmax - tmin), so a table argument equals the
+// difference of the dates to rounding AT THE SCALE OF THE DIFFERENCES.  Correctly rounded dates on a
+// lattice whose origin is within the span of the data (max |t| <= span: k / (n - 1) with forecasts
+// beyond 1, slope (days - origin), whole-day numbers, which are exact) fit within 2: eps / 2 |t_i| from
+// each date and eps / 2 span from h = span / qmax.  tests/sanitize/plan_check.cpp sweeps the rule.
+// The bound is NOT taken at the magnitude of the dates (it was: 16 eps max(|t|, 1) per point).  Dates
+// far from their origin (decimal years 2020 + k / 52, 1e4 + k / (n - 1)) carry a representation noise
+// of eps |t| / 2 each, many eps of the span, and tables built on them were off by up to 4e-10 k(0)
+// per entry (logml of a 321-point series by 9e-10 relative, on the device).  Such dates are refused
+// and evaluated directly, which is right to rounding for any dates and slower; a caller who wants
+// the tables subtracts the origin first (whole-day dates minus a whole-day origin are exact).
+constexpr double LATTICE_FIT_ACCEPT = 2.5, LATTICE_SNAP = 1e-9;
+constexpr int LATTICE_MAX_STEPS = 1 << 20;
+inline bool detect_lattice(const std::vector<double> &t, double *h_out, std::vector<int32_t> *q,
+                           int *R_out) {
+    const size_t n = t.size();
+    if (n < 2) return false;
+    double tmin = t[0], tmax = t[0];
+    for (double v : t) { tmin = std::min(tmin, v); tmax = std::max(tmax, v); }
+    if (!(tmax > tmin) || !std::isfinite(tmax) || !std::isfinite(tmin)) return false;
+    const double span = tmax - tmin;
+    const double tol = LATTICE_SNAP * span;
+    double g = 0.0;
+    for (double v : t) {
+        double a = v - tmin;
+        if (a <= tol) continue;
+        if (g == 0.0) { g = a; continue; }
+        double x = g, y = a;          // Euclid with snapping
+        for (int it = 0; it < 64 && y > tol; ++it) {
+            double r = std::fmod(x, y);
+            if (y - r <= tol) r = 0.0;
+            x = y;
+            y = r;
+        }
+        g = x;
+        if (g < span / (double)LATTICE_MAX_STEPS) return false;
+    }
+    if (g <= 0.0) return false;
+    const double qmaxd = std::round(span / g);
+    if (qmaxd < 1.0 || qmaxd > (double)LATTICE_MAX_STEPS) return false;
+    // a lattice far sparser than the data (a few points on a very fine grid) would cost more in
+    // tables (R entries per stationary subtree and item) than direct evaluation costs in the fill
+    if (qmaxd > 16.0 * (double)n + 4096.0) return false;
+    const double h = span / qmaxd;
+    q->resize(n);
+    double lo = 0.0, hi = 0.0;
+    for (size_t i = 0; i < n; ++i) {
+        const double a = t[i] - tmin, bv = a - t[i];
+        const double a_err = (t[i] - (a - bv)) + (-tmin - bv);      // t_i - tmin = a + a_err exactly
+        const double qi = std::round(a / h);
+        const double e = std::fma(-qi, h, a) + a_err;
+        lo = i ? std::min(lo, e) : e;
+        hi = i ? std::max(hi, e) : e;
+        if (hi - lo > LATTICE_FIT_ACCEPT * 2.220446049250313e-16 * span) return false;
+        (*q)[i] = (int32_t)qi;
+    }
+    *h_out = h;
+    *R_out = (int)qmaxd + 1;
+    return true;
+}
 
 // ---- the fill ----------------------------------------------------------------------------------------
 enum FillRoute {

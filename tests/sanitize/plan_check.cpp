@@ -4,9 +4,11 @@
 // at most SM_MAX_SWEEPS sweeps — and must carry every aux row-block exactly once; the inverse phase of
 // a gradient job must give every block column to one wave.  Then the other route rules of
 // csrc/ngp_plan.h over their whole domain, for the relations the host layer relies on
-// (check_routes).  Host code only (hipcc --cuda-host-only).
+// (check_routes), and the acceptance rule of lattice dates (check_lattice).  Host code only (hipcc
+// --cuda-host-only).
 #include <cstddef>
 #include <cstdio>
+#include <random>
 #include <vector>
 
 #include "../../nowcastautogp_amd/csrc/ngp_internal.h"
@@ -137,8 +139,109 @@ static void check_routes() {
                       "split-k pieces of %d groups exceed the slots", groups);
 }
 
+// ---- detect_lattice ------------------------------------------------------------------------------------
+// Whatever it accepts is read from tables at |q_i - q_j| h in place of t_i - t_j, so acceptance has to
+// mean max_ij |(t_i - t_j) - (q_i - q_j) h| <= LATTICE_FIT eps span: the table arguments are the date
+// differences to rounding at the scale of the differences.  The multiple is measured, not chosen: the
+// worst value the two [0, 1] families (k / (n - 1) and 7 k / (7 (n - 1)), n = 2 .. 4096) show is
+// LATTICE_FIT_MEASURED, and four times that is allowed to every accepted series (the rule itself
+// stops at LATTICE_FIT_ACCEPT = 2.5, ngp_plan.h: below this bound, above the 2 that correctly rounded
+// dates with their origin inside the span can reach).
+// (In long double, the fp64 dates and h taken as exact: e_i = t_i - q_i h, max_ij = max e - min e.)
+constexpr double LATTICE_FIT_MEASURED = 0.73;     // eps span; printed by every run ("worst fit")
+constexpr double LATTICE_FIT = 4.0 * LATTICE_FIT_MEASURED;
+static_assert(LATTICE_FIT_ACCEPT < LATTICE_FIT, "the rule accepts more than the sweep allows");
+constexpr double EPS = 2.220446049250313e-16;
+
+// fit of an accepted series in units of eps span, -1: refused
+static double lattice_fit(const std::vector<double> &t) {
+    double h = 0.0;
+    std::vector<int32_t> q;
+    int R = 0;
+    if (!detect_lattice(t, &h, &q, &R)) return -1.0;
+    long double lo = 0, hi = 0, tmin = t[0], tmax = t[0];
+    int qmax = 0;
+    for (size_t i = 0; i < t.size(); ++i) {
+        const long double e = (long double)t[i] - (long double)q[i] * (long double)h;
+        if (i == 0 || e < lo) lo = e;
+        if (i == 0 || e > hi) hi = e;
+        tmin = std::min<long double>(tmin, t[i]);
+        tmax = std::max<long double>(tmax, t[i]);
+        qmax = std::max(qmax, (int)q[i]);
+        CHECK(q[i] >= 0 && q[i] < R, "index %d outside a table of %d", (int)q[i], R);
+    }
+    CHECK(qmax == R - 1, "the table has %d entries, the largest index is %d", R, qmax);
+    return (double)((hi - lo) / ((long double)EPS * (tmax - tmin)));
+}
+
+static void check_lattice() {
+    double worst_unit = 0.0, worst_any = 0.0;
+    int accepted[6] = {}, total = 0;
+    std::mt19937_64 rng(7);
+    std::vector<double> t;
+    auto family = [&](int n, int f, int k) -> double {
+        switch (f) {
+            case 0: return (double)k / (double)(n - 1);                     // unit
+            case 1: return (7.0 * k) / (7.0 * (n - 1));                     // days over the last day
+            case 2: return 19000.0 + 7.0 * k;                               // whole days, weekly
+            case 3: return 2020.0 + (double)k / 52.0;                       // decimal years
+            case 4: return 100.0 + (double)k / (double)(n - 1);
+            case 5: return 1e4 + (double)k / (double)(n - 1);
+            case 6: return -1.0 + 0.3 * (double)k / (double)(n - 1);
+            default: return (double)k / (double)(n - 1 - (n - 1) / 9);      // forecasts beyond 1 (n >= 10: up to 1.125)
+        }
+    };
+    for (int n = 2; n <= 4096; ++n) {
+        ++total;
+        for (int f = 0; f < 8; ++f) {
+            t.resize((size_t)n);
+            for (int k = 0; k < n; ++k) t[(size_t)k] = family(n, f, k);
+            const double fit = lattice_fit(t);
+            if (f <= 2 || f == 7) {
+                CHECK(fit >= 0.0, "family %d refused at n = %d", f, n);
+                if (f <= 1) worst_unit = std::max(worst_unit, fit);
+            }
+            if (fit >= 0.0 && f < 6) ++accepted[f];
+            worst_any = std::max(worst_any, fit);
+            CHECK(fit <= LATTICE_FIT, "family %d, n = %d: accepted with a fit of %.2f eps span", f, n, fit);
+        }
+        // descending whole days and daily steps from another origin
+        for (int k = 0; k < n; ++k) t[(size_t)k] = 738000.0 - (double)k;
+        CHECK(lattice_fit(t) == 0.0, "descending whole days at n = %d", n);
+        if (n % 16 && n > 2) continue;
+        // a random sparse subset of a fine lattice on either side of the table-cost refusal, in the
+        // shifted conventions as well; then a random nudge of one date
+        for (int rep = 0; rep < 4; ++rep) {
+            const int Q = 16 * n + 4096 + (rep & 1 ? 8 : -8);
+            std::vector<int> idx((size_t)n);
+            for (int k = 0; k < n; ++k) idx[(size_t)k] = (int)(rng() % (uint64_t)(Q + 1));
+            idx[0] = 0; idx[1] = Q; if (n > 2) idx[2] = 1;
+            const double origin = rep & 2 ? 2020.0 : 0.0;
+            for (int k = 0; k < n; ++k) t[(size_t)k] = origin + (double)idx[(size_t)k] / (double)Q;
+            double fit = lattice_fit(t);
+            if (n > 2) CHECK((rep & 1) ? fit < 0.0 : true, "n = %d: a table of %d entries accepted", n, Q + 1);
+            if (n > 2 && !(rep & 1) && origin == 0.0) CHECK(fit >= 0.0, "n = %d: a sparse lattice of %d steps refused", n, Q);
+            worst_any = std::max(worst_any, fit);
+            CHECK(fit <= LATTICE_FIT, "sparse, n = %d rep %d: fit %.2f eps span", n, rep, fit);
+            for (int k = 0; k < n; ++k) t[(size_t)k] = family(n, rep & 2 ? 3 : 0, k);
+            const size_t j = (size_t)(rng() % (uint64_t)n);
+            const double mag = std::pow(10.0, -16.0 + 9.0 * (double)(rng() % 1000) / 1000.0);   // 1e-16 .. 1e-7 of the span
+            t[j] += mag * (t[(size_t)n - 1] - t[0]);
+            fit = lattice_fit(t);
+            worst_any = std::max(worst_any, fit);
+            CHECK(fit <= LATTICE_FIT, "nudged by %.1e of the span, n = %d rep %d: fit %.2f eps span", mag, n, rep, fit);
+        }
+    }
+    CHECK(worst_unit <= LATTICE_FIT_MEASURED && worst_unit > 0.5 * LATTICE_FIT_MEASURED,
+          "the measured fit of the [0, 1] families is %.3f eps span, the constant says %.3f", worst_unit, LATTICE_FIT_MEASURED);
+    printf("lattice sweep: %d lengths, worst fit of the [0, 1] families %.3f eps span, of anything accepted %.3f; "
+           "accepted: unit %d, days/last %d, whole days %d, decimal years %d, 100 + u %d, 1e4 + u %d\n",
+           total, worst_unit, worst_any, accepted[0], accepted[1], accepted[2], accepted[3], accepted[4], accepted[5]);
+}
+
 int main() {
     check_routes();
+    check_lattice();
     int accepted = 0, refused = 0;
     for (int grad = 0; grad < 2; ++grad)
         for (int n0 = 64; n0 <= 320; n0 += 64)

@@ -1,6 +1,7 @@
 """The planner of the short-series launch (``small_plan``, csrc/ngp_plan.h) checked on the host
 over every geometry it can be asked about (tests/sanitize/plan_check.cpp): what it accepts fits the
-kernel's registers, LDS and sweep count and carries every aux row-block exactly once.  No GPU."""
+kernel's registers, LDS and sweep count and carries every aux row-block exactly once; and ``detect_lattice`` over the date families of
+tests/date_cases.py: what it accepts fits its lattice to a measured multiple of eps span.  No GPU."""
 import os
 import shutil
 import subprocess
@@ -19,3 +20,5 @@ def test_every_accepted_geometry_fits_the_kernel(tmp_path):
     out = subprocess.run([exe], capture_output=True, text=True, timeout=300)
     assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-2000:]
     assert "0 failures" in out.stdout and "1024 geometries accepted" in out.stdout, out.stdout[-500:]
+    # the acceptance rule of lattice dates (detect_lattice), swept over n = 2 .. 4096 in the same program
+    assert "lattice sweep: 4095 lengths" in out.stdout, out.stdout[-800:]
