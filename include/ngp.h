@@ -100,6 +100,8 @@ typedef struct ngp_spec {
 enum { NGP_PREC_F64 = 0, NGP_PREC_MIXED = 1 };
 /* info[] < 0: not a pivot index */
 #define NGP_INFO_NOT_REFINED (-2)
+#define NGP_INFO_NOT_FINITE (-3)      /* ngp_mixture_crps_mapped: the score is infinite / undefined */
+#define NGP_INFO_NOT_CONVERGED (-4)   /* ngp_mixture_crps_mapped: panel cap reached, values returned */
 
 /* One particle's covariance kernel: the tree in postfix (RPN) order
  * (left subtree, right subtree, operator); params are consumed in RPN order. */
@@ -506,6 +508,65 @@ ngp_status ngp_mixture_path_targets_indep(ngp_ctx *ctx, int32_t P, int32_t S, in
                                           const double *probs, double *q, double *mean,
                                           int64_t *count, int64_t *hist, double *values,
                                           int32_t *info);
+
+/* ---- exact CRPS and mean on the natural and log scales ----------------------------------------
+ * ngp_mixture_crps scores on the scale the mixture is Gaussian on.  The reference's vignette fits
+ * on a Box-Cox scale, maps the draws back and scores crps(log(y), log.(X))
+ * (docs/vignettes/getting-started.jl:704-747); hubs score on the natural and on the log scale.
+ * Quantiles carry over through a monotone map, the CRPS and the mean do not — but both are
+ * integrals in the mixture's own CDF.  With g ONE ngp_inv_transform, edge rules as above, and s the
+ * score scale
+ *   NGP_SCORE_NATURAL  s(v) = v            NGP_SCORE_LOG  s(v) = log(v + shift)
+ * psi = s o g non-decreasing, Y = psi(X), yt = s(y) and x0 where psi crosses yt:
+ *   CRPS(Y, yt) = int (F_X(x) - 1{x >= x0})^2 dpsi(x)  +  |yt - psi(x0)|
+ *   E[Y]        = psi(x0) + int_{x > x0} (1 - F_X) dpsi - int_{x < x0} F_X dpsi
+ * (the second term of the CRPS is nonzero only for a y the forecast cannot reach, x0 clipped).
+ * Flat stretches of psi — the clamp at 0, the Box-Cox floor — contribute nothing to the integrals;
+ * the atom they create is in F_X already.  The integrals run over [lo, hi], the range outside of
+ * which every component's tail, times the growth of psi there, is below 1e-18,
+ * split at x0 and at the boundaries of g, in uniform panels no wider than the smallest standard
+ * deviation of the date, each with a Gauss-Kronrod 7/15 pair.
+ *   w, mu, var      as ngp_mixture_crps
+ *   inv             const void * to ONE ngp_inv_transform, as the path targets pass it
+ *   scale, shift    shift >= 0, finite; ignored for NGP_SCORE_NATURAL
+ *   y [m]           observations on the ORIGINAL scale
+ *   tol             requested relative accuracy of crps; <= 0: the default, 1e-10
+ *   crps [m]        CRPS(Y_j, yt_j) on the score scale (the K15 sums)
+ *   mean [m]        E[Y_j] on the score scale; may be NULL
+ *   err [m]         the call's own estimate of the absolute quadrature error of crps[j], the sum of
+ *                   |K15 - G7| over the panels; may be NULL
+ *   info [m]        0, or
+ *                   c + 1: component c is bad at date j, as in the calls above (date NaN, other
+ *                     dates untouched);
+ *                   NGP_INFO_NOT_CONVERGED (-4): a date whose err exceeds tol |crps| is integrated
+ *                     again at half the panel width, alone, up to 8,192 panels per date; at that
+ *                     cap with err still above tol |crps| the values ARE returned, with this code;
+ *                   NGP_INFO_NOT_FINITE (-3), date NaN: the score is infinite or psi is not
+ *                     monotone where the mass is —
+ *                       NGP_SCORE_LOG with shift = 0 (more precisely g + shift <= 0) on a stretch
+ *                       that reaches into [lo, hi], i.e. positive mass where g = 0;
+ *                       NGP_INV_BOXCOX with lam < 0 and more than 1e-12 of the date's mass beyond
+ *                       the pole x = -1 / lam, where the reference's rule maps to 0 (mass within
+ *                       that tolerance is ignored: the integral stops at the pole);
+ *                       a result that is not finite in fp64 (exp overflow).
+ * Accuracy: |crps - exact| <= err + 1e-13 sum_c w_c E|Y_c - yt| (the floor ngp_mixture_crps is
+ * granted), and err <= tol |crps| whenever info = 0.  Identities:
+ *   NGP_INV_IDENTITY + NATURAL                     = ngp_mixture_crps(y)
+ *   NGP_INV_EXP (offset 0) + LOG (shift 0)         = ngp_mixture_crps(log y)
+ *   one component, NGP_INV_EXP (offset 0) + NATURAL = the lognormal closed form (Baran & Lerch
+ *     2015):  y (2 Phi(z) - 1) - 2 exp(mu + sd^2 / 2) (Phi(z - sd) + Phi(sd / sqrt 2) - 1),
+ *     z = (ln y - mu) / sd
+ * NGP_ERR_ARG, before anything touches a device: as ngp_mixture_crps, plus an unknown scale or
+ * inv.kind; a non-finite shift, tol, lam, offset or cap; shift < 0; a non-finite y, or a y where
+ * s(y) is undefined (y + shift <= 0 for NGP_SCORE_LOG).  Limits: those of ngp_mixture_crps.
+ * Bitwise reproducible from call to call; a date's bits do not depend on the other dates of the
+ * call (fixed-order sums, no floating-point atomics).  Thread-safe through the context's lock; not
+ * combined with concurrent callers; not counted in ngp_profile.                                  */
+enum { NGP_SCORE_NATURAL = 0, NGP_SCORE_LOG = 1 };
+ngp_status ngp_mixture_crps_mapped(ngp_ctx *ctx, int32_t C, int32_t m, const double *w,
+                                   const double *mu, const double *var, const void *inv,
+                                   int32_t scale, double shift, const double *y, double tol,
+                                   double *crps, double *mean, double *err, int32_t *info);
 
 /* ---- cached factor ------------------------------
  * A fitted model is queried many times with the same particles and the same

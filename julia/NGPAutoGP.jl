@@ -505,6 +505,31 @@ struct InvTransform
     offset::Float64
     cap::Float64
 end
+
+const NGP_SCORE_NATURAL = Int32(0)
+const NGP_SCORE_LOG = Int32(1)
+
+"""
+Exact CRPS and mean of the forecast after the inverse transformation `inv`, on the natural scale
+(`scale = NGP_SCORE_NATURAL`) or on log(. + shift) (`NGP_SCORE_LOG`), against y [m] on the ORIGINAL
+scale: returns (crps, mean, err, info) (`ngp_mixture_crps_mapped`); `tol <= 0`: the default.
+"""
+function mixture_crps_mapped(c::Context, w::Vector{Float64}, mu::Matrix{Float64}, var::Matrix{Float64},
+                             inv::InvTransform, scale::Integer, shift::Real, y::Vector{Float64};
+                             tol::Real = 0.0)
+    C, m = _check_marginals(w, mu, var)
+    length(y) == m || throw(DimensionMismatch("y has one entry per date"))
+    out = Vector{Float64}(undef, m); mean = Vector{Float64}(undef, m); err = Vector{Float64}(undef, m)
+    info = zeros(Int32, m)
+    iv = Ref(inv)
+    GC.@preserve iv check(ccall((:ngp_mixture_crps_mapped, LIBNGP), Int32,
+                (Ptr{Cvoid}, Int32, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Cvoid},
+                 Int32, Float64, Ptr{Float64}, Float64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+                 Ptr{Int32}),
+                c.h, C, m, w, mu, var, Base.unsafe_convert(Ptr{Cvoid}, iv), Int32(scale),
+                Float64(shift), y, Float64(tol), out, mean, err, info), "ngp_mixture_crps_mapped")
+    return out, mean, err, info
+end
 struct PathTarget
     kind::Int32
     j0::Int32        # 0-based, as the header: the window j0 .. j1 is inclusive

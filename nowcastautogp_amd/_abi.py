@@ -18,6 +18,9 @@ NGP_SPLIT_PLUS, NGP_SPLIT_CHANGEPOINT, NGP_SPLIT_TIMES = 0, 1, 2   # ngp_kernel_
 NGP_NUM_KERNEL_CLASSES = 14
 NGP_PREC_F64, NGP_PREC_MIXED = 0, 1
 NGP_INFO_NOT_REFINED = -2
+NGP_INFO_NOT_FINITE = -3
+NGP_INFO_NOT_CONVERGED = -4
+NGP_SCORE_NATURAL, NGP_SCORE_LOG = 0, 1
 
 # parameters consumed per opcode (index = opcode), include/ngp.h enum
 N_PARAMS = (0, 1, 3, 2, 3, 3, 0, 0, 2)

@@ -41,6 +41,7 @@ SYMBOLS = (
     "ngp_kernel_components", "ngp_factor_components",
     "ngp_kernel_terms", "ngp_factor_components_nowcast",
     "ngp_mixture_path_targets", "ngp_mixture_path_targets_indep",
+    "ngp_mixture_crps_mapped",
 )
 
 
@@ -130,6 +131,8 @@ def load():
         "ngp_mixture_quantiles": (i32, [vp, i32, i32, f64p, f64p, f64p, i32, f64p, f64p, i32p]),
         "ngp_mixture_crps": (i32, [vp, i32, i32, f64p, f64p, f64p, f64p, f64p, i32p]),
         "ngp_microbench_mixture_pairs": (i32, [vp, i32, f64p]),
+        "ngp_mixture_crps_mapped": (i32, [vp, i32, i32, f64p, f64p, f64p, C.POINTER(NgpInvTransform),
+                                          i32, C.c_double, f64p, C.c_double, f64p, f64p, f64p, i32p]),
         "ngp_mixture_path_targets": (i32, [vp, i32, i32, i32, f64p, f64p, f64p, i32, C.c_uint64,
                                            C.POINTER(NgpInvTransform), i32, C.POINTER(NgpPathTarget),
                                            i32, f64p, f64p, f64p, C.POINTER(i64), C.POINTER(i64),
@@ -735,6 +738,25 @@ class Context:
         _chk(load().ngp_mixture_crps(self._h, C_, m, dptr(w), dptr(mu), dptr(var), dptr(y),
                                      dptr(out), iptr(info)), "ngp_mixture_crps")
         return out, info
+
+    def mixture_crps_mapped(self, w, mu, var, inv, scale: int, shift: float, y, tol: float = 0.0):
+        """Exact CRPS and mean after the inverse transformation, on the natural or the log scale
+        (``ngp_mixture_crps_mapped``): ``inv`` = (kind, lam, offset, cap), ``scale``
+        NGP_SCORE_NATURAL / NGP_SCORE_LOG, y [m] on the original scale ->
+        (crps [m], mean [m], err [m], info [m])."""
+        w, mu, var = self._marginals(w, mu, var, "mixture_crps_mapped")
+        C_, m = mu.shape
+        y = as_f64(y)
+        if y.shape != (m,):
+            raise ValueError("mixture_crps_mapped: y [m]")
+        iv = NgpInvTransform(int(inv[0]), float(inv[1]), float(inv[2]), float(inv[3]))
+        out, mean, err = np.empty(m), np.empty(m), np.empty(m)
+        info = np.zeros(m, dtype=np.int32)
+        _chk(load().ngp_mixture_crps_mapped(self._h, C_, m, dptr(w), dptr(mu), dptr(var),
+                                            C.byref(iv), int(scale), float(shift), dptr(y),
+                                            float(tol), dptr(out), dptr(mean), dptr(err),
+                                            iptr(info)), "ngp_mixture_crps_mapped")
+        return out, mean, err, info
 
     def logml_grad_flat(self, ka: KernelArray, t, y):
         """``ngp_logml_grad_batch`` on a prepared kernel array; the gradients come back as ONE

@@ -105,6 +105,11 @@ class HipEngine:
         """Closed-form per-date CRPS on the device (``ngp_mixture_crps``)."""
         return self.ctx.mixture_crps(w, mu, var, y)
 
+    def mixture_crps_mapped(self, w, mu, var, inv, scale, shift, y, tol=0.0):
+        """Exact CRPS and mean on the natural / log scale on the device
+        (``ngp_mixture_crps_mapped``)."""
+        return self.ctx.mixture_crps_mapped(w, mu, var, inv, scale, shift, y, tol)
+
     def factor(self, programs, t, y):
         """Factorise once, keep L on the device (``ngp_factor``): repeated forecasts of a fitted
         model only pay for their appended / forecast rows."""
@@ -950,6 +955,117 @@ def _abs_moment(d, v):
     return d * _erf(r).astype(np.float64) + s * np.exp(-r * r) / math.sqrt(math.pi)
 
 
+def _host_mapped(w, mu, var, inv, scale, shift, y):
+    """Host stand-in for ``ngp_mixture_crps_mapped`` (small mixtures): composite Gauss-Legendre 20
+    in fp64 on panels of half the smallest sd between the same breakpoints, once at that width and
+    once at half of it — the difference is the error estimate.  Returns (crps, mean, err, info)."""
+    from ._abi import (NGP_INFO_NOT_FINITE, NGP_INV_BOXCOX, NGP_INV_EXP, NGP_INV_IDENTITY,
+                       NGP_INV_LOGISTIC100)
+    kind, lam, offset = int(inv[0]), float(inv[1]), float(inv[2])
+    is_exp = kind == NGP_INV_EXP or (kind == NGP_INV_BOXCOX and lam == 0.0)
+    gx, gw = np.polynomial.legendre.leggauss(20)
+
+    def g(x):
+        with np.errstate(all="ignore"):
+            if kind == NGP_INV_IDENTITY:
+                return x
+            if is_exp:
+                return np.maximum(np.exp(x) - offset, 0.0)
+            if kind == NGP_INV_LOGISTIC100:
+                return np.maximum(100.0 / (1.0 + np.exp(-x)) - offset, 0.0)
+            base = lam * x + 1.0
+            if lam > 0:
+                return np.maximum(np.maximum(base, 1e-10) ** (1.0 / lam) - offset, 0.0)
+            safe = np.where(base > 0, base, 1.0)
+            return np.maximum(np.where(base > 0, safe ** (1.0 / lam) - offset, 0.0), 0.0)
+
+    def dpsi(x):
+        with np.errstate(all="ignore"):
+            if kind == NGP_INV_IDENTITY:
+                d = np.ones_like(x)
+            elif is_exp:
+                d = np.exp(x)
+            elif kind == NGP_INV_LOGISTIC100:
+                sg = 1.0 / (1.0 + np.exp(-x))
+                d = 100.0 * sg * (1.0 - sg)
+            else:
+                d = (lam * x + 1.0) ** (1.0 / lam - 1.0)
+            return d / (g(x) + shift) if scale else d
+
+    def s(v):
+        with np.errstate(all="ignore"):
+            return np.log(v + shift) if scale else v
+
+    xL, xR, gmin = -np.inf, np.inf, -np.inf
+    if kind == NGP_INV_IDENTITY:
+        xL = -shift if scale else -np.inf
+    else:
+        gmin = float(g(np.float64(-np.inf)))
+        if is_exp:
+            xL = math.log(offset) if offset > 0 else -np.inf
+        elif kind == NGP_INV_LOGISTIC100:
+            xL = (np.inf if offset >= 100 else
+                  math.log(offset / (100.0 - offset)) if offset > 0 else -np.inf)
+        else:
+            edge = (1e-10 - 1.0) / lam
+            xL, xR = (edge, np.inf) if lam > 0 else (-np.inf, edge)
+            if offset > 0:
+                xL = max(xL, (offset ** lam - 1.0) / lam)
+    m = mu.shape[1]
+    out, mean, err = np.full(m, np.nan), np.full(m, np.nan), np.full(m, np.nan)
+    info = np.zeros(m, dtype=np.int32)
+    for j in range(m):
+        mj, ij = mu[:, j], 1.0 / np.sqrt(2.0 * var[:, j])
+        sd = np.sqrt(var[:, j])
+        lo, hi = float(np.min(mj - 10.0 * sd)), float(np.max(mj + (10.0 + 2.0 * sd) * sd))
+
+        def tail(x, upper):
+            t = (x[None, :] - mj[:, None]) * ij[:, None]
+            return w @ (0.5 * _erfc(t if upper else -t).astype(np.float64))
+
+        if ((xR < hi and tail(np.array([xR]), True)[0] > 1e-12)
+                or (scale and not gmin + shift > 0 and xL > lo)):
+            info[j] = NGP_INFO_NOT_FINITE
+            continue
+        alo = min(max(lo, xL), hi)
+        ahi = max(min(hi, xR), alo)
+        v = y[j] + offset
+        if kind == NGP_INV_IDENTITY:
+            xy = y[j]
+        elif y[j] <= gmin or not v > 0:
+            xy = -np.inf
+        elif is_exp:
+            xy = math.log(v)
+        elif kind == NGP_INV_LOGISTIC100:
+            xy = np.inf if v >= 100 else math.log(v / (100.0 - v))
+        else:
+            xy = (v ** lam - 1.0) / lam
+        x0 = min(max(xy, alo), ahi)
+        psi0, yt = float(s(g(np.float64(x0)))), float(s(np.float64(y[j])))
+        clip = 0.0 if alo < xy < ahi else abs(yt - psi0)
+        vals = []
+        for width in (0.5 * sd.min(), 0.25 * sd.min()):
+            c2 = m1 = 0.0
+            for a, b, upper in ((alo, x0, False), (x0, ahi, True)):
+                if not b > a:
+                    continue
+                n = max(1, int(math.ceil((b - a) / width)))
+                e = np.linspace(a, b, n + 1)
+                h = 0.5 * np.diff(e)
+                x = ((e[:-1] + h)[:, None] + h[:, None] * gx[None, :]).ravel()
+                T = tail(x, upper)
+                d = dpsi(x) * (h[:, None] * gw[None, :]).ravel()
+                c2 += float(np.sum(T * T * d))
+                m1 += float(np.sum(T * d)) * (1.0 if upper else -1.0)
+            vals.append((c2 + clip, psi0 + m1))
+        out[j], mean[j] = vals[1]
+        err[j] = abs(vals[1][0] - vals[0][0])
+        if not (np.isfinite(out[j]) and np.isfinite(mean[j])):
+            out[j] = mean[j] = err[j] = np.nan
+            info[j] = NGP_INFO_NOT_FINITE
+    return out, mean, err, info
+
+
 class MixtureMarginals:
     """The per-date marginals of a Gaussian mixture — ``means`` [C, m], ``variances`` [C, m],
     ``weights`` [C] — and their exact summaries, each returned date-major ([m], [m, Q]: the
@@ -960,10 +1076,17 @@ class MixtureMarginals:
                       elementwise to the exact quantiles — for a monotone non-decreasing map (the
                       inverses of ``nowcast.get_transformations``, clamp at 0 included) that IS the
                       quantile on the original scale
-        crps(y)       E|X - y| - E|X - X'| / 2 in closed form, on the MODEL's (transformed) scale,
-                      as the reference's vignette scores it (crps(data_transform(y), ...))
+        crps(y)       E|X - y| - E|X - X'| / 2 in closed form, on the MODEL's (transformed) scale.
+                      The reference's vignette scores crps(log(y), log.(X)) on draws mapped back
+                      to counts: that is this number only when the fit used a log transformation.
+                      For any other fit, and for the natural scale, pass ``inv_transformation``
+                      (an inverse of ``nowcast.get_transformations``) and ``scale="natural"`` or
+                      ``"log"`` (log(. + shift)): the exact CRPS of the transformed forecast against
+                      y on the ORIGINAL scale, by quadrature in the mixture's own CDF
+                      (``ngp_mixture_crps_mapped``); ``return_error=True`` adds its error estimate
+        mean()        of the model's scale; with ``inv_transformation`` / ``scale`` of the mapped one
+        wis(y, levels) weighted interval score from the exact quantiles, on either scale
         pit(y)        F_j(y_j)
-        mean()
 
     With an engine that has ``mixture_cdf`` / ``mixture_quantiles`` / ``mixture_crps`` (the HIP
     library, include/ngp.h) those compute; without one the same formulas run on the host with
@@ -1025,8 +1148,72 @@ class MixtureMarginals:
         return F, f
 
     # ---- summaries --------------------------------------------------------------------------
-    def mean(self):
-        return self.weights @ self.means
+    def mean(self, inv_transformation=None, scale="model", shift=0.0, tol=None):
+        if inv_transformation is None and scale == "model":
+            return self.weights @ self.means
+        return self._mapped(None, inv_transformation, scale, shift, tol)[1]
+
+    # ---- scores on the natural / log scale ----------------------------------------------------
+    def _mapped(self, y, inv_transformation, scale, shift, tol):
+        """(crps, mean, err) of s(g(X)) per date; y None: any admissible y (the mean does not
+        depend on it)"""
+        from ._abi import NGP_INFO_NOT_CONVERGED, NGP_INFO_NOT_FINITE, NGP_INV_IDENTITY
+        if scale not in ("natural", "log"):
+            raise ValueError('scale: "model", "natural" or "log"')
+        inv = (getattr(inv_transformation, "ngp_inv", None) if inv_transformation is not None
+               else (NGP_INV_IDENTITY, 0.0, 0.0, 0.0))
+        if inv is None:
+            raise ValueError("inv_transformation: an inverse of nowcast.get_transformations")
+        sc = 1 if scale == "log" else 0
+        m = self.means.shape[1]
+        if y is None:
+            centre = self.weights @ self.means
+            y = np.asarray(inv_transformation(centre) if inv_transformation is not None else centre,
+                           dtype=np.float64)
+            if sc:
+                y = np.maximum(y, 1.0 - shift)
+        y = np.asarray(y, dtype=np.float64).reshape(-1)
+        if y.size != m:
+            raise ValueError("MixtureMarginals.crps: y [m]")
+        dev = self._device("mixture_crps_mapped")
+        if dev is not None:
+            out, mean, err, info = dev(self.weights, self.means, self.variances, inv, sc,
+                                       float(shift), y, 0.0 if tol is None else float(tol))
+        else:
+            self._check(self._host_info())
+            out, mean, err, info = _host_mapped(*self._active(), inv, sc, float(shift), y)
+        self._check(np.where(info > 0, info, 0))
+        if np.any(info == NGP_INFO_NOT_FINITE):
+            raise ArithmeticError("the score is infinite or the inverse is not monotone where the "
+                                  f"forecast has mass (dates {np.flatnonzero(info == NGP_INFO_NOT_FINITE)})")
+        if np.any(info == NGP_INFO_NOT_CONVERGED):
+            import warnings
+            warnings.warn("mixture_crps_mapped: panel cap reached, see the error estimate")
+        return out, mean, err
+
+    def wis(self, y, levels, inv_transformation=None, scale="model", shift=0.0):
+        """Weighted interval score (Bracher et al. 2021) from the exact quantiles: ``levels`` the
+        central coverage levels 1 - alpha in (0, 1);
+        (|y - med| / 2 + sum_k alpha_k / 2 IS_alpha_k) / (K + 1 / 2) per date, on the model's
+        scale, or with ``inv_transformation`` on the natural / log(. + shift) scale (y then on the
+        original scale)."""
+        lv = np.atleast_1d(np.asarray(levels, dtype=np.float64))
+        if lv.ndim != 1 or not np.all((lv > 0) & (lv < 1)):
+            raise ValueError("MixtureMarginals.wis: levels in (0, 1)")
+        if scale not in ("model", "natural", "log"):
+            raise ValueError('scale: "model", "natural" or "log"')
+        alpha = 1.0 - lv
+        probs = np.concatenate([[0.5], alpha / 2, 1.0 - alpha / 2])
+        kw = {} if inv_transformation is None else {"inv_transformation": inv_transformation}
+        q = self.quantile(probs, **kw)                                    # [m, 1 + 2 K]
+        y = np.asarray(y, dtype=np.float64).reshape(-1)
+        if scale == "log":
+            q, y = np.log(q + shift), np.log(y + shift)
+        K = lv.size
+        lo, hi = q[:, 1:1 + K], q[:, 1 + K:]
+        yy = y[:, None]
+        score = (hi - lo) + (2.0 / alpha) * (np.maximum(lo - yy, 0.0) + np.maximum(yy - hi, 0.0))
+        return (0.5 * np.abs(y - q[:, 0]) + (0.5 * alpha * score).sum(axis=1)) / (K + 0.5)
 
     def cdf(self, x):
         x = np.asarray(x, dtype=np.float64)
@@ -1078,7 +1265,11 @@ class MixtureMarginals:
             hi = np.where(live & ~below, mid, hi)
         return hi
 
-    def crps(self, y):
+    def crps(self, y, inv_transformation=None, scale="model", shift=0.0, tol=None,
+             return_error=False):
+        if inv_transformation is not None or scale != "model":
+            out, _, err = self._mapped(y, inv_transformation, scale, shift, tol)
+            return (out, err) if return_error else out
         y = np.asarray(y, dtype=np.float64).reshape(-1)
         m = self.means.shape[1]
         if y.size != m:
@@ -1273,7 +1464,9 @@ class AtomMixtureMarginals(MixtureMarginals):
     """A mixture whose share ``atom`` sits in a point mass at 0 (particles that have no component
     of a group contribute exactly 0 to that group); ``means`` / ``variances`` / ``weights`` are the
     continuous components, the weights summing to 1 among themselves.  The point mass is handled
-    here, on the host; the continuous rest is a ``MixtureMarginals`` like any other."""
+    here, on the host; the continuous rest is a ``MixtureMarginals`` like any other.  The scores
+    on the natural / log scale (``crps`` / ``mean`` / ``wis`` with ``inv_transformation`` or a
+    ``scale`` other than "model") are NOT implemented for it: they raise ``NotImplementedError``."""
 
     def __init__(self, means, variances, weights, atom: float, engine=None):
         super().__init__(means, variances, weights, engine=engine)
@@ -1284,8 +1477,18 @@ class AtomMixtureMarginals(MixtureMarginals):
     def _rest(self):
         return MixtureMarginals(self.means, self.variances, self.weights, engine=self.engine)
 
-    def mean(self):
+    @staticmethod
+    def _model_scale_only(inv_transformation, scale):
+        if inv_transformation is not None or scale != "model":
+            raise NotImplementedError("AtomMixtureMarginals: scores on the model's scale only")
+
+    def mean(self, inv_transformation=None, scale="model", shift=0.0, tol=None):
+        self._model_scale_only(inv_transformation, scale)
         return (1.0 - self.atom) * super().mean()
+
+    def wis(self, y, levels, inv_transformation=None, scale="model", shift=0.0):
+        self._model_scale_only(inv_transformation, scale)
+        return super().wis(y, levels)
 
     def cdf(self, x):
         x = np.asarray(x, dtype=np.float64)
@@ -1310,7 +1513,9 @@ class AtomMixtureMarginals(MixtureMarginals):
         from .nowcast import _apply
         return _apply(inv_transformation, q)
 
-    def crps(self, y):
+    def crps(self, y, inv_transformation=None, scale="model", shift=0.0, tol=None,
+             return_error=False):
+        self._model_scale_only(inv_transformation, scale)
         y = np.asarray(y, dtype=np.float64).reshape(-1)
         a, rest = self.atom, self._rest()
         c_rest = rest.crps(y)                                     # E|X - y| - E|X - X'| / 2 of the rest

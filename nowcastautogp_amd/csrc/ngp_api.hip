@@ -3086,6 +3086,118 @@ extern "C" ngp_status ngp_mixture_crps(ngp_ctx *c, int32_t C, int32_t m, const d
     return mixture_summary(c, MIX_CRPS, C, m, w, mu, var, 1, y, crps, info);
 }
 
+// ---------------------------------------------------------------------------------------
+// CRPS and mean after a monotone map (ngp_mixture_crps_mapped; ngp_mixture_mapped_kernels.h)
+//
+// The host validates, stages as the summaries above do, reads back one small record per date
+// (the scan kernel: range, boundaries of the map, the point where it crosses y), plans each date's
+// panels from its record alone and runs the panel and reduce kernels; dates whose error estimate
+// is above the tolerance go round again at half the width, alone, until the per-date cap.
+extern "C" ngp_status ngp_mixture_crps_mapped(ngp_ctx *c, int32_t C, int32_t m, const double *w,
+                                              const double *mu, const double *var, const void *inv_,
+                                              int32_t scale, double shift, const double *y,
+                                              double tol, double *crps, double *mean, double *err,
+                                              int32_t *info) {
+    const ngp_inv_transform *inv = (const ngp_inv_transform *)inv_;
+    if (!c || !inv || !y || !crps || !info || m < 1) return NGP_ERR_ARG;
+    if (scale != NGP_SCORE_NATURAL && scale != NGP_SCORE_LOG) return NGP_ERR_ARG;
+    if (inv->kind < NGP_INV_IDENTITY || inv->kind > NGP_INV_BOXCOX || !std::isfinite(inv->lam) ||
+        !std::isfinite(inv->offset) || !std::isfinite(inv->cap) || !std::isfinite(shift) ||
+        !std::isfinite(tol) || shift < 0.0)
+        return NGP_ERR_ARG;
+    if (m > MIX_MAX_DATES) return NGP_ERR_TOO_LARGE;       // bounds the loop below
+    for (int32_t j = 0; j < m; ++j)
+        if (!std::isfinite(y[j]) || (scale == NGP_SCORE_LOG && !(y[j] + shift > 0.0)))
+            return NGP_ERR_ARG;
+    if (!(tol > 0.0)) tol = MIXMAP_DEFAULT_TOL;
+    MixStaged h;
+    ngp_status st = mixture_stage(C, m, w, mu, var, info, &h);
+    if (st) return st;
+    const size_t Cn = (size_t)h.C;
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    MixBlocks blk(c);
+    double *dw = nullptr, *dmu = nullptr, *dvar = nullptr, *dinv = nullptr, *dy = nullptr,
+           *drec = nullptr;
+    if ((st = blk.take(&dw, Cn)) || (st = blk.take(&dmu, Cn * m)) || (st = blk.take(&dvar, Cn * m)) ||
+        (st = blk.take(&dinv, Cn * m)) || (st = blk.take(&dy, (size_t)m)) ||
+        (st = blk.take(&drec, (size_t)m * MIXMAP_REC)))
+        return st;
+    std::vector<double> rec((size_t)m * MIXMAP_REC, 0.0);
+    hipError_t e = hipMemcpyAsync(dw, h.w.data(), 8 * Cn, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(dmu, h.mu.data(), 8 * Cn * m, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(dvar, h.var.data(), 8 * Cn * m, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(dy, y, 8 * (size_t)m, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) {
+        launch_mixture_prep(dvar, dinv, (int64_t)(Cn * m), s);
+        launch_mixmap_scan(h.C, m, *inv, scale, shift, dw, dmu, dinv, dy, drec, s);
+        e = hipMemcpyAsync(rec.data(), drec, 8 * rec.size(), hipMemcpyDeviceToHost, s);
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e == hipSuccess) e = hipGetLastError();
+    if (e != hipSuccess) return (ngp_status)(e > 0 ? e : 999);
+
+    const double nan = std::nan("");
+    std::vector<MixMapPlan> work;
+    work.reserve(m);
+    for (int32_t j = 0; j < m; ++j) {
+        crps[j] = nan;
+        if (mean) mean[j] = nan;
+        if (err) err[j] = nan;
+        if (h.bad[j]) continue;
+        if (rec[(size_t)j * MIXMAP_REC + MIXMAP_REC_FLAG] != 0.0) {
+            info[j] = NGP_INFO_NOT_FINITE;
+            continue;
+        }
+        work.push_back(mixmap_plan(j, &rec[(size_t)j * MIXMAP_REC]));
+    }
+    std::vector<double> res;
+    while (!work.empty()) {
+        const size_t nw = work.size();
+        int32_t maxp = 1;
+        for (const MixMapPlan &p : work) maxp = std::max(maxp, p.npanels);
+        MixBlocks round(c);                                // this width's buffers, given back below
+        double *dplan = nullptr, *dslab = nullptr, *dres = nullptr;
+        static_assert(sizeof(MixMapPlan) % 8 == 0, "plans are allocated in doubles");
+        if ((st = round.take(&dplan, nw * (sizeof(MixMapPlan) / 8))) ||
+            (st = round.take(&dslab, nw * (size_t)maxp * 3)) || (st = round.take(&dres, nw * 3)))
+            return st;
+        res.assign(nw * 3, 0.0);
+        e = hipMemcpyAsync(dplan, work.data(), nw * sizeof(MixMapPlan), hipMemcpyHostToDevice, s);
+        if (e == hipSuccess) {
+            launch_mixmap_panels(h.C, (int)nw, maxp, *inv, scale, shift, (const MixMapPlan *)dplan,
+                                 dw, dmu, dinv, dslab, dres, s);
+            e = hipMemcpyAsync(res.data(), dres, 8 * res.size(), hipMemcpyDeviceToHost, s);
+        }
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (e == hipSuccess) e = hipGetLastError();
+        if (e != hipSuccess) return (ngp_status)(e > 0 ? e : 999);
+        std::vector<MixMapPlan> next;
+        for (size_t k = 0; k < nw; ++k) {
+            const int32_t j = work[k].date;
+            const double *r = &rec[(size_t)j * MIXMAP_REC];
+            const double cj = res[k * 3] + r[MIXMAP_REC_CLIP], ej = res[k * 3 + 1];
+            const double mj = r[MIXMAP_REC_PSI0] + res[k * 3 + 2];
+            if (!std::isfinite(cj) || !std::isfinite(mj) || !std::isfinite(ej)) {
+                info[j] = NGP_INFO_NOT_FINITE;             // the outputs stay NaN
+                continue;
+            }
+            const bool done = ej <= tol * std::fabs(cj);
+            if (!done && mixmap_refine(&work[k])) {
+                next.push_back(work[k]);
+                continue;
+            }
+            crps[j] = cj;
+            if (mean) mean[j] = mj;
+            if (err) err[j] = ej;
+            if (!done) info[j] = NGP_INFO_NOT_CONVERGED;
+        }
+        work.swap(next);
+    }
+    return NGP_OK;
+}
+
 // pair terms of the CRPS cross sum per second with the operands in registers (no loads, no LDS):
 // the ceiling mix_crps_pairs_kernel is measured against (scripts/summary_probe.py)
 extern "C" ngp_status ngp_microbench_mixture_pairs(ngp_ctx *c, int32_t iters, double *pairs_per_s) {

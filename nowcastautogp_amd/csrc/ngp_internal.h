@@ -221,6 +221,7 @@ enum { COL_FULL = 0, COL_FAT = 1, COL_THIN = 2, COL_AUX = 3 };   // launch_chol_
 // accounting of the launches: host-only headers over the structs above
 #include "ngp_plan.h"
 #include "ngp_cost.h"
+#include "ngp_mixmap_plan.h"
 namespace ngp {
 
 void launch_chol_small(const JobGeom &g, const ChunkPtrs &p, int Bc, const SmallPlan &pl, hipStream_t s);
@@ -305,6 +306,17 @@ void launch_mixture_quantiles(int C, int m, const double *w, const double *mu, c
 void launch_mixture_crps(int C, int m, const double *w, const double *mu, const double *var,
                          const double *y, double *slab, double *crps, hipStream_t s);
 void launch_mixture_pair_rate(int iters, int blocks, double *out, hipStream_t s);
+// ---- CRPS and mean after a monotone map (ngp_mixture_mapped_kernels.h) ----------------------
+// The scan kernel leaves one record per date; the host plans the panels of a date from it
+// (mixmap_plan) and relaunches only the dates that need a finer width.
+// (constants, the per-date record, MixMapPlan and the planner: ngp_mixmap_plan.h — plain C++, so
+// that the host tests can drive the planner on its own)
+void launch_mixmap_scan(int C, int m, const ngp_inv_transform &inv, int scale, double shift,
+                        const double *w, const double *mu, const double *invsd, const double *y,
+                        double *rec, hipStream_t s);
+void launch_mixmap_panels(int C, int nwork, int maxp, const ngp_inv_transform &inv, int scale,
+                          double shift, const MixMapPlan *plans, const double *w, const double *mu,
+                          const double *invsd, double *slab, double *res, hipStream_t s);
 // ---- functionals of whole sample paths (ngp_path_kernels.h) ---------------------------------
 constexpr int PATH_LCHUNK = 2048;      // doubles of L staged in LDS at a time (whole rows)
 constexpr int PATH_SLICE = 4096;       // values per workgroup in the reduce and select passes
