@@ -156,6 +156,8 @@ ngp_status  ngp_kernel_check(const ngp_kernel *k);
  * reach batches of P x (concurrent tasks) items.  A result is the one a single call over the combined
  * items would give: equal to the caller's own call up to the last bits (batch size decides
  * launch shapes and therefore summation order, as it always did — see DESIGN.md section 4.14).
+ * ngp_grad_job_hmc (a whole trajectory on one job) takes the context's lock from its first launch
+ * to its results and is never combined: callers that arrive meanwhile wait as for any other call.
  * ngp_set_combining(ctx, 0) switches it off (every call then waits for ctx's lock and runs alone);
  * 1 (default) is as described; 2 combines what is pending but never waits for company (without the
  * wait a convoy of T tasks alternates between groups of 1 and T - 1: measured 1.45 x slower at
@@ -269,6 +271,54 @@ ngp_status ngp_grad_job_run(ngp_grad_job *job, double *logml, double *grad, int3
  * items per chunk of its last run, 1 if the two leaves run side by side }.  Leaf items keep the
  * caller's order.                                                                                */
 ngp_status ngp_grad_job_info(const ngp_grad_job *job, int32_t *out5);
+/* One whole HMC leapfrog trajectory of every item of a staged job in one call: n_leapfrog + 1
+ * gradient evaluations with the leapfrog update between them on the device, one synchronisation,
+ * one copy back (mcmc_parameters!, src/forecasting.jl:65,148: one call per move instead of one per
+ * leapfrog).  Latents are laid out as the gradient is: per item n_params_b entries in the caller's
+ * (RPN) order followed by the noise latent, items back to back.  The arithmetic is that of the
+ * Python mirror's autogp._hmc_move / potential, operation for operation:
+ *   evaluation at z: a non-finite z is replaced for the evaluation (NaN -> 0, +-inf -> +-50);
+ *     theta(z) by kind — real: z; unit: sigmoid(z); gamma: 2 sigmoid(mu + sigma z); period,
+ *     wildcard: exp(mu + sigma z) — with the argument clamped to +-700 (sigmoid) / +-300 (exp);
+ *     theta clipped to +-1e6, positive kinds >= 1e-12, gamma to [1e-9, 2 - 1e-9], unit to
+ *     [1e-9, 1 - 1e-9]; ok = info == 0, logml finite, every gradient entry finite;
+ *     U = ok ? -logml + z'z / 2 : +inf;  dU = ok ? -grad * dtheta/dz + z : 0, and 0 where frozen.
+ *   pm = mom - eps/2 dU(z0); n_leapfrog times: z += eps pm, evaluate, pm -= eps dU (the last: eps/2).
+ *   K0 = mom'mom / 2, K1 = pm'pm / 2; U0 / U1, logml1, info1: first / last evaluation; theta1: the
+ *   parameters of the last evaluation; z1 = z, mom1 = pm; z_trace row s: the z of evaluation s.
+ * An item that fails at an intermediate evaluation keeps moving (dU = 0 there).  The library draws
+ * nothing: momenta and the accept decision stay with the caller.  A job carried by two leaves runs
+ * the trajectory of the general leaf, then that of the Toeplitz leaf (items are independent).
+ * Every evaluation is the launch sequence of ngp_grad_job_run: its logml / gradient are the bits a
+ * run gives for the same parameters.  After the call the job holds the parameters of the last
+ * evaluation (theta1): a following ngp_grad_job_run evaluates exactly those.  The call holds the
+ * context's lock for the whole trajectory of a leaf and is not combined with concurrent callers; a
+ * job on two leaves takes the lock once per leaf, so another caller's work may run between the two
+ * trajectories (never inside one).  If the second leaf fails after the first succeeded, the call
+ * returns the error, the outputs are not valid, and the items of the first leaf already hold their
+ * last parameters on the device while the job's one-shot form still holds the old ones: send
+ * parameters again (ngp_grad_job_set_params) before the job is run.
+ * NGP_ERR_ARG: a null pointer, n_leapfrog < 1, a non-finite eps, a kind above 4, prior_sigma <= 0
+ * (or a non-finite prior entry) for a kind in use.  NGP_ERR_TOO_LARGE: n_leapfrog above 65,536
+ * (the library's limit on one call; the trace alone would be 65,537 rows), or no room for the
+ * working storage or the arena.  The step kernel is booked under profile class 4 together with
+ * the fills and the tables kernel of the evaluations: n_leapfrog + 2 more launch records there. */
+typedef struct {
+    int32_t n_leapfrog;            /* >= 1 */
+    double  eps;
+    double  prior_mu[5], prior_sigma[5];   /* indexed by latent kind; kinds 0 and 1 ignore them */
+} ngp_hmc_config;
+/* cfg: const void * to ONE ngp_hmc_config; kind / frozen: const void * to one byte (uint8_t) per
+ * latent — declared so for the reason given at ngp_mixture_path_targets (the header's parameter
+ * types stay scalars, arrays of scalars, handles and the three mirrored structs).               */
+ngp_status ngp_grad_job_hmc(ngp_grad_job *job, const void *cfg,
+                            const void *kind,    /* per latent: 0 real, 1 unit, 2 gamma, 3 period, 4 wildcard */
+                            const void *frozen,  /* per latent, may be NULL: dU forced to 0 (fixed noise) */
+                            const double *z0, const double *mom,   /* per latent */
+                            double *z1, double *mom1, double *theta1,  /* per latent, out */
+                            double *U0, double *K0, double *U1, double *K1, double *logml1, /* [B] */
+                            int32_t *info1,          /* [B] info of the LAST evaluation */
+                            double *z_trace);        /* may be NULL: [n_leapfrog + 1][latents] */
 void       ngp_grad_job_destroy(ngp_grad_job *job);
 
 /* ---- particle weights -----------------------------------------------------
@@ -700,7 +750,8 @@ ngp_status ngp_factor_components_nowcast(ngp_factor *f, int32_t d, const double 
  * HIP-event timing of the kernels a job launches, on the stream they are
  * launched on.  Classes: 0 = chol_col_glds_kernel (fat steps: trailing-update
  * GEMM + fused solve, the dominant kernel), 1 = chol_diag, 2 = gram,
- * 3 = epilogue, 4 = cov fill, 5 = K^-1 = W W' of a gradient job (grad_kinv*), 6 = chol_col_kernel (thin /
+ * 3 = epilogue, 4 = cov fill (and the other elementwise kernels around an evaluation: the lattice
+ * tables, the leapfrog step of ngp_grad_job_hmc), 5 = K^-1 = W W' of a gradient job (grad_kinv*), 6 = chol_col_kernel (thin /
  * full steps, aux solves of a resident factor), 7 = aux_update_kernel,
  * 8 = diag_ahead_kernel (side stream, overlaps classes 1 and 6), 9 = the
  * mixed-precision fat steps (chol_col_glds_kernel<MIXED>), 10 = Gram refinement

@@ -197,6 +197,50 @@ function run!(job::GradJob, progs::Union{Nothing,Vector{Program}} = nothing)
     return lm, [grad[offs[i]+1:offs[i+1]] for i in 1:B], info
 end
 
+"`ngp_hmc_config` of include/ngp.h: the prior entries are indexed by latent kind (0 real, 1 unit,
+2 gamma, 3 period, 4 wildcard)."
+struct NgpHmcConfig
+    n_leapfrog::Int32
+    eps::Float64
+    prior_mu::NTuple{5,Float64}
+    prior_sigma::NTuple{5,Float64}
+end
+
+const KIND_CODE = Dict(:real => 0x00, :unit => 0x01, :gamma => 0x02, :period => 0x03, :wildcard => 0x04)
+
+"""
+    hmc!(job, kinds, z0, mom, n_leapfrog, eps, prior; frozen = nothing)
+
+`ngp_grad_job_hmc`: one whole leapfrog trajectory of every item of the staged job in ONE call
+(n_leapfrog + 1 gradient evaluations, the update between them on the device).  `kinds` (UInt8,
+`KIND_CODE`), `z0`, `mom`, `frozen` hold one entry per latent: an item's parameters in program
+order, then its noise, items back to back.  The library draws nothing: momenta and the accept
+decision stay here.  Returns a named tuple (z1, mom1, theta1, U0, K0, U1, K1, logml1, info1).
+"""
+function hmc!(job::GradJob, kinds::Vector{UInt8}, z0::Vector{Float64}, mom::Vector{Float64},
+              n_leapfrog::Int, eps::Float64, prior; frozen::Union{Nothing,Vector{UInt8}} = nothing)
+    B, NL = length(job.sizes), sum(job.sizes)
+    @assert length(kinds) == NL && length(z0) == NL && length(mom) == NL
+    mu(k) = Float64(prior[k][:mu]); sg(k) = Float64(prior[k][:sigma])
+    cfg = Ref(NgpHmcConfig(Int32(n_leapfrog), eps,
+                           (0.0, 0.0, mu(:gamma), mu(:period), mu(:wildcard)),
+                           (1.0, 1.0, sg(:gamma), sg(:period), sg(:wildcard))))
+    z1, mom1, theta1 = (Vector{Float64}(undef, NL) for _ in 1:3)
+    U0, K0, U1, K1, lm1 = (Vector{Float64}(undef, B) for _ in 1:5)
+    info1 = zeros(Int32, B)
+    fr = frozen === nothing ? UInt8[] : frozen
+    GC.@preserve cfg kinds fr begin
+        check(ccall((:ngp_grad_job_hmc, LIBNGP), Int32,
+                    (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64},
+                     Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+                     Ptr{Float64}, Ptr{Float64}, Ptr{Int32}, Ptr{Float64}),
+                    job.h, Base.unsafe_convert(Ptr{Cvoid}, cfg), pointer(kinds),
+                    frozen === nothing ? C_NULL : pointer(fr), z0, mom, z1, mom1, theta1, U0, K0, U1, K1,
+                    lm1, info1, C_NULL), "ngp_grad_job_hmc")
+    end
+    return (; z1, mom1, theta1, U0, K0, U1, K1, logml1 = lm1, info1)
+end
+
 function Base.close(job::GradJob)
     if job.h != C_NULL
         ccall((:ngp_grad_job_destroy, LIBNGP), Cvoid, (Ptr{Cvoid},), job.h)
@@ -951,7 +995,55 @@ function _hmc_move!(ms::Vector{GPModel}, t, ys, n_leapfrog::Int, eps::Float64)
 end
 _hmc_move!(m::GPModel, t, y, n_leapfrog::Int, eps::Float64) = _hmc_move!([m], t, [y], n_leapfrog, eps)
 
-const DEFAULT_HMC = (n_leapfrog = 10, eps = 0.02)
+"The transition with the whole trajectory in ONE library call (`hmc!`, ngp_grad_job_hmc): one `ccall`
+per move instead of one per leapfrog.  Momenta and accept uniforms are drawn here, from the same
+generators in the same order as `_hmc_move!`.  The arithmetic is the LIBRARY's, i.e. the Python
+mirror's `potential` (include/ngp.h): z = +-Inf is evaluated as +-50, theta is kept inside the gamma
+and unit margins (1e-9) as well as above 1e-12, and the installed parameters are those clipped
+values.  `_hmc_move!` above clamps z to +-50 and only the noise from below, so the two paths of the
+shim agree where no clamp bites (every ordinary move) and differ at the margins."
+function _hmc_move_device!(ms::Vector{GPModel}, t, ys, n_leapfrog::Int, eps::Float64)
+    prior = ms[1].config.prior
+    fixed_noise = ms[1].config.noise !== nothing
+    items = [(j, k) for (j, m) in enumerate(ms) for k in 1:length(m.particles)]
+    parts = [ms[j].particles[k] for (j, k) in items]
+    Y = _item_y(ys, [j for (j, _) in items])
+    kinds = [vcat(param_kinds(p), [:wildcard]) for p in parts]
+    z0 = [[untransform(th, k, prior) for (th, k) in zip(vcat(p.params, p.noise), kd)]
+          for (p, kd) in zip(parts, kinds)]
+    mom = [randn(ms[j].rng, length(z0[i])) for (i, (j, _)) in enumerate(items)]
+    fixed_noise && foreach(p -> (p[end] = 0.0), mom)
+    frozen = nothing
+    if fixed_noise
+        frozen = reduce(vcat, [vcat(zeros(UInt8, length(z) - 1), 0x01) for z in z0])
+    end
+    codes = UInt8[KIND_CODE[k] for kd in kinds for k in kd]
+    dev = grad_stage(ms[1].ctx, parts, t, Y)
+    local out
+    try
+        out = hmc!(dev, codes, reduce(vcat, z0), reduce(vcat, mom), n_leapfrog, eps, prior; frozen)
+    finally
+        close(dev)
+    end
+    offs = cumsum([0; dev.sizes])
+    acc = 0
+    for (i, (j, k)) in enumerate(items)
+        H0, H1 = out.U0[i] + out.K0[i], out.U1[i] + out.K1[i]
+        u = rand(ms[j].rng)
+        if isfinite(H1) && log(u) < H0 - H1
+            th = out.theta1[offs[i]+1:offs[i+1]]
+            ms[j].particles[k] = Program(parts[i].ops, th[1:end-1], th[end])
+            ms[j].logml[k] = out.logml1[i]; acc += 1
+        end
+    end
+    return acc
+end
+
+"`hmc_config` may carry `device = true`: every move is then one call of ngp_grad_job_hmc."
+_hmc_step!(ms, t, ys, cfg) = get(cfg, :device, false) ?
+    _hmc_move_device!(ms, t, ys, cfg.n_leapfrog, cfg.eps) : _hmc_move!(ms, t, ys, cfg.n_leapfrog, cfg.eps)
+
+const DEFAULT_HMC = (n_leapfrog = 10, eps = 0.02, device = false)
 
 "AutoGP.mcmc_parameters!(model, n_hmc) — src/forecasting.jl:65, 148"
 function mcmc_parameters!(m::GPModel, n_hmc::Int; hmc_config = DEFAULT_HMC)
@@ -961,7 +1053,7 @@ end
 function mcmc_parameters_lockstep!(ms::Vector{GPModel}, n_hmc::Int; hmc_config = DEFAULT_HMC)
     t, ys = _group_obs(ms)
     for _ in 1:n_hmc
-        _hmc_move!(ms, t, ys, hmc_config.n_leapfrog, hmc_config.eps)
+        _hmc_step!(ms, t, ys, hmc_config)
     end
     return ms
 end
@@ -977,7 +1069,7 @@ function mcmc_structure_lockstep!(ms::Vector{GPModel}, n_mcmc::Int, n_hmc::Int;
     for _ in 1:n_mcmc
         _structure_move!(ms, t, ys)
         for _ in 1:n_hmc
-            _hmc_move!(ms, t, ys, hmc_config.n_leapfrog, hmc_config.eps)
+            _hmc_step!(ms, t, ys, hmc_config)
         end
     end
     return ms

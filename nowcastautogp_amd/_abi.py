@@ -66,6 +66,12 @@ NGP_TARGET_SUM, NGP_TARGET_MAX, NGP_TARGET_DIFF, NGP_TARGET_ARGMAX, NGP_TARGET_E
 PATH_MAX_TARGETS = PATH_MAX_LEVELS = 64
 
 
+class NgpHmcConfig(C.Structure):
+    """``ngp_hmc_config``: the prior entries are indexed by latent kind (``gp.KIND_CODES``)."""
+    _fields_ = [("n_leapfrog", C.c_int32), ("eps", C.c_double), ("prior_mu", C.c_double * 5),
+                ("prior_sigma", C.c_double * 5)]
+
+
 class NgpProfile(C.Structure):
     _fields_ = [
         ("ms", C.c_double * NGP_NUM_KERNEL_CLASSES),

@@ -13,7 +13,7 @@ from typing import Optional, Sequence
 
 import numpy as np
 
-from ._abi import (KernelArray, NgpInvTransform, NgpKernel, NgpPathTarget, NgpProfile, NgpSpec,
+from ._abi import (KernelArray, NgpHmcConfig, NgpInvTransform, NgpKernel, NgpPathTarget, NgpProfile, NgpSpec,
                    as_f64, c_double_p, c_int32_p, dptr, iptr)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -42,6 +42,7 @@ SYMBOLS = (
     "ngp_kernel_terms", "ngp_factor_components_nowcast",
     "ngp_mixture_path_targets", "ngp_mixture_path_targets_indep",
     "ngp_mixture_crps_mapped",
+    "ngp_grad_job_hmc",
 )
 
 
@@ -95,6 +96,8 @@ def load():
         "ngp_grad_job_set_params": (i32, [vp, f64p, f64p]),
         "ngp_grad_job_run": (i32, [vp, f64p, f64p, i32p]),
         "ngp_grad_job_info": (i32, [vp, i32p]),
+        "ngp_grad_job_hmc": (i32, [vp, vp, vp, vp, f64p, f64p, f64p, f64p, f64p, f64p, f64p, f64p,
+                                   f64p, f64p, i32p, f64p]),
         "ngp_grad_job_destroy": (None, [vp]),
         "ngp_weights_normalize": (i32, [i32, f64p, f64p, f64p, f64p]),
         "ngp_weights_normalize_cols": (i32, [i32, i32, f64p, f64p, f64p, f64p]),
@@ -339,6 +342,42 @@ class GradJob:
         lm, info = np.empty(self.n), np.zeros(self.n, dtype=np.int32)
         _chk(L.ngp_grad_job_run(self._h, dptr(lm), dptr(grad), iptr(info)), "ngp_grad_job_run")
         return lm, grad, info
+
+    def hmc(self, codes, z0, mom, n_leapfrog: int, eps: float, prior, frozen=None,
+            trace: bool = False) -> dict:
+        """``ngp_grad_job_hmc``: one whole leapfrog trajectory of every item on the device.
+        ``codes`` (``gp.KIND_CODES``), ``z0``, ``mom`` and ``frozen`` are per latent, laid out as the
+        gradient is (an item's parameters in program order, then its noise); ``prior`` is the
+        config's ``{"gamma" | "period" | "wildcard": {"mu", "sigma"}}``.  Returns ``z1``, ``mom1``,
+        ``theta1`` per latent, ``U0``, ``K0``, ``U1``, ``K1``, ``logml1``, ``info1`` per item and,
+        with ``trace``, ``z_trace`` [n_leapfrog + 1][latents].  The job then holds ``theta1``."""
+        codes = np.ascontiguousarray(codes, dtype=np.uint8)
+        z0, mom = as_f64(z0), as_f64(mom)
+        if codes.size != self._ngrad or z0.size != self._ngrad or mom.size != self._ngrad:
+            raise ValueError("GradJob.hmc: one entry per latent (parameters and noise of every item)")
+        fr = None
+        if frozen is not None:
+            fr = np.ascontiguousarray(frozen, dtype=np.uint8)
+            if fr.size != self._ngrad:
+                raise ValueError("GradJob.hmc: frozen has one entry per latent")
+        cfg = NgpHmcConfig()
+        cfg.n_leapfrog, cfg.eps = int(n_leapfrog), float(eps)
+        for name, code in (("gamma", 2), ("period", 3), ("wildcard", 4)):
+            cfg.prior_mu[code] = float(prior[name]["mu"])
+            cfg.prior_sigma[code] = float(prior[name]["sigma"])
+        cfg.prior_sigma[0] = cfg.prior_sigma[1] = 1.0
+        out = {k: np.empty(self._ngrad) for k in ("z1", "mom1", "theta1")}
+        out.update({k: np.empty(self.n) for k in ("U0", "K0", "U1", "K1", "logml1")})
+        out["info1"] = np.zeros(self.n, dtype=np.int32)
+        if trace:
+            out["z_trace"] = np.empty((int(n_leapfrog) + 1, self._ngrad))
+        _chk(load().ngp_grad_job_hmc(
+            self._h, C.cast(C.pointer(cfg), C.c_void_p), codes.ctypes.data_as(C.c_void_p),
+            fr.ctypes.data_as(C.c_void_p) if fr is not None else None, dptr(z0), dptr(mom),
+            dptr(out["z1"]), dptr(out["mom1"]), dptr(out["theta1"]), dptr(out["U0"]), dptr(out["K0"]),
+            dptr(out["U1"]), dptr(out["K1"]), dptr(out["logml1"]), iptr(out["info1"]),
+            dptr(out["z_trace"]) if trace else None), "ngp_grad_job_hmc")
+        return out
 
     def info(self) -> dict:
         """``ngp_grad_job_info``: how the batch is carried (leaves, chunk sizes of the last run)."""

@@ -584,12 +584,17 @@ def _structure_move(models: Sequence[GPModel], t, ys):
     return acc
 
 
-def _hmc_move(models: Sequence[GPModel], t, ys, n_leapfrog: int, eps: float, Y=None):
+def _hmc_move(models: Sequence[GPModel], t, ys, n_leapfrog: int, eps: float, Y=None,
+              device: bool = False):
     """One HMC transition per particle on the N(0,1) latents z of (parameters, noise):
     U(z) = -log p(y | theta(z)) + |z|^2 / 2, gradient through the engine's logml gradient.
     All particles of all models move together: the latents live in one flat vector (``sl[i]`` is
     item i's slice), every leapfrog stage is ONE engine call of P x D items (per-item y rows when
-    D > 1) and a handful of numpy operations."""
+    D > 1) and a handful of numpy operations.
+    ``device`` (``hmc_config["device"]``): with an engine whose staged job has it, the whole
+    trajectory is ONE library call (``ngp_grad_job_hmc``: the same arithmetic on the device, the
+    latents never leave it between evaluations); momenta and accept uniforms are drawn here either
+    way, from the same generators in the same order."""
     prior = models[0].config.prior
     fixed_noise = models[0].config.noise is not None
     items = [(j, k) for j, m in enumerate(models) for k in range(len(m.particles))]
@@ -664,28 +669,43 @@ def _hmc_move(models: Sequence[GPModel], t, ys, n_leapfrog: int, eps: float, Y=N
             dU[last] = 0.0
         return U, dU, lm
 
+    on_device = bool(device) and job is not None and hasattr(job, "hmc")
     try:
-        U0, dU, _ = potential(z0)
-        mom = np.concatenate([prng[i].standard_normal(int(sizes[i])) for i in range(B)])
-        if fixed_noise:
-            mom[last] = 0.0
-        H0 = U0 + 0.5 * sums(mom * mom)
-        z = z0.copy()
-        pm = mom - 0.5 * eps * dU
-        lm1 = U1 = None
-        for step in range(n_leapfrog):
-            z = z + eps * pm
-            U1, dU, lm1 = potential(z)
-            pm = pm - (eps if step < n_leapfrog - 1 else 0.5 * eps) * dU
+        if on_device:
+            mom = np.concatenate([prng[i].standard_normal(int(sizes[i])) for i in range(B)])
+            frozen = None
+            if fixed_noise:
+                mom[last] = 0.0
+                frozen = np.zeros(codes.size, dtype=np.uint8)
+                frozen[last] = 1
+            out = job.hmc(codes, z0, mom, n_leapfrog, eps, prior, frozen=frozen)
+            H0 = out["U0"] + out["K0"]
+            with np.errstate(invalid="ignore", over="ignore"):
+                H1 = out["U1"] + out["K1"]
+            th_new, lm1 = out["theta1"], out["logml1"]
+        else:
+            U0, dU, _ = potential(z0)
+            mom = np.concatenate([prng[i].standard_normal(int(sizes[i])) for i in range(B)])
+            if fixed_noise:
+                mom[last] = 0.0
+            H0 = U0 + 0.5 * sums(mom * mom)
+            z = z0.copy()
+            pm = mom - 0.5 * eps * dU
+            lm1 = U1 = None
+            for step in range(n_leapfrog):
+                z = z + eps * pm
+                U1, dU, lm1 = potential(z)
+                pm = pm - (eps if step < n_leapfrog - 1 else 0.5 * eps) * dU
     finally:
         if job is not None:   # the device arena goes back whatever a step raised
             job.close()
-    with np.errstate(invalid="ignore", over="ignore"):
-        H1 = U1 + 0.5 * sums(pm * pm)
-    # what is installed on acceptance is what the last evaluation saw: clipped into the open domain
-    # of every kind, so no particle ever carries a saturated parameter (an infinite latent)
-    zc = z if np.isfinite(z).all() else np.nan_to_num(z, nan=0.0, posinf=50.0, neginf=-50.0)
-    th_new = gp.clip_flat(np.clip(to_theta(zc)[0], -1e6, 1e6), codes)
+    if not on_device:
+        with np.errstate(invalid="ignore", over="ignore"):
+            H1 = U1 + 0.5 * sums(pm * pm)
+        # what is installed on acceptance is what the last evaluation saw: clipped into the open domain
+        # of every kind, so no particle ever carries a saturated parameter (an infinite latent)
+        zc = z if np.isfinite(z).all() else np.nan_to_num(z, nan=0.0, posinf=50.0, neginf=-50.0)
+        th_new = gp.clip_flat(np.clip(to_theta(zc)[0], -1e6, 1e6), codes)
     acc = 0
     for i, (j, k) in enumerate(items):
         u = prng[i].random()      # drawn for every particle: the stream does not depend on H
@@ -698,7 +718,9 @@ def _hmc_move(models: Sequence[GPModel], t, ys, n_leapfrog: int, eps: float, Y=N
     return acc
 
 
-DEFAULT_HMC = {"n_leapfrog": 10, "eps": 0.02}
+# "device": run each move's whole trajectory in one library call (ngp_grad_job_hmc) where the
+# engine's staged job offers it; off by default
+DEFAULT_HMC = {"n_leapfrog": 10, "eps": 0.02, "device": False}
 
 
 def mcmc_parameters(model: GPModel, n_hmc: int, hmc_config: Optional[dict] = None) -> None:
@@ -722,7 +744,7 @@ def mcmc_parameters_lockstep(models: Sequence[GPModel], n_hmc: int,
         _obs = (t, ys, _all_items_y(models, ys))
     t, ys, Y = _obs
     for _ in range(int(n_hmc)):
-        _hmc_move(models, t, ys, cfgd["n_leapfrog"], cfgd["eps"], Y)
+        _hmc_move(models, t, ys, cfgd["n_leapfrog"], cfgd["eps"], Y, cfgd["device"])
     return _obs
 
 
@@ -736,7 +758,7 @@ def mcmc_structure_lockstep(models: Sequence[GPModel], n_mcmc: int, n_hmc: int,
     for _ in range(int(n_mcmc)):
         _structure_move(models, t, ys)
         for _ in range(int(n_hmc)):
-            _hmc_move(models, t, ys, cfgd["n_leapfrog"], cfgd["eps"], Y)
+            _hmc_move(models, t, ys, cfgd["n_leapfrog"], cfgd["eps"], Y, cfgd["device"])
 
 
 # ---------------------------------------------------------------------------------------------

@@ -2114,6 +2114,15 @@ struct GradLeaf {
     bool progs_dirty = false;              // set_params since the last upload
     ngp_spec spec{};
     int last_chunk = 0;                    // items per memory-driven chunk of the last run (ngp_grad_job_info)
+    // trajectories (ngp_grad_job_hmc): the leaf's latents in the caller's order, on the device from
+    // the first trajectory to the job's end
+    //   [off | slot || kind | frozen | z | pm || theta | U0 K0 U1 K1 logml1 | info1 || trace rows]
+    // kind .. pm go up in one copy per call, z .. info1 come back in one
+    unsigned char *hmc = nullptr;
+    size_t t_off = 0, t_slot = 0, t_kind = 0, t_frozen = 0, t_z = 0, t_pm = 0, t_theta = 0, t_sc = 0,
+           t_info = 0, t_trace = 0, t_rows = 0;
+    std::vector<int32_t> loff;             // [B + 1] first latent of every item
+    PinVec<unsigned char> t_up, t_down;
 };
 
 // What a gradient evaluation is staged under: the context's spec and the switches that pick its
@@ -2295,6 +2304,7 @@ struct LeafRun {
     void *d_L = nullptr, *d_dinv = nullptr, *d_tab = nullptr, *d_sig = nullptr, *d_dtab = nullptr,
          *d_kinv = nullptr, *d_alpha = nullptr, *d_quad = nullptr, *d_part = nullptr, *d_items = nullptr;
     std::vector<int32_t> h_items;   // alive until the lane is synchronised
+    bool items_ready = false;       // a later evaluation of a trajectory: d_items holds the sorted items
     double *splitk = nullptr;       // pair runs: the context's split-k buffer for this leaf's value kernels
 
     size_t item_bytes() const {
@@ -2339,7 +2349,8 @@ struct LeafRun {
     }
 
     // everything of the evaluation on the lane's streams; the caller synchronises ln.main
-    ngp_status launch(const Lane &ln, EventTimer &tm, bool no_lane_split) {
+    // copy_out: the results follow the last kernel into h_out (a trajectory reads them on the device)
+    ngp_status launch(const Lane &ln, EventTimer &tm, bool no_lane_split, bool copy_out = true) {
         ngp_ctx *c = j->ctx;
         const JobGeom &g = j->g;
         const int B = j->B;
@@ -2347,7 +2358,7 @@ struct LeafRun {
         const int GP = NGP_MAX_PARAMS + 1;
         hipStream_t s = ln.main;
         const DevSpec sp = dev_spec(j->spec);
-        h_items.assign((size_t)B, 0);
+        if (!items_ready) h_items.assign((size_t)B, 0);
         unsigned char *const io = j->io;
         void *const d_prog = io, *const d_t = io + j->o_t, *const d_y = io + j->o_y,
                     *const d_q = g.lattice ? io + j->o_q : nullptr, *const d_info = io + j->o_info,
@@ -2414,8 +2425,8 @@ struct LeafRun {
             // sized for it
             const bool by_size = contract_by_size(g, tp, bc);
             int32_t counts[GRAD_BUCKETS] = {};
-            if (by_size) {
-                for (int i = 0; i < bc; ++i) ++counts[grad_bucket(j->n_ops[(size_t)(b0 + i)])];
+            if (by_size) for (int i = 0; i < bc; ++i) ++counts[grad_bucket(j->n_ops[(size_t)(b0 + i)])];
+            if (by_size && !items_ready) {
                 int32_t pos[GRAD_BUCKETS], acc = 0;
                 for (int k = 0; k < GRAD_BUCKETS; ++k) { pos[k] = acc; acc += counts[k]; }
                 for (int i = 0; i < bc; ++i)
@@ -2441,7 +2452,7 @@ struct LeafRun {
                 });
             }
         }
-        e = hipMemcpyAsync(j->h_out.data(), d_info, j->h_out.size(), hipMemcpyDeviceToHost, s);
+        if (copy_out) e = hipMemcpyAsync(j->h_out.data(), d_info, j->h_out.size(), hipMemcpyDeviceToHost, s);
         return e == hipSuccess ? NGP_OK : (ngp_status)e;
     }
 
@@ -2543,6 +2554,162 @@ ngp_status grad_pair_run(GradLeaf *a, double *lm_a, double *g_a, int32_t *info_a
     return NGP_OK;
 }
 
+// One trajectory of a leaf (ngp_grad_job_hmc): kind / frozen / z0 / mom and the outputs are the
+// leaf's latents back to back in the caller's order.  The working storage is laid out once, the
+// n_leapfrog + 1 evaluations are LeafRun::launch as ngp_grad_job_run enqueues it, the step kernel
+// between them writes the next parameters into the device programs; one copy back, one
+// synchronisation.  z_trace: null or [n_leapfrog + 1][latents of the leaf].
+struct HmcOut {
+    double *z1, *mom1, *theta1, *U0, *K0, *U1, *K1, *lm1;
+    int32_t *info1;
+    double *trace;
+};
+
+ngp_status grad_leaf_hmc(GradLeaf *j, const ngp_hmc_config *cfg, const uint8_t *kind,
+                         const uint8_t *frozen, const double *z0, const double *mom, const HmcOut &o) {
+    ngp_ctx *c = j->ctx;
+    const int B = j->B, L = cfg->n_leapfrog;
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIPCHK(hipSetDevice(c->device));
+    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    const size_t rows = o.trace ? (size_t)L + 1 : 0;
+    if (!j->hmc || rows > j->t_rows) {
+        // first trajectory of the job (or the first that asks for a longer trace): the arena, and
+        // the maps that do not change — item offsets, and the inverse of GradLeaf::perm
+        j->loff.assign((size_t)B + 1, 0);
+        for (int i = 0; i < B; ++i) j->loff[(size_t)i + 1] = j->loff[(size_t)i] + j->n_params[(size_t)i] + 1;
+        const size_t NL = (size_t)j->loff[(size_t)B];
+        j->t_off = 0;
+        j->t_slot = al(4 * ((size_t)B + 1));
+        j->t_kind = j->t_slot + al(NL);
+        j->t_frozen = j->t_kind + al(NL);
+        j->t_z = j->t_frozen + al(NL);
+        j->t_pm = j->t_z + al(8 * NL);
+        j->t_theta = j->t_pm + al(8 * NL);
+        j->t_sc = j->t_theta + al(8 * NL);
+        j->t_info = j->t_sc + 5 * al(8 * (size_t)B);
+        j->t_trace = j->t_info + al(4 * (size_t)B);
+        void *q = nullptr;
+        const ngp_status st = c->alloc(&q, j->t_trace + 8 * NL * rows);
+        if (st) return st;
+        c->release(j->hmc);
+        j->hmc = (unsigned char *)q;
+        j->t_rows = rows;
+        j->t_up.assign(j->t_theta - j->t_kind, 0);
+        j->t_down.assign(j->t_trace - j->t_z, 0);
+        PinVec<unsigned char> maps(j->t_kind, 0);
+        std::memcpy(maps.data(), j->loff.data(), 4 * ((size_t)B + 1));
+        for (int i = 0; i < B; ++i) {
+            unsigned char *sl = maps.data() + j->t_slot + j->loff[(size_t)i];
+            const int np = j->n_params[(size_t)i];
+            for (int k = 0; k < np; ++k) sl[j->perm[(size_t)i][(size_t)k]] = (unsigned char)k;
+            sl[np] = (unsigned char)np;
+        }
+        hipError_t e = hipMemcpyAsync(j->hmc, maps.data(), maps.size(), hipMemcpyHostToDevice, c->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);   // `maps` ends with this block
+        if (e != hipSuccess) return (ngp_status)e;
+    }
+    const size_t NL = (size_t)j->loff[(size_t)B];
+    {
+        unsigned char *up = j->t_up.data();
+        std::memcpy(up, kind, NL);
+        if (frozen) std::memcpy(up + (j->t_frozen - j->t_kind), frozen, NL);
+        else std::memset(up + (j->t_frozen - j->t_kind), 0, NL);
+        std::memcpy(up + (j->t_z - j->t_kind), z0, 8 * NL);
+        std::memcpy(up + (j->t_pm - j->t_kind), mom, 8 * NL);
+    }
+    LeafRun r;
+    r.j = j;
+    const size_t item_bytes = r.item_bytes();
+    if ((size_t)B * item_bytes > c->mem_cap) c->refresh_mem_cap();
+    r.Bc = (int)std::min<size_t>(std::min<size_t>((size_t)B, MAX_CHUNK_ITEMS),
+                                 std::max<size_t>(1, c->mem_cap / item_bytes));
+    for (;; r.Bc = (r.Bc + 1) / 2) {
+        const ngp_status st = ws_layout(c, [&](WsPlan &w) { return r.layout(w); });
+        if (!st) break;
+        if (st != NGP_ERR_TOO_LARGE || r.Bc <= 1) return st;
+    }
+    j->last_chunk = r.Bc;
+    hipStream_t s = c->stream;
+    unsigned char *const h = j->hmc;
+    HmcDev a{};
+    a.progs = (DevProgram *)j->io;
+    a.grad = (const double *)(j->io + j->o_grad);
+    a.logml = (const double *)(j->io + j->o_logml);
+    a.info = (const int32_t *)(j->io + j->o_info);
+    a.off = (const int32_t *)(h + j->t_off);
+    a.slot = h + j->t_slot;
+    a.kind = h + j->t_kind;
+    a.frozen = h + j->t_frozen;
+    a.z = (double *)(h + j->t_z);
+    a.pm = (double *)(h + j->t_pm);
+    a.theta = (double *)(h + j->t_theta);
+    const size_t scb = al(8 * (size_t)B);
+    a.U0 = (double *)(h + j->t_sc);
+    a.K0 = (double *)(h + j->t_sc + scb);
+    a.U1 = (double *)(h + j->t_sc + 2 * scb);
+    a.K1 = (double *)(h + j->t_sc + 3 * scb);
+    a.lm1 = (double *)(h + j->t_sc + 4 * scb);
+    a.info1 = (int32_t *)(h + j->t_info);
+    a.eps = cfg->eps;
+    for (int k = 0; k < 5; ++k) {
+        a.mu[k] = k >= 2 ? cfg->prior_mu[k] : 0.0;
+        a.sigma[k] = k >= 2 ? cfg->prior_sigma[k] : 1.0;
+    }
+    a.B = B;
+    double *const trace = o.trace ? (double *)(h + j->t_trace) : nullptr;
+    EventTimer tm(c->profiling, s);
+    // the device writes its own parameters from here on: whatever set_params left is superseded
+    j->progs_dirty = false;
+    hipError_t e = hipMemcpyAsync(h + j->t_kind, j->t_up.data(), j->t_up.size(), hipMemcpyHostToDevice, s);
+    ngp_status st = NGP_OK;
+    auto step = [&](int phase, int row) {
+        a.phase = phase;
+        a.trace = trace && row >= 0 ? trace + (size_t)row * NL : nullptr;
+        tm.run(4, 0.0, 0.0, [&] { launch_hmc_step(a, s); });
+    };
+    if (e == hipSuccess) {
+        step(HMC_INIT, 0);
+        for (int ev = 0; ev <= L && !st; ++ev) {
+            st = r.launch(lane_of(c), tm, false, false);
+            r.items_ready = true;
+            if (!st) step(ev == L ? HMC_LAST : ev == 0 ? HMC_FIRST : HMC_MIDDLE, ev == L ? -1 : ev + 1);
+        }
+        if (!st) e = hipMemcpyAsync(j->t_down.data(), h + j->t_z, j->t_down.size(), hipMemcpyDeviceToHost, s);
+        if (!st && e == hipSuccess && trace)
+            e = hipMemcpyAsync(o.trace, trace, 8 * NL * ((size_t)L + 1), hipMemcpyDeviceToHost, s);
+    }
+    const hipError_t es = hipStreamSynchronize(s);
+    if (e == hipSuccess) e = es;
+    if (e == hipSuccess) e = hipGetLastError();
+    tm.resolve(c->prof);
+    if (!j->h_in.empty()) PinVec<unsigned char>().swap(j->h_in);   // the staging copy has left it
+    if (st || e != hipSuccess) {
+        j->progs_dirty = true;   // the device programs are not the host's: the next run sends them
+        return st ? st : (ngp_status)e;
+    }
+    const unsigned char *dn = j->t_down.data();
+    auto at = [&](size_t t_x) { return dn + (t_x - j->t_z); };
+    std::memcpy(o.z1, at(j->t_z), 8 * NL);
+    std::memcpy(o.mom1, at(j->t_pm), 8 * NL);
+    std::memcpy(o.theta1, at(j->t_theta), 8 * NL);
+    std::memcpy(o.U0, at(j->t_sc), 8 * (size_t)B);
+    std::memcpy(o.K0, at(j->t_sc + scb), 8 * (size_t)B);
+    std::memcpy(o.U1, at(j->t_sc + 2 * scb), 8 * (size_t)B);
+    std::memcpy(o.K1, at(j->t_sc + 3 * scb), 8 * (size_t)B);
+    std::memcpy(o.lm1, at(j->t_sc + 4 * scb), 8 * (size_t)B);
+    std::memcpy(o.info1, at(j->t_info), 4 * (size_t)B);
+    // the host copy of the programs follows the device's: the parameters of the last evaluation
+    for (int i = 0; i < B; ++i) {
+        DevProgram &P = j->hp[(size_t)i];
+        const double *th = o.theta1 + j->loff[(size_t)i];
+        const int np = j->n_params[(size_t)i];
+        for (int q = 0; q < np; ++q) P.params[q] = th[j->perm[(size_t)i][(size_t)q]];
+        P.noise = th[np];
+    }
+    return NGP_OK;
+}
+
 void grad_leaf_destroy(GradLeaf *j) {
     if (!j) return;
     {
@@ -2551,6 +2718,7 @@ void grad_leaf_destroy(GradLeaf *j) {
         // a staging buffer that was kept must outlive its copy
         if (!j->h_in.empty()) (void)hipStreamSynchronize(j->ctx->stream);
         j->ctx->release(j->io);
+        j->ctx->release(j->hmc);
     }
     delete j;
 }
@@ -2811,6 +2979,84 @@ static ngp_status grad_job_run_resident(ngp_grad_job *j, double *logml, double *
     };
     ngp_status st = run_leaf(j->gen, j->idx_gen);
     if (!st) st = run_leaf(j->toep, j->idx_toep);
+    return st;
+}
+
+extern "C" ngp_status ngp_grad_job_hmc(ngp_grad_job *j, const void *cfg_, const void *kind_,
+                                       const void *frozen_, const double *z0, const double *mom,
+                                       double *z1, double *mom1, double *theta1, double *U0, double *K0,
+                                       double *U1, double *K1, double *logml1, int32_t *info1,
+                                       double *z_trace) {
+    const ngp_hmc_config *cfg = (const ngp_hmc_config *)cfg_;
+    const uint8_t *kind = (const uint8_t *)kind_, *frozen = (const uint8_t *)frozen_;
+    if (!j || !cfg || !kind || !z0 || !mom || !z1 || !mom1 || !theta1 || !U0 || !K0 || !U1 || !K1 ||
+        !logml1 || !info1)
+        return NGP_ERR_ARG;
+    if (cfg->n_leapfrog < 1 || !std::isfinite(cfg->eps)) return NGP_ERR_ARG;
+    if (cfg->n_leapfrog > 65536) return NGP_ERR_TOO_LARGE;   // the limit include/ngp.h states
+    const int B = j->B;
+    const size_t NL = j->goff[(size_t)B];
+    for (size_t q = 0; q < NL; ++q) {
+        const int kd = kind[q];
+        if (kd > 4) return NGP_ERR_ARG;
+        if (kd >= 2 && !(cfg->prior_sigma[kd] > 0.0 && std::isfinite(cfg->prior_sigma[kd]) &&
+                         std::isfinite(cfg->prior_mu[kd])))
+            return NGP_ERR_ARG;
+    }
+    const int L = cfg->n_leapfrog;
+    auto run_leaf = [&](GradLeaf *leaf, const std::vector<int32_t> &idx) -> ngp_status {
+        if (!leaf) return NGP_OK;
+        if ((int)idx.size() == B)
+            return grad_leaf_hmc(leaf, cfg, kind, frozen, z0, mom,
+                                 HmcOut{z1, mom1, theta1, U0, K0, U1, K1, logml1, info1, z_trace});
+        // a leaf of some of the items: their latents gathered, the outputs scattered back
+        size_t nl = 0;
+        for (int32_t i : idx) nl += j->goff[(size_t)i + 1] - j->goff[(size_t)i];
+        const size_t nb = idx.size();
+        std::vector<uint8_t> kd(nl), fr(frozen ? nl : 0);
+        std::vector<double> in(2 * nl), out(3 * nl + 5 * nb), tr(z_trace ? nl * ((size_t)L + 1) : 0);
+        std::vector<int32_t> inf(nb);
+        size_t off = 0;
+        for (int32_t i : idx) {
+            const size_t g0 = j->goff[(size_t)i], len = j->goff[(size_t)i + 1] - g0;
+            std::memcpy(kd.data() + off, kind + g0, len);
+            if (frozen) std::memcpy(fr.data() + off, frozen + g0, len);
+            std::memcpy(in.data() + off, z0 + g0, 8 * len);
+            std::memcpy(in.data() + nl + off, mom + g0, 8 * len);
+            off += len;
+        }
+        double *sc = out.data() + 3 * nl;
+        const ngp_status st = grad_leaf_hmc(
+            leaf, cfg, kd.data(), frozen ? fr.data() : nullptr, in.data(), in.data() + nl,
+            HmcOut{out.data(), out.data() + nl, out.data() + 2 * nl, sc, sc + nb, sc + 2 * nb, sc + 3 * nb,
+                   sc + 4 * nb, inf.data(), z_trace ? tr.data() : nullptr});
+        if (st) return st;
+        off = 0;
+        for (size_t a = 0; a < nb; ++a) {
+            const size_t i = (size_t)idx[a], g0 = j->goff[i], len = j->goff[i + 1] - g0;
+            std::memcpy(z1 + g0, out.data() + off, 8 * len);
+            std::memcpy(mom1 + g0, out.data() + nl + off, 8 * len);
+            std::memcpy(theta1 + g0, out.data() + 2 * nl + off, 8 * len);
+            for (int r = 0; z_trace && r <= L; ++r)
+                std::memcpy(z_trace + (size_t)r * NL + g0, tr.data() + (size_t)r * nl + off, 8 * len);
+            U0[i] = sc[a]; K0[i] = sc[nb + a]; U1[i] = sc[2 * nb + a]; K1[i] = sc[3 * nb + a];
+            logml1[i] = sc[4 * nb + a];
+            info1[i] = inf[a];
+            off += len;
+        }
+        return NGP_OK;
+    };
+    // items are independent: the whole trajectory of the general leaf, then that of the Toeplitz leaf
+    // (each under the context's lock; a failure of the second leaves the job as include/ngp.h says)
+    ngp_status st = run_leaf(j->gen, j->idx_gen);
+    if (!st) st = run_leaf(j->toep, j->idx_toep);
+    if (!st && !j->h_k.empty()) {   // the one-shot form of the job follows (a combined run reads it)
+        for (int i = 0; i < B; ++i) {
+            const size_t g0 = j->goff[(size_t)i], np = j->poff[(size_t)i + 1] - j->poff[(size_t)i];
+            if (np) std::memcpy(j->h_params.data() + j->poff[(size_t)i], theta1 + g0, 8 * np);
+            j->h_k[(size_t)i].noise = theta1[g0 + np];
+        }
+    }
     return st;
 }
 

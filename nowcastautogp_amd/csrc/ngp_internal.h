@@ -358,6 +358,25 @@ struct PathBufs {
 };
 hipError_t launch_path_targets(const PathGeom &g, const PathBufs &p, const ngp_inv_transform &inv,
                                uint64_t seed, hipStream_t s);
+// ---- the leapfrog step of ngp_grad_job_hmc (ngp_hmc_kernels.h) -------------------------------
+// INIT writes theta(z0) for evaluation 0; FIRST, MIDDLE and LAST follow evaluations 0, 1 .. L - 1
+// and L of a trajectory of L leapfrogs.
+enum { HMC_INIT = 0, HMC_FIRST = 1, HMC_MIDDLE = 2, HMC_LAST = 3 };
+struct HmcDev {
+    DevProgram *progs;             // [B] the leaf's programs: params[] / noise are written
+    const double *grad, *logml;    // the leaf's d_grad [B][NGP_MAX_PARAMS + 1], d_logml [B]
+    const int32_t *info;           // d_info [B]
+    const int32_t *off;            // [B + 1] an item's first latent in the flat arrays below
+    const uint8_t *slot;           // per latent: its device parameter slot (the noise: n_params)
+    const uint8_t *kind, *frozen;  // per latent
+    double *z, *pm, *theta;        // per latent, the caller's order
+    double *trace;                 // null, or the row of z_trace this step fills
+    double *U0, *K0, *U1, *K1, *lm1;   // [B]
+    int32_t *info1;                // [B]
+    double eps, mu[5], sigma[5];
+    int32_t B, phase;
+};
+void launch_hmc_step(const HmcDev &a, hipStream_t s);
 void launch_mfma_bench(double *out, int iters, int blocks, hipStream_t s);
 void launch_mfma_bench_detail(unsigned long long *stamps, int iters, int blocks, hipStream_t s);
 void launch_mfma_layout_probe(const double *A, const double *Bm, double *Dout, hipStream_t s);

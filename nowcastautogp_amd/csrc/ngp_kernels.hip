@@ -51,6 +51,7 @@
 #include "ngp_tree_kernels.h"
 #include "ngp_component_kernels.h"
 #include "ngp_grad_kernels.h"
+#include "ngp_hmc_kernels.h"
 
 namespace ngp {
 
