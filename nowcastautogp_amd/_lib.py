@@ -656,23 +656,27 @@ class Context:
                                       C.byref(h)), "ngp_factor_create")
         return Factor(self, h, ka.n)
 
-    def mixture_sample(self, w, mu, sigma, draws: int, seed: int):
+    def mixture_sample(self, w, mu, sigma, draws: int, seed: int, want_comp: bool = True,
+                       want_info: bool = True):
         """S mixtures over the same P components, sampled on the device (``ngp_mixture_sample``):
-        w [S,P], mu [P,S,m], sigma [P,m,m] -> (out [S,draws,m], comp [S,draws], info [P])."""
+        w [S,P], mu [P,S,m], sigma [P,m,m] -> (out [S,draws,m], comp [S,draws], info [P]);
+        want_comp / want_info = False: NULL is passed for that output and None returned."""
         w, mu, sigma = as_f64(w), as_f64(mu), as_f64(sigma)
         S, P = w.shape
         m = mu.shape[2]
         if mu.shape != (P, S, m) or sigma.shape != (P, m, m):
             raise ValueError("mixture_sample: w [S,P], mu [P,S,m], sigma [P,m,m]")
         out = np.empty((S, int(draws), m))
-        comp = np.zeros((S, int(draws)), dtype=np.int32)
-        info = np.zeros(P, dtype=np.int32)
+        comp = np.zeros((S, int(draws)), dtype=np.int32) if want_comp else None
+        info = np.zeros(P, dtype=np.int32) if want_info else None
         _chk(load().ngp_mixture_sample(self._h, P, S, m, dptr(w), dptr(mu), dptr(sigma),
                                        int(draws), C.c_uint64(int(seed) & (2**64 - 1)), dptr(out),
-                                       iptr(comp), iptr(info)), "ngp_mixture_sample")
+                                       iptr(comp) if want_comp else None,
+                                       iptr(info) if want_info else None), "ngp_mixture_sample")
         return out, comp, info
 
-    def mixture_sample_indep(self, w, mu, sigma, draws: int, seeds):
+    def mixture_sample_indep(self, w, mu, sigma, draws: int, seeds, want_comp: bool = True,
+                             want_info: bool = True):
         """S independent mixtures of P components each (``ngp_mixture_sample_indep``): w [S,P],
         mu [S,P,m], sigma [S,P,m,m], seeds [S] -> (out [S,draws,m], comp [S,draws], info [S,P]);
         mixture s draws what ``mixture_sample`` with S = 1 and seed = seeds[s] draws."""
@@ -683,11 +687,12 @@ class Context:
             raise ValueError("mixture_sample_indep: w [S,P], mu [S,P,m], sigma [S,P,m,m], seeds [S]")
         sd = np.array([int(v) & (2**64 - 1) for v in seeds], dtype=np.uint64)
         out = np.empty((S, int(draws), m))
-        comp = np.zeros((S, int(draws)), dtype=np.int32)
-        info = np.zeros((S, P), dtype=np.int32)
+        comp = np.zeros((S, int(draws)), dtype=np.int32) if want_comp else None
+        info = np.zeros((S, P), dtype=np.int32) if want_info else None
         _chk(load().ngp_mixture_sample_indep(self._h, P, S, m, dptr(w), dptr(mu), dptr(sigma),
                                              int(draws), sd.ctypes.data_as(C.POINTER(C.c_uint64)),
-                                             dptr(out), iptr(comp), iptr(info)),
+                                             dptr(out), iptr(comp) if want_comp else None,
+                                             iptr(info) if want_info else None),
              "ngp_mixture_sample_indep")
         return out, comp, info
 
