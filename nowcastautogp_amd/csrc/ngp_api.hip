@@ -13,16 +13,21 @@
 #include <mutex>
 #include <new>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "ngp_internal.h"
 
 using namespace ngp;
 
-#define HIPCHK(expr)                                                     \
-    do {                                                                 \
-        hipError_t e__ = (expr);                                         \
-        if (e__ != hipSuccess) return (ngp_status)(e__ > 0 ? e__ : 999); \
+// the only place a HIP error becomes a status: the positive HIP code
+static ngp_status hip_status(hipError_t e) {
+    return e == hipSuccess ? NGP_OK : (ngp_status)(e > 0 ? e : 999);
+}
+#define HIPCHK(expr)                                    \
+    do {                                                \
+        hipError_t e__ = (expr);                        \
+        if (e__ != hipSuccess) return hip_status(e__);  \
     } while (0)
 
 // ---- page-locked host memory for everything that crosses the bus ---------------------------
@@ -118,7 +123,7 @@ template <class T> using PinVec = std::vector<T, PinnedAlloc<T>>;
 }  // namespace
 
 namespace {
-struct ScopedEvent {   // destroyed on every exit path of the microbenchmarks
+struct ScopedEvent {   // a timing event of a microbenchmark
     hipEvent_t e = nullptr;
     ScopedEvent() { (void)hipEventCreate(&e); }
     ~ScopedEvent() { if (e) (void)hipEventDestroy(e); }
@@ -499,6 +504,70 @@ struct WsPlan {
     }
 };
 
+// A one-shot call on a context: the execution lock, the device, the blocks the call takes from the
+// context's allocator and the first error of its copies and launches.  After an error every further
+// step is skipped, so a call is written straight down and asks once, at sync(), how it went.
+// Whatever a call has queued may read host memory of its frame and writes blocks that go back to
+// the cache when it ends: sync() waits for the stream also after an error, and a call that leaves
+// with work queued is synchronised by the destructor before its blocks are released.
+class DevCall {
+    static constexpr int MAX_BLOCKS = 32;   // the trajectory targets take 27; nothing here touches the heap
+    ngp_ctx *c;
+    std::unique_lock<std::mutex> lk;
+    void *blocks[MAX_BLOCKS];
+    int n_blocks = 0;
+    ngp_status st = NGP_OK;
+    bool queued = false;
+    DevCall &copy(void *dst, const void *src, size_t bytes, hipMemcpyKind kind) {
+        return run([&] { return hipMemcpyAsync(dst, src, bytes, kind, c->stream); });
+    }
+public:
+    explicit DevCall(ngp_ctx *ctx) : c(ctx), lk(ctx->mu) { st = hip_status(hipSetDevice(c->device)); }
+    // an inner scope of a call in flight (the rounds of a loop): same lock, blocks of its own
+    explicit DevCall(DevCall &outer) : c(outer.c), st(outer.st) {}
+    DevCall(const DevCall &) = delete;
+    ~DevCall() {   // the lock is held here: unlocked() is the only place that drops it
+        (void)sync();
+        for (int i = 0; i < n_blocks; ++i) c->release(blocks[i]);
+    }
+    ngp_status status() const { return st; }
+    template <class T> DevCall &take(T **p, size_t count) {
+        void *q = nullptr;
+        if (!st && n_blocks == MAX_BLOCKS) st = NGP_ERR_TOO_LARGE;
+        if (!st && !(st = c->alloc(&q, sizeof(T) * count))) blocks[n_blocks++] = q;
+        *p = static_cast<T *>(q);
+        return *this;
+    }
+    // host work that takes the context's lock itself (a staged job's run and fetch), on this thread:
+    // the lock is dropped around it, the blocks stay held; skipped after an error, its status is kept
+    template <class F> DevCall &unlocked(F &&work) {
+        if (st) return *this;
+        lk.unlock();
+        st = work();
+        lk.lock();
+        return *this;
+    }
+    DevCall &up(void *dev, const void *host, size_t bytes) { return copy(dev, host, bytes, hipMemcpyHostToDevice); }
+    DevCall &down(void *host, const void *dev, size_t bytes) { return copy(host, dev, bytes, hipMemcpyDeviceToHost); }
+    // launches: void, or the hipError_t of what they asked of the runtime
+    template <class F> DevCall &run(F &&launches) {
+        if (st) return *this;
+        queued = true;
+        if constexpr (std::is_void<decltype(launches())>::value) launches();
+        else st = hip_status(launches());
+        return *this;
+    }
+    ngp_status sync() {
+        if (queued) {
+            hipError_t e = hipStreamSynchronize(c->stream);
+            if (e == hipSuccess) e = hipGetLastError();
+            if (!st) st = hip_status(e);
+            queued = false;
+        }
+        return st;
+    }
+};
+
 static DevSpec dev_spec(const ngp_spec &s) {
     return DevSpec{s.se_form, s.periodic_form, s.cp_form, s.precision, s.jitter, s.mixed_tau};
 }
@@ -552,7 +621,7 @@ extern "C" ngp_status ngp_ctx_create(int32_t device, ngp_ctx **out) {
     hipError_t e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
     if (e != hipSuccess) {
         delete c;
-        return (ngp_status)e;
+        return hip_status(e);
     }
     if (hipStreamCreateWithFlags(&c->side, hipStreamNonBlocking) != hipSuccess ||
         hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming) != hipSuccess ||
@@ -1365,7 +1434,7 @@ extern "C" ngp_status ngp_job_run(ngp_job *j) {
     hipError_t err = hipStreamSynchronize(s);
     if (err == hipSuccess) err = hipGetLastError();
     tm.resolve(c->prof);
-    if (err != hipSuccess) return (ngp_status)err;
+    if (err != hipSuccess) return hip_status(err);
     j->copy_in_flight = false;
     j->ran = true;
     return NGP_OK;
@@ -1543,8 +1612,8 @@ namespace {
 ngp_status factor_run(ngp_factor *f, ngp_job *j, bool create, const CompPtrs *comp = nullptr,
                       double *comp_work = nullptr, int64_t comp_work_stride = 0) {
     ngp_ctx *c = f->ctx;
-    std::lock_guard<std::mutex> lk(c->mu);
-    HIPCHK(hipSetDevice(c->device));
+    DevCall call(c);   // the lock, the device and the tables; the launches below are the staged job's
+    if (call.status()) return call.status();
     JobGeom &g = j->g;
     g.item_stride = f->item_stride;
     hipStream_t s = c->stream;
@@ -1552,17 +1621,11 @@ ngp_status factor_run(ngp_factor *f, ngp_job *j, bool create, const CompPtrs *co
     const DevSpec sp = dev_spec(f->spec);
     EventTimer tm(c->profiling, s);
     const int P = f->P;
-    void *tab = nullptr, *sig = nullptr;
-    struct Scratch {   // the tables go back to the allocator on every exit path
-        ngp_ctx *c; void *&a, *&b;
-        ~Scratch() { c->release(a); c->release(b); }
-    } scratch{c, tab, sig};
+    double *tab = nullptr, *sig = nullptr;
     if (g.n0 > 0) {
-        if (g.lattice) {
-            ngp_status st = c->alloc(&tab, sizeof(double) * (size_t)g.maxstat * g.R * P);
-            if (!st) st = c->alloc(&sig, sizeof(double) * (size_t)g.maxcp * g.npts * P);
-            if (st) return st;
-        }
+        if (g.lattice &&
+            call.take(&tab, (size_t)g.maxstat * g.R * P).take(&sig, (size_t)g.maxcp * g.npts * P).status())
+            return call.status();
         ChunkPtrs p{};
         p.L = f->L;
         p.dinv = f->dinv;
@@ -1572,8 +1635,8 @@ ngp_status factor_run(ngp_factor *f, ngp_job *j, bool create, const CompPtrs *co
         p.y0 = j->y0;
         p.logdet = j->logdet;
         p.info = j->info;
-        p.tab = (double *)tab;
-        p.sig = (double *)sig;
+        p.tab = tab;
+        p.sig = sig;
         p.qpts = j->qpts;
         const size_t mstep = (size_t)P * NB * NB;
         if (g.lattice) tm.run(4, 0.0, 0.0, [&] { launch_tables(g, p, P, sp, s); });
@@ -1609,8 +1672,8 @@ ngp_status factor_run(ngp_factor *f, ngp_job *j, bool create, const CompPtrs *co
     }
     EpiPtrs e = epi_ptrs_of(*j);
     if (g.lattice && g.n0 > 0) {
-        e.tab = (const double *)tab;
-        e.sig = (const double *)sig;
+        e.tab = tab;
+        e.sig = sig;
         e.qpts = j->qpts;
     }
     if (comp) {
@@ -1623,7 +1686,7 @@ ngp_status factor_run(ngp_factor *f, ngp_job *j, bool create, const CompPtrs *co
     hipError_t err = hipStreamSynchronize(s);
     if (err == hipSuccess) err = hipGetLastError();
     tm.resolve(c->prof);
-    if (err != hipSuccess) return (ngp_status)err;
+    if (err != hipSuccess) return hip_status(err);
     j->ran = true;
     return NGP_OK;
 }
@@ -1970,46 +2033,33 @@ ngp_status components_query(ngp_factor *f, int32_t d, const double *t_add, int32
     std::memcpy(h_in.data(), hp.data(), o_first);
     std::memcpy(h_in.data() + o_first, first.data(), 4 * first.size());
     std::memcpy(h_in.data() + o_sig, sig_off.data(), 8 * sig_off.size());
-    void *d_in = nullptr, *d_mu = nullptr, *d_sigma = nullptr, *d_var = nullptr, *d_work = nullptr;
     {
-        std::lock_guard<std::mutex> lk(c->mu);
-        if (hipSetDevice(c->device) != hipSuccess) st = NGP_ERR_NO_DEVICE;
-        if (!st) st = c->alloc(&d_in, in_bytes);
-        if (!st) st = c->alloc(&d_mu, 8 * n_mu);
-        if (!st && sigma) st = c->alloc(&d_sigma, 8 * (size_t)sig_total);
-        if (!st && var) st = c->alloc(&d_var, 8 * n_out);
-        if (!st) st = c->alloc(&d_work, 8 * (size_t)P * (size_t)work_stride);
-        if (!st && hipMemcpyAsync(d_in, h_in.data(), in_bytes, hipMemcpyHostToDevice, c->stream) != hipSuccess)
-            st = NGP_ERR_STATE;
-    }
-    if (!st) {
-        CompPtrs cp{};
-        cp.progs = (const DevProgram *)d_in;
-        cp.first = (const int32_t *)((unsigned char *)d_in + o_first);
-        cp.sig_off = (const int64_t *)((unsigned char *)d_in + o_sig);
-        cp.mu = (double *)d_mu;
-        cp.sigma = (double *)d_sigma;
-        cp.var = (double *)d_var;
-        cp.m = m;
-        cp.cmax = cmax;
-        st = factor_run(f, job, /*create=*/false, &cp, (double *)d_work, work_stride);
-    }
-    if (!st) st = ngp_job_fetch(job, nullptr, logml_full, nullptr, nullptr, info);
-    {
-        std::lock_guard<std::mutex> lk(c->mu);
-        hipStream_t s = c->stream;
-        hipError_t e = hipSuccess;
-        if (!st && hipSetDevice(c->device) != hipSuccess) st = NGP_ERR_NO_DEVICE;
-        if (!st) {
-            e = hipMemcpyAsync(mu, d_mu, 8 * n_mu, hipMemcpyDeviceToHost, s);
-            if (e == hipSuccess && sigma)
-                e = hipMemcpyAsync(sigma, d_sigma, 8 * (size_t)sig_total, hipMemcpyDeviceToHost, s);
-            if (e == hipSuccess && var) e = hipMemcpyAsync(var, d_var, 8 * n_out, hipMemcpyDeviceToHost, s);
-        }
-        // (also on an error path: the staging copy may still be reading h_in)
-        const hipError_t es = hipStreamSynchronize(s);
-        if (!st && (e != hipSuccess || es != hipSuccess)) st = (ngp_status)(e != hipSuccess ? e : es);
-        c->release(d_in); c->release(d_mu); c->release(d_sigma); c->release(d_var); c->release(d_work);
+        // the call keeps its blocks while the job runs and is fetched under the lock those take
+        // themselves (same thread, same device)
+        DevCall call(c);
+        unsigned char *d_in = nullptr;
+        double *d_mu = nullptr, *d_sigma = nullptr, *d_var = nullptr, *d_work = nullptr;
+        call.take(&d_in, in_bytes).take(&d_mu, n_mu);
+        if (sigma) call.take(&d_sigma, (size_t)sig_total);
+        if (var) call.take(&d_var, n_out);
+        call.take(&d_work, (size_t)P * (size_t)work_stride).up(d_in, h_in.data(), in_bytes);
+        call.unlocked([&] {
+            CompPtrs cp{};
+            cp.progs = (const DevProgram *)d_in;
+            cp.first = (const int32_t *)(d_in + o_first);
+            cp.sig_off = (const int64_t *)(d_in + o_sig);
+            cp.mu = d_mu;
+            cp.sigma = d_sigma;
+            cp.var = d_var;
+            cp.m = m;
+            cp.cmax = cmax;
+            const ngp_status ran = factor_run(f, job, /*create=*/false, &cp, d_work, work_stride);
+            return ran ? ran : ngp_job_fetch(job, nullptr, logml_full, nullptr, nullptr, info);
+        });
+        call.down(mu, d_mu, 8 * n_mu);
+        if (sigma) call.down(sigma, d_sigma, 8 * (size_t)sig_total);
+        if (var) call.down(var, d_var, 8 * n_out);
+        st = call.sync();   // also when the job failed: the staging copy reads h_in
     }
     ngp_job_destroy(job);
     return st;
@@ -2058,37 +2108,27 @@ extern "C" ngp_status ngp_cov_batch(ngp_ctx *c, int32_t B, const ngp_kernel *ker
         ngp_status st = compile_program(&kernels[i], &hp[(size_t)i], nullptr);
         if (st) return st;
     }
-    std::lock_guard<std::mutex> lk(c->mu);
-    HIPCHK(hipSetDevice(c->device));
-    void *dp = nullptr, *d1 = nullptr, *d2 = nullptr, *dout = nullptr;
+    DevCall call(c);
+    DevProgram *dp = nullptr;
+    double *d1 = nullptr, *d2 = nullptr, *dout = nullptr;
     const size_t nout = (size_t)B * n1 * n2;
-    ngp_status st;
-    if ((st = c->alloc(&dp, sizeof(DevProgram) * (size_t)B)) ||
-        (st = c->alloc(&d1, sizeof(double) * (size_t)n1)) ||
-        (st = c->alloc(&d2, sizeof(double) * (size_t)n2)) ||
-        (st = c->alloc(&dout, sizeof(double) * nout))) {
-        c->release(dp); c->release(d1); c->release(d2); c->release(dout);
-        return st;
-    }
+    call.take(&dp, (size_t)B).take(&d1, (size_t)n1).take(&d2, (size_t)n2).take(&dout, nout);
     hipStream_t s = c->stream;
-    hipError_t e = hipMemcpyAsync(dp, hp.data(), sizeof(DevProgram) * (size_t)B,
-                                  hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(d1, t1, sizeof(double) * (size_t)n1, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(d2, t2, sizeof(double) * (size_t)n2, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) {
-        EventTimer tm(c->profiling, s);
-        tm.run(4, 0.0, 8.0 * (double)nout, [&] {
-            for (int b0 = 0; b0 < B; b0 += (int)MAX_CHUNK_ITEMS)   // items are blockIdx.y
-                launch_cov((const DevProgram *)dp + b0, std::min(B - b0, (int)MAX_CHUNK_ITEMS),
-                           (const double *)d1, n1, (const double *)d2, n2, add_diag,
-                           (double *)dout + (size_t)b0 * n1 * n2, dev_spec(c->spec), s);
-        });
-        e = hipMemcpyAsync(out, dout, sizeof(double) * nout, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-        tm.resolve(c->prof);
-    }
-    c->release(dp); c->release(d1); c->release(d2); c->release(dout);
-    return e == hipSuccess ? NGP_OK : (ngp_status)e;
+    EventTimer tm(c->profiling, s);
+    call.up(dp, hp.data(), sizeof(DevProgram) * (size_t)B)
+        .up(d1, t1, sizeof(double) * (size_t)n1)
+        .up(d2, t2, sizeof(double) * (size_t)n2)
+        .run([&] {
+            tm.run(4, 0.0, 8.0 * (double)nout, [&] {
+                for (int b0 = 0; b0 < B; b0 += (int)MAX_CHUNK_ITEMS)   // items are blockIdx.y
+                    launch_cov(dp + b0, std::min(B - b0, (int)MAX_CHUNK_ITEMS), d1, n1, d2, n2, add_diag,
+                               dout + (size_t)b0 * n1 * n2, dev_spec(c->spec), s);
+            });
+        })
+        .down(out, dout, sizeof(double) * nout);
+    const ngp_status st = call.sync();
+    tm.resolve(c->prof);
+    return st;
 }
 
 // ---------------------------------------------------------------------------------------
@@ -2377,7 +2417,7 @@ struct LeafRun {
         // a re-run: info | logdet are contiguous in the arena (short jobs: written outright)
         if (e == hipSuccess && !j->fresh && !small_job(g, Bc))
             e = hipMemsetAsync(d_info, 0, j->o_grad - j->o_info, s);
-        if (e != hipSuccess) return (ngp_status)e;
+        if (e != hipSuccess) return hip_status(e);
         j->progs_dirty = false;
         j->fresh = false;
         for (int b0 = 0; b0 < B; b0 += Bc) {
@@ -2453,7 +2493,7 @@ struct LeafRun {
             }
         }
         if (copy_out) e = hipMemcpyAsync(j->h_out.data(), d_info, j->h_out.size(), hipMemcpyDeviceToHost, s);
-        return e == hipSuccess ? NGP_OK : (ngp_status)e;
+        return hip_status(e);
     }
 
     // after the lane is synchronised: device parameter order -> caller's order; d/d noise last
@@ -2500,7 +2540,7 @@ ngp_status grad_leaf_run(GradLeaf *j, double *logml, double *grad, int32_t *info
     if (e == hipSuccess) e = hipGetLastError();
     tm.resolve(c->prof);
     if (st) return st;
-    if (e != hipSuccess) return (ngp_status)e;
+    if (e != hipSuccess) return hip_status(e);
     r.unpack(logml, grad, info);
     return NGP_OK;
 }
@@ -2548,7 +2588,7 @@ ngp_status grad_pair_run(GradLeaf *a, double *lm_a, double *g_a, int32_t *info_a
     tmb.resolve(c->prof);
     if (sa) return sa;
     if (sb) return sb;
-    if (e != hipSuccess) return (ngp_status)e;
+    if (e != hipSuccess) return hip_status(e);
     ra.unpack(lm_a, g_a, info_a);
     rb.unpack(lm_b, g_b, info_b);
     return NGP_OK;
@@ -2607,7 +2647,7 @@ ngp_status grad_leaf_hmc(GradLeaf *j, const ngp_hmc_config *cfg, const uint8_t *
         }
         hipError_t e = hipMemcpyAsync(j->hmc, maps.data(), maps.size(), hipMemcpyHostToDevice, c->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(c->stream);   // `maps` ends with this block
-        if (e != hipSuccess) return (ngp_status)e;
+        if (e != hipSuccess) return hip_status(e);
     }
     const size_t NL = (size_t)j->loff[(size_t)B];
     {
@@ -2686,7 +2726,7 @@ ngp_status grad_leaf_hmc(GradLeaf *j, const ngp_hmc_config *cfg, const uint8_t *
     if (!j->h_in.empty()) PinVec<unsigned char>().swap(j->h_in);   // the staging copy has left it
     if (st || e != hipSuccess) {
         j->progs_dirty = true;   // the device programs are not the host's: the next run sends them
-        return st ? st : (ngp_status)e;
+        return st ? st : hip_status(e);
     }
     const unsigned char *dn = j->t_down.data();
     auto at = [&](size_t t_x) { return dn + (t_x - j->t_z); };
@@ -3144,44 +3184,25 @@ static ngp_status mixture_sample_impl(ngp_ctx *c, int32_t P, int32_t S, int32_t 
     if (!c || !w || !mu || !sigma || !out || P <= 0 || S <= 0 || m <= 0 || draws <= 0)
         return NGP_ERR_ARG;
     if (m > NGP_MAX_AUX) return NGP_ERR_TOO_LARGE;
-    std::lock_guard<std::mutex> lk(c->mu);
-    HIPCHK(hipSetDevice(c->device));
-    hipStream_t s = c->stream;
+    DevCall call(c);
     const size_t ncomp_mats = seeds ? (size_t)S * P : (size_t)P;
     const size_t nw = (size_t)S * P, nmu = (size_t)P * S * m, nsg = ncomp_mats * m * m,
                  nout = (size_t)S * draws * m, ncomp = (size_t)S * draws;
-    void *dw = nullptr, *dmu = nullptr, *dsg = nullptr, *dout = nullptr, *dcomp = nullptr,
-         *dinfo = nullptr, *dseeds = nullptr;
-    auto freeall = [&] {
-        c->release(dw); c->release(dmu); c->release(dsg); c->release(dout); c->release(dcomp);
-        c->release(dinfo); c->release(dseeds);
-    };
-    ngp_status st;
-    if ((st = c->alloc(&dw, 8 * nw)) || (st = c->alloc(&dmu, 8 * nmu)) ||
-        (st = c->alloc(&dsg, 8 * nsg)) || (st = c->alloc(&dout, 8 * nout)) ||
-        (st = c->alloc(&dcomp, 4 * ncomp)) || (st = c->alloc(&dinfo, 4 * ncomp_mats)) ||
-        (seeds && (st = c->alloc(&dseeds, 8 * (size_t)S)))) {
-        freeall();
-        return st;
-    }
-    hipError_t e = hipMemcpyAsync(dw, w, 8 * nw, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(dmu, mu, 8 * nmu, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(dsg, sigma, 8 * nsg, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess && seeds)
-        e = hipMemcpyAsync(dseeds, seeds, 8 * (size_t)S, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) {
-        launch_mixture_sample(P, S, m, (const double *)dw, (const double *)dmu, (double *)dsg, draws,
-                              seed, (const uint64_t *)dseeds, (double *)dout, (int32_t *)dcomp,
-                              (int32_t *)dinfo, s);
-        e = hipMemcpyAsync(out, dout, 8 * nout, hipMemcpyDeviceToHost, s);
-    }
-    if (e == hipSuccess && comp) e = hipMemcpyAsync(comp, dcomp, 4 * ncomp, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess && info)
-        e = hipMemcpyAsync(info, dinfo, 4 * ncomp_mats, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e == hipSuccess) e = hipGetLastError();
-    freeall();
-    return e == hipSuccess ? NGP_OK : (ngp_status)e;
+    double *dw = nullptr, *dmu = nullptr, *dsg = nullptr, *dout = nullptr;
+    int32_t *dcomp = nullptr, *dinfo = nullptr;
+    uint64_t *dseeds = nullptr;
+    call.take(&dw, nw).take(&dmu, nmu).take(&dsg, nsg).take(&dout, nout).take(&dcomp, ncomp)
+        .take(&dinfo, ncomp_mats);
+    if (seeds) call.take(&dseeds, (size_t)S);
+    call.up(dw, w, 8 * nw).up(dmu, mu, 8 * nmu).up(dsg, sigma, 8 * nsg);
+    if (seeds) call.up(dseeds, seeds, 8 * (size_t)S);
+    call.run([&] {
+            launch_mixture_sample(P, S, m, dw, dmu, dsg, draws, seed, dseeds, dout, dcomp, dinfo, c->stream);
+        })
+        .down(out, dout, 8 * nout);
+    if (comp) call.down(comp, dcomp, 4 * ncomp);
+    if (info) call.down(info, dinfo, 4 * ncomp_mats);
+    return call.sync();
 }
 
 extern "C" ngp_status ngp_mixture_sample_indep(ngp_ctx *c, int32_t P, int32_t S, int32_t m,
@@ -3247,21 +3268,18 @@ ngp_status mixture_stage(int32_t C, int32_t m, const double *w, const double *mu
     return NGP_OK;
 }
 
-// device blocks of one call, given back on every exit path
-struct MixBlocks {
-    ngp_ctx *c;
-    std::vector<void *> held;
-    explicit MixBlocks(ngp_ctx *ctx) : c(ctx) {}
-    ~MixBlocks() { for (void *p : held) c->release(p); }
-    ngp_status take(double **p, size_t count) {
-        void *q = nullptr;
-        const ngp_status st = c->alloc(&q, 8 * count);
-        if (st) return st;
-        held.push_back(q);
-        *p = (double *)q;
-        return NGP_OK;
-    }
-};
+// every level strictly inside (0, 1) (a NaN is not)
+bool probs_open_unit(const double *probs, int32_t n) {
+    for (int32_t i = 0; i < n; ++i)
+        if (!(probs[i] > 0.0 && probs[i] < 1.0)) return false;
+    return true;
+}
+
+// a known kind and finite parameters (what more a call asks of the map is checked at that call)
+bool inv_transform_ok(const ngp_inv_transform *inv) {
+    return inv->kind >= NGP_INV_IDENTITY && inv->kind <= NGP_INV_BOXCOX && std::isfinite(inv->lam) &&
+           std::isfinite(inv->offset) && std::isfinite(inv->cap);
+}
 
 enum { MIX_CDF = 0, MIX_QUANTILES = 1, MIX_CRPS = 2 };
 
@@ -3271,42 +3289,35 @@ ngp_status mixture_summary(ngp_ctx *c, int kind, int32_t C, int32_t m, const dou
                            double *res, int32_t *info) {
     if (!c || !pts || !res || npts < 1) return NGP_ERR_ARG;
     if (npts > MIX_MAX_POINTS) return NGP_ERR_TOO_LARGE;
-    if (kind == MIX_QUANTILES)
-        for (int32_t k = 0; k < npts; ++k)
-            if (!(pts[k] > 0.0 && pts[k] < 1.0)) return NGP_ERR_ARG;
+    if (kind == MIX_QUANTILES && !probs_open_unit(pts, npts)) return NGP_ERR_ARG;
     MixStaged h;
     ngp_status st = mixture_stage(C, m, w, mu, var, info, &h);
     if (st) return st;
     const size_t Cn = (size_t)h.C, nres = (size_t)m * npts;
     const size_t npin = kind == MIX_QUANTILES ? (size_t)npts : nres;
-    std::lock_guard<std::mutex> lk(c->mu);
-    HIPCHK(hipSetDevice(c->device));
+    DevCall call(c);
     hipStream_t s = c->stream;
-    MixBlocks blk(c);
     double *dw = nullptr, *dmu = nullptr, *dvar = nullptr, *daux = nullptr, *dpts = nullptr,
            *dres = nullptr;
     // aux: inv [m][C] for the CDF and the quantiles, the slab of tile partials for the CRPS
     const size_t naux = kind == MIX_CRPS ? (size_t)m * (size_t)mix_tile_pairs(h.C) : Cn * m;
-    if ((st = blk.take(&dw, Cn)) || (st = blk.take(&dmu, Cn * m)) || (st = blk.take(&dvar, Cn * m)) ||
-        (st = blk.take(&daux, naux)) || (st = blk.take(&dpts, npin)) || (st = blk.take(&dres, nres)))
-        return st;
-    hipError_t e = hipMemcpyAsync(dw, h.w.data(), 8 * Cn, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(dmu, h.mu.data(), 8 * Cn * m, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(dvar, h.var.data(), 8 * Cn * m, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(dpts, pts, 8 * npin, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) {
-        if (kind == MIX_CRPS) {
-            launch_mixture_crps(h.C, m, dw, dmu, dvar, dpts, daux, dres, s);
-        } else {
-            launch_mixture_prep(dvar, daux, (int64_t)(Cn * m), s);
-            if (kind == MIX_CDF) launch_mixture_cdf(h.C, m, dw, dmu, daux, npts, dpts, dres, s);
-            else launch_mixture_quantiles(h.C, m, dw, dmu, daux, npts, dpts, dres, s);
-        }
-        e = hipMemcpyAsync(res, dres, 8 * nres, hipMemcpyDeviceToHost, s);
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e == hipSuccess) e = hipGetLastError();
-    if (e != hipSuccess) return (ngp_status)(e > 0 ? e : 999);
+    call.take(&dw, Cn).take(&dmu, Cn * m).take(&dvar, Cn * m).take(&daux, naux).take(&dpts, npin)
+        .take(&dres, nres);
+    call.up(dw, h.w.data(), 8 * Cn)
+        .up(dmu, h.mu.data(), 8 * Cn * m)
+        .up(dvar, h.var.data(), 8 * Cn * m)
+        .up(dpts, pts, 8 * npin)
+        .run([&] {
+            if (kind == MIX_CRPS) {
+                launch_mixture_crps(h.C, m, dw, dmu, dvar, dpts, daux, dres, s);
+            } else {
+                launch_mixture_prep(dvar, daux, (int64_t)(Cn * m), s);
+                if (kind == MIX_CDF) launch_mixture_cdf(h.C, m, dw, dmu, daux, npts, dpts, dres, s);
+                else launch_mixture_quantiles(h.C, m, dw, dmu, daux, npts, dpts, dres, s);
+            }
+        })
+        .down(res, dres, 8 * nres);
+    if ((st = call.sync())) return st;
     for (int32_t j = 0; j < m; ++j)
         if (h.bad[j])
             for (int32_t k = 0; k < npts; ++k) res[(size_t)j * npts + k] = std::nan("");
@@ -3347,9 +3358,7 @@ extern "C" ngp_status ngp_mixture_crps_mapped(ngp_ctx *c, int32_t C, int32_t m, 
     const ngp_inv_transform *inv = (const ngp_inv_transform *)inv_;
     if (!c || !inv || !y || !crps || !info || m < 1) return NGP_ERR_ARG;
     if (scale != NGP_SCORE_NATURAL && scale != NGP_SCORE_LOG) return NGP_ERR_ARG;
-    if (inv->kind < NGP_INV_IDENTITY || inv->kind > NGP_INV_BOXCOX || !std::isfinite(inv->lam) ||
-        !std::isfinite(inv->offset) || !std::isfinite(inv->cap) || !std::isfinite(shift) ||
-        !std::isfinite(tol) || shift < 0.0)
+    if (!inv_transform_ok(inv) || !std::isfinite(shift) || !std::isfinite(tol) || shift < 0.0)
         return NGP_ERR_ARG;
     if (m > MIX_MAX_DATES) return NGP_ERR_TOO_LARGE;       // bounds the loop below
     for (int32_t j = 0; j < m; ++j)
@@ -3360,32 +3369,27 @@ extern "C" ngp_status ngp_mixture_crps_mapped(ngp_ctx *c, int32_t C, int32_t m, 
     ngp_status st = mixture_stage(C, m, w, mu, var, info, &h);
     if (st) return st;
     const size_t Cn = (size_t)h.C;
-    std::lock_guard<std::mutex> lk(c->mu);
-    HIPCHK(hipSetDevice(c->device));
+    std::vector<double> rec((size_t)m * MIXMAP_REC, 0.0);   // (before the call: it outlives what reads and writes it)
+    std::vector<MixMapPlan> work;
+    std::vector<double> res;
+    DevCall call(c);
     hipStream_t s = c->stream;
-    MixBlocks blk(c);
     double *dw = nullptr, *dmu = nullptr, *dvar = nullptr, *dinv = nullptr, *dy = nullptr,
            *drec = nullptr;
-    if ((st = blk.take(&dw, Cn)) || (st = blk.take(&dmu, Cn * m)) || (st = blk.take(&dvar, Cn * m)) ||
-        (st = blk.take(&dinv, Cn * m)) || (st = blk.take(&dy, (size_t)m)) ||
-        (st = blk.take(&drec, (size_t)m * MIXMAP_REC)))
-        return st;
-    std::vector<double> rec((size_t)m * MIXMAP_REC, 0.0);
-    hipError_t e = hipMemcpyAsync(dw, h.w.data(), 8 * Cn, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(dmu, h.mu.data(), 8 * Cn * m, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(dvar, h.var.data(), 8 * Cn * m, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(dy, y, 8 * (size_t)m, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) {
-        launch_mixture_prep(dvar, dinv, (int64_t)(Cn * m), s);
-        launch_mixmap_scan(h.C, m, *inv, scale, shift, dw, dmu, dinv, dy, drec, s);
-        e = hipMemcpyAsync(rec.data(), drec, 8 * rec.size(), hipMemcpyDeviceToHost, s);
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e == hipSuccess) e = hipGetLastError();
-    if (e != hipSuccess) return (ngp_status)(e > 0 ? e : 999);
+    call.take(&dw, Cn).take(&dmu, Cn * m).take(&dvar, Cn * m).take(&dinv, Cn * m).take(&dy, (size_t)m)
+        .take(&drec, (size_t)m * MIXMAP_REC);
+    call.up(dw, h.w.data(), 8 * Cn)
+        .up(dmu, h.mu.data(), 8 * Cn * m)
+        .up(dvar, h.var.data(), 8 * Cn * m)
+        .up(dy, y, 8 * (size_t)m)
+        .run([&] {
+            launch_mixture_prep(dvar, dinv, (int64_t)(Cn * m), s);
+            launch_mixmap_scan(h.C, m, *inv, scale, shift, dw, dmu, dinv, dy, drec, s);
+        })
+        .down(rec.data(), drec, 8 * rec.size());
+    if ((st = call.sync())) return st;
 
     const double nan = std::nan("");
-    std::vector<MixMapPlan> work;
     work.reserve(m);
     for (int32_t j = 0; j < m; ++j) {
         crps[j] = nan;
@@ -3398,27 +3402,22 @@ extern "C" ngp_status ngp_mixture_crps_mapped(ngp_ctx *c, int32_t C, int32_t m, 
         }
         work.push_back(mixmap_plan(j, &rec[(size_t)j * MIXMAP_REC]));
     }
-    std::vector<double> res;
     while (!work.empty()) {
         const size_t nw = work.size();
         int32_t maxp = 1;
         for (const MixMapPlan &p : work) maxp = std::max(maxp, p.npanels);
-        MixBlocks round(c);                                // this width's buffers, given back below
-        double *dplan = nullptr, *dslab = nullptr, *dres = nullptr;
-        static_assert(sizeof(MixMapPlan) % 8 == 0, "plans are allocated in doubles");
-        if ((st = round.take(&dplan, nw * (sizeof(MixMapPlan) / 8))) ||
-            (st = round.take(&dslab, nw * (size_t)maxp * 3)) || (st = round.take(&dres, nw * 3)))
-            return st;
+        DevCall round(call);                               // this width's buffers, given back below
+        MixMapPlan *dplan = nullptr;
+        double *dslab = nullptr, *dres = nullptr;
+        round.take(&dplan, nw).take(&dslab, nw * (size_t)maxp * 3).take(&dres, nw * 3);
         res.assign(nw * 3, 0.0);
-        e = hipMemcpyAsync(dplan, work.data(), nw * sizeof(MixMapPlan), hipMemcpyHostToDevice, s);
-        if (e == hipSuccess) {
-            launch_mixmap_panels(h.C, (int)nw, maxp, *inv, scale, shift, (const MixMapPlan *)dplan,
-                                 dw, dmu, dinv, dslab, dres, s);
-            e = hipMemcpyAsync(res.data(), dres, 8 * res.size(), hipMemcpyDeviceToHost, s);
-        }
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-        if (e == hipSuccess) e = hipGetLastError();
-        if (e != hipSuccess) return (ngp_status)(e > 0 ? e : 999);
+        round.up(dplan, work.data(), nw * sizeof(MixMapPlan))
+            .run([&] {
+                launch_mixmap_panels(h.C, (int)nw, maxp, *inv, scale, shift, dplan, dw, dmu, dinv, dslab,
+                                     dres, s);
+            })
+            .down(res.data(), dres, 8 * res.size());
+        if ((st = round.sync())) return st;
         std::vector<MixMapPlan> next;
         for (size_t k = 0; k < nw; ++k) {
             const int32_t j = work[k].date;
@@ -3448,19 +3447,20 @@ extern "C" ngp_status ngp_mixture_crps_mapped(ngp_ctx *c, int32_t C, int32_t m, 
 // the ceiling mix_crps_pairs_kernel is measured against (scripts/summary_probe.py)
 extern "C" ngp_status ngp_microbench_mixture_pairs(ngp_ctx *c, int32_t iters, double *pairs_per_s) {
     if (!c || !pairs_per_s || iters <= 0) return NGP_ERR_ARG;
-    std::lock_guard<std::mutex> lk(c->mu);
-    HIPCHK(hipSetDevice(c->device));
+    DevCall call(c);
     const int blocks = 256 * 8;
-    MixBlocks blk(c);
     double *out = nullptr;
-    ngp_status st = blk.take(&out, (size_t)blocks * 256);
-    if (st) return st;
+    call.take(&out, (size_t)blocks * 256);
     ScopedEvent a, b;
-    launch_mixture_pair_rate(iters, blocks, out, c->stream);  // warm-up
-    HIPCHK(hipEventRecord(a, c->stream));
-    launch_mixture_pair_rate(iters, blocks, out, c->stream);
-    HIPCHK(hipEventRecord(b, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
+    call.run([&] {
+            launch_mixture_pair_rate(iters, blocks, out, c->stream);  // warm-up
+            return hipEventRecord(a, c->stream);
+        })
+        .run([&] {
+            launch_mixture_pair_rate(iters, blocks, out, c->stream);
+            return hipEventRecord(b, c->stream);
+        });
+    if (call.sync()) return call.status();
     float ms = 0.f;
     HIPCHK(hipEventElapsedTime(&ms, a, b));
     *pairs_per_s = (double)blocks * 256.0 * (double)iters / ((double)ms * 1e-3);
@@ -3482,10 +3482,7 @@ ngp_status path_targets_impl(ngp_ctx *c, int32_t P, int32_t S, int32_t m, const 
     if (!c || !w || !mu || !sigma || !inv || !targets || !probs || !q || !mean || !count || !hist ||
         P <= 0 || S <= 0 || m <= 0 || draws < 1 || T < 1 || Q < 1)
         return NGP_ERR_ARG;
-    if (inv->kind < NGP_INV_IDENTITY || inv->kind > NGP_INV_BOXCOX || !std::isfinite(inv->lam) ||
-        !std::isfinite(inv->offset) || !std::isfinite(inv->cap) ||
-        (inv->kind == NGP_INV_BOXCOX && !(inv->cap > 0.0)))
-        return NGP_ERR_ARG;
+    if (!inv_transform_ok(inv) || (inv->kind == NGP_INV_BOXCOX && !(inv->cap > 0.0))) return NGP_ERR_ARG;
     if (T > PATH_MAX_TARGETS || Q > PATH_MAX_LEVELS) return NGP_ERR_TOO_LARGE;   // bounds the loops below
     for (int32_t t = 0; t < T; ++t) {
         const ngp_path_target &tg = targets[t];
@@ -3493,8 +3490,7 @@ ngp_status path_targets_impl(ngp_ctx *c, int32_t P, int32_t S, int32_t m, const 
             tg.j0 > tg.j1 || !std::isfinite(tg.thr))
             return NGP_ERR_ARG;
     }
-    for (int32_t i = 0; i < Q; ++i)
-        if (!(probs[i] > 0.0 && probs[i] < 1.0)) return NGP_ERR_ARG;
+    if (!probs_open_unit(probs, Q)) return NGP_ERR_ARG;
     const int64_t N = (int64_t)S * draws, Bn = seeds ? (int64_t)S * P : (int64_t)P;
     if (m > NGP_MAX_AUX || N > INT32_MAX || (int64_t)S * P > INT32_MAX) return NGP_ERR_TOO_LARGE;
 
@@ -3520,63 +3516,42 @@ ngp_status path_targets_impl(ngp_ctx *c, int32_t P, int32_t S, int32_t m, const 
                  Tr = std::max<size_t>(real.size(), 1), slices = (size_t)path_slices(N);
     const size_t nw = (size_t)S * P, nmu = (size_t)P * S * m, nsg = B * m * m;
 
-    std::lock_guard<std::mutex> lk(c->mu);
-    HIPCHK(hipSetDevice(c->device));
+    std::vector<int32_t> hinfo(B, 0);
+    std::vector<double> hq(Tr * R, 0.0);
+    DevCall call(c);
+    if (call.status()) return call.status();
     c->refresh_mem_cap();
     if ((double)(8 * Tn + 12) * (double)Nn + 8.0 * (double)(nw + nmu + nsg) > (double)c->mem_cap)
         return NGP_ERR_TOO_LARGE;
-    hipStream_t s = c->stream;
-    MixBlocks blk(c);
-    auto take = [&](auto **p, size_t bytes) {
-        double *d = nullptr;
-        const ngp_status st = blk.take(&d, (bytes + 7) / 8);
-        *p = reinterpret_cast<std::remove_reference_t<decltype(*p)>>(d);
-        return st;
-    };
     double *dw = nullptr, *dmu = nullptr;
     uint64_t *dseeds = nullptr;
     int64_t *dranks = nullptr;
     int32_t *dreal = nullptr;
     ngp_path_target *dtargets = nullptr;
     PathBufs b{};
-    ngp_status st;
-    if ((st = take(&dw, 8 * nw)) || (st = take(&dmu, 8 * nmu)) || (st = take(&b.chol, 8 * nsg)) ||
-        (seeds && (st = take(&dseeds, 8 * (size_t)S))) || (st = take(&b.info, 4 * B)) ||
-        (st = take(&b.bkt, 4 * Nn)) || (st = take(&b.order, 4 * Nn)) || (st = take(&b.rank, 4 * Nn)) ||
-        (st = take(&b.cnt, 4 * B)) || (st = take(&b.off, 4 * (B + 1))) ||
-        (st = take(&b.wgoff, 4 * (B + 1))) || (st = take(&dtargets, sizeof(ngp_path_target) * Tn)) ||
-        (st = take(&dreal, 4 * Tr)) || (st = take(&dranks, 8 * R)) ||
-        (st = take(&b.values, 8 * Tn * Nn)) || (st = take(&b.partial, 8 * Tn * slices)) ||
-        (st = take(&b.mean, 8 * Tn)) || (st = take(&b.count, 8 * Tn)) ||
-        (st = take(&b.hist, 8 * Tn * m)) || (st = take(&b.prefix, 8 * Tr * R)) ||
-        (st = take(&b.gpre, 8 * Tr * R)) || (st = take(&b.krem, 8 * Tr * R)) ||
-        (st = take(&b.grp, 4 * Tr * R)) || (st = take(&b.ng, 4 * Tr)) ||
-        (st = take(&b.ghist, 4 * Tr * R * 256)) || (st = take(&b.q, 8 * Tr * R)))
-        return st;
+    call.take(&dw, nw).take(&dmu, nmu).take(&b.chol, nsg);
+    if (seeds) call.take(&dseeds, (size_t)S);
+    call.take(&b.info, B).take(&b.bkt, Nn).take(&b.order, Nn).take(&b.rank, Nn).take(&b.cnt, B)
+        .take(&b.off, B + 1).take(&b.wgoff, B + 1).take(&dtargets, Tn).take(&dreal, Tr).take(&dranks, R)
+        .take(&b.values, Tn * Nn).take(&b.partial, Tn * slices).take(&b.mean, Tn).take(&b.count, Tn)
+        .take(&b.hist, Tn * m).take(&b.prefix, Tr * R).take(&b.gpre, Tr * R).take(&b.krem, Tr * R)
+        .take(&b.grp, Tr * R).take(&b.ng, Tr).take(&b.ghist, Tr * R * 256).take(&b.q, Tr * R);
+
     b.w = dw; b.mu = dmu; b.seeds = dseeds; b.targets = dtargets; b.real = dreal; b.ranks = dranks;
 
-    std::vector<int32_t> hinfo(B, 0);
-    std::vector<double> hq(Tr * R, 0.0);
-    hipError_t e = hipMemcpyAsync(dw, w, 8 * nw, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(dmu, mu, 8 * nmu, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(b.chol, sigma, 8 * nsg, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess && seeds) e = hipMemcpyAsync(dseeds, seeds, 8 * (size_t)S, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess)
-        e = hipMemcpyAsync(dtargets, targets, sizeof(ngp_path_target) * Tn, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess && !real.empty())
-        e = hipMemcpyAsync(dreal, real.data(), 4 * real.size(), hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(dranks, ranks.data(), 8 * R, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = launch_path_targets(g, b, *inv, seed, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(mean, b.mean, 8 * Tn, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(count, b.count, 8 * Tn, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(hist, b.hist, 8 * Tn * m, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess && !real.empty())
-        e = hipMemcpyAsync(hq.data(), b.q, 8 * real.size() * R, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess && values) e = hipMemcpyAsync(values, b.values, 8 * Tn * Nn, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(hinfo.data(), b.info, 4 * B, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e == hipSuccess) e = hipGetLastError();
-    if (e != hipSuccess) return (ngp_status)(e > 0 ? e : 999);
+    call.up(dw, w, 8 * nw).up(dmu, mu, 8 * nmu).up(b.chol, sigma, 8 * nsg);
+    if (seeds) call.up(dseeds, seeds, 8 * (size_t)S);
+    call.up(dtargets, targets, sizeof(ngp_path_target) * Tn);
+    if (!real.empty()) call.up(dreal, real.data(), 4 * real.size());
+    call.up(dranks, ranks.data(), 8 * R)
+        .run([&] { return launch_path_targets(g, b, *inv, seed, c->stream); })
+        .down(mean, b.mean, 8 * Tn)
+        .down(count, b.count, 8 * Tn)
+        .down(hist, b.hist, 8 * Tn * m);
+    if (!real.empty()) call.down(hq.data(), b.q, 8 * real.size() * R);
+    if (values) call.down(values, b.values, 8 * Tn * Nn);
+    call.down(hinfo.data(), b.info, 4 * B);
+    if (call.sync()) return call.status();
 
     if (info) std::copy(hinfo.begin(), hinfo.end(), info);
     const double nan = std::nan("");
@@ -4236,8 +4211,9 @@ extern "C" ngp_status ngp_weights_allgather_normalize(ngp_comm *m, int32_t P_tot
     auto first_of = [&](int r) { int32_t v = 0; (void)ngp_shard(P_total, m->world, r, &v, nullptr); return (int)v; };
     const int mine = rows_of(m->rank), pmax = rows_of(0);
     ngp_ctx *c = m->ctx;
-    std::lock_guard<std::mutex> lk(c->mu);
-    HIPCHK(hipSetDevice(c->device));
+    std::vector<double> h_all;
+    DevCall call(c);   // for the lock, the device and the copies: the buffers are the communicator's
+    if (call.status()) return call.status();
     hipStream_t s = c->stream;
     // ragged shards: every rank sends pmax rows (its own, then padding).  The buffers stay with the
     // communicator; every rank sees the same (P_total, D), so they grow on all ranks in the same
@@ -4259,17 +4235,15 @@ extern "C" ngp_status ngp_weights_allgather_normalize(ngp_comm *m, int32_t P_tot
         m->cap = cnt;
     }
     void *d_send = m->d_send, *d_recv = m->d_recv;
-    std::vector<double> h_all(cnt * (size_t)m->world);
-    hipError_t e = hipMemsetAsync(d_send, 0, 8 * cnt, s);
-    if (e == hipSuccess)
-        e = hipMemcpyAsync(d_send, logw_local, 8 * (size_t)mine * D, hipMemcpyHostToDevice, s);
+    h_all.resize(cnt * (size_t)m->world);
     int rc = 0;
-    if (e == hipSuccess) rc = rccl().AllGather(d_send, d_recv, cnt, RCCL_FLOAT64, m->comm, s);
-    if (e == hipSuccess && rc == 0)
-        e = hipMemcpyAsync(h_all.data(), d_recv, 8 * h_all.size(), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess && rc == 0) e = hipStreamSynchronize(s);
+    call.run([&] { return hipMemsetAsync(d_send, 0, 8 * cnt, s); })
+        .up(d_send, logw_local, 8 * (size_t)mine * D)
+        .run([&] { rc = rccl().AllGather(d_send, d_recv, cnt, RCCL_FLOAT64, m->comm, s); });
+    if (rc == 0) call.down(h_all.data(), d_recv, 8 * h_all.size());
+    const ngp_status gathered = call.sync();
     if (rc != 0) return NGP_ERR_UNAVAILABLE;
-    if (e != hipSuccess) return (ngp_status)e;
+    if (gathered) return gathered;
     // compact the padded shards to [P_total x D], then the columns as ngp_weights_normalize_cols
     std::vector<double> wn((size_t)P_total * D);
     const ngp_status st = ngp_weights_unpad_normalize(P_total, m->world, D, h_all.data(), wn.data(), ess, log_norm);
@@ -4285,20 +4259,21 @@ extern "C" ngp_status ngp_weights_allgather_normalize(ngp_comm *m, int32_t P_tot
 // ---------------------------------------------------------------------------------------
 extern "C" ngp_status ngp_microbench_mfma_f64(ngp_ctx *c, int32_t iters, double *tflops) {
     if (!c || !tflops || iters <= 0) return NGP_ERR_ARG;
-    std::lock_guard<std::mutex> lk(c->mu);
-    HIPCHK(hipSetDevice(c->device));
+    DevCall call(c);
     iters = (iters + 3) / 4 * 4;
     const int blocks = 256 * 4;  // 4 workgroups of 4 waves per CU
-    void *out = nullptr;
-    ngp_status st = c->alloc(&out, sizeof(double) * (size_t)blocks * 256);
-    if (st) return st;
-    struct Rel { ngp_ctx *c; void *p; ~Rel() { c->release(p); } } rel{c, out};
+    double *out = nullptr;
+    call.take(&out, (size_t)blocks * 256);
     ScopedEvent a, b;
-    launch_mfma_bench((double *)out, iters, blocks, c->stream);  // warm-up
-    HIPCHK(hipEventRecord(a, c->stream));
-    launch_mfma_bench((double *)out, iters, blocks, c->stream);
-    HIPCHK(hipEventRecord(b, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
+    call.run([&] {
+            launch_mfma_bench(out, iters, blocks, c->stream);  // warm-up
+            return hipEventRecord(a, c->stream);
+        })
+        .run([&] {
+            launch_mfma_bench(out, iters, blocks, c->stream);
+            return hipEventRecord(b, c->stream);
+        });
+    if (call.sync()) return call.status();
     float ms = 0.f;
     HIPCHK(hipEventElapsedTime(&ms, a, b));
     *tflops = (double)blocks * 4.0 * (double)iters * 2048.0 / ((double)ms * 1e-3) * 1e-12;
@@ -4310,24 +4285,24 @@ extern "C" ngp_status ngp_microbench_mfma_f64(ngp_ctx *c, int32_t iters, double 
 extern "C" ngp_status ngp_microbench_mfma_f64_detail(ngp_ctx *c, int32_t iters,
                                                      int32_t blocks_per_cu, double *out) {
     if (!c || !out || iters <= 0 || blocks_per_cu <= 0 || blocks_per_cu > 8) return NGP_ERR_ARG;
-    std::lock_guard<std::mutex> lk(c->mu);
-    HIPCHK(hipSetDevice(c->device));
     iters = (iters + 3) / 4 * 4;
     const int blocks = 256 * blocks_per_cu;
     const int waves = blocks * 4;
-    void *st = nullptr;
-    ngp_status s0 = c->alloc(&st, sizeof(unsigned long long) * 2 * (size_t)waves);
-    if (s0) return s0;
-    struct Rel { ngp_ctx *c; void *p; ~Rel() { c->release(p); } } rel{c, st};
-    ScopedEvent a, b;
-    launch_mfma_bench_detail((unsigned long long *)st, iters, blocks, c->stream);
-    HIPCHK(hipEventRecord(a, c->stream));
-    launch_mfma_bench_detail((unsigned long long *)st, iters, blocks, c->stream);
-    HIPCHK(hipEventRecord(b, c->stream));
     std::vector<unsigned long long> h(2 * (size_t)waves);
-    HIPCHK(hipMemcpyAsync(h.data(), st, sizeof(unsigned long long) * h.size(),
-                          hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
+    DevCall call(c);
+    unsigned long long *stamps = nullptr;
+    call.take(&stamps, 2 * (size_t)waves);
+    ScopedEvent a, b;
+    call.run([&] {
+            launch_mfma_bench_detail(stamps, iters, blocks, c->stream);
+            return hipEventRecord(a, c->stream);
+        })
+        .run([&] {
+            launch_mfma_bench_detail(stamps, iters, blocks, c->stream);
+            return hipEventRecord(b, c->stream);
+        })
+        .down(h.data(), stamps, sizeof(unsigned long long) * h.size());
+    if (call.sync()) return call.status();
     float ms = 0.f;
     HIPCHK(hipEventElapsedTime(&ms, a, b));
     std::vector<double> cyc((size_t)waves), ghz((size_t)waves);
@@ -4347,24 +4322,25 @@ extern "C" ngp_status ngp_microbench_mfma_f64_detail(ngp_ctx *c, int32_t iters,
 extern "C" ngp_status ngp_microbench_hbm(ngp_ctx *c, int64_t bytes, double *write_gbs,
                                          double *copy_gbs) {
     if (!c || bytes < 4096) return NGP_ERR_ARG;
-    std::lock_guard<std::mutex> lk(c->mu);
-    HIPCHK(hipSetDevice(c->device));
+    DevCall call(c);
     const int64_t n = bytes / 16 * 2;
-    void *a = nullptr, *b = nullptr;
-    ngp_status st = c->alloc(&a, (size_t)n * 8);
-    if (st) return st;
-    st = c->alloc(&b, (size_t)n * 8);
-    if (st) { c->release(a); return st; }
-    struct Rel { ngp_ctx *c; void *p, *q; ~Rel() { c->release(p); c->release(q); } } rel{c, a, b};
+    double *a = nullptr, *b = nullptr;
+    call.take(&a, (size_t)n).take(&b, (size_t)n);
     ScopedEvent e0, e1, e2;
-    launch_stream_write((double *)a, n, c->stream);
-    launch_stream_copy((double *)b, (const double *)a, n, c->stream);
-    HIPCHK(hipEventRecord(e0, c->stream));
-    launch_stream_write((double *)a, n, c->stream);
-    HIPCHK(hipEventRecord(e1, c->stream));
-    launch_stream_copy((double *)b, (const double *)a, n, c->stream);
-    HIPCHK(hipEventRecord(e2, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
+    call.run([&] {
+            launch_stream_write(a, n, c->stream);
+            launch_stream_copy(b, a, n, c->stream);
+            return hipEventRecord(e0, c->stream);
+        })
+        .run([&] {
+            launch_stream_write(a, n, c->stream);
+            return hipEventRecord(e1, c->stream);
+        })
+        .run([&] {
+            launch_stream_copy(b, a, n, c->stream);
+            return hipEventRecord(e2, c->stream);
+        });
+    if (call.sync()) return call.status();
     float w = 0.f, cp = 0.f;
     HIPCHK(hipEventElapsedTime(&w, e0, e1));
     HIPCHK(hipEventElapsedTime(&cp, e1, e2));
@@ -4381,24 +4357,14 @@ extern "C" ngp_status ngp_microbench_hbm(ngp_ctx *c, int64_t bytes, double *writ
 extern "C" ngp_status ngp_selftest_mfma_layout(ngp_ctx *c, const double *A, const double *Bm,
                                                double *D) {
     if (!c || !A || !Bm || !D) return NGP_ERR_ARG;
-    std::lock_guard<std::mutex> lk(c->mu);
-    HIPCHK(hipSetDevice(c->device));
-    void *da = nullptr, *db = nullptr, *dd = nullptr;
-    ngp_status st;
-    if ((st = c->alloc(&da, 64 * 8)) || (st = c->alloc(&db, 64 * 8)) ||
-        (st = c->alloc(&dd, 512 * 8))) {
-        c->release(da); c->release(db); c->release(dd);
-        return st;
-    }
-    hipError_t e = hipMemcpyAsync(da, A, 64 * 8, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(db, Bm, 64 * 8, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) {
-        launch_mfma_layout_probe((const double *)da, (const double *)db, (double *)dd, c->stream);
-        e = hipMemcpyAsync(D, dd, 512 * 8, hipMemcpyDeviceToHost, c->stream);
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    c->release(da); c->release(db); c->release(dd);
-    return e == hipSuccess ? NGP_OK : (ngp_status)e;
+    DevCall call(c);
+    double *da = nullptr, *db = nullptr, *dd = nullptr;
+    call.take(&da, 64).take(&db, 64).take(&dd, 512);
+    call.up(da, A, 64 * 8)
+        .up(db, Bm, 64 * 8)
+        .run([&] { launch_mfma_layout_probe(da, db, dd, c->stream); })
+        .down(D, dd, 512 * 8);
+    return call.sync();
 }
 
 // D (32 x 32, row-major) = A (32 x 2) B (2 x 32) through one v_mfma_f32_32x32x2_f32 with the operand
@@ -4406,22 +4372,12 @@ extern "C" ngp_status ngp_selftest_mfma_layout(ngp_ctx *c, const double *A, cons
 extern "C" ngp_status ngp_selftest_mfma_f32_layout(ngp_ctx *c, const float *A, const float *Bm,
                                                    float *D) {
     if (!c || !A || !Bm || !D) return NGP_ERR_ARG;
-    std::lock_guard<std::mutex> lk(c->mu);
-    HIPCHK(hipSetDevice(c->device));
-    void *da = nullptr, *db = nullptr, *dd = nullptr;
-    ngp_status st;
-    if ((st = c->alloc(&da, 64 * 4)) || (st = c->alloc(&db, 64 * 4)) ||
-        (st = c->alloc(&dd, 1024 * 4))) {
-        c->release(da); c->release(db); c->release(dd);
-        return st;
-    }
-    hipError_t e = hipMemcpyAsync(da, A, 64 * 4, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(db, Bm, 64 * 4, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) {
-        launch_mfma_f32_probe((const float *)da, (const float *)db, (float *)dd, c->stream);
-        e = hipMemcpyAsync(D, dd, 1024 * 4, hipMemcpyDeviceToHost, c->stream);
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    c->release(da); c->release(db); c->release(dd);
-    return e == hipSuccess ? NGP_OK : (ngp_status)e;
+    DevCall call(c);
+    float *da = nullptr, *db = nullptr, *dd = nullptr;
+    call.take(&da, 64).take(&db, 64).take(&dd, 1024);
+    call.up(da, A, 64 * 4)
+        .up(db, Bm, 64 * 4)
+        .run([&] { launch_mfma_f32_probe(da, db, dd, c->stream); })
+        .down(D, dd, 1024 * 4);
+    return call.sync();
 }

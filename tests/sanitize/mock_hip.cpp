@@ -174,7 +174,13 @@ hipError_t hipMemcpy(void *d, const void *s, size_t n, int) {
     memcpy(d, s, n);
     return 0;
 }
+// mock_hip_fail_copy_after, mock_hip_syncs; g_syncs_at_fail: the count when the ordered copy failed
+static std::atomic<long> g_copy_fail_in{0}, g_syncs{0}, g_syncs_at_fail{0};
 hipError_t hipMemcpyAsync(void *d, const void *s, size_t n, int k, hipStream_t st) {
+    if (g_copy_fail_in.load() > 0 && g_copy_fail_in.fetch_sub(1) == 1) {   // copies nothing
+        g_syncs_at_fail.store(g_syncs.load());
+        return 1;
+    }
     if (tr().on) {
         char buf[96];
         std::snprintf(buf, sizeof buf, "C k%d %zu s%d", k, n, ordinal(tr().streams, st));
@@ -205,6 +211,7 @@ hipError_t hipStreamDestroy(hipStream_t s) {
 // a "busy device": every synchronisation takes mock_hip_set_sync_delay_us microseconds, so that
 // concurrent callers pile up behind the one that holds the context (combine_stress.cpp)
 hipError_t hipStreamSynchronize(hipStream_t) {
+    ++g_syncs;
     const long us = g_sync_us.load();
     if (us > 0) std::this_thread::sleep_for(std::chrono::microseconds(us));
     return 0;
@@ -325,6 +332,13 @@ const char *mock_hip_trace_digest(long *lines, unsigned long long *hash) {
 void mock_hip_trace_flush(void) { trace_flush(); }
 // allocations above `bytes` fail (0: no limit) — the reserve loops of the library cut their chunks
 void mock_hip_set_alloc_limit(size_t bytes) { g_alloc_limit.store(bytes); }
+// the n-th hipMemcpyAsync from now on returns 1 and copies nothing (0: switched off); returns how
+// many copies the previous order still had to wait for (0: it has failed its copy, or there was none)
+long mock_hip_fail_copy_after(long n) { return g_copy_fail_in.exchange(n > 0 ? n : 0); }
+// hipStreamSynchronize calls so far
+long mock_hip_syncs(void) { return g_syncs.load(); }
+// the same count at the moment the copy ordered by mock_hip_fail_copy_after failed
+long mock_hip_syncs_at_failed_copy(void) { return g_syncs_at_fail.load(); }
 // what hipMemGetInfo reports (2 GiB unless set; memory is only touched where the host layer copies)
 void mock_hip_set_device_bytes(size_t bytes) { g_device_bytes.store(bytes); }
 }

@@ -1,0 +1,197 @@
+// The one-shot device calls of the C-ABI at small fixed shapes: the table that oneshot_trace.cpp
+// records and oneshot_faults.cpp breaks.  A one-shot call takes the context, allocates a few device
+// blocks, copies up, launches, copies down, synchronises and gives the blocks back, all inside one
+// call.  The component queries need a resident factor: `setup` makes it and `teardown` destroys it,
+// outside of what is recorded or broken.
+#pragma once
+#include <cstdint>
+#include <functional>
+#include <string>
+#include <vector>
+
+#include "../../include/ngp.h"
+
+namespace oneshot {
+
+struct Entry {
+    std::string name;
+    std::function<ngp_status(ngp_ctx *)> call;
+    std::function<ngp_status(ngp_ctx *)> setup;   // may be empty
+    std::function<void()> teardown;               // may be empty
+    // the call's first copies that are those of the job it stages: that code reports a failed copy
+    // as NGP_ERR_STATE, every other copy of a one-shot call as the HIP code
+    long job_copies = 0;
+};
+
+// ---- ngp_cov_batch: B = 3 mixed trees, n1 = 5, n2 = 4 -------------------------------------------
+struct Cov {
+    int32_t ops0[1] = {NGP_OP_SQEXP}, ops1[3] = {NGP_OP_LINEAR, NGP_OP_SQEXP, NGP_OP_TIMES},
+            ops2[5] = {NGP_OP_SQEXP, NGP_OP_PERIODIC, NGP_OP_PLUS, NGP_OP_LINEAR, NGP_OP_TIMES};
+    double par0[2] = {0.3, 0.8}, par1[5] = {0.5, 0.1, 0.5, 0.2, 0.7},
+           par2[8] = {0.4, 0.6, 0.25, 0.2, 0.4, 0.5, 0.1, 0.5};
+    ngp_kernel ks[3];
+    double t1[5] = {0.0, 0.125, 0.25, 0.5, 0.75}, t2[4] = {0.0625, 0.25, 0.875, 1.0}, out[3 * 5 * 4];
+    Cov() {
+        ks[0] = {1, 2, ops0, par0, 0.05};
+        ks[1] = {3, 5, ops1, par1, 0.02};
+        ks[2] = {5, 8, ops2, par2, 0.1};
+    }
+};
+
+// ---- the sampler and the trajectory targets: P = 3, S = 2, m = 5, draws = 8 ---------------------
+struct Paths {
+    static constexpr int P = 3, S = 2, m = 5, draws = 8, T = 3, Q = 3;
+    std::vector<double> w, mu, sigma, sigma_indep, out, q, mean, values;
+    std::vector<int32_t> comp, info;
+    std::vector<int64_t> count, hist;
+    uint64_t seeds[S] = {7u, 9u};
+    // one target that has quantiles, the first date of the maximum, an exceedance
+    ngp_path_target tg[T] = {{NGP_TARGET_SUM, 0, m - 1, 0.0}, {NGP_TARGET_ARGMAX, 1, 3, 0.0},
+                             {NGP_TARGET_EXCEED, 0, 2, 1.5}};
+    double probs[Q] = {0.45, 0.5, 0.9};   // N = 16 paths: ranks 8, 8, 15
+    ngp_inv_transform inv = {NGP_INV_BOXCOX, -0.3, 0.25, 1.0e4};
+    Paths() {
+        w.assign((size_t)S * P, 1.0 / P);
+        mu.assign((size_t)P * S * m, 0.5);
+        auto diag = [&](std::vector<double> &sg, size_t mats) {
+            sg.assign(mats * m * m, 0.0);
+            for (size_t k = 0; k < mats; ++k)
+                for (int j = 0; j < m; ++j) sg[(k * m + j) * m + j] = 0.04 + 0.01 * (double)k;
+        };
+        diag(sigma, P);
+        diag(sigma_indep, (size_t)S * P);
+        out.assign((size_t)S * draws * m, 0.0);
+        comp.assign((size_t)S * draws, 0);
+        info.assign((size_t)S * P, 0);
+        q.assign((size_t)T * Q, 0.0);
+        mean.assign(T, 0.0);
+        count.assign(T, 0);
+        hist.assign((size_t)T * m, 0);
+        values.assign((size_t)T * S * draws, 0.0);
+    }
+    ngp_status sample(ngp_ctx *c, bool extras) {
+        return ngp_mixture_sample(c, P, S, m, w.data(), mu.data(), sigma.data(), draws, 11u, out.data(),
+                                  extras ? comp.data() : nullptr, extras ? info.data() : nullptr);
+    }
+    ngp_status sample_indep(ngp_ctx *c, bool extras) {
+        return ngp_mixture_sample_indep(c, P, S, m, w.data(), mu.data(), sigma_indep.data(), draws, seeds,
+                                        out.data(), extras ? comp.data() : nullptr,
+                                        extras ? info.data() : nullptr);
+    }
+    ngp_status targets(ngp_ctx *c, bool with_values) {
+        return ngp_mixture_path_targets(c, P, S, m, w.data(), mu.data(), sigma.data(), draws, 11u, &inv, T, tg,
+                                        Q, probs, q.data(), mean.data(), count.data(), hist.data(),
+                                        with_values ? values.data() : nullptr, info.data());
+    }
+    ngp_status targets_indep(ngp_ctx *c, bool with_values) {
+        return ngp_mixture_path_targets_indep(c, P, S, m, w.data(), mu.data(), sigma_indep.data(), draws,
+                                              seeds, &inv, T, tg, Q, probs, q.data(), mean.data(),
+                                              count.data(), hist.data(),
+                                              with_values ? values.data() : nullptr, info.data());
+    }
+};
+
+// ---- the summaries: C = 5 with one zero weight, m = 7, K = Q = 3, one date with a bad component --
+struct Mix {
+    static constexpr int C = 5, m = 7, K = 3;
+    double w[C] = {0.3, 0.0, 0.2, 0.4, 0.1}, mu[C * m], var[C * m], x[m * K], probs[K] = {0.1, 0.5, 0.9},
+           y[m], res[m * K], mean[m], err[m];
+    int32_t info[m];
+    ngp_inv_transform ident = {NGP_INV_IDENTITY, 0.0, 0.0, 0.0}, boxcox = {NGP_INV_BOXCOX, 0.5, 0.25, 1.0e4};
+    Mix() {
+        for (int c = 0; c < C; ++c)
+            for (int j = 0; j < m; ++j) {
+                mu[c * m + j] = 1.0 + 0.25 * c + 0.125 * j;
+                var[c * m + j] = 0.04 + 0.01 * ((c + j) % 3);
+            }
+        var[2 * m + 4] = -1.0;             // component 2 (positive weight) is bad on date 4
+        for (int j = 0; j < m; ++j) {
+            y[j] = 1.5 + 0.125 * j;
+            for (int k = 0; k < K; ++k) x[j * K + k] = 1.0 + 0.5 * k + 0.125 * j;
+        }
+    }
+    ngp_status cdf(ngp_ctx *c) { return ngp_mixture_cdf(c, C, m, w, mu, var, K, x, res, info); }
+    ngp_status quantiles(ngp_ctx *c) { return ngp_mixture_quantiles(c, C, m, w, mu, var, K, probs, res, info); }
+    ngp_status crps(ngp_ctx *c) { return ngp_mixture_crps(c, C, m, w, mu, var, y, res, info); }
+    ngp_status mapped(ngp_ctx *c, bool log_scale) {
+        return ngp_mixture_crps_mapped(c, C, m, w, mu, var, log_scale ? &boxcox : &ident,
+                                       log_scale ? NGP_SCORE_LOG : NGP_SCORE_NATURAL, log_scale ? 0.5 : 0.0, y,
+                                       0.0, res, mean, err, info);
+    }
+};
+
+// ---- the component queries: a resident factor of P = 2, n = 70; d = 0 and d = 2 -----------------
+struct Comp {
+    static constexpr int P = 2, n = 70, m = 3, d = 2, D = 2;
+    int32_t ops0[3] = {NGP_OP_SQEXP, NGP_OP_PERIODIC, NGP_OP_PLUS}, ops1[3] = {NGP_OP_LINEAR, NGP_OP_SQEXP, NGP_OP_TIMES};
+    double par0[5] = {0.3, 0.8, 0.4, 0.25, 0.5}, par1[5] = {0.5, 0.1, 0.5, 0.2, 0.7};
+    ngp_kernel ks[P], comps[3];
+    int32_t counts[P] = {2, 1};
+    double t[n], y[n], t_add[d], y_add[D * d], t_new[m];
+    // 3 components in all; sigma: 2 m x 2 m and m x m
+    double mu[3 * D * m], sigma[(2 * m) * (2 * m) + m * m], var[3 * m], lf[P * D];
+    int32_t info[P];
+    ngp_factor *f = nullptr;
+    Comp() {
+        ks[0] = {3, 5, ops0, par0, 0.05};
+        ks[1] = {3, 5, ops1, par1, 0.02};
+        comps[0] = {1, 2, ops0, par0, 0.0};           // SqExp | Periodic of the first tree
+        comps[1] = {1, 3, ops0 + 1, par0 + 2, 0.0};
+        comps[2] = ks[1];                             // the second tree is one component
+        for (int i = 0; i < n; ++i) { t[i] = i / 128.0; y[i] = ((i * 37) % 11) / 11.0 - 0.5; }
+        for (int i = 0; i < d; ++i) t_add[i] = (n + i) / 128.0;
+        for (int i = 0; i < D * d; ++i) y_add[i] = 0.1 * (i % 3);
+        for (int i = 0; i < m; ++i) t_new[i] = (n + d + i) / 128.0;
+    }
+    ngp_status create(ngp_ctx *c) { return ngp_factor_create(c, P, ks, n, t, y, 0, &f); }
+    void destroy() { ngp_factor_destroy(f); f = nullptr; }
+    ngp_status query(bool nowcast) {
+        if (!nowcast) return ngp_factor_components(f, counts, comps, m, t_new, mu, sigma, var, info);
+        return ngp_factor_components_nowcast(f, d, t_add, D, y_add, counts, comps, m, t_new, lf, mu, sigma, var,
+                                             info);
+    }
+};
+
+struct Probes {
+    double A[64], B[64], D[512], r[4];
+    float Af[64], Bf[64], Df[1024];
+    Probes() {
+        for (int i = 0; i < 64; ++i) { A[i] = 1.0 + i; B[i] = 0.5 - i; Af[i] = (float)A[i]; Bf[i] = (float)B[i]; }
+    }
+};
+
+inline std::vector<Entry> table() {
+    static Cov cov;
+    static Paths pa;
+    static Mix mx;
+    static Comp cq;
+    static Probes pr;
+    auto make = [](ngp_ctx *c) { return cq.create(c); };
+    auto drop = [] { cq.destroy(); };
+    return {
+        {"ngp_cov_batch", [](ngp_ctx *c) { return ngp_cov_batch(c, 3, cov.ks, 5, cov.t1, 4, cov.t2, 1, cov.out); }},
+        {"ngp_mixture_sample comp info", [](ngp_ctx *c) { return pa.sample(c, true); }},
+        {"ngp_mixture_sample", [](ngp_ctx *c) { return pa.sample(c, false); }},
+        {"ngp_mixture_sample_indep comp info", [](ngp_ctx *c) { return pa.sample_indep(c, true); }},
+        {"ngp_mixture_sample_indep", [](ngp_ctx *c) { return pa.sample_indep(c, false); }},
+        {"ngp_mixture_cdf", [](ngp_ctx *c) { return mx.cdf(c); }},
+        {"ngp_mixture_quantiles", [](ngp_ctx *c) { return mx.quantiles(c); }},
+        {"ngp_mixture_crps", [](ngp_ctx *c) { return mx.crps(c); }},
+        {"ngp_mixture_crps_mapped natural identity", [](ngp_ctx *c) { return mx.mapped(c, false); }},
+        {"ngp_mixture_crps_mapped log boxcox", [](ngp_ctx *c) { return mx.mapped(c, true); }},
+        {"ngp_mixture_path_targets values", [](ngp_ctx *c) { return pa.targets(c, true); }},
+        {"ngp_mixture_path_targets", [](ngp_ctx *c) { return pa.targets(c, false); }},
+        {"ngp_mixture_path_targets_indep values", [](ngp_ctx *c) { return pa.targets_indep(c, true); }},
+        {"ngp_mixture_path_targets_indep", [](ngp_ctx *c) { return pa.targets_indep(c, false); }},
+        {"ngp_factor_components", [](ngp_ctx *) { return cq.query(false); }, make, drop, 1},
+        {"ngp_factor_components_nowcast", [](ngp_ctx *) { return cq.query(true); }, make, drop, 1},
+        {"ngp_selftest_mfma_layout", [](ngp_ctx *c) { return ngp_selftest_mfma_layout(c, pr.A, pr.B, pr.D); }},
+        {"ngp_selftest_mfma_f32_layout", [](ngp_ctx *c) { return ngp_selftest_mfma_f32_layout(c, pr.Af, pr.Bf, pr.Df); }},
+        {"ngp_microbench_mfma_f64", [](ngp_ctx *c) { return ngp_microbench_mfma_f64(c, 1, pr.r); }},
+        {"ngp_microbench_mfma_f64_detail", [](ngp_ctx *c) { return ngp_microbench_mfma_f64_detail(c, 1, 1, pr.r); }},
+        {"ngp_microbench_mixture_pairs", [](ngp_ctx *c) { return ngp_microbench_mixture_pairs(c, 1, pr.r); }},
+        {"ngp_microbench_hbm", [](ngp_ctx *c) { return ngp_microbench_hbm(c, 4096, pr.r, pr.r + 1); }},
+    };
+}
+
+}  // namespace oneshot
