@@ -504,12 +504,59 @@ struct WsPlan {
     }
 };
 
-// A one-shot call on a context: the execution lock, the device, the blocks the call takes from the
-// context's allocator and the first error of its copies and launches.  After an error every further
-// step is skipped, so a call is written straight down and asks once, at sync(), how it went.
-// Whatever a call has queued may read host memory of its frame and writes blocks that go back to
-// the cache when it ends: sync() waits for the stream also after an error, and a call that leaves
-// with work queued is synchronised by the destructor before its blocks are released.
+struct EventTimer {  // HIP events on the launch stream, resolved after the job's final sync
+    struct Rec { int cls; hipEvent_t a, b; double flops, bytes; };
+    std::vector<Rec> recs;
+    bool on;
+    hipStream_t s;
+    EventTimer(bool on_, hipStream_t s_) : on(on_), s(s_) {}
+    ~EventTimer() {   // an error path left before resolve()
+        for (auto &r : recs) {
+            (void)hipEventDestroy(r.a);
+            (void)hipEventDestroy(r.b);
+        }
+    }
+    // `on_stream`: the stream f launches on when it is not the timer's own (diag-ahead tiles)
+    template <class F> void run(int cls, double flops, double bytes, F &&f,
+                                hipStream_t on_stream = nullptr) {
+        if (!on) { f(); return; }
+        hipStream_t es = on_stream ? on_stream : s;
+        Rec r{cls, nullptr, nullptr, flops, bytes};
+        (void)hipEventCreate(&r.a);
+        (void)hipEventCreate(&r.b);
+        (void)hipEventRecord(r.a, es);
+        f();
+        (void)hipEventRecord(r.b, es);
+        recs.push_back(r);
+    }
+    template <class F> void run(const Cost &c, F &&f, hipStream_t on_stream = nullptr) {
+        run(c.cls, c.flops, c.bytes, std::forward<F>(f), on_stream);
+    }
+    void resolve(ngp_profile &p) {
+        for (auto &r : recs) {
+            float ms = 0.f;
+            if (hipEventElapsedTime(&ms, r.a, r.b) == hipSuccess) {
+                p.ms[r.cls] += ms;
+                p.launches[r.cls] += 1;
+                p.flops[r.cls] += r.flops;
+                p.bytes[r.cls] += r.bytes;
+            }
+            (void)hipEventDestroy(r.a);
+            (void)hipEventDestroy(r.b);
+        }
+        recs.clear();
+    }
+};
+
+// A call or a staged run on a context: the execution lock, the device, the timers of its launches,
+// the blocks it takes from the context's allocator and the first error of its copies, memsets and
+// launches.  After an error every further step is skipped, so a run is written straight down and asks
+// once, at sync(), how it went.  Whatever it has queued may read and write host memory of its frame,
+// of its job and of the caller, and blocks that go back to the cache when it ends: sync() waits for
+// every stream the run used also after an error, asks the runtime for its last error once and books
+// the timers into the profile; a scope that is left with work queued is synchronised by the
+// destructor before its blocks are released.  Host memory that a queued copy targets is declared
+// before the scope (or lives in the job).
 class DevCall {
     static constexpr int MAX_BLOCKS = 32;   // the trajectory targets take 27; nothing here touches the heap
     ngp_ctx *c;
@@ -517,24 +564,41 @@ class DevCall {
     void *blocks[MAX_BLOCKS];
     int n_blocks = 0;
     ngp_status st = NGP_OK;
-    bool queued = false;
-    DevCall &copy(void *dst, const void *src, size_t bytes, hipMemcpyKind kind) {
-        return run([&] { return hipMemcpyAsync(dst, src, bytes, kind, c->stream); });
+    bool queued = false, lane1 = false;
+    EventTimer tm1;   // launches on lane 1 (second_lane)
+    DevCall &copy(void *dst, const void *src, size_t bytes, hipMemcpyKind kind, hipStream_t s) {
+        return run([&] { return hipMemcpyAsync(dst, src, bytes, kind, s ? s : c->stream); });
     }
 public:
-    explicit DevCall(ngp_ctx *ctx) : c(ctx), lk(ctx->mu) { st = hip_status(hipSetDevice(c->device)); }
+    EventTimer tm;    // launches on the context's stream
+    explicit DevCall(ngp_ctx *ctx) : c(ctx), lk(ctx->mu), tm1(false, nullptr), tm(ctx->profiling, ctx->stream) {
+        st = hip_status(hipSetDevice(c->device));
+    }
     // an inner scope of a call in flight (the rounds of a loop): same lock, blocks of its own
-    explicit DevCall(DevCall &outer) : c(outer.c), st(outer.st) {}
+    explicit DevCall(DevCall &outer) : c(outer.c), st(outer.st), tm1(false, nullptr), tm(false, outer.c->stream) {}
     DevCall(const DevCall &) = delete;
     ~DevCall() {   // the lock is held here: unlocked() is the only place that drops it
         (void)sync();
         for (int i = 0; i < n_blocks; ++i) c->release(blocks[i]);
     }
     ngp_status status() const { return st; }
+    DevCall &fail(ngp_status s) {   // an error of the host's own (no room): the steps after it are skipped
+        if (!st) st = s;
+        return *this;
+    }
     template <class T> DevCall &take(T **p, size_t count) {
         void *q = nullptr;
         if (!st && n_blocks == MAX_BLOCKS) st = NGP_ERR_TOO_LARGE;
         if (!st && !(st = c->alloc(&q, sizeof(T) * count))) blocks[n_blocks++] = q;
+        *p = static_cast<T *>(q);
+        return *this;
+    }
+    // a block that outlives the call (a job's arena, a resident factor): *p is set when there is one, and
+    // whoever owns *p releases it (`owned`: the list a job releases)
+    template <class T> DevCall &keep(T **p, size_t count, std::vector<void *> *owned = nullptr) {
+        void *q = nullptr;
+        if (st || (st = c->alloc(&q, sizeof(T) * count))) return *this;
+        if (owned) owned->push_back(q);
         *p = static_cast<T *>(q);
         return *this;
     }
@@ -547,8 +611,17 @@ public:
         lk.lock();
         return *this;
     }
-    DevCall &up(void *dev, const void *host, size_t bytes) { return copy(dev, host, bytes, hipMemcpyHostToDevice); }
-    DevCall &down(void *host, const void *dev, size_t bytes) { return copy(host, dev, bytes, hipMemcpyDeviceToHost); }
+    // s: the lane's stream when it is not the context's
+    DevCall &up(void *dev, const void *host, size_t bytes, hipStream_t s = nullptr) {
+        return copy(dev, host, bytes, hipMemcpyHostToDevice, s);
+    }
+    DevCall &down(void *host, const void *dev, size_t bytes, hipStream_t s = nullptr) {
+        return copy(host, dev, bytes, hipMemcpyDeviceToHost, s);
+    }
+    DevCall &move(void *dst, const void *src, size_t bytes) { return copy(dst, src, bytes, hipMemcpyDeviceToDevice, nullptr); }
+    DevCall &zero(void *dev, size_t bytes, hipStream_t s = nullptr) {
+        return run([&] { return hipMemsetAsync(dev, 0, bytes, s ? s : c->stream); });
+    }
     // launches: void, or the hipError_t of what they asked of the runtime
     template <class F> DevCall &run(F &&launches) {
         if (st) return *this;
@@ -557,13 +630,40 @@ public:
         else st = hip_status(launches());
         return *this;
     }
-    ngp_status sync() {
+    // launches booked by a timer of this scope: t.run(a...) (EventTimer::run)
+    template <class... A> DevCall &timed(EventTimer &t, A &&...a) {
+        return run([&] { t.run(std::forward<A>(a)...); });
+    }
+    // a run on two lanes (grad_pair_run): the timer of lane 1, which sync() then waits for as well
+    EventTimer &second_lane() {
+        lane1 = true;
+        tm1.on = tm.on;
+        tm1.s = c->lane_main[1];
+        return tm1;
+    }
+    // work an earlier call left on the stream (a kept staging copy) is this scope's to wait for
+    DevCall &pending() { queued = true; return *this; }
+    // what this scope queued stays with a job that outlives it, which waits for it before it lets go
+    // of what the work reads and writes (a small job's staging copy: ngp_job_destroy, grad_leaf_destroy)
+    void handed_over() { queued = false; }
+    // a host round trip inside a run: waits for every stream used, does not end the scope
+    ngp_status wait() {
         if (queued) {
             hipError_t e = hipStreamSynchronize(c->stream);
+            if (lane1) {
+                const hipError_t e1 = hipStreamSynchronize(c->lane_main[1]);
+                if (e == hipSuccess) e = e1;
+            }
             if (e == hipSuccess) e = hipGetLastError();
             if (!st) st = hip_status(e);
             queued = false;
         }
+        return st;
+    }
+    ngp_status sync() {
+        (void)wait();
+        tm.resolve(c->prof);
+        tm1.resolve(c->prof);
         return st;
     }
 };
@@ -798,54 +898,18 @@ struct ngp_job {
     // NGP_PREC_MIXED: per item, filled by ngp_job_run
     std::vector<int32_t> refine_steps;
     std::vector<double> refine_delta, frac32;
+    // The one place the outcome of a run reaches the job, after the run's scope has synchronised
+    // (nothing is in flight any more).  A failed run leaves the job as staged-and-never-run with logdet
+    // / info dirty: the next run is an ordinary re-run (it clears them), a fetch is refused.
+    // fetched: the run brought the result region to h_out behind its last kernel
+    void run_ended(ngp_status st, bool fetched) {
+        copy_in_flight = zeroed = false;
+        ran = st == NGP_OK;
+        out_fetched = ran && fetched;
+    }
 };
 
 namespace {
-
-struct EventTimer {  // HIP events on the launch stream, resolved after the job's final sync
-    struct Rec { int cls; hipEvent_t a, b; double flops, bytes; };
-    std::vector<Rec> recs;
-    bool on;
-    hipStream_t s;
-    EventTimer(bool on_, hipStream_t s_) : on(on_), s(s_) {}
-    ~EventTimer() {   // an error path left before resolve()
-        for (auto &r : recs) {
-            (void)hipEventDestroy(r.a);
-            (void)hipEventDestroy(r.b);
-        }
-    }
-    // `on_stream`: the stream f launches on when it is not the timer's own (diag-ahead tiles)
-    template <class F> void run(int cls, double flops, double bytes, F &&f,
-                                hipStream_t on_stream = nullptr) {
-        if (!on) { f(); return; }
-        hipStream_t es = on_stream ? on_stream : s;
-        Rec r{cls, nullptr, nullptr, flops, bytes};
-        (void)hipEventCreate(&r.a);
-        (void)hipEventCreate(&r.b);
-        (void)hipEventRecord(r.a, es);
-        f();
-        (void)hipEventRecord(r.b, es);
-        recs.push_back(r);
-    }
-    template <class F> void run(const Cost &c, F &&f, hipStream_t on_stream = nullptr) {
-        run(c.cls, c.flops, c.bytes, std::forward<F>(f), on_stream);
-    }
-    void resolve(ngp_profile &p) {
-        for (auto &r : recs) {
-            float ms = 0.f;
-            if (hipEventElapsedTime(&ms, r.a, r.b) == hipSuccess) {
-                p.ms[r.cls] += ms;
-                p.launches[r.cls] += 1;
-                p.flops[r.cls] += r.flops;
-                p.bytes[r.cls] += r.bytes;
-            }
-            (void)hipEventDestroy(r.a);
-            (void)hipEventDestroy(r.b);
-        }
-        recs.clear();
-    }
-};
-
 
 // The left-looking factorisation of one chunk (every item's block columns in lock step): which step
 // runs in which form is ngp_plan.h's (col_step, small_job, two_lane, splitk_eligible, ahead_early),
@@ -957,12 +1021,21 @@ void factor_chunk_lanes(const Lane &ln, const JobGeom &g, const ChunkPtrs &p0, i
     }
 }
 
-template <class T> ngp_status job_alloc(ngp_job *j, T **p, size_t count) {
-    void *v = nullptr;
-    ngp_status st = j->ctx->alloc(&v, count * sizeof(T));
-    if (st) return st;
-    j->owned.push_back(v);
-    *p = (T *)v;
+// The one copy that carries a staged job's inputs up (bytes of h_in to io); a failure is
+// NGP_ERR_STATE.  A small staging buffer stays with the job — no wait here: the run is queued right
+// behind the copy, and the job's destroy waits for it if no run did; a large one is given back once
+// the copy has left it.
+ngp_status stage_up(DevCall &call, hipStream_t s, void *io, PinVec<unsigned char> &h_in, size_t bytes) {
+    call.run([&] {
+        if (hipMemcpyAsync(io, h_in.data(), bytes, hipMemcpyHostToDevice, s) != hipSuccess) call.fail(NGP_ERR_STATE);
+    });
+    if (call.status()) return call.status();
+    if (bytes <= STAGE_KEEP_BYTES) {
+        call.handed_over();
+        return NGP_OK;
+    }
+    if (call.wait()) return NGP_ERR_STATE;
+    PinVec<unsigned char>().swap(h_in);
     return NGP_OK;
 }
 
@@ -1039,23 +1112,18 @@ ngp_status stage_general(ngp_ctx *c, int P, const ngp_kernel *kernels, int n, co
         }
     }
 
-    std::lock_guard<std::mutex> lk(c->mu);
-    HIPCHK(hipSetDevice(c->device));
+    // (the job before the scope: on a failure the scope ends, synchronised, before the job is destroyed)
+    std::unique_ptr<ngp_job, void (*)(ngp_job *)> job(new (std::nothrow) ngp_job(), ngp_job_destroy);
+    ngp_job *j = job.get();
+    if (!j) return NGP_ERR_TOO_LARGE;
+    j->ctx = c;
+    DevCall call(c);
     g.invariant = c->invariant ? 1 : 0;
     g.short_series = c->short_series ? 1 : 0;
     if (stores_structured(g, P, c->toeplitz, c->spec.precision)) g.toep = toep_stride;
-    ngp_job *j = new (std::nothrow) ngp_job();
-    if (!j) return NGP_ERR_TOO_LARGE;
-    j->ctx = c;
     j->g = g;
     j->n = n;
     j->spec = c->spec;
-    ngp_status st = NGP_OK;
-    auto fail = [&](ngp_status s) {
-        for (void *p : j->owned) c->release(p);
-        delete j;
-        return s;
-    };
     const int ny = g.y_shared ? 1 : P;
     if (g.lattice && g.n0 > 0) j->fill.sort_items(hp.data(), P);
     // ONE device arena for everything that crosses the bus, inputs first, outputs last:
@@ -1103,7 +1171,12 @@ ngp_status stage_general(ngp_ctx *c, int P, const ngp_kernel *kernels, int n, co
         j->fill.copy_to(h);
     }
     unsigned char *io = nullptr;
-    if ((st = job_alloc(j, &io, off))) return fail(st);
+    j->work_stride = (int64_t)g.da * g.da + (int64_t)m * g.da + g.da + 8;
+    call.keep(&io, off, &j->owned)
+        .keep(&j->G, (size_t)P * g.naux * g.naux, &j->owned)
+        .keep(&j->work, (size_t)P * j->work_stride, &j->owned)
+        .keep(&j->zbuf, (size_t)std::max((int64_t)P * D * g.da, (int64_t)1), &j->owned);
+    if (call.status()) return call.status();   // nothing is queued yet
     j->progs = (DevProgram *)(io + o_progs);
     j->t0 = (double *)(io + o_t0);
     j->taux = (double *)(io + o_taux);
@@ -1125,24 +1198,11 @@ ngp_status stage_general(ngp_ctx *c, int P, const ngp_kernel *kernels, int n, co
     j->out_off[3] = o_mu - o_info;
     j->out_off[4] = o_sigma - o_info;
     j->out_bytes = off - o_info;
-    if ((st = job_alloc(j, &j->G, (size_t)P * g.naux * g.naux))) return fail(st);
-    j->work_stride = (int64_t)g.da * g.da + (int64_t)m * g.da + g.da + 8;
-    if ((st = job_alloc(j, &j->work, (size_t)P * j->work_stride))) return fail(st);
-    if ((st = job_alloc(j, &j->zbuf, (size_t)std::max((int64_t)P * D * g.da, (int64_t)1))))
-        return fail(st);
-    hipStream_t s = c->stream;
-    if (hipMemcpyAsync(io, j->h_in.data(), in_bytes, hipMemcpyHostToDevice, s) != hipSuccess)
-        return fail(NGP_ERR_STATE);
+    const ngp_status st = stage_up(call, c->stream, io, j->h_in, in_bytes);
+    if (st) return st;
     j->zeroed = true;
-    j->copy_in_flight = true;
-    // a small staging buffer stays with the job (no wait here: the run is queued right behind the
-    // copy); a large one is given back once the copy has left it
-    if (in_bytes > STAGE_KEEP_BYTES) {
-        if (hipStreamSynchronize(s) != hipSuccess) return fail(NGP_ERR_STATE);
-        PinVec<unsigned char>().swap(j->h_in);
-        j->copy_in_flight = false;
-    }
-    *out = j;
+    j->copy_in_flight = !j->h_in.empty();
+    *out = job.release();
     return NGP_OK;
 }
 
@@ -1189,15 +1249,22 @@ struct RefineBufs {
     int32_t *items = nullptr;                          // [Bc] items a later step still works on
 };
 
+// What the refinement of a chunk keeps on the host.  Queued copies read and write these: the owner
+// declares them before the run's scope.
+struct RefineHost {
+    std::vector<double> dprev, dboth;
+    std::vector<int32_t> active, still;
+};
+
 // G <- X K^-1 X' refined against the fp64 covariance (see kapply_kernel).  On entry the aux rows
 // of the slab hold W = X L^-T and p.dinv every block inverse M_j ([nb0][mstep]).  steps / delta
-// (host, [bc]) receive the per-item step count and last correction; returns the items that did
-// not reach `tol` within `max_steps` in not_refined.
-ngp_status refine_chunk(ngp_ctx *c, const JobGeom &g, const ChunkPtrs &p, const RefineBufs &rb,
-                        double *Gchunk, int bc, size_t mstep, const ngp_spec &spec,
-                        const DevSpec &sp, EventTimer &tm, int32_t *steps, double *delta_out,
-                        std::vector<int> *not_refined) {
-    hipStream_t s = c->stream;
+// (host, [bc]) receive the per-item step count and last correction; the items that did not reach
+// `tol` within `max_steps` go to not_refined.  Every step reads its corrections back: one wait() of
+// the run's scope each, and nothing of it is in flight when this returns.
+void refine_chunk(DevCall &call, hipStream_t s, const JobGeom &g, const ChunkPtrs &p, const RefineBufs &rb,
+                  double *Gchunk, int bc, size_t mstep, const ngp_spec &spec, const DevSpec &sp,
+                  RefineHost &h, int32_t *steps, double *delta_out, std::vector<int> *not_refined) {
+    EventTimer &tm = call.tm;
     const double naux = (double)g.naux, n0 = (double)g.n0;
     ChunkPtrs pf = p;          // the sweeps are fp64: no shadow rows, no tile maxima
     pf.L32 = nullptr;
@@ -1207,64 +1274,79 @@ ngp_status refine_chunk(ngp_ctx *c, const JobGeom &g, const ChunkPtrs &p, const 
     int na = bc;               // items still being refined (pf.items: their indices; null = all)
     auto backward = [&](int accumulate) {
         for (int cc = g.nb0 - 1; cc >= 0; --cc)
-            tm.run(10, na * naux * 2.0 * NB * (double)(cc + 1) * NB,
-                   na * 8.0 * ((double)NB * NB * (cc + 1) + 2.0 * naux * NB * (cc + 1)), [&] {
-                       launch_aux_back(g, pf, p.dinv, mstep, rb.A, accumulate, na, cc, s);
-                   });
+            call.timed(tm, 10, na * naux * 2.0 * NB * (double)(cc + 1) * NB,
+                       na * 8.0 * ((double)NB * NB * (cc + 1) + 2.0 * naux * NB * (cc + 1)), [&] {
+                           launch_aux_back(g, pf, p.dinv, mstep, rb.A, accumulate, na, cc, s);
+                       });
     };
     backward(0);               // A_0 = W L^-1
-    std::vector<double> dprev((size_t)bc, 1.0), dboth(2 * (size_t)bc, 0.0);
-    std::vector<int32_t> active((size_t)bc);
-    for (int i = 0; i < bc; ++i) { steps[i] = 0; delta_out[i] = 0.0; active[(size_t)i] = i; }
+    h.dprev.assign((size_t)bc, 1.0);
+    h.dboth.assign(2 * (size_t)bc, 0.0);
+    h.active.resize((size_t)bc);
+    for (int i = 0; i < bc; ++i) { steps[i] = 0; delta_out[i] = 0.0; h.active[(size_t)i] = i; }
     for (int it = 1;; ++it) {
-        tm.run(10, na * 2.0 * naux * n0 * n0, na * 8.0 * 3.0 * naux * n0,
-               [&] { launch_kapply(g, pf, rb.A, rb.X, rb.R, na, sp, s); });
-        tm.run(10, na * 4.0 * naux * naux * n0, na * 8.0 * 3.0 * naux * n0, [&] {
-            launch_refine_gram(g, rb.A, rb.X, rb.R, rb.S, rb.T, rb.U, Gchunk, rb.delta, na,
-                               pf.items, s);
+        call.timed(tm, 10, na * 2.0 * naux * n0 * n0, na * 8.0 * 3.0 * naux * n0,
+                   [&] { launch_kapply(g, pf, rb.A, rb.X, rb.R, na, sp, s); });
+        call.timed(tm, 10, na * 4.0 * naux * naux * n0, na * 8.0 * 3.0 * naux * n0, [&] {
+            launch_refine_gram(g, rb.A, rb.X, rb.R, rb.S, rb.T, rb.U, Gchunk, rb.delta, na, pf.items, s);
         });
-        HIPCHK(hipMemcpyAsync(dboth.data(), rb.delta, sizeof(double) * 2 * (size_t)bc,
-                              hipMemcpyDeviceToHost, s));
-        HIPCHK(hipStreamSynchronize(s));
-        std::vector<int32_t> still;
-        for (int i : active) {
-            const double d = dboth[2 * (size_t)i];
+        if (call.down(h.dboth.data(), rb.delta, sizeof(double) * 2 * (size_t)bc).wait()) break;
+        h.still.clear();
+        for (int i : h.active) {
+            const double d = h.dboth[2 * (size_t)i];
             // What is left after this step's correction d is about d * rho, rho the contraction
             // of the iteration: measured as d / d_previous from the second step on, and from the
             // residual itself (max_a |R_a| / |X_a|) at the first, whichever is larger.
-            double rho = dboth[2 * (size_t)i + 1];
-            if (it > 1) rho = std::max(rho, d / dprev[(size_t)i]);
+            double rho = h.dboth[2 * (size_t)i + 1];
+            if (it > 1) rho = std::max(rho, d / h.dprev[(size_t)i]);
             const double est = d * std::min(rho, 1.0);
             steps[i] = it;
             delta_out[i] = d;
-            dprev[(size_t)i] = d;
-            if (!(est <= spec.refine_tol)) still.push_back(i);   // NaN stays
+            h.dprev[(size_t)i] = d;
+            if (!(est <= spec.refine_tol)) h.still.push_back(i);   // NaN stays
         }
-        active.swap(still);
-        if (active.empty() || it >= spec.refine_max) break;
-        // the next step only touches the items that are not there yet
-        na = (int)active.size();
-        HIPCHK(hipMemcpy(rb.items, active.data(), 4 * (size_t)na, hipMemcpyHostToDevice));
+        h.active.swap(h.still);
+        if (h.active.empty() || it >= spec.refine_max) break;
+        // the next step only touches the items that are not there yet (h.active is not written again
+        // before the next wait)
+        na = (int)h.active.size();
+        call.up(rb.items, h.active.data(), 4 * (size_t)na);
         pf.items = rb.items;
         // A += (R L^-T) L^-1: R into the aux rows, forward sweep (the resident-factor kernels),
         // backward sweep accumulating into A
-        for (int i : active)
-            HIPCHK(hipMemcpyAsync(p.L + (size_t)i * g.item_stride + (size_t)g.n0 * g.ld,
-                                  rb.R + (size_t)i * g.naux_pad * g.n0,
-                                  (size_t)g.naux_pad * g.n0 * 8, hipMemcpyDeviceToDevice, s));
+        for (int i : h.active)
+            call.move(p.L + (size_t)i * g.item_stride + (size_t)g.n0 * g.ld, rb.R + (size_t)i * g.naux_pad * g.n0,
+                      (size_t)g.naux_pad * g.n0 * 8);
         for (int jj = 0; jj < g.nb0; ++jj) {
             ChunkPtrs pj = pf;
             pj.dinv = p.dinv + (size_t)jj * mstep;
-            tm.run(10, na * naux * (double)NB * NB, na * 8.0 * 3.0 * naux * NB,
-                   [&] { launch_chol_col(g, pj, na, jj, COL_AUX, jj * NB, s); });
-            tm.run(10, na * naux * 2.0 * NB * (double)(g.n0 - (jj + 1) * NB),
-                   na * 8.0 * (g.n0 - (jj + 1) * NB) * (2.0 * naux + NB),
-                   [&] { launch_aux_update(g, pj, na, jj, s); });
+            call.timed(tm, 10, na * naux * (double)NB * NB, na * 8.0 * 3.0 * naux * NB,
+                       [&] { launch_chol_col(g, pj, na, jj, COL_AUX, jj * NB, s); });
+            call.timed(tm, 10, na * naux * 2.0 * NB * (double)(g.n0 - (jj + 1) * NB),
+                       na * 8.0 * (g.n0 - (jj + 1) * NB) * (2.0 * naux + NB),
+                       [&] { launch_aux_update(g, pj, na, jj, s); });
         }
         backward(1);
     }
-    for (int i : active) not_refined->push_back(i);
-    return NGP_OK;
+    if (!call.status()) not_refined->assign(h.active.begin(), h.active.end());
+}
+
+// what a chunk's kernels read of a staged job, from item b0 on; the factor storage and the tables are
+// the caller's (the workspace of a run, a resident factor)
+ChunkPtrs chunk_ptrs_of(const ngp_job &j, int b0, double *L, double *dinv, double *tab, double *sig) {
+    ChunkPtrs p{};
+    p.L = L;
+    p.dinv = dinv;
+    p.progs = j.progs + b0;
+    p.t0 = j.t0;
+    p.taux = j.taux;
+    p.y0 = j.y0 + (j.g.y_shared ? 0 : (int64_t)b0 * j.g.n0);
+    p.logdet = j.logdet + b0;
+    p.info = j.info + b0;
+    p.tab = tab;
+    p.sig = sig;
+    p.qpts = j.qpts;
+    return p;
 }
 
 }  // namespace
@@ -1272,26 +1354,26 @@ ngp_status refine_chunk(ngp_ctx *c, const JobGeom &g, const ChunkPtrs &p, const 
 extern "C" ngp_status ngp_job_run(ngp_job *j) {
     if (!j) return NGP_ERR_ARG;
     ngp_ctx *c = j->ctx;
-    std::lock_guard<std::mutex> lk(c->mu);
-    HIPCHK(hipSetDevice(c->device));
+    // host memory that queued copies of the run write (mixed jobs): before the scope, which ends synchronised
+    std::vector<unsigned> hc;
+    std::vector<int32_t> hi;
+    RefineHost rh;
+    DevCall call(c);
+    EventTimer &tm = call.tm;
     const JobGeom &g = j->g;
     hipStream_t s = c->stream;
     const DevSpec sp = dev_spec(j->spec);
-    EventTimer tm(c->profiling, s);
     // a re-run: the first one finds the zeros the staging copy brought.  (Short jobs: chol_small_kernel
     // writes both outright; whatever the chunk size turns out to be, it is at most the batch.)
-    if (!j->zeroed && !(g.n0 > 0 && small_job(g, g.B) && j->spec.precision != NGP_PREC_MIXED)) {
-        HIPCHK(hipMemsetAsync(j->logdet, 0, sizeof(double) * (size_t)g.B, s));
-        HIPCHK(hipMemsetAsync(j->info, 0, sizeof(int32_t) * (size_t)g.B, s));
-    }
-    j->zeroed = false;
+    if (!j->zeroed && !(g.n0 > 0 && small_job(g, g.B) && j->spec.precision != NGP_PREC_MIXED))
+        call.zero(j->logdet, sizeof(double) * (size_t)g.B).zero(j->info, sizeof(int32_t) * (size_t)g.B);
     const bool mixed = mixed_eligible(g, j->spec.precision);
     const bool refine = mixed && j->spec.refine_max > 0;
     j->refine_steps.assign((size_t)g.B, 0);
     j->refine_delta.assign((size_t)g.B, 0.0);
     j->frac32.assign((size_t)g.B, 0.0);
     // the run's working storage comes from the context's workspace (ngp_ctx::ws_reserve): nothing
-    // to give back on the exit paths, the next call overwrites it
+    // to give back, the next call overwrites it
     void *Lbuf = nullptr, *dinv = nullptr, *tab = nullptr, *sig = nullptr;
     void *L32 = nullptr, *tmx = nullptr, *cnt = nullptr, *order_buf = nullptr, *order_prev = nullptr;
     RefineBufs rb;
@@ -1352,65 +1434,51 @@ extern "C" ngp_status ngp_job_run(ngp_job *j) {
             if (st != NGP_ERR_TOO_LARGE || Bc <= 1) break;
         }
         single_chunk = Bc >= g.B;
-        if (st) return st;
+        call.fail(st);
         const Lane ln = lane_of(c);
-        for (int b0 = 0; b0 < g.B; b0 += Bc) {
+        std::vector<int> bad;
+        for (int b0 = 0; b0 < g.B && !call.status(); b0 += Bc) {
             const int bc = std::min(Bc, g.B - b0);
-            ChunkPtrs p{};
-            p.L = (double *)Lbuf;
-            p.dinv = (double *)dinv;
-            p.progs = j->progs + b0;
-            p.t0 = j->t0;
-            p.taux = j->taux;
-            p.y0 = j->y0 + (g.y_shared ? 0 : (int64_t)b0 * g.n0);
-            p.logdet = j->logdet + b0;
-            p.info = j->info + b0;
-            p.tab = (double *)tab;
-            p.sig = (double *)sig;
-            p.qpts = j->qpts;
+            ChunkPtrs p = chunk_ptrs_of(*j, b0, (double *)Lbuf, (double *)dinv, (double *)tab, (double *)sig);
             if (j->fill_io) j->fill.share_of(j->fill_io, b0, bc, &p);
             if (mixed) {
                 p.L32 = (float *)L32;
                 p.tmax = (float *)tmx;
                 p.mixcnt = (unsigned *)cnt;
                 p.auxX = rb.X;
-                HIPCHK(hipMemsetAsync(cnt, 0, 8 * (size_t)bc, s));
+                call.zero(cnt, 8 * (size_t)bc);
             }
-            if (g.lattice)
-                tm.run(4, 0.0, 0.0, [&] { launch_tables(g, p, bc, sp, s); });
-            tm.run(cost_fill(g, bc, p.n_fill_single), [&] { launch_fill(g, p, bc, sp, s); });
-            if (mixed) HIPCHK(hipMemsetAsync(order_prev, 0, 4 * (size_t)bc, s));
+            if (g.lattice) call.timed(tm, 4, 0.0, 0.0, [&] { launch_tables(g, p, bc, sp, s); });
+            call.timed(tm, cost_fill(g, bc, p.n_fill_single), [&] { launch_fill(g, p, bc, sp, s); });
+            if (mixed) call.zero(order_prev, 4 * (size_t)bc);
             double *Gchunk = j->G + (int64_t)b0 * g.naux * g.naux;
             // short jobs: the one launch of the factorisation leaves G too
             const bool gram_inside = !mixed && mstep == 0 && small_job(g, bc);
             if (gram_inside) p.G = Gchunk;
-            factor_chunk(ln, g, p, bc, tm, mstep, mixed ? &sp : nullptr, (int32_t *)order_buf,
-                         (unsigned *)order_prev);
+            call.run([&] {
+                factor_chunk(ln, g, p, bc, tm, mstep, mixed ? &sp : nullptr, (int32_t *)order_buf,
+                             (unsigned *)order_prev);
+            });
             if (!gram_inside)
-                tm.run(cost_gram(g, bc), [&] { launch_gram(g, (const double *)Lbuf, Gchunk, bc, s); });
-            if (mixed) {
-                std::vector<unsigned> hc(2 * (size_t)bc);
-                HIPCHK(hipMemcpyAsync(hc.data(), cnt, 8 * (size_t)bc, hipMemcpyDeviceToHost, s));
-                std::vector<int> bad;
-                if (refine) {
-                    ngp_status rs = refine_chunk(c, g, p, rb, Gchunk, bc, mstep, j->spec, sp, tm,
-                                                 j->refine_steps.data() + b0,
-                                                 j->refine_delta.data() + b0, &bad);
-                    if (rs) { tm.resolve(c->prof); return rs; }
-                } else {
-                    HIPCHK(hipStreamSynchronize(s));
-                }
-                for (int i = 0; i < bc; ++i) {
-                    const double a = hc[2 * (size_t)i], b = hc[2 * (size_t)i + 1];
-                    j->frac32[(size_t)(b0 + i)] = (a + b) > 0.0 ? a / (a + b) : 0.0;
-                }
-                if (!bad.empty()) {   // keep a pivot failure if the factorisation reported one
-                    std::vector<int32_t> hi((size_t)bc);
-                    HIPCHK(hipMemcpy(hi.data(), p.info, 4 * (size_t)bc, hipMemcpyDeviceToHost));
-                    for (int i : bad)
-                        if (hi[(size_t)i] == 0) hi[(size_t)i] = NGP_INFO_NOT_REFINED;
-                    HIPCHK(hipMemcpy(p.info, hi.data(), 4 * (size_t)bc, hipMemcpyHostToDevice));
-                }
+                call.timed(tm, cost_gram(g, bc), [&] { launch_gram(g, (const double *)Lbuf, Gchunk, bc, s); });
+            if (!mixed) continue;
+            hc.assign(2 * (size_t)bc, 0u);
+            call.down(hc.data(), cnt, 8 * (size_t)bc);
+            bad.clear();
+            if (refine)
+                refine_chunk(call, s, g, p, rb, Gchunk, bc, mstep, j->spec, sp, rh, j->refine_steps.data() + b0,
+                             j->refine_delta.data() + b0, &bad);
+            if (call.wait()) break;
+            for (int i = 0; i < bc; ++i) {
+                const double a = hc[2 * (size_t)i], b = hc[2 * (size_t)i + 1];
+                j->frac32[(size_t)(b0 + i)] = (a + b) > 0.0 ? a / (a + b) : 0.0;
+            }
+            if (!bad.empty()) {   // keep a pivot failure if the factorisation reported one
+                hi.assign((size_t)bc, 0);
+                if (call.down(hi.data(), p.info, 4 * (size_t)bc).wait()) break;
+                for (int i : bad)
+                    if (hi[(size_t)i] == 0) hi[(size_t)i] = NGP_INFO_NOT_REFINED;
+                (void)call.up(p.info, hi.data(), 4 * (size_t)bc).wait();   // hi is the next chunk's too
             }
         }
     }
@@ -1421,23 +1489,18 @@ extern "C" ngp_status ngp_job_run(ngp_job *j) {
         e.sig = (const double *)sig;
         e.qpts = j->qpts;
     }
-    tm.run(3, 0.0, 0.0, [&] { launch_epilogue(g, e, sp, s); });
+    call.timed(tm, 3, 0.0, 0.0, [&] { launch_epilogue(g, e, sp, s); });
     // small results travel behind the last kernel, in the same queue: a fetch after the run's
     // synchronisation would be a second host round trip (25 us of a 24-item call: the copy started
     // that long after the epilogue had ended)
-    j->out_fetched = false;
-    if (j->out_bytes <= FETCH_PACKED_BYTES) {
+    const bool packed = j->out_bytes <= FETCH_PACKED_BYTES;
+    if (packed) {
         j->h_out.resize(j->out_bytes);
-        if (hipMemcpyAsync(j->h_out.data(), j->info, j->out_bytes, hipMemcpyDeviceToHost, s) == hipSuccess)
-            j->out_fetched = true;
+        call.down(j->h_out.data(), j->info, j->out_bytes);
     }
-    hipError_t err = hipStreamSynchronize(s);
-    if (err == hipSuccess) err = hipGetLastError();
-    tm.resolve(c->prof);
-    if (err != hipSuccess) return hip_status(err);
-    j->copy_in_flight = false;
-    j->ran = true;
-    return NGP_OK;
+    const ngp_status st = call.sync();
+    j->run_ended(st, packed);
+    return st;
 }
 
 extern "C" ngp_status ngp_job_mixed_stats(ngp_job *j, int32_t *refine_steps, double *refine_delta,
@@ -1452,57 +1515,45 @@ extern "C" ngp_status ngp_job_mixed_stats(ngp_job *j, int32_t *refine_steps, dou
     return NGP_OK;
 }
 
+// (j->ran: a run has synchronised since the job was staged, so no staging copy is in flight)
 extern "C" ngp_status ngp_job_fetch(ngp_job *j, double *logml_base, double *logml_full, double *mu,
                                     double *sigma, int32_t *info) {
     if (!j) return NGP_ERR_ARG;
     if (!j->ran) return NGP_ERR_STATE;
-    ngp_ctx *c = j->ctx;
-    std::lock_guard<std::mutex> lk(c->mu);
-    HIPCHK(hipSetDevice(c->device));
     const JobGeom &g = j->g;
-    hipStream_t s = c->stream;
-    if (j->out_bytes <= FETCH_PACKED_BYTES) {   // small results: one copy of the whole region
-        if (!j->out_fetched) {                  // (normally ngp_job_run has brought it already)
+    const size_t B = (size_t)g.B;
+    const bool packed = j->out_bytes <= FETCH_PACKED_BYTES;   // small results: one copy of the whole region
+    DevCall call(j->ctx);
+    if (packed) {
+        if (!j->out_fetched) {   // (normally ngp_job_run has brought it already)
             j->h_out.resize(j->out_bytes);
-            HIPCHK(hipMemcpyAsync(j->h_out.data(), j->info, j->out_bytes, hipMemcpyDeviceToHost, s));
-            HIPCHK(hipStreamSynchronize(s));
-            j->copy_in_flight = false;
+            call.down(j->h_out.data(), j->info, j->out_bytes);
         }
-        const unsigned char *h = j->h_out.data();
-        if (info) std::memcpy(info, h + j->out_off[0], 4 * (size_t)g.B);
-        if (logml_base) std::memcpy(logml_base, h + j->out_off[1], 8 * (size_t)g.B);
-        if (logml_full) std::memcpy(logml_full, h + j->out_off[2], 8 * (size_t)g.B * g.D);
-        if (mu && g.m > 0) std::memcpy(mu, h + j->out_off[3], 8 * (size_t)g.B * g.D * g.m);
-        if (sigma && g.m > 0) std::memcpy(sigma, h + j->out_off[4], 8 * (size_t)g.B * g.m * g.m);
-        return NGP_OK;
+    } else {
+        if (logml_base) call.down(logml_base, j->logml_base, 8 * B);
+        if (logml_full) call.down(logml_full, j->logml_full, 8 * B * g.D);
+        if (mu && g.m > 0) call.down(mu, j->mu, 8 * B * g.D * g.m);
+        if (sigma && g.m > 0) call.down(sigma, j->sigma, 8 * B * g.m * g.m);
+        if (info) call.down(info, j->info, 4 * B);
     }
-    if (logml_base)
-        HIPCHK(hipMemcpyAsync(logml_base, j->logml_base, sizeof(double) * (size_t)g.B,
-                              hipMemcpyDeviceToHost, s));
-    if (logml_full)
-        HIPCHK(hipMemcpyAsync(logml_full, j->logml_full, sizeof(double) * (size_t)g.B * g.D,
-                              hipMemcpyDeviceToHost, s));
-    if (mu && g.m > 0)
-        HIPCHK(hipMemcpyAsync(mu, j->mu, sizeof(double) * (size_t)g.B * g.D * g.m,
-                              hipMemcpyDeviceToHost, s));
-    if (sigma && g.m > 0)
-        HIPCHK(hipMemcpyAsync(sigma, j->sigma, sizeof(double) * (size_t)g.B * g.m * g.m,
-                              hipMemcpyDeviceToHost, s));
-    if (info)
-        HIPCHK(hipMemcpyAsync(info, j->info, sizeof(int32_t) * (size_t)g.B, hipMemcpyDeviceToHost,
-                              s));
-    HIPCHK(hipStreamSynchronize(s));
-    j->copy_in_flight = false;
+    const ngp_status st = call.sync();
+    if (st || !packed) return st;
+    const unsigned char *h = j->h_out.data();
+    if (info) std::memcpy(info, h + j->out_off[0], 4 * B);
+    if (logml_base) std::memcpy(logml_base, h + j->out_off[1], 8 * B);
+    if (logml_full) std::memcpy(logml_full, h + j->out_off[2], 8 * B * g.D);
+    if (mu && g.m > 0) std::memcpy(mu, h + j->out_off[3], 8 * B * g.D * g.m);
+    if (sigma && g.m > 0) std::memcpy(sigma, h + j->out_off[4], 8 * B * g.m * g.m);
     return NGP_OK;
 }
 
 extern "C" void ngp_job_destroy(ngp_job *j) {
     if (!j) return;
     {
-        std::lock_guard<std::mutex> lk(j->ctx->mu);
-        // staged but never fetched: the staging copy may still be reading j->h_in
-        if (j->copy_in_flight && hipSetDevice(j->ctx->device) == hipSuccess)
-            (void)hipStreamSynchronize(j->ctx->stream);
+        DevCall call(j->ctx);
+        // staged but never run: the staging copy may still be reading j->h_in
+        if (j->copy_in_flight) call.pending();
+        (void)call.sync();
         for (void *p : j->owned) j->ctx->release(p);
     }
     delete j;
@@ -1612,63 +1663,42 @@ namespace {
 ngp_status factor_run(ngp_factor *f, ngp_job *j, bool create, const CompPtrs *comp = nullptr,
                       double *comp_work = nullptr, int64_t comp_work_stride = 0) {
     ngp_ctx *c = f->ctx;
-    DevCall call(c);   // the lock, the device and the tables; the launches below are the staged job's
-    if (call.status()) return call.status();
+    DevCall call(c);
+    EventTimer &tm = call.tm;
     JobGeom &g = j->g;
     g.item_stride = f->item_stride;
     hipStream_t s = c->stream;
     j->spec = f->spec;
     const DevSpec sp = dev_spec(f->spec);
-    EventTimer tm(c->profiling, s);
     const int P = f->P;
+    const size_t ld_bytes = sizeof(double) * (size_t)P, info_bytes = sizeof(int32_t) * (size_t)P;
     double *tab = nullptr, *sig = nullptr;
     if (g.n0 > 0) {
-        if (g.lattice &&
-            call.take(&tab, (size_t)g.maxstat * g.R * P).take(&sig, (size_t)g.maxcp * g.npts * P).status())
-            return call.status();
-        ChunkPtrs p{};
-        p.L = f->L;
-        p.dinv = f->dinv;
-        p.progs = j->progs;
-        p.t0 = j->t0;
-        p.taux = j->taux;
-        p.y0 = j->y0;
-        p.logdet = j->logdet;
-        p.info = j->info;
-        p.tab = tab;
-        p.sig = sig;
-        p.qpts = j->qpts;
+        if (g.lattice) call.take(&tab, (size_t)g.maxstat * g.R * P).take(&sig, (size_t)g.maxcp * g.npts * P);
+        const ChunkPtrs p = chunk_ptrs_of(*j, 0, f->L, f->dinv, tab, sig);
         const size_t mstep = (size_t)P * NB * NB;
-        if (g.lattice) tm.run(4, 0.0, 0.0, [&] { launch_tables(g, p, P, sp, s); });
+        if (g.lattice) call.timed(tm, 4, 0.0, 0.0, [&] { launch_tables(g, p, P, sp, s); });
         if (create) {
-            HIPCHK(hipMemsetAsync(j->logdet, 0, sizeof(double) * (size_t)P, s));
-            HIPCHK(hipMemsetAsync(j->info, 0, sizeof(int32_t) * (size_t)P, s));
-            tm.run(cost_fill(g, P, 0), [&] { launch_fill(g, p, P, sp, s); });
-            factor_chunk(lane_of(c), g, p, P, tm, mstep);
-            HIPCHK(hipMemcpyAsync(f->logdet, j->logdet, sizeof(double) * (size_t)P,
-                                  hipMemcpyDeviceToDevice, s));
-            HIPCHK(hipMemcpyAsync(f->info, j->info, sizeof(int32_t) * (size_t)P,
-                                  hipMemcpyDeviceToDevice, s));
+            call.zero(j->logdet, ld_bytes).zero(j->info, info_bytes);
+            call.timed(tm, cost_fill(g, P, 0), [&] { launch_fill(g, p, P, sp, s); });
+            call.run([&] { factor_chunk(lane_of(c), g, p, P, tm, mstep); });
+            call.move(f->logdet, j->logdet, ld_bytes).move(f->info, j->info, info_bytes);
         } else {
-            HIPCHK(hipMemcpyAsync(j->logdet, f->logdet, sizeof(double) * (size_t)P,
-                                  hipMemcpyDeviceToDevice, s));
-            HIPCHK(hipMemcpyAsync(j->info, f->info, sizeof(int32_t) * (size_t)P,
-                                  hipMemcpyDeviceToDevice, s));
-            tm.run(cost_fill_aux(g, P), [&] { launch_fill(g, p, P, sp, s, /*aux_only=*/true); });
+            call.move(j->logdet, f->logdet, ld_bytes).move(j->info, f->info, info_bytes);
+            call.timed(tm, cost_fill_aux(g, P), [&] { launch_fill(g, p, P, sp, s, /*aux_only=*/true); });
             if (comp)
-                tm.run(4, 0.0, 8.0 * P * (double)g.m * g.n0, [&] { launch_component_fill(g, p, *comp, P, sp, s); });
+                call.timed(tm, 4, 0.0, 8.0 * P * (double)g.m * g.n0, [&] { launch_component_fill(g, p, *comp, P, sp, s); });
             // right-looking sweep of the aux rows through the resident factor
             for (int jj = 0; jj < g.nb0; ++jj) {
                 ChunkPtrs pj = p;
                 pj.dinv = f->dinv + (size_t)jj * mstep;
-                tm.run(cost_aux_solve(g, P), [&] { launch_chol_col(g, pj, P, jj, COL_AUX, jj * NB, s); });
-                tm.run(cost_aux_update(g, P, jj), [&] { launch_aux_update(g, pj, P, jj, s); });
+                call.timed(tm, cost_aux_solve(g, P), [&] { launch_chol_col(g, pj, P, jj, COL_AUX, jj * NB, s); });
+                call.timed(tm, cost_aux_update(g, P, jj), [&] { launch_aux_update(g, pj, P, jj, s); });
             }
         }
-        tm.run(cost_gram(g, P), [&] { launch_gram(g, f->L, j->G, P, s); });
+        call.timed(tm, cost_gram(g, P), [&] { launch_gram(g, f->L, j->G, P, s); });
     } else {
-        HIPCHK(hipMemsetAsync(j->logdet, 0, sizeof(double) * (size_t)P, s));
-        HIPCHK(hipMemsetAsync(j->info, 0, sizeof(int32_t) * (size_t)P, s));
+        call.zero(j->logdet, ld_bytes).zero(j->info, info_bytes);
     }
     EpiPtrs e = epi_ptrs_of(*j);
     if (g.lattice && g.n0 > 0) {
@@ -1679,16 +1709,13 @@ ngp_status factor_run(ngp_factor *f, ngp_job *j, bool create, const CompPtrs *co
     if (comp) {
         e.work = comp_work;
         e.work_stride = comp_work_stride;
-        tm.run(3, 0.0, 0.0, [&] { launch_component_epilogue(g, e, *comp, sp, s); });
+        call.timed(tm, 3, 0.0, 0.0, [&] { launch_component_epilogue(g, e, *comp, sp, s); });
     } else {
-        tm.run(3, 0.0, 0.0, [&] { launch_epilogue(g, e, sp, s); });
+        call.timed(tm, 3, 0.0, 0.0, [&] { launch_epilogue(g, e, sp, s); });
     }
-    hipError_t err = hipStreamSynchronize(s);
-    if (err == hipSuccess) err = hipGetLastError();
-    tm.resolve(c->prof);
-    if (err != hipSuccess) return hip_status(err);
-    j->ran = true;
-    return NGP_OK;
+    const ngp_status st = call.sync();
+    j->run_ended(st, false);
+    return st;
 }
 
 }  // namespace
@@ -1735,16 +1762,10 @@ extern "C" ngp_status ngp_factor_create(ngp_ctx *c, int32_t P, const ngp_kernel 
     }
     ngp_status st = NGP_OK;
     {
-        std::lock_guard<std::mutex> lk(c->mu);
-        if (hipSetDevice(c->device) != hipSuccess) st = NGP_ERR_NO_DEVICE;
-        void *q = nullptr;
-        if (!st && f->n0 > 0) {
-            if (!(st = c->alloc(&q, sizeof(double) * (size_t)f->item_stride * P))) f->L = (double *)q;
-            if (!st && !(st = c->alloc(&q, sizeof(double) * (size_t)f->nb0 * P * NB * NB)))
-                f->dinv = (double *)q;
-        }
-        if (!st && !(st = c->alloc(&q, sizeof(double) * (size_t)P))) f->logdet = (double *)q;
-        if (!st && !(st = c->alloc(&q, sizeof(int32_t) * (size_t)P))) f->info = (int32_t *)q;
+        DevCall call(c);
+        if (call.status()) st = NGP_ERR_NO_DEVICE;
+        if (f->n0 > 0) call.keep(&f->L, (size_t)f->item_stride * P).keep(&f->dinv, (size_t)f->nb0 * P * NB * NB);
+        if (!st) st = call.keep(&f->logdet, (size_t)P).keep(&f->info, (size_t)P).status();
     }
     ngp_job *job = nullptr;
     static const double dummy = 0.0;
@@ -2114,21 +2135,16 @@ extern "C" ngp_status ngp_cov_batch(ngp_ctx *c, int32_t B, const ngp_kernel *ker
     const size_t nout = (size_t)B * n1 * n2;
     call.take(&dp, (size_t)B).take(&d1, (size_t)n1).take(&d2, (size_t)n2).take(&dout, nout);
     hipStream_t s = c->stream;
-    EventTimer tm(c->profiling, s);
     call.up(dp, hp.data(), sizeof(DevProgram) * (size_t)B)
         .up(d1, t1, sizeof(double) * (size_t)n1)
         .up(d2, t2, sizeof(double) * (size_t)n2)
-        .run([&] {
-            tm.run(4, 0.0, 8.0 * (double)nout, [&] {
-                for (int b0 = 0; b0 < B; b0 += (int)MAX_CHUNK_ITEMS)   // items are blockIdx.y
-                    launch_cov(dp + b0, std::min(B - b0, (int)MAX_CHUNK_ITEMS), d1, n1, d2, n2, add_diag,
-                               dout + (size_t)b0 * n1 * n2, dev_spec(c->spec), s);
-            });
+        .timed(call.tm, 4, 0.0, 8.0 * (double)nout, [&] {
+            for (int b0 = 0; b0 < B; b0 += (int)MAX_CHUNK_ITEMS)   // items are blockIdx.y
+                launch_cov(dp + b0, std::min(B - b0, (int)MAX_CHUNK_ITEMS), d1, n1, d2, n2, add_diag,
+                           dout + (size_t)b0 * n1 * n2, dev_spec(c->spec), s);
         })
         .down(out, dout, sizeof(double) * nout);
-    const ngp_status st = call.sync();
-    tm.resolve(c->prof);
-    return st;
+    return call.sync();
 }
 
 // ---------------------------------------------------------------------------------------
@@ -2163,6 +2179,16 @@ struct GradLeaf {
            t_info = 0, t_trace = 0, t_rows = 0;
     std::vector<int32_t> loff;             // [B + 1] first latent of every item
     PinVec<unsigned char> t_up, t_down;
+    // The one place the outcome of a run or a trajectory reaches the leaf, after its scope has
+    // synchronised: the staging copy has left h_in, and after a failure the device holds neither the
+    // host's programs nor clean info / logdet — the next run sends and clears them.
+    void run_ended(ngp_status st) {
+        if (!h_in.empty()) PinVec<unsigned char>().swap(h_in);
+        if (st) {
+            progs_dirty = true;
+            fresh = false;
+        }
+    }
 };
 
 // What a gradient evaluation is staged under: the context's spec and the switches that pick its
@@ -2192,6 +2218,8 @@ static bool grad_route_same(const GradRoute &a, const GradRoute &b) {
 
 namespace {
 
+void grad_leaf_destroy(GradLeaf *j);
+
 // toep_path: the items are stationary trees on a regular series — aux rows [y' ; e_1'] instead of
 // [I ; y'] (the caller, ngp_grad_stage, has checked both)
 // yrows: item b's observations are yrows[b][0..n) (y / ldy are then not read) — a subset of a
@@ -2203,9 +2231,10 @@ ngp_status grad_leaf_stage(ngp_ctx *c, int32_t B, const ngp_kernel *kernels, int
     *out = nullptr;
     GradLeaf *j = new (std::nothrow) GradLeaf();
     if (!j) return NGP_ERR_TOO_LARGE;
-    std::unique_ptr<GradLeaf> guard(j);
-    j->toep_path = toep_path;
     j->ctx = c;
+    // (the leaf before the scope: on a failure the scope ends, synchronised, before the leaf is destroyed)
+    std::unique_ptr<GradLeaf, void (*)(GradLeaf *)> guard(j, grad_leaf_destroy);
+    j->toep_path = toep_path;
     j->B = B;
     j->n = n;
     j->hp.resize((size_t)B);
@@ -2285,35 +2314,19 @@ ngp_status grad_leaf_stage(ngp_ctx *c, int32_t B, const ngp_kernel *kernels, int
         if (g.lattice) std::memcpy(j->h_in.data() + j->o_q, h_q.data(), 4 * (size_t)g.n0);
         j->fill.copy_to(j->h_in.data());
     }
-    std::lock_guard<std::mutex> lk(c->mu);
-    HIPCHK(hipSetDevice(c->device));
+    DevCall call(c);
     j->spec = route.spec;
     g.invariant = route.invariant ? 1 : 0;
     g.short_series = route.short_series ? 1 : 0;
     // (gradient jobs store every tile: their tables are per leaf, and on a regular series the
     // stationary trees — the ones structured storage could serve — are on the Toeplitz path)
-    void *q = nullptr;
-    ngp_status st = c->alloc(&q, j->io_bytes);
-    if (st) return st;
-    j->io = (unsigned char *)q;
+    if (call.keep(&j->io, j->io_bytes).status()) return call.status();   // nothing is queued yet
     // the front part goes up in one copy (info and logdet arrive as the zeros the factorisation
     // expects): a 24-particle call of a fit on a short series is a chain of dependent launches a
     // few microseconds long, and each separate copy or memset was one more of them
-    if (hipMemcpyAsync(j->io, j->h_in.data(), j->h_in.size(), hipMemcpyHostToDevice, c->stream) !=
-        hipSuccess) {
-        c->release(j->io);
-        return NGP_ERR_STATE;
-    }
+    const ngp_status st = stage_up(call, c->stream, j->io, j->h_in, j->h_in.size());
+    if (st) return st;
     j->fresh = true;
-    // a small staging buffer stays with the job (the run is queued right behind the copy); a
-    // large one is given back once the copy has left it
-    if (j->h_in.size() > STAGE_KEEP_BYTES) {
-        if (hipStreamSynchronize(c->stream) != hipSuccess) {
-            c->release(j->io);
-            return NGP_ERR_STATE;
-        }
-        PinVec<unsigned char>().swap(j->h_in);
-    }
     *out = guard.release();
     return NGP_OK;
 }
@@ -2343,7 +2356,7 @@ struct LeafRun {
     int Bc = 0;
     void *d_L = nullptr, *d_dinv = nullptr, *d_tab = nullptr, *d_sig = nullptr, *d_dtab = nullptr,
          *d_kinv = nullptr, *d_alpha = nullptr, *d_quad = nullptr, *d_part = nullptr, *d_items = nullptr;
-    std::vector<int32_t> h_items;   // alive until the lane is synchronised
+    std::vector<int32_t> h_items;   // read by a queued copy: a LeafRun is declared before its run's scope
     bool items_ready = false;       // a later evaluation of a trajectory: d_items holds the sorted items
     double *splitk = nullptr;       // pair runs: the context's split-k buffer for this leaf's value kernels
 
@@ -2388,9 +2401,10 @@ struct LeafRun {
         return r;
     }
 
-    // everything of the evaluation on the lane's streams; the caller synchronises ln.main
+    // everything of the evaluation on the lane's streams, as steps of the run's scope, which waits for
+    // the lane; tm: the scope's timer of that lane
     // copy_out: the results follow the last kernel into h_out (a trajectory reads them on the device)
-    ngp_status launch(const Lane &ln, EventTimer &tm, bool no_lane_split, bool copy_out = true) {
+    void launch(DevCall &call, const Lane &ln, EventTimer &tm, bool no_lane_split, bool copy_out = true) {
         ngp_ctx *c = j->ctx;
         const JobGeom &g = j->g;
         const int B = j->B;
@@ -2404,20 +2418,16 @@ struct LeafRun {
                     *const d_q = g.lattice ? io + j->o_q : nullptr, *const d_info = io + j->o_info,
                     *const d_logdet = io + j->o_logdet, *const d_grad = io + j->o_grad,
                     *const d_logml = io + j->o_logml;
-        hipError_t e = hipSuccess;
         // new parameters for the same trees: the programs go up again, nothing else.  On a lattice the
         // first kernel of the chain (tables_kernel) fetches them from the page-locked host copy itself
         // and leaves the device copy for the rest — a copy ahead of the chain cost 20 us of a 24-item
         // call's 110.
         const bool fetch_in_kernel = j->progs_dirty && g.lattice && g.n0 > 0 &&
                                      pinned_pool().is_pinned(j->hp.data());
-        if (j->progs_dirty && !fetch_in_kernel)
-            e = hipMemcpyAsync(d_prog, j->hp.data(), sizeof(DevProgram) * (size_t)B,
-                               hipMemcpyHostToDevice, s);
+        if (j->progs_dirty && !fetch_in_kernel) call.up(d_prog, j->hp.data(), sizeof(DevProgram) * (size_t)B, s);
         // a re-run: info | logdet are contiguous in the arena (short jobs: written outright)
-        if (e == hipSuccess && !j->fresh && !small_job(g, Bc))
-            e = hipMemsetAsync(d_info, 0, j->o_grad - j->o_info, s);
-        if (e != hipSuccess) return hip_status(e);
+        if (!j->fresh && !small_job(g, Bc)) call.zero(d_info, j->o_grad - j->o_info, s);
+        // (for the evaluations that follow in this scope; a failure takes both back: GradLeaf::run_ended)
         j->progs_dirty = false;
         j->fresh = false;
         for (int b0 = 0; b0 < B; b0 += Bc) {
@@ -2438,21 +2448,21 @@ struct LeafRun {
             p.dtab = (double *)d_dtab;
             p.splitk_part = splitk;
             if (g.lattice) j->fill.share_of(io, b0, bc, &p);
-            if (g.lattice) tm.run(4, 0.0, 0.0, [&] { launch_tables(g, p, bc, sp, s); });
-            tm.run(cost_fill_grad(g, bc, tp), [&] { launch_fill(g, p, bc, sp, s); });
+            if (g.lattice) call.timed(tm, 4, 0.0, 0.0, [&] { launch_tables(g, p, bc, sp, s); });
+            call.timed(tm, cost_fill_grad(g, bc, tp), [&] { launch_fill(g, p, bc, sp, s); });
             const size_t mstep = tp ? (size_t)bc * NB * NB : 0;
-            factor_chunk(ln, g, p, bc, tm, mstep, nullptr, nullptr, nullptr, no_lane_split);
+            call.run([&] { factor_chunk(ln, g, p, bc, tm, mstep, nullptr, nullptr, nullptr, no_lane_split); });
             if (tp) {
                 // z'z, then A = X K^-1 by one backward sweep of the two aux rows
-                tm.run(cost_toep_quad(g, bc),
+                call.timed(tm, cost_toep_quad(g, bc),
                        [&] { launch_toep_quad(g, (const double *)d_L, (double *)d_quad, bc, s); });
                 for (int cc = g.nb0 - 1; cc >= 0; --cc)
-                    tm.run(cost_toep_back(bc, cc), [&] {
+                    call.timed(tm, cost_toep_back(bc, cc), [&] {
                         launch_aux_back(g, p, p.dinv, mstep, (double *)d_kinv, 0, bc, cc, s);
                     });
             } else {
                 const bool kinv_small = kinv_route(g, bc) == KINV_SMALL;
-                tm.run(cost_kinv(g, bc), [&] {
+                call.timed(tm, cost_kinv(g, bc), [&] {
                     if (kinv_small)
                         launch_grad_kinv_small(g, (const double *)d_L, (double *)d_kinv, (double *)d_alpha,
                                                (double *)d_quad, bc, s);
@@ -2471,19 +2481,17 @@ struct LeafRun {
                 for (int k = 0; k < GRAD_BUCKETS; ++k) { pos[k] = acc; acc += counts[k]; }
                 for (int i = 0; i < bc; ++i)
                     h_items[(size_t)b0 + (size_t)pos[grad_bucket(j->n_ops[(size_t)(b0 + i)])]++] = i;
-                const hipError_t ce = hipMemcpyAsync((int32_t *)d_items + b0, h_items.data() + b0,
-                                                     4 * (size_t)bc, hipMemcpyHostToDevice, s);
-                if (ce != hipSuccess) return (ngp_status)ce;
+                call.up((int32_t *)d_items + b0, h_items.data() + b0, 4 * (size_t)bc, s);
             }
             if (tp) {
-                tm.run(cost_toep_grad(g, bc), [&] {
+                call.timed(tm, cost_toep_grad(g, bc), [&] {
                     launch_toep_grad(g, p, (const double *)d_kinv, (double *)d_alpha,
                                      (const double *)d_quad, (double *)d_part,
                                      (double *)d_grad + (int64_t)b0 * GP, (double *)d_logml + b0, bc, sp,
                                      s, by_size ? (const int32_t *)d_items + b0 : nullptr, counts);
                 });
             } else {
-                tm.run(cost_contract(g, bc), [&] {
+                call.timed(tm, cost_contract(g, bc), [&] {
                     launch_grad_contract(g, p, (const double *)d_kinv, (const double *)d_alpha,
                                          (const double *)d_quad, (double *)d_part,
                                          (double *)d_grad + (int64_t)b0 * GP, (double *)d_logml + b0,
@@ -2492,14 +2500,12 @@ struct LeafRun {
                 });
             }
         }
-        if (copy_out) e = hipMemcpyAsync(j->h_out.data(), d_info, j->h_out.size(), hipMemcpyDeviceToHost, s);
-        return hip_status(e);
+        if (copy_out) call.down(j->h_out.data(), d_info, j->h_out.size(), s);
     }
 
     // after the lane is synchronised: device parameter order -> caller's order; d/d noise last
     void unpack(double *logml, double *grad, int32_t *info) {
         const int GP = NGP_MAX_PARAMS + 1;
-        if (!j->h_in.empty()) PinVec<unsigned char>().swap(j->h_in);   // the staging copy has left it
         const int32_t *h_info = (const int32_t *)j->h_out.data();
         const double *h_grad = (const double *)(j->h_out.data() + (j->o_grad - j->o_info)),
                      *h_lm = (const double *)(j->h_out.data() + (j->o_logml - j->o_info));
@@ -2516,33 +2522,34 @@ struct LeafRun {
     }
 };
 
+// The memory-driven chunk of a leaf's run, laid out in the context's workspace (r.Bc and the d_*
+// pointers): as many items as the memory figure allows, halved when the device cannot hold that
+// after all (other handles, rounding).
+ngp_status chunk_for(ngp_ctx *c, LeafRun &r) {
+    const size_t B = (size_t)r.j->B, item_bytes = r.item_bytes();
+    if (B * item_bytes > c->mem_cap) c->refresh_mem_cap();   // large job: today's figure
+    r.Bc = (int)std::min<size_t>(std::min<size_t>(B, MAX_CHUNK_ITEMS), std::max<size_t>(1, c->mem_cap / item_bytes));
+    for (;; r.Bc = (r.Bc + 1) / 2) {
+        const ngp_status st = ws_layout(c, [&](WsPlan &w) { return r.layout(w); });
+        if (!st) r.j->last_chunk = r.Bc;
+        if (st != NGP_ERR_TOO_LARGE || r.Bc <= 1) return st;
+    }
+}
+
 ngp_status grad_leaf_run(GradLeaf *j, double *logml, double *grad, int32_t *info) {
     if (!j || !grad) return NGP_ERR_ARG;
     ngp_ctx *c = j->ctx;
-    std::lock_guard<std::mutex> lk(c->mu);
-    HIPCHK(hipSetDevice(c->device));
     LeafRun r;
     r.j = j;
-    const size_t item_bytes = r.item_bytes();
-    if ((size_t)j->B * item_bytes > c->mem_cap) c->refresh_mem_cap();   // large job: today's figure
-    r.Bc = (int)std::min<size_t>(std::min<size_t>((size_t)j->B, MAX_CHUNK_ITEMS),
-                                 std::max<size_t>(1, c->mem_cap / item_bytes));
-    // the chunk is halved when the device cannot hold it after all (other handles, rounding)
-    for (;; r.Bc = (r.Bc + 1) / 2) {
-        const ngp_status st = ws_layout(c, [&](WsPlan &w) { return r.layout(w); });
-        if (!st) break;
-        if (st != NGP_ERR_TOO_LARGE || r.Bc <= 1) return st;
-    }
-    j->last_chunk = r.Bc;
-    EventTimer tm(c->profiling, c->stream);
-    ngp_status st = r.launch(lane_of(c), tm, false);
-    hipError_t e = hipStreamSynchronize(c->stream);
-    if (e == hipSuccess) e = hipGetLastError();
-    tm.resolve(c->prof);
-    if (st) return st;
-    if (e != hipSuccess) return hip_status(e);
-    r.unpack(logml, grad, info);
-    return NGP_OK;
+    DevCall call(c);
+    if (call.status()) return call.status();
+    const ngp_status fit = chunk_for(c, r);
+    if (fit) return fit;   // nothing is queued yet
+    r.launch(call, lane_of(c), call.tm, false);
+    const ngp_status st = call.sync();
+    j->run_ended(st);
+    if (!st) r.unpack(logml, grad, info);
+    return st;
 }
 
 // The two leaves of a SMALL mixed batch side by side, each on its own pair of streams (the lanes of
@@ -2552,12 +2559,12 @@ ngp_status grad_leaf_run(GradLeaf *j, double *logml, double *grad, int32_t *info
 ngp_status grad_pair_run(GradLeaf *a, double *lm_a, double *g_a, int32_t *info_a, GradLeaf *b,
                          double *lm_b, double *g_b, int32_t *info_b) {
     ngp_ctx *c = a->ctx;
-    std::lock_guard<std::mutex> lk(c->mu);
-    HIPCHK(hipSetDevice(c->device));
-    if (!c->make_lanes(2)) return NGP_ERR_TOO_LARGE;
     LeafRun ra, rb;
     ra.j = a;
     rb.j = b;
+    DevCall call(c);
+    if (call.status()) return call.status();
+    if (!c->make_lanes(2)) return NGP_ERR_TOO_LARGE;
     ra.Bc = a->last_chunk = a->B;
     rb.Bc = b->last_chunk = b->B;
     WsPlan measure{c, true}, take{c, false};
@@ -2567,28 +2574,25 @@ ngp_status grad_pair_run(GradLeaf *a, double *lm_a, double *g_a, int32_t *info_a
     if (measure.total > c->mem_cap) return NGP_ERR_TOO_LARGE;
     ngp_status st = c->ws_reserve(measure.total);
     if (st) return st;
-    if ((st = ra.layout(take)) || (st = rb.layout(take))) return st;
+    if ((st = ra.layout(take)) || (st = rb.layout(take))) return st;   // nothing is queued yet
     // the Toeplitz leaf runs on the value kernels: their split-k fat steps of late columns (small
     // chunks) need the context's buffer, which factor_chunk only reserves for a chunk it owns whole
     if (b->toep_path && splitk_eligible(b->g, b->B, false, false) && c->splitk_reserve(b->B) == NGP_OK)
         rb.splitk = c->splitk_part;
     const Lane l0 = lane_of(c);
     const Lane l1 = lane_of(c, 1);
+    EventTimer &tm1 = call.second_lane();
     // what the context's stream holds (the staging copies of both leaves) comes first on lane 1 too
-    (void)hipEventRecord(c->ev_lane_go, c->stream);
-    (void)hipStreamWaitEvent(l1.main, c->ev_lane_go, 0);
-    EventTimer tma(c->profiling, l0.main), tmb(c->profiling, l1.main);
-    ngp_status sa = ra.launch(l0, tma, true);
-    ngp_status sb = rb.launch(l1, tmb, true);
-    hipError_t e = hipStreamSynchronize(l0.main);
-    const hipError_t e1 = hipStreamSynchronize(l1.main);
-    if (e == hipSuccess) e = e1;
-    if (e == hipSuccess) e = hipGetLastError();
-    tma.resolve(c->prof);
-    tmb.resolve(c->prof);
-    if (sa) return sa;
-    if (sb) return sb;
-    if (e != hipSuccess) return hip_status(e);
+    call.run([&] {
+        (void)hipEventRecord(c->ev_lane_go, c->stream);
+        (void)hipStreamWaitEvent(l1.main, c->ev_lane_go, 0);
+    });
+    ra.launch(call, l0, call.tm, true);
+    rb.launch(call, l1, tm1, true);
+    st = call.sync();
+    a->run_ended(st);
+    b->run_ended(st);
+    if (st) return st;
     ra.unpack(lm_a, g_a, info_a);
     rb.unpack(lm_b, g_b, info_b);
     return NGP_OK;
@@ -2609,8 +2613,12 @@ ngp_status grad_leaf_hmc(GradLeaf *j, const ngp_hmc_config *cfg, const uint8_t *
                          const uint8_t *frozen, const double *z0, const double *mom, const HmcOut &o) {
     ngp_ctx *c = j->ctx;
     const int B = j->B, L = cfg->n_leapfrog;
-    std::lock_guard<std::mutex> lk(c->mu);
-    HIPCHK(hipSetDevice(c->device));
+    // read by queued copies: before the scope
+    PinVec<unsigned char> maps;
+    LeafRun r;
+    r.j = j;
+    DevCall call(c);
+    if (call.status()) return call.status();
     auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
     const size_t rows = o.trace ? (size_t)L + 1 : 0;
     if (!j->hmc || rows > j->t_rows) {
@@ -2629,15 +2637,14 @@ ngp_status grad_leaf_hmc(GradLeaf *j, const ngp_hmc_config *cfg, const uint8_t *
         j->t_sc = j->t_theta + al(8 * NL);
         j->t_info = j->t_sc + 5 * al(8 * (size_t)B);
         j->t_trace = j->t_info + al(4 * (size_t)B);
-        void *q = nullptr;
-        const ngp_status st = c->alloc(&q, j->t_trace + 8 * NL * rows);
-        if (st) return st;
+        unsigned char *q = nullptr;
+        if (call.keep(&q, j->t_trace + 8 * NL * rows).status()) return call.status();   // nothing is queued yet
         c->release(j->hmc);
-        j->hmc = (unsigned char *)q;
+        j->hmc = q;
         j->t_rows = rows;
         j->t_up.assign(j->t_theta - j->t_kind, 0);
         j->t_down.assign(j->t_trace - j->t_z, 0);
-        PinVec<unsigned char> maps(j->t_kind, 0);
+        maps.assign(j->t_kind, 0);
         std::memcpy(maps.data(), j->loff.data(), 4 * ((size_t)B + 1));
         for (int i = 0; i < B; ++i) {
             unsigned char *sl = maps.data() + j->t_slot + j->loff[(size_t)i];
@@ -2645,9 +2652,13 @@ ngp_status grad_leaf_hmc(GradLeaf *j, const ngp_hmc_config *cfg, const uint8_t *
             for (int k = 0; k < np; ++k) sl[j->perm[(size_t)i][(size_t)k]] = (unsigned char)k;
             sl[np] = (unsigned char)np;
         }
-        hipError_t e = hipMemcpyAsync(j->hmc, maps.data(), maps.size(), hipMemcpyHostToDevice, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);   // `maps` ends with this block
-        if (e != hipSuccess) return hip_status(e);
+        // the arena is the job's only with its maps in it: a round trip of its own, once per job
+        if (call.up(j->hmc, maps.data(), maps.size()).wait()) {
+            c->release(j->hmc);
+            j->hmc = nullptr;
+            j->t_rows = 0;
+            return call.status();   // synchronised
+        }
     }
     const size_t NL = (size_t)j->loff[(size_t)B];
     {
@@ -2658,18 +2669,8 @@ ngp_status grad_leaf_hmc(GradLeaf *j, const ngp_hmc_config *cfg, const uint8_t *
         std::memcpy(up + (j->t_z - j->t_kind), z0, 8 * NL);
         std::memcpy(up + (j->t_pm - j->t_kind), mom, 8 * NL);
     }
-    LeafRun r;
-    r.j = j;
-    const size_t item_bytes = r.item_bytes();
-    if ((size_t)B * item_bytes > c->mem_cap) c->refresh_mem_cap();
-    r.Bc = (int)std::min<size_t>(std::min<size_t>((size_t)B, MAX_CHUNK_ITEMS),
-                                 std::max<size_t>(1, c->mem_cap / item_bytes));
-    for (;; r.Bc = (r.Bc + 1) / 2) {
-        const ngp_status st = ws_layout(c, [&](WsPlan &w) { return r.layout(w); });
-        if (!st) break;
-        if (st != NGP_ERR_TOO_LARGE || r.Bc <= 1) return st;
-    }
-    j->last_chunk = r.Bc;
+    const ngp_status fit = chunk_for(c, r);
+    if (fit) return fit;   // nothing is queued
     hipStream_t s = c->stream;
     unsigned char *const h = j->hmc;
     HmcDev a{};
@@ -2698,36 +2699,25 @@ ngp_status grad_leaf_hmc(GradLeaf *j, const ngp_hmc_config *cfg, const uint8_t *
     }
     a.B = B;
     double *const trace = o.trace ? (double *)(h + j->t_trace) : nullptr;
-    EventTimer tm(c->profiling, s);
     // the device writes its own parameters from here on: whatever set_params left is superseded
     j->progs_dirty = false;
-    hipError_t e = hipMemcpyAsync(h + j->t_kind, j->t_up.data(), j->t_up.size(), hipMemcpyHostToDevice, s);
-    ngp_status st = NGP_OK;
+    call.up(h + j->t_kind, j->t_up.data(), j->t_up.size());
     auto step = [&](int phase, int row) {
         a.phase = phase;
         a.trace = trace && row >= 0 ? trace + (size_t)row * NL : nullptr;
-        tm.run(4, 0.0, 0.0, [&] { launch_hmc_step(a, s); });
+        call.timed(call.tm, 4, 0.0, 0.0, [&] { launch_hmc_step(a, s); });
     };
-    if (e == hipSuccess) {
-        step(HMC_INIT, 0);
-        for (int ev = 0; ev <= L && !st; ++ev) {
-            st = r.launch(lane_of(c), tm, false, false);
-            r.items_ready = true;
-            if (!st) step(ev == L ? HMC_LAST : ev == 0 ? HMC_FIRST : HMC_MIDDLE, ev == L ? -1 : ev + 1);
-        }
-        if (!st) e = hipMemcpyAsync(j->t_down.data(), h + j->t_z, j->t_down.size(), hipMemcpyDeviceToHost, s);
-        if (!st && e == hipSuccess && trace)
-            e = hipMemcpyAsync(o.trace, trace, 8 * NL * ((size_t)L + 1), hipMemcpyDeviceToHost, s);
+    step(HMC_INIT, 0);
+    for (int ev = 0; ev <= L && !call.status(); ++ev) {
+        r.launch(call, lane_of(c), call.tm, false, false);
+        r.items_ready = true;
+        step(ev == L ? HMC_LAST : ev == 0 ? HMC_FIRST : HMC_MIDDLE, ev == L ? -1 : ev + 1);
     }
-    const hipError_t es = hipStreamSynchronize(s);
-    if (e == hipSuccess) e = es;
-    if (e == hipSuccess) e = hipGetLastError();
-    tm.resolve(c->prof);
-    if (!j->h_in.empty()) PinVec<unsigned char>().swap(j->h_in);   // the staging copy has left it
-    if (st || e != hipSuccess) {
-        j->progs_dirty = true;   // the device programs are not the host's: the next run sends them
-        return st ? st : hip_status(e);
-    }
+    call.down(j->t_down.data(), h + j->t_z, j->t_down.size());
+    if (trace) call.down(o.trace, trace, 8 * NL * ((size_t)L + 1));
+    const ngp_status st = call.sync();
+    j->run_ended(st);   // (after a failure the device programs are not the host's: the next run sends them)
+    if (st) return st;
     const unsigned char *dn = j->t_down.data();
     auto at = [&](size_t t_x) { return dn + (t_x - j->t_z); };
     std::memcpy(o.z1, at(j->t_z), 8 * NL);
@@ -2753,10 +2743,10 @@ ngp_status grad_leaf_hmc(GradLeaf *j, const ngp_hmc_config *cfg, const uint8_t *
 void grad_leaf_destroy(GradLeaf *j) {
     if (!j) return;
     {
-        std::lock_guard<std::mutex> lk(j->ctx->mu);
-        (void)hipSetDevice(j->ctx->device);
+        DevCall call(j->ctx);
         // a staging buffer that was kept must outlive its copy
-        if (!j->h_in.empty()) (void)hipStreamSynchronize(j->ctx->stream);
+        if (!j->h_in.empty()) call.pending();
+        (void)call.sync();
         j->ctx->release(j->io);
         j->ctx->release(j->hmc);
     }

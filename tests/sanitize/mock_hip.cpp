@@ -15,6 +15,7 @@
 // every run.  Identical consecutive lines are written once with a repeat count.  In digest mode the
 // lines are not printed but counted and hashed (FNV-1a, 64 bit), and the launches are tallied by
 // kernel (with the grid of its first launch); the driver prints both per call.
+#include <algorithm>
 #include <atomic>
 #include <chrono>
 #include <cstdint>
@@ -52,6 +53,7 @@ struct Trace {
     std::unordered_map<std::string, int> ids;
     std::unordered_map<const void *, int> streams, events;
     int n_streams = 0, n_events = 0;
+    std::vector<int> launch_streams;     // stream ordinals that saw a launch since mock_hip_launch_streams()
     std::string last;
     long repeat = 0;
 };
@@ -225,7 +227,8 @@ hipError_t hipStreamWaitEvent(hipStream_t s, hipEvent_t e, unsigned) {
     return 0;
 }
 // events made for timing (EventTimer: a pair per launch, made and destroyed at once) stay unnumbered
-hipError_t hipEventCreate(hipEvent_t *e) { *e = (hipEvent_t)malloc(8); return 0; }
+static std::atomic<long> g_timing_events{0};
+hipError_t hipEventCreate(hipEvent_t *e) { *e = (hipEvent_t)malloc(8); ++g_timing_events; return 0; }
 hipError_t hipEventCreateWithFlags(hipEvent_t *e, unsigned) {
     *e = (hipEvent_t)malloc(8);
     if (tr().on) tr().events[*e] = tr().n_events++;
@@ -268,6 +271,9 @@ hipError_t hipLaunchKernel(const void *fn, dim3_ g, dim3_ b, void **args, size_t
             if (it == t.tally.end()) t.tally.push_back({id->second, 1, g});
             else ++it->n;
         }
+        const int so = ordinal(t.streams, s);
+        if (std::find(t.launch_streams.begin(), t.launch_streams.end(), so) == t.launch_streams.end())
+            t.launch_streams.push_back(so);
         trace_args(name, args, extra, sizeof extra);
         std::snprintf(buf, sizeof buf, "L K%d %u,%u,%u %u %zu s%d%s", id->second, g.x, g.y, g.z, b.x,
                       shm, ordinal(t.streams, s), extra);
@@ -339,6 +345,14 @@ long mock_hip_fail_copy_after(long n) { return g_copy_fail_in.exchange(n > 0 ? n
 long mock_hip_syncs(void) { return g_syncs.load(); }
 // the same count at the moment the copy ordered by mock_hip_fail_copy_after failed
 long mock_hip_syncs_at_failed_copy(void) { return g_syncs_at_fail.load(); }
+// events made for timing so far (EventTimer: two per timed launch record)
+long mock_hip_timing_events(void) { return g_timing_events.load(); }
+// how many different streams saw a kernel launch since the last call of this function (trace on)
+long mock_hip_launch_streams(void) {
+    const long n = (long)tr().launch_streams.size();
+    tr().launch_streams.clear();
+    return n;
+}
 // what hipMemGetInfo reports (2 GiB unless set; memory is only touched where the host layer copies)
 void mock_hip_set_device_bytes(size_t bytes) { g_device_bytes.store(bytes); }
 }

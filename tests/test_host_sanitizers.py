@@ -8,7 +8,9 @@ factors, error returns — and by tests/sanitize/combine_stress.cpp: bursts of c
 callers behind a "busy device" (the mock's synchronisation sleeps), i.e. the flat combining of
 include/ngp.h "concurrent callers": no lost wake-up, every caller's arrays written, a burst costs
 about one call's launches — and by tests/sanitize/oneshot_faults.cpp: every one-shot device call with
-each of its copies and its largest allocation failing in turn.  No GPU is involved (GPU sanitizers are not available on this pool)."""
+each of its copies and its largest allocation failing in turn — and by
+tests/sanitize/staged_faults.cpp: the same for every step of the staged runs, with the step repeated
+on the job the failure left.  No GPU is involved (GPU sanitizers are not available on this pool)."""
 import os
 import shutil
 import subprocess
@@ -53,7 +55,7 @@ def build(tmp, flags, tag, driver="host_stress"):
     ("asan", ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"],
      {"ASAN_OPTIONS": "detect_leaks=1", "UBSAN_OPTIONS": "print_stacktrace=1"}),
 ])
-@pytest.mark.parametrize("driver", ["host_stress", "combine_stress", "oneshot_faults"])
+@pytest.mark.parametrize("driver", ["host_stress", "combine_stress", "oneshot_faults", "staged_faults"])
 def test_host_layer_under_sanitizers(tmp_path, tag, flags, env, driver):
     exe = build(str(tmp_path), flags, tag, driver)
     out = subprocess.run([exe], capture_output=True, text=True, timeout=600,
