@@ -559,6 +559,65 @@ ngp_status ngp_mixture_path_targets_indep(ngp_ctx *ctx, int32_t P, int32_t S, in
                                           int64_t *count, int64_t *hist, double *values,
                                           int32_t *info);
 
+/* ---- scores of the paths themselves: energy score and sample CRPS ----------------------------
+ * A forecast is a matrix of draws, dates x N paths, and the reference scores every approach from
+ * those draws: per date mean |X - y| minus half the mean of |X_i - X_j| over the pairs i < j
+ * (docs/vignettes/getting-started.jl:689-702, after data_transform = log, :746) — an O(N^2) loop.
+ * Over a window of dates the same expression with the Euclidean norm is the energy score, the
+ * multivariate CRPS (Gneiting & Raftery 2007), which also sees paths of the wrong shape.
+ * Per window w = [j0, j1] (inclusive), with u_i = s(x_i[j0..j1]), v = s(y[j0..j1]) and s
+ * NGP_SCORE_NATURAL or NGP_SCORE_LOG with shift, as in ngp_mixture_crps_mapped:
+ *   term_obs  = (1 / N) sum_i |u_i - v|_2
+ *   term_pair = (1 / D) sum_(i < k) |u_i - u_k|_2      fair = 1: D = N (N - 1) / 2 (the vignette's
+ *               estimator); fair = 0: D = N^2 / 2 (the V-statistic, as scoringutils computes it)
+ *   es        = term_obs - term_pair / 2
+ * A window of one date gives the sample CRPS of that date.  Windows may overlap or repeat.
+ *   x [N x m]       paths on the ORIGINAL scale, path-major (row i is path i)
+ *   y [m]           observations on the original scale
+ *   win [W x 2]     j0, j1 of every window
+ *   es [W]; term_obs [W], term_pair [W], info [W] may be NULL
+ *   info[w]         0, or NGP_INFO_NOT_FINITE (-3), the window's outputs NaN: a path value or s(.)
+ *                   of one inside the window is not finite — with NGP_SCORE_LOG every x + shift <= 0,
+ *                   e.g. a clamp at 0 with shift 0 — or the values are finite but so large (about
+ *                   1e154 apart and beyond; the largest finite double NGP_INV_BOXCOX caps at) that a
+ *                   squared difference overflows and a sum is not finite.  Other windows are not
+ *                   affected.
+ * ngp_mixture_path_scores draws the N = S draws paths on the device with the sampler (indep = 0:
+ * the layouts of ngp_mixture_sample, keyed by seeds[0]; indep = 1: those of
+ * ngp_mixture_sample_indep, seeds [S]), applies the ONE ngp_inv_transform inv with the edge rules of
+ * the trajectory targets and scores them as above; the paths never leave the device.  They are the
+ * sampler's paths to rounding; bit equality with them is not promised.  chol_info ([P], or [S x P]
+ * with indep = 1; may be NULL) is the sampler's info; a failed component of positive weight makes
+ * every output NaN (info[w] = NGP_INFO_NOT_FINITE for every window).
+ * Accuracy: the squared distance of a pair is summed from the DIFFERENCES u_ij - u_kj date by date,
+ * never from a Gram product, so near-identical paths (1e6 + 1e-3 z; a clamp at exactly 0) keep
+ * their distance.  Every sum runs in a fixed order and no chain of additions is longer than 2,048
+ * terms: each term is within (2,048 + m + 8) 2^-53 relative of a long double evaluation of the
+ * same s(.) values (2.6e-13 for m <= 192), tested to 1e-12 per term and 1e-12 (term_obs +
+ * term_pair / 2) for es, the floor ngp_mixture_crps is granted.
+ * Bitwise reproducible from call to call; a window's bits do not depend on the other windows of
+ * the call (no floating-point atomics).
+ * NGP_ERR_ARG, before anything touches a device: null context or required array; N, m, W or draws
+ * < 1; fair = 1 with N < 2; a window outside [0, m) or with j0 > j1; scale, fair or indep not one
+ * of their values; shift non-finite or < 0; a non-finite y, or a y where s(y) is undefined; for the
+ * mixture form also what ngp_mixture_path_targets refuses (null w, mu, sigma, seeds, inv; P or S
+ * < 1; an unknown inv.kind; non-finite lam, offset, cap; NGP_INV_BOXCOX with cap <= 0).
+ * Limits (NGP_ERR_TOO_LARGE): N <= 2^20, W <= 4,096, m <= 65,535 (ensemble form) or NGP_MAX_AUX
+ * (mixture form), and the paths (twice 8 N m bytes) plus the partial sums (8 W per 128 x 128 tile
+ * of the pairs' upper triangle) must fit in device memory.
+ * Thread-safe through the context's lock; not combined with concurrent callers; not counted in
+ * ngp_profile.  (NGP_SCORE_* are declared with ngp_mixture_crps_mapped below.)                    */
+ngp_status ngp_ensemble_scores(ngp_ctx *ctx, int32_t N, int32_t m, const double *x,
+                               const double *y, int32_t scale, double shift, int32_t fair,
+                               int32_t W, const int32_t *win, double *es, double *term_obs,
+                               double *term_pair, int32_t *info);
+ngp_status ngp_mixture_path_scores(ngp_ctx *ctx, int32_t P, int32_t S, int32_t m, const double *w,
+                                   const double *mu, const double *sigma, int32_t indep,
+                                   int32_t draws, const uint64_t *seeds, const void *inv,
+                                   const double *y, int32_t scale, double shift, int32_t fair,
+                                   int32_t W, const int32_t *win, double *es, double *term_obs,
+                                   double *term_pair, int32_t *info, int32_t *chol_info);
+
 /* ---- exact CRPS and mean on the natural and log scales ----------------------------------------
  * ngp_mixture_crps scores on the scale the mixture is Gaussian on.  The reference's vignette fits
  * on a Box-Cox scale, maps the draws back and scores crps(log(y), log.(X))

@@ -624,6 +624,58 @@ function mixture_path_targets(c::Context, w::Array{Float64}, mu::Array{Float64},
 end
 
 """
+Energy score per window of dates of N paths (`ngp_ensemble_scores`): `x` is m x N (a column is a
+path on the original scale, as `forecast` returns its draws), `y` has m entries, `win` is 2 x W with
+the 0-based inclusive `j0, j1` of every window; a window of one date is the sample CRPS of that
+date.  Returns `(es, term_obs, term_pair, info)`.
+"""
+function ensemble_scores(c::Context, x::Matrix{Float64}, y::Vector{Float64}, win::Matrix{Int32};
+                         scale::Integer = NGP_SCORE_NATURAL, shift::Real = 0.0, fair::Bool = true)
+    m, N = size(x)
+    length(y) == m || throw(DimensionMismatch("y has one entry per date"))
+    size(win, 1) == 2 || throw(DimensionMismatch("win is 2 x W"))
+    W = size(win, 2)
+    es = Vector{Float64}(undef, W); to = Vector{Float64}(undef, W); tp = Vector{Float64}(undef, W)
+    info = zeros(Int32, W)
+    check(ccall((:ngp_ensemble_scores, LIBNGP), Int32,
+                (Ptr{Cvoid}, Int32, Int32, Ptr{Float64}, Ptr{Float64}, Int32, Float64, Int32, Int32,
+                 Ptr{Int32}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}),
+                c.h, N, m, x, y, Int32(scale), Float64(shift), Int32(fair), W, win, es, to, tp, info),
+          "ngp_ensemble_scores")
+    return es, to, tp, info
+end
+
+"""
+The same scores of the paths `mixture_sample` (one `seed`) / `mixture_sample_indep` (a vector of S
+seeds) draws for the same arguments, mapped through `inv` and scored on the device without coming
+back (`ngp_mixture_path_scores`).  Returns `(es, term_obs, term_pair, info)`.
+"""
+function mixture_path_scores(c::Context, w::Array{Float64}, mu::Array{Float64}, sigma::Array{Float64},
+                             draws::Integer, seed::Union{Integer,Vector{UInt64}}, inv::InvTransform,
+                             y::Vector{Float64}, win::Matrix{Int32};
+                             scale::Integer = NGP_SCORE_NATURAL, shift::Real = 0.0, fair::Bool = true)
+    P, S, m = size(w, 1), size(w, 2), size(mu, 1)              # column-major views of [S x P], [.. x m]
+    length(y) == m || throw(DimensionMismatch("y has one entry per date"))
+    size(win, 1) == 2 || throw(DimensionMismatch("win is 2 x W"))
+    indep = !(seed isa Integer)
+    seeds = indep ? seed : UInt64[UInt64(seed)]
+    indep && length(seeds) != S && throw(DimensionMismatch("one seed per mixture"))
+    W = size(win, 2)
+    es = Vector{Float64}(undef, W); to = Vector{Float64}(undef, W); tp = Vector{Float64}(undef, W)
+    info = zeros(Int32, W); cinfo = zeros(Int32, indep ? P * S : P)
+    rinv = Ref(inv)
+    check(ccall((:ngp_mixture_path_scores, LIBNGP), Int32,
+                (Ptr{Cvoid}, Int32, Int32, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int32, Int32,
+                 Ptr{UInt64}, Ptr{Cvoid}, Ptr{Float64}, Int32, Float64, Int32, Int32, Ptr{Int32},
+                 Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}, Ptr{Int32}),
+                c.h, P, S, m, w, mu, sigma, Int32(indep), draws, seeds, rinv, y, Int32(scale),
+                Float64(shift), Int32(fair), W, win, es, to, tp, info, cinfo),
+          "ngp_mixture_path_scores")
+    raise_if_not_posdef(cinfo)
+    return es, to, tp, info
+end
+
+"""
 The one collective of the path for a multi-GPU Julia host (one process per GPU): RCCL, opened by
 libngp at run time.  Rank 0 calls `comm_unique_id()` and hands the 128 bytes to the other ranks by
 whatever the host uses (Distributed.jl, MPI, a file); every rank then builds `Comm(ctx, id, rank, world)`.

@@ -43,6 +43,7 @@ SYMBOLS = (
     "ngp_mixture_path_targets", "ngp_mixture_path_targets_indep",
     "ngp_mixture_crps_mapped",
     "ngp_grad_job_hmc",
+    "ngp_ensemble_scores", "ngp_mixture_path_scores",
 )
 
 
@@ -144,6 +145,11 @@ def load():
                                                  C.POINTER(C.c_uint64), C.POINTER(NgpInvTransform),
                                                  i32, C.POINTER(NgpPathTarget), i32, f64p, f64p,
                                                  f64p, C.POINTER(i64), C.POINTER(i64), f64p, i32p]),
+        "ngp_ensemble_scores": (i32, [vp, i32, i32, f64p, f64p, i32, C.c_double, i32, i32, i32p, f64p,
+                                      f64p, f64p, i32p]),
+        "ngp_mixture_path_scores": (i32, [vp, i32, i32, i32, f64p, f64p, f64p, i32, i32,
+                                          C.POINTER(C.c_uint64), C.POINTER(NgpInvTransform), f64p, i32,
+                                          C.c_double, i32, i32, i32p, f64p, f64p, f64p, i32p, i32p]),
         "ngp_set_structured_storage": (i32, [vp, i32]),
         "ngp_set_combining": (i32, [vp, i32]),
         "ngp_set_batch_invariant": (i32, [vp, i32]),
@@ -736,6 +742,64 @@ class Context:
                 self._h, P, S, m, dptr(w), dptr(mu), dptr(sigma), int(draws),
                 C.c_uint64(int(seed) & (2**64 - 1)), *tail), "ngp_mixture_path_targets")
         return dict(q=q, mean=mean, count=count, hist=hist, values=values, info=info)
+
+    @staticmethod
+    def _windows(windows, who):
+        win = np.ascontiguousarray(np.asarray(windows, dtype=np.int32).reshape(-1, 2))
+        if win.shape[0] < 1:
+            raise ValueError(f"{who}: at least one window (j0, j1)")
+        return win
+
+    def ensemble_scores(self, x, y, windows, scale: int = 0, shift: float = 0.0, fair: bool = True):
+        """Energy score per window of dates of N paths (``ngp_ensemble_scores``): x [N,m] paths on
+        the original scale (path-major), y [m], windows [(j0, j1), ...] inclusive ->
+        dict(es [W], term_obs [W], term_pair [W], info [W]).  A window of one date is the sample
+        CRPS of that date."""
+        x, y = as_f64(x), as_f64(y)
+        if x.ndim != 2 or y.shape != (x.shape[1],):
+            raise ValueError("ensemble_scores: x [N,m], y [m]")
+        win = self._windows(windows, "ensemble_scores")
+        W = win.shape[0]
+        es, to, tp = np.empty(W), np.empty(W), np.empty(W)
+        info = np.zeros(W, dtype=np.int32)
+        _chk(load().ngp_ensemble_scores(self._h, x.shape[0], x.shape[1], dptr(x), dptr(y), int(scale),
+                                        float(shift), int(bool(fair)), W, iptr(win), dptr(es), dptr(to),
+                                        dptr(tp), iptr(info)), "ngp_ensemble_scores")
+        return dict(es=es, term_obs=to, term_pair=tp, info=info)
+
+    def mixture_path_scores(self, w, mu, sigma, draws: int, seed, inv, y, windows, scale: int = 0,
+                            shift: float = 0.0, fair: bool = True):
+        """Energy score per window of the paths the sampler draws, scored on the device without
+        bringing them back (``ngp_mixture_path_scores``): w, mu, sigma, draws and ``seed`` (a
+        scalar: shared components; S seeds: independent mixtures) as ``mixture_path_targets``;
+        ``inv`` = (kind, lam, offset, cap); y [m] on the original scale ->
+        dict(es, term_obs, term_pair, info [W], chol_info)."""
+        w, mu, sigma, y = as_f64(w), as_f64(mu), as_f64(sigma), as_f64(y)
+        indep = not np.isscalar(seed)
+        if w.ndim != 2 or mu.ndim != 3:
+            raise ValueError("mixture_path_scores: w [S,P], mu [P,S,m] ([S,P,m] with S seeds)")
+        S, P = w.shape
+        m = mu.shape[2]
+        if indep:
+            if mu.shape != (S, P, m) or sigma.shape != (S, P, m, m) or len(seed) != S:
+                raise ValueError("mixture_path_scores: w [S,P], mu [S,P,m], sigma [S,P,m,m], seeds [S]")
+        elif mu.shape != (P, S, m) or sigma.shape != (P, m, m):
+            raise ValueError("mixture_path_scores: w [S,P], mu [P,S,m], sigma [P,m,m]")
+        if y.shape != (m,):
+            raise ValueError("mixture_path_scores: y [m]")
+        win = self._windows(windows, "mixture_path_scores")
+        W = win.shape[0]
+        sd = np.array([int(v) & (2**64 - 1) for v in (seed if indep else [seed])], dtype=np.uint64)
+        iv = NgpInvTransform(int(inv[0]), float(inv[1]), float(inv[2]), float(inv[3]))
+        es, to, tp = np.empty(W), np.empty(W), np.empty(W)
+        info = np.zeros(W, dtype=np.int32)
+        cinfo = np.zeros((S, P) if indep else P, dtype=np.int32)
+        _chk(load().ngp_mixture_path_scores(
+            self._h, P, S, m, dptr(w), dptr(mu), dptr(sigma), int(indep), int(draws),
+            sd.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(iv), dptr(y), int(scale), float(shift),
+            int(bool(fair)), W, iptr(win), dptr(es), dptr(to), dptr(tp), iptr(info), iptr(cinfo)),
+            "ngp_mixture_path_scores")
+        return dict(es=es, term_obs=to, term_pair=tp, info=info, chol_info=cinfo)
 
     @staticmethod
     def _marginals(w, mu, var, who):

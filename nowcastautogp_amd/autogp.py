@@ -93,6 +93,18 @@ class HipEngine:
         return self.ctx.mixture_path_targets(w, mu, sigma, draws, seed, inv, targets, probs,
                                              want_values)
 
+    def ensemble_scores(self, x, y, windows, scale=0, shift=0.0, fair=True):
+        """Energy score / sample CRPS per window of paths x [N, m] on the device
+        (``ngp_ensemble_scores``)."""
+        return self.ctx.ensemble_scores(x, y, windows, scale, shift, fair)
+
+    def mixture_path_scores(self, w, mu, sigma, draws, seed, inv, y, windows, scale=0, shift=0.0,
+                            fair=True):
+        """The same scores of the sampler's paths without bringing them back
+        (``ngp_mixture_path_scores``)."""
+        return self.ctx.mixture_path_scores(w, mu, sigma, draws, seed, inv, y, windows, scale, shift,
+                                            fair)
+
     def mixture_cdf(self, w, mu, var, x):
         """CDF of a mixture's per-date marginals on the device (``ngp_mixture_cdf``)."""
         return self.ctx.mixture_cdf(w, mu, var, x)
@@ -1774,24 +1786,9 @@ class PathTargets:
         return self._values[t]
 
 
-def path_targets(mixes_or_arrays, targets, probs, draws: int, seed=None, inv_transformation=None, *,
-                 engine=None, want_values: bool = False) -> PathTargets:
-    """Functionals of whole sample paths of forecast mixtures on the original scale: totals over a
-    window, peak value and date, exceedance, change between two dates (include/ngp.h "trajectory
-    targets").
-
-    ``mixes_or_arrays``: one ``MixtureMVN`` or a sequence of them on the same dates (their paths
-    are pooled; mixture j is keyed by ``seed[j]``, taken from its own stream when ``seed`` is None,
-    as ``rand_lockstep`` takes it), or arrays ``(w [S,P], mu [P,S,m], sigma [P,m,m])`` with one
-    seed — S mixtures over shared components, the layout of ``ngp_mixture_sample`` — or
-    ``(w [S,P], mu [S,P,m], sigma [S,P,m,m])`` with S seeds.  The paths are those the sampler draws
-    for the same arguments.  ``targets``: ``(kind, j0, j1[, thr])``, kind one of "sum", "max",
-    "diff", "argmax", "exceed", window inclusive.
-
-    ``inv_transformation`` None (identity) or a callable that carries ``ngp_inv`` (the inverses of
-    ``nowcast.get_transformations``) runs wholly on the device when the engine has
-    ``mixture_path_targets``; any other callable, or an engine without that entry, takes the host
-    path — the engine's sampler (numpy without one), then numpy with the same definitions."""
+def _mixture_arrays(mixes_or_arrays, seed, who: str):
+    """(w, mu, sigma, seed) in the sampler's layouts from one ``MixtureMVN``, a sequence of them or
+    the arrays themselves (``path_targets``); seed a scalar (shared components) or a list of S."""
     if isinstance(mixes_or_arrays, MixtureMVN):
         mixes_or_arrays = [mixes_or_arrays]
     if isinstance(mixes_or_arrays[0], MixtureMVN):
@@ -1801,7 +1798,7 @@ def path_targets(mixes_or_arrays, targets, probs, draws: int, seed=None, inv_tra
         elif np.isscalar(seed):
             seed = [int(seed)] if len(mixes) == 1 else None
         if seed is None or len(seed) != len(mixes):
-            raise ValueError("path_targets: one seed per mixture")
+            raise ValueError(f"{who}: one seed per mixture")
         w = np.stack([mx.weights for mx in mixes])
         mu = np.stack([mx.means for mx in mixes])
         sigma = np.stack([mx.covs for mx in mixes])
@@ -1809,23 +1806,16 @@ def path_targets(mixes_or_arrays, targets, probs, draws: int, seed=None, inv_tra
     else:
         w, mu, sigma = (np.asarray(a, dtype=np.float64) for a in mixes_or_arrays)
         if seed is None:
-            raise ValueError("path_targets: arrays need a seed")
+            raise ValueError(f"{who}: arrays need a seed")
         seed = int(seed) if np.isscalar(seed) else [int(v) for v in seed]
+    return w, mu, sigma, seed
+
+
+def _host_paths(engine, w, mu, sigma, draws: int, seed, inv_transformation):
+    """x [N, m]: the engine's sampler (numpy without one) for the arguments of ``_mixture_arrays``,
+    then the inverse transformation in numpy — the host path of ``path_targets``."""
     indep = not np.isscalar(seed)
     S, m, N = w.shape[0], mu.shape[2], w.shape[0] * int(draws)
-    tgs = _target_tuples(targets, m)
-    probs = np.asarray(probs, dtype=np.float64).reshape(-1)
-    if probs.size < 1 or not np.all((probs > 0.0) & (probs < 1.0)):
-        raise ValueError("path_targets: levels in (0, 1)")
-    inv = (0, 0.0, 0.0, 0.0) if inv_transformation is None else getattr(inv_transformation, "ngp_inv", None)
-    device = getattr(engine, "mixture_path_targets", None) if engine is not None else None
-    if device is not None and inv is not None:
-        o = device(w, mu, sigma, int(draws), seed, inv, tgs, probs, want_values)
-        bad = np.argwhere(np.atleast_1d(o["info"]) != 0)
-        if bad.size:
-            raise PosDefException(int(o["info"][tuple(bad[0])]), int(bad[0][-1]))
-        return PathTargets(tgs, probs, o["q"], o["mean"], o["count"], o["hist"], N, o["values"], True)
-    # host path: the sampler's draws, numpy for the rest
     sampler = getattr(engine, "mixture_sample_indep" if indep else "mixture_sample", None)
     if sampler is not None:
         x, _, info = sampler(w, mu, sigma, int(draws), seed)
@@ -1853,6 +1843,177 @@ def path_targets(mixes_or_arrays, targets, probs, draws: int, seed=None, inv_tra
     if inv_transformation is not None:
         from .nowcast import _apply
         x = _apply(inv_transformation, x)
+    return x
+
+
+def path_targets(mixes_or_arrays, targets, probs, draws: int, seed=None, inv_transformation=None, *,
+                 engine=None, want_values: bool = False) -> PathTargets:
+    """Functionals of whole sample paths of forecast mixtures on the original scale: totals over a
+    window, peak value and date, exceedance, change between two dates (include/ngp.h "trajectory
+    targets").
+
+    ``mixes_or_arrays``: one ``MixtureMVN`` or a sequence of them on the same dates (their paths
+    are pooled; mixture j is keyed by ``seed[j]``, taken from its own stream when ``seed`` is None,
+    as ``rand_lockstep`` takes it), or arrays ``(w [S,P], mu [P,S,m], sigma [P,m,m])`` with one
+    seed — S mixtures over shared components, the layout of ``ngp_mixture_sample`` — or
+    ``(w [S,P], mu [S,P,m], sigma [S,P,m,m])`` with S seeds.  The paths are those the sampler draws
+    for the same arguments.  ``targets``: ``(kind, j0, j1[, thr])``, kind one of "sum", "max",
+    "diff", "argmax", "exceed", window inclusive.
+
+    ``inv_transformation`` None (identity) or a callable that carries ``ngp_inv`` (the inverses of
+    ``nowcast.get_transformations``) runs wholly on the device when the engine has
+    ``mixture_path_targets``; any other callable, or an engine without that entry, takes the host
+    path — the engine's sampler (numpy without one), then numpy with the same definitions."""
+    w, mu, sigma, seed = _mixture_arrays(mixes_or_arrays, seed, "path_targets")
+    m, N = mu.shape[2], w.shape[0] * int(draws)
+    tgs = _target_tuples(targets, m)
+    probs = np.asarray(probs, dtype=np.float64).reshape(-1)
+    if probs.size < 1 or not np.all((probs > 0.0) & (probs < 1.0)):
+        raise ValueError("path_targets: levels in (0, 1)")
+    inv = (0, 0.0, 0.0, 0.0) if inv_transformation is None else getattr(inv_transformation, "ngp_inv", None)
+    device = getattr(engine, "mixture_path_targets", None) if engine is not None else None
+    if device is not None and inv is not None:
+        o = device(w, mu, sigma, int(draws), seed, inv, tgs, probs, want_values)
+        bad = np.argwhere(np.atleast_1d(o["info"]) != 0)
+        if bad.size:
+            raise PosDefException(int(o["info"][tuple(bad[0])]), int(bad[0][-1]))
+        return PathTargets(tgs, probs, o["q"], o["mean"], o["count"], o["hist"], N, o["values"], True)
+    x = _host_paths(engine, w, mu, sigma, int(draws), seed, inv_transformation)
     values = path_functionals(x, tgs)
     q, mean, count, hist = summarize_path_values(values, tgs, probs, m)
     return PathTargets(tgs, probs, q, mean, count, hist, N, values if want_values else None, False)
+
+
+# ---------------------------------------------------------------------------------------------
+# scores of the paths themselves: energy score and sample CRPS (include/ngp.h "scores of the
+# paths themselves"; the reference's crps / score_forecast, docs/vignettes/getting-started.jl:689-718)
+# ---------------------------------------------------------------------------------------------
+SCORE_SCALES = {"natural": 0, "log": 1}
+NGP_INFO_NOT_FINITE = -3
+_SCORE_CHUNK = 1 << 22          # numbers the numpy fallback holds per block of pairs
+
+
+def _score_scale(scale) -> int:
+    code = SCORE_SCALES[scale] if isinstance(scale, str) and scale in SCORE_SCALES else scale
+    if isinstance(code, str) or int(code) not in SCORE_SCALES.values():
+        raise ValueError(f"scale {scale!r}: one of {sorted(SCORE_SCALES)}")
+    return int(code)
+
+
+def _score_windows(windows, m: int):
+    """None -> every single date, then the whole horizon; else [(j0, j1), ...] inclusive"""
+    if windows is None:
+        return [(j, j) for j in range(m)] + [(0, m - 1)], list(range(m)), [m]
+    win = [(int(a), int(b)) for a, b in windows]
+    if not win or any(not 0 <= a <= b < m for a, b in win):
+        raise ValueError(f"windows: at least one (j0, j1) with 0 <= j0 <= j1 < {m}")
+    single = [i for i, (a, b) in enumerate(win) if a == b]
+    return win, single, [i for i in range(len(win)) if i not in set(single)]
+
+
+def host_ensemble_scores(x, y, windows, scale: int = 0, shift: float = 0.0, fair: bool = True):
+    """numpy fallback of ``ngp_ensemble_scores`` with the same definitions: x [N, m] paths, y [m],
+    windows [(j0, j1)].  The pairs are worked in blocks of rows, the squared distance from
+    differences date by date, so that it never holds N^2 numbers at once."""
+    x, y = np.asarray(x, dtype=np.float64), np.asarray(y, dtype=np.float64)
+    N = x.shape[0]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        u = np.log(x + shift) if scale == 1 else x
+        v = np.log(y + shift) if scale == 1 else y
+    W = len(windows)
+    es, to, tp = np.full(W, np.nan), np.full(W, np.nan), np.full(W, np.nan)
+    info = np.zeros(W, dtype=np.int32)
+    D = 0.5 * N * (N - 1) if fair else 0.5 * N * N
+    rows = max(1, _SCORE_CHUNK // N)
+    idx = np.arange(N)
+    for wi, (j0, j1) in enumerate(windows):
+        uw = u[:, j0:j1 + 1]
+        if not np.all(np.isfinite(uw)):
+            info[wi] = NGP_INFO_NOT_FINITE
+            continue
+        with np.errstate(over="ignore", invalid="ignore"):
+            to[wi] = np.sqrt(((uw - v[j0:j1 + 1]) ** 2).sum(axis=1)).sum() / N
+        total = 0.0
+        for a in range(0, N, rows):
+            blk = uw[a:a + rows]
+            d2 = np.zeros((blk.shape[0], N))
+            for j in range(uw.shape[1]):
+                df = blk[:, j][:, None] - uw[:, j][None, :]
+                with np.errstate(over="ignore", invalid="ignore"):
+                    d2 += df * df
+            total += np.sqrt(d2)[idx[None, :] > idx[a:a + rows][:, None]].sum()      # i < k only
+        if not (np.isfinite(to[wi]) and np.isfinite(total)):      # finite values, squares that overflow
+            to[wi], info[wi] = np.nan, NGP_INFO_NOT_FINITE
+            continue
+        tp[wi] = total / D
+        es[wi] = to[wi] - 0.5 * tp[wi]
+    return dict(es=es, term_obs=to, term_pair=tp, info=info)
+
+
+class EnsembleScores:
+    """Scores of an ensemble of paths per window of dates (``ensemble_scores``):
+
+        crps     the one-date windows' scores, in window order: the sample CRPS per date
+        energy   the scores of the windows of more than one date (by default one: the horizon)
+        terms    dict(term_obs = mean |X - y|, term_pair = mean |X - X'|), per window
+        es, info, windows   every window's score and status (NGP_INFO_NOT_FINITE: NaN)
+    """
+
+    def __init__(self, windows, out, single, longer, device=False):
+        self.windows = list(windows)
+        self.es, self.info = out["es"], out["info"]
+        self.terms = dict(term_obs=out["term_obs"], term_pair=out["term_pair"])
+        self.crps, self.energy = self.es[single], self.es[longer]
+        self.device = bool(device)
+
+
+def ensemble_scores(x, y, windows=None, scale="natural", shift=0.0, fair=True, engine=None) -> EnsembleScores:
+    """Energy score ES = E|X - y| - 1/2 E|X - X'| of the draws x [dates, draws] (as ``forecast``
+    returns them) against y [dates], per window of dates; a one-date window is the sample CRPS the
+    reference's vignette computes.  ``windows`` None: every single date plus the whole horizon.
+    ``scale`` "natural" or "log" (of x + shift); ``fair`` True: pairs i < j over N (N - 1) / 2 (the
+    vignette's estimator), False: over N^2 / 2 (scoringutils).  An engine with ``ensemble_scores``
+    does the all-pairs work on the device; without one numpy does, in blocks of pairs."""
+    x = np.asarray(x, dtype=np.float64)
+    y = np.asarray(y, dtype=np.float64).reshape(-1)
+    if x.ndim != 2 or x.shape[0] != y.size or x.shape[0] < 1 or x.shape[1] < 1:
+        raise ValueError("ensemble_scores: x [dates, draws], y [dates]")
+    code = _score_scale(scale)
+    if not (np.isfinite(shift) and shift >= 0.0):
+        raise ValueError("ensemble_scores: shift finite and >= 0")
+    if fair and x.shape[1] < 2:
+        raise ValueError("ensemble_scores: fair=True needs two draws")
+    if not np.all(np.isfinite(y)) or (code == 1 and not np.all(y + shift > 0.0)):
+        raise ValueError("ensemble_scores: y finite, and y + shift > 0 on the log scale")
+    win, single, longer = _score_windows(windows, x.shape[0])
+    paths = np.ascontiguousarray(x.T)
+    device = getattr(engine, "ensemble_scores", None) if engine is not None else None
+    if device is not None:
+        return EnsembleScores(win, device(paths, y, win, code, float(shift), bool(fair)), single, longer, True)
+    return EnsembleScores(win, host_ensemble_scores(paths, y, win, code, float(shift), bool(fair)),
+                          single, longer, False)
+
+
+def path_scores(mixes_or_arrays, y, draws: int, seed=None, inv_transformation=None, *, windows=None,
+                scale="natural", shift=0.0, fair=True, engine=None) -> EnsembleScores:
+    """``ensemble_scores`` of the paths the sampler draws from forecast mixtures (the arguments of
+    ``path_targets``), mapped through ``inv_transformation``.  With an engine that has
+    ``mixture_path_scores`` and an inverse that carries ``ngp_inv`` the paths are drawn, mapped and
+    scored on the device and never come back; otherwise the host path of ``path_targets`` draws
+    them and ``ensemble_scores`` scores them."""
+    w, mu, sigma, seed = _mixture_arrays(mixes_or_arrays, seed, "path_scores")
+    m = mu.shape[2]
+    y = np.asarray(y, dtype=np.float64).reshape(-1)
+    inv = (0, 0.0, 0.0, 0.0) if inv_transformation is None else getattr(inv_transformation, "ngp_inv", None)
+    device = getattr(engine, "mixture_path_scores", None) if engine is not None else None
+    if device is None or inv is None:
+        x = _host_paths(engine, w, mu, sigma, int(draws), seed, inv_transformation)
+        return ensemble_scores(x.T, y, windows, scale, shift, fair, engine)
+    if y.size != m:
+        raise ValueError("path_scores: y [dates]")
+    win, single, longer = _score_windows(windows, m)
+    o = device(w, mu, sigma, int(draws), seed, inv, y, win, _score_scale(scale), float(shift), bool(fair))
+    bad = np.argwhere(np.atleast_1d(o["chol_info"]) != 0)
+    if bad.size:
+        raise PosDefException(int(o["chol_info"][tuple(bad[0])]), int(bad[0][-1]))
+    return EnsembleScores(win, o, single, longer, True)

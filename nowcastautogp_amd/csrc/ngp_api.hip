@@ -3596,6 +3596,147 @@ extern "C" ngp_status ngp_mixture_path_targets_indep(ngp_ctx *c, int32_t P, int3
 }
 
 // ---------------------------------------------------------------------------------------
+// Energy score and sample CRPS of paths (ngp_ensemble_scores / ngp_mixture_path_scores; kernels:
+// ngp_score_kernels.h)
+//
+// The host validates, stages the paths (ensemble form) or has the sampler draw them into a device
+// buffer (mixture form), launches, and turns the two [W] totals into the scores.
+namespace {
+struct ScoreMixture {       // the mixture form's inputs (null for the ensemble form)
+    int32_t P, S, draws, indep;
+    const double *w, *mu, *sigma;
+    const uint64_t *seeds;
+    const ngp_inv_transform *inv;
+    int32_t *chol_info;
+};
+
+// what both forms ask of N, m, the windows and y; TOO_LARGE before any array is read
+ngp_status score_args(int64_t N, int32_t m, int32_t m_max, const double *y, int32_t scale, double shift,
+                      int32_t fair, int32_t W, const int32_t *win, const double *es) {
+    if (!y || !win || !es || N < 1 || m < 1 || W < 1) return NGP_ERR_ARG;
+    if (scale != NGP_SCORE_NATURAL && scale != NGP_SCORE_LOG) return NGP_ERR_ARG;
+    if ((fair != 0 && fair != 1) || (fair == 1 && N < 2)) return NGP_ERR_ARG;
+    if (!std::isfinite(shift) || shift < 0.0) return NGP_ERR_ARG;
+    if (N > SCORE_MAX_PATHS || W > SCORE_MAX_WINDOWS || m > m_max) return NGP_ERR_TOO_LARGE;
+    for (int32_t w = 0; w < W; ++w)
+        if (win[2 * w] < 0 || win[2 * w + 1] >= m || win[2 * w] > win[2 * w + 1]) return NGP_ERR_ARG;
+    for (int32_t j = 0; j < m; ++j)
+        if (!std::isfinite(y[j]) || (scale == NGP_SCORE_LOG && !(y[j] + shift > 0.0))) return NGP_ERR_ARG;
+    return NGP_OK;
+}
+
+ngp_status scores_impl(ngp_ctx *c, int32_t N, int32_t m, const double *x, const ScoreMixture *mix,
+                       const double *y, int32_t scale, double shift, int32_t fair, int32_t W,
+                       const int32_t *win, double *es, double *term_obs, double *term_pair,
+                       int32_t *info) {
+    const size_t Nn = (size_t)N, Wn = (size_t)W, nxm = Nn * (size_t)m;
+    const size_t prow = (size_t)score_tile_pairs(N), orow = (size_t)score_slices(N);
+    const size_t prow1 = (size_t)score_folded((int64_t)prow), orow1 = (size_t)score_folded((int64_t)orow);
+    bool long_windows = false;
+    for (int32_t w = 0; w < W; ++w) long_windows = long_windows || win[2 * w + 1] - win[2 * w] >= SCORE_FOLD;
+    const size_t B = mix ? (mix->indep ? (size_t)mix->S * mix->P : (size_t)mix->P) : 0;
+    const size_t nw = mix ? (size_t)mix->S * mix->P : 0, nmu = nw * (size_t)m, nsg = B * (size_t)m * m;
+
+    std::vector<int32_t> hflag((size_t)m, 0), hcinfo(B, 0);
+    std::vector<double> hobs(Wn, 0.0), hpair(Wn, 0.0);
+    DevCall call(c);
+    if (call.status()) return call.status();
+    c->refresh_mem_cap();
+    if (8.0 * ((double)nxm * 2.0 + (double)Wn * (double)(prow + prow1 + orow + orow1) +
+               (double)(nw + nmu + nsg)) > (double)c->mem_cap)
+        return NGP_ERR_TOO_LARGE;
+    ScoreBufs b{};
+    double *dx = nullptr, *dy = nullptr, *dw = nullptr, *dmu = nullptr, *dsg = nullptr;
+    int32_t *dwin = nullptr, *dcinfo = nullptr;
+    uint64_t *dseeds = nullptr;
+    call.take(&dx, nxm).take(&dy, (size_t)m).take(&b.u, nxm).take(&b.v, (size_t)m).take(&b.flag, (size_t)m)
+        .take(&dwin, 2 * Wn).take(&b.pair[0], prow * Wn).take(&b.pair[1], prow1 * Wn)
+        .take(&b.obs[0], orow * Wn).take(&b.obs[1], orow1 * Wn);
+    if (mix) {
+        call.take(&dw, nw).take(&dmu, nmu).take(&dsg, nsg).take(&dcinfo, B);
+        if (mix->indep) call.take(&dseeds, (size_t)mix->S);
+        call.up(dw, mix->w, 8 * nw).up(dmu, mix->mu, 8 * nmu).up(dsg, mix->sigma, 8 * nsg);
+        if (mix->indep) call.up(dseeds, mix->seeds, 8 * (size_t)mix->S);
+        call.run([&] {   // the sampler as ngp_mixture_sample launches it, its paths kept on the device
+            launch_mixture_sample(mix->P, mix->S, m, dw, dmu, dsg, mix->draws, mix->indep ? 0 : mix->seeds[0],
+                                  dseeds, dx, nullptr, dcinfo, c->stream);
+        });
+    } else {
+        call.up(dx, x, 8 * nxm);
+    }
+    b.x = dx; b.y = dy; b.win = dwin;
+    const double *dobs = nullptr, *dpair = nullptr;
+    call.up(dy, y, 8 * (size_t)m).up(dwin, win, 8 * Wn)
+        .run([&] {
+            return launch_scores(N, m, W, long_windows, mix ? mix->inv : nullptr, scale, shift, b, &dobs,
+                                 &dpair, c->stream);
+        });
+    if (call.status()) return call.status();
+    call.down(hobs.data(), dobs, 8 * Wn).down(hpair.data(), dpair, 8 * Wn).down(hflag.data(), b.flag, 4 * (size_t)m);
+    if (mix) call.down(hcinfo.data(), dcinfo, 4 * B);
+    if (call.sync()) return call.status();
+
+    // a failed component that paths can come from: nothing the call returns is free of it
+    bool failed = false;
+    if (mix) {
+        if (mix->chol_info) std::copy(hcinfo.begin(), hcinfo.end(), mix->chol_info);
+        for (size_t k = 0; k < B && !failed; ++k) {
+            if (!hcinfo[k]) continue;
+            if (mix->indep) failed = mix->w[k] > 0.0;
+            else for (int32_t sc = 0; sc < mix->S && !failed; ++sc) failed = mix->w[(size_t)sc * mix->P + k] > 0.0;
+        }
+    }
+    const double nan = std::nan("");
+    const double pairs = fair ? 0.5 * (double)N * (double)(N - 1) : 0.5 * (double)N * (double)N;
+    for (int32_t w = 0; w < W; ++w) {
+        bool bad = failed;
+        for (int32_t j = win[2 * w]; j <= win[2 * w + 1] && !bad; ++j) bad = hflag[j] != 0;
+        // finite values whose differences overflow when squared (1e155 and beyond; the largest finite
+        // double a Box-Cox image is capped at): the window has no finite score either
+        bad = bad || !std::isfinite(hobs[w]) || !std::isfinite(hpair[w]);
+        const double to = bad ? nan : hobs[w] / (double)N;
+        const double tp = bad ? nan : hpair[w] / pairs;
+        es[w] = bad ? nan : to - 0.5 * tp;
+        if (term_obs) term_obs[w] = to;
+        if (term_pair) term_pair[w] = tp;
+        if (info) info[w] = bad ? NGP_INFO_NOT_FINITE : 0;
+    }
+    return NGP_OK;
+}
+}  // namespace
+
+extern "C" ngp_status ngp_ensemble_scores(ngp_ctx *c, int32_t N, int32_t m, const double *x,
+                                          const double *y, int32_t scale, double shift, int32_t fair,
+                                          int32_t W, const int32_t *win, double *es, double *term_obs,
+                                          double *term_pair, int32_t *info) {
+    if (!c || !x) return NGP_ERR_ARG;
+    const ngp_status st = score_args(N, m, SCORE_MAX_DATES, y, scale, shift, fair, W, win, es);
+    if (st) return st;
+    return scores_impl(c, N, m, x, nullptr, y, scale, shift, fair, W, win, es, term_obs, term_pair, info);
+}
+
+extern "C" ngp_status ngp_mixture_path_scores(ngp_ctx *c, int32_t P, int32_t S, int32_t m,
+                                              const double *w, const double *mu, const double *sigma,
+                                              int32_t indep, int32_t draws, const uint64_t *seeds,
+                                              const void *inv_, const double *y, int32_t scale,
+                                              double shift, int32_t fair, int32_t W, const int32_t *win,
+                                              double *es, double *term_obs, double *term_pair,
+                                              int32_t *info, int32_t *chol_info) {
+    const ngp_inv_transform *inv = (const ngp_inv_transform *)inv_;
+    if (!c || !w || !mu || !sigma || !seeds || !inv || P <= 0 || S <= 0 || m <= 0 || draws < 1 ||
+        (indep != 0 && indep != 1))
+        return NGP_ERR_ARG;
+    if (!inv_transform_ok(inv) || (inv->kind == NGP_INV_BOXCOX && !(inv->cap > 0.0))) return NGP_ERR_ARG;
+    const int64_t N = (int64_t)S * draws;
+    const ngp_status st = score_args(N, m, NGP_MAX_AUX, y, scale, shift, fair, W, win, es);
+    if (st) return st;
+    if ((int64_t)S * P > INT32_MAX) return NGP_ERR_TOO_LARGE;
+    const ScoreMixture mix{P, S, draws, indep, w, mu, sigma, seeds, inv, chol_info};
+    return scores_impl(c, (int32_t)N, m, nullptr, &mix, y, scale, shift, fair, W, win, es, term_obs,
+                       term_pair, info);
+}
+
+// ---------------------------------------------------------------------------------------
 // Combining concurrent callers (flat combining)
 //
 // The reference enters the boundary from one task per nowcast scenario (Threads.@spawn,

@@ -358,6 +358,34 @@ struct PathBufs {
 };
 hipError_t launch_path_targets(const PathGeom &g, const PathBufs &p, const ngp_inv_transform &inv,
                                uint64_t seed, hipStream_t s);
+// ---- energy score and sample CRPS of an ensemble of paths (ngp_score_kernels.h) ---------------
+// The pair term is cut into SCORE_TILE x SCORE_TILE tiles of the upper triangle of (path, path),
+// one partial per (tile, window) in slab [score_tile_pairs(N)][W]; term_obs leaves one partial per
+// (slice of SCORE_THREADS paths, window).  Both slabs are then folded SCORE_REDUCE rows at a time,
+// in row order, until one row is left.
+constexpr int SCORE_THREADS = 256;
+constexpr int SCORE_TILE = 128;        // paths per tile side: a thread owns 8 x 8 pairs
+constexpr int SCORE_DCHUNK = 16;       // dates of both tiles staged in LDS at a time (32 KiB)
+constexpr int SCORE_FOLD = 2048;       // dates after which a squared distance moves to a second accumulator
+constexpr int SCORE_REDUCE = 2048;     // rows of a slab one workgroup folds
+constexpr int SCORE_MAX_PATHS = 1 << 20, SCORE_MAX_WINDOWS = 4096, SCORE_MAX_DATES = 65535;
+static_assert(SCORE_FOLD % SCORE_DCHUNK == 0, "a fold falls on a chunk boundary");
+inline int64_t score_tiles(int64_t N) { return (N + SCORE_TILE - 1) / SCORE_TILE; }
+inline int64_t score_tile_pairs(int64_t N) { const int64_t nt = score_tiles(N); return nt * (nt + 1) / 2; }
+inline int64_t score_slices(int64_t N) { return (N + SCORE_THREADS - 1) / SCORE_THREADS; }
+inline int64_t score_folded(int64_t rows) { return (rows + SCORE_REDUCE - 1) / SCORE_REDUCE; }
+struct ScoreBufs {
+    const double *x, *y;           // [N][m] paths (path-major), [m] observations, original scale
+    double *u, *v;                 // [m][N] s(paths), [m] s(y)
+    int32_t *flag;                 // [m] nonzero: a value of that date is not finite on the score scale (zeroed by the launcher)
+    const int32_t *win;            // [W][2]
+    double *pair[2], *obs[2];      // slabs: [score_tile_pairs(N)][W] / [score_folded(..)][W]; [score_slices(N)][W] / [score_folded(..)][W]
+};
+// inv: the inverse transformation applied to x first, or null.  obs_sum / pair_sum: where the [W]
+// totals (before the division by N and D) are left, inside the slabs.
+hipError_t launch_scores(int N, int m, int W, bool long_windows, const ngp_inv_transform *inv,
+                         int scale, double shift, const ScoreBufs &b, const double **obs_sum,
+                         const double **pair_sum, hipStream_t s);
 // ---- the leapfrog step of ngp_grad_job_hmc (ngp_hmc_kernels.h) -------------------------------
 // INIT writes theta(z0) for evaluation 0; FIRST, MIDDLE and LAST follow evaluations 0, 1 .. L - 1
 // and L of a trajectory of L leapfrogs.

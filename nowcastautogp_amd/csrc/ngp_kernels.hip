@@ -697,6 +697,7 @@ void launch_mixture_sample(int P, int S, int m, const double *w, const double *m
 }  // namespace ngp
 #include "ngp_path_kernels.h"   // uses philox4x32_10, u01 and small_chol_kernel above
 #include "ngp_mixture_mapped_kernels.h"   // uses path_inv and the block reductions of ngp_mixture_kernels.h
+#include "ngp_score_kernels.h"   // uses path_inv and mix_block_sum
 namespace ngp {
 
 // ---------------------------------------------------------------------------------------

@@ -39,7 +39,7 @@ GPConfig = gp.GPConfig
 __all__ = ["TData", "GPModel", "GPConfig", "create_transformed_data", "make_and_fit_model",
            "forecast", "forecast_with_nowcasts", "create_nowcast_data", "forecast_mixture",
            "forecast_mixture_with_nowcasts", "get_transformations", "forecast_targets",
-           "forecast_targets_with_nowcasts"]
+           "forecast_targets_with_nowcasts", "score_forecast", "forecast_scores_with_nowcasts"]
 
 
 class TData:
@@ -687,6 +687,90 @@ def forecast_targets_with_nowcasts(base_model: GPModel, nowcasts: Sequence[TData
     x = np.ascontiguousarray(x)
     return _targets_of_paths(x if inv_transformation is None else _apply(inv_transformation, x),
                              targets, probs, want_values)
+
+
+def score_forecast(forecasts, y, *, horizon: Optional[int] = None, scale="log", shift: float = 0.0,
+                   fair: bool = True, engine=None):
+    """The vignette's ``score_forecast`` (reference docs/vignettes/getting-started.jl:689-718, with
+    ``data_transform = log`` as at :746) on a draws matrix [dates, draws] from any of the five
+    approaches, ``forecast_n_hmc`` included: ``(mean CRPS over the first `horizon` dates, energy
+    score of those dates' paths)``, both on ``scale`` ("log": of value + shift; "natural").
+    ``horizon`` None: every date.  ``fair`` True is the vignette's estimator.  ``engine``: one with
+    ``ensemble_scores`` (``model._eng()``) does the all-pairs work on the device, None numpy."""
+    x = np.asarray(forecasts, dtype=np.float64)
+    y = np.asarray(y, dtype=np.float64).reshape(-1)
+    h = x.shape[0] if horizon is None else int(horizon)
+    assert 1 <= h <= x.shape[0], "Not enough data to score full horizon"
+    assert y.size >= h, "Not enough data to score full horizon"
+    sc = autogp.ensemble_scores(x[:h], y[:h], None, scale, shift, fair, engine)
+    return float(np.mean(sc.crps)), float(sc.energy[0])
+
+
+def forecast_scores_with_nowcasts(base_model: GPModel, nowcasts: Sequence[TData], forecast_dates, y,
+                                  forecast_draws_per_nowcast: int, *, windows=None, scale="log",
+                                  shift: float = 0.0, fair: bool = True,
+                                  inv_transformation: Optional[Callable] = None, n_mcmc: int = 0,
+                                  n_hmc: int = 0, ess_threshold: float = 0.0, lockstep: bool = True,
+                                  hmc_config: Optional[dict] = None) -> "autogp.EnsembleScores":
+    """``autogp.ensemble_scores`` of the paths ``forecast_with_nowcasts`` returns against ``y``
+    [dates] (original scale): the sample CRPS per date and the energy score of the horizon
+    (``windows`` None), or of the given windows of dates.
+
+    Follows ``forecast_targets_with_nowcasts`` step for step — same asserts, weight update,
+    resampling, use of the random streams and sampler seed — so from one snapshot and seed it
+    scores exactly the matrix ``forecast_with_nowcasts`` would return; where that function goes
+    through the device the paths are drawn, mapped and scored there and never come back.
+    ``forecast_n_hmc`` (a new mixture before every draw) is not taken: score those draws with
+    ``score_forecast``.  Sharded runs raise ``NotImplementedError``."""
+    assert len(nowcasts) > 0, "nowcasts vector must not be empty"
+    assert not (n_mcmc > 0 and n_hmc == 0), \
+        "If n_mcmc > 0, n_hmc must also be > 0 for MCMC refinement"
+    assert 0.0 <= ess_threshold <= 1.0, "ess_threshold must be between 0 and 1"
+    if autogp.distributed.world()[1] > 1:
+        raise NotImplementedError("forecast_scores_with_nowcasts: single-rank runs only")
+    dates = list(forecast_dates)
+    draws = int(forecast_draws_per_nowcast)
+    eng = base_model._eng()
+    kw = dict(windows=windows, scale=scale, shift=shift, fair=fair, engine=eng)
+
+    def of_host_paths(x):       # x [dates, N] on the model's scale, drawn on the host
+        x = np.ascontiguousarray(x)
+        return autogp.ensemble_scores(x if inv_transformation is None else _apply(inv_transformation, x),
+                                      y, **kw)
+
+    same_dates = all(list(nc.ds) == list(nowcasts[0].ds) for nc in nowcasts)
+    if n_mcmc == 0 and n_hmc == 0 and same_dates and lockstep:
+        w, means, covs, low, rng, sampler = _nowcast_mixtures_batched(base_model, nowcasts, dates,
+                                                                      ess_threshold)
+        P = w.shape[1]
+        if sampler is None:       # forecast_with_nowcasts draws these on the host, scenario by scenario
+            res = np.empty((len(dates), len(nowcasts) * draws))
+            for sc in range(len(nowcasts)):
+                wsc = w[sc]
+                if low[sc]:
+                    wsc = np.bincount(rng.choice(P, size=P, p=wsc), minlength=P) / P
+                res[:, sc * draws:(sc + 1) * draws] = autogp.MixtureMVN(means[:, sc, :], covs, wsc,
+                                                                        rng).rand(draws)
+            return of_host_paths(res)
+        if low.any():
+            w[low] = rng.multinomial(P, w[low]) / P
+        seed = int(rng.integers(0, 2**63 - 1))
+        return autogp.path_scores((w, means, covs), y, draws, seed, inv_transformation, **kw)
+    if lockstep and same_dates:
+        models = _refined_clones_lockstep(base_model, nowcasts, n_mcmc, n_hmc, ess_threshold,
+                                          hmc_config)
+        mixes = autogp.predict_mvn_lockstep(models, dates)
+        m, P = mixes[0].means.shape[1], mixes[0].means.shape[0]
+        if (getattr(eng, "mixture_sample_indep", None) is not None and len(mixes) >= 2 and draws > 1
+                and m > 0 and all(mx.sampler is not None and mx.means.shape == (P, m) for mx in mixes)):
+            return autogp.path_scores(mixes, y, draws, None, inv_transformation, **kw)
+        return of_host_paths(np.hstack(autogp.rand_lockstep(mixes, draws, eng)))
+    cols = []
+    for nc in nowcasts:
+        mdl = _clone_for_scenario(base_model)
+        _refine_scenario(mdl, nc, n_mcmc, n_hmc, ess_threshold, hmc_config)
+        cols.append(autogp.predict_mvn(mdl, dates).rand(draws))
+    return of_host_paths(np.hstack(cols))
 
 
 def _clone_for_scenario(base_model: GPModel) -> GPModel:
