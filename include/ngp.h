@@ -805,6 +805,39 @@ ngp_status ngp_factor_components_nowcast(ngp_factor *f, int32_t d, const double 
                                          double *logml_full, double *mu, double *sigma, double *var,
                                          int32_t *info);
 
+/* ---- long horizons from the resident factor ---------------------------------------
+ * ngp_factor_nowcast carries its dates as aux rows of the factorisation, so tail + d + m + 1 <=
+ * NGP_MAX_AUX.  ngp_factor_predict_long does not: the dates (with the tail observations, the
+ * appended points and y) are the right-hand-side panel of ONE blocked triangular solve against the
+ * resident L (fp64 matrix cores), followed by the Schur algebra of the small conditioning block.
+ * A daily grid over a year is one query.
+ *   d, t_add, D, y_add, t_new, noise_on_new   exactly as ngp_factor_nowcast; d = 0 (D, t_add and
+ *                                             y_add are then ignored) is plain predict
+ *   mu    [P][max(D, 1)][m]   the layout of ngp_factor_nowcast's mu
+ *   var   [P][m]              always written; the diagonal of sigma, bit for bit
+ *   sigma [P][m][m]           may be NULL: no m x m object is then formed, on the device or on the
+ *                             bus; mu and var have the same bits either way.  Exactly symmetric.
+ *   info  [P]                 as ngp_factor_logml, plus a non-positive pivot among the tail and the
+ *                             appended points (n0 + k, n0 = 64 floor(n / 64)); may be NULL.  An item
+ *                             with info > 0 is NaN in all its outputs; other items are not affected.
+ * For arguments both calls accept the result is ngp_factor_nowcast's, to rounding (same jitter and
+ * noise conventions).  The weight update (logml_base / logml_full) is not part of this call:
+ * ngp_factor_nowcast with m = 0 gives it.
+ * Limits (NGP_ERR_TOO_LARGE, before anything touches a device): m <= NGP_MAX_LONG_HORIZON and
+ * (n mod 64) + d + 1 <= NGP_MAX_AUX; then what the device memory holds for ONE particle — the
+ * particles are worked through in chunks sized to the memory, a large P is never refused.
+ * NGP_ERR_ARG: null f, t_new, mu or var; m < 1; d < 0; d > 0 with D < 1 or null t_add / y_add.
+ * Runs under the factor's spec (always fp64); thread-safe through the context's lock like the
+ * other factor queries; not combined with concurrent callers.  Bitwise reproducible from call to
+ * call (fixed summation orders, no floating-point atomics).  Profile classes: the panel fill and
+ * the small blocks are booked under 4, the solve under 6, the products of the solved rows under 2,
+ * the conditioning block and the per-date algebra under 3.                                     */
+#define NGP_MAX_LONG_HORIZON 4096
+ngp_status ngp_factor_predict_long(ngp_factor *f, int32_t d, const double *t_add,
+                                   int32_t D, const double *y_add,
+                                   int32_t m, const double *t_new, int32_t noise_on_new,
+                                   double *mu, double *var, double *sigma, int32_t *info);
+
 /* ---- measurement hooks -----------------------------------------------------
  * HIP-event timing of the kernels a job launches, on the stream they are
  * launched on.  Classes: 0 = chol_col_glds_kernel (fat steps: trailing-update

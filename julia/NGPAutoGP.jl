@@ -330,6 +330,31 @@ function nowcast(f::Factor, t_add::Vector{Float64}, y_add::Matrix{Float64}, t_ne
 end
 
 """
+One query for a horizon of up to `NGP_MAX_LONG_HORIZON` dates (include/ngp.h
+`ngp_factor_predict_long`): the dates are the panel of a triangular solve against the resident
+factor, not aux rows, so `horizon_room` does not bound them.  `t_add` / `y_add` as `nowcast`
+(empty: plain predict).  Without `want_sigma` no m x m array is formed.  No weight update:
+`nowcast` with no dates gives it.
+"""
+function predict_long(f::Factor, t_new::Vector{Float64};
+                      t_add::Vector{Float64} = Float64[],
+                      y_add::Matrix{Float64} = Matrix{Float64}(undef, 0, 1),
+                      noise_on_new::Bool = true, want_sigma::Bool = true)
+    P, d, D, m = f.P, length(t_add), max(size(y_add, 2), 1), length(t_new)
+    mu = Array{Float64}(undef, m, D, P)
+    var = Matrix{Float64}(undef, m, P)
+    sigma = want_sigma ? Array{Float64}(undef, m, m, P) : nothing
+    info = zeros(Int32, P)
+    check(ccall((:ngp_factor_predict_long, LIBNGP), Int32,
+                (Ptr{Cvoid}, Int32, Ptr{Float64}, Int32, Ptr{Float64}, Int32, Ptr{Float64}, Int32,
+                 Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}),
+                f.h, d, t_add, D, y_add, m, t_new, noise_on_new, mu, var,
+                want_sigma ? pointer(sigma) : Ptr{Float64}(C_NULL), info),
+          "ngp_factor_predict_long")
+    return (mu = mu, var = var, sigma = sigma, info = info)
+end
+
+"""
 The additive components of a program (include/ngp.h `ngp_kernel_components`): the maximal non-Plus
 subtrees under the root's Plus nodes, left to right, each a `Program` of its own.
 """

@@ -44,6 +44,7 @@ SYMBOLS = (
     "ngp_mixture_crps_mapped",
     "ngp_grad_job_hmc",
     "ngp_ensemble_scores", "ngp_mixture_path_scores",
+    "ngp_factor_predict_long",
 )
 
 
@@ -124,6 +125,8 @@ def load():
         "ngp_factor_nowcast": (i32, [vp, i32, f64p, i32, f64p, i32, f64p, i32, f64p, f64p, f64p,
                                      f64p, i32p]),
         "ngp_factor_destroy": (None, [vp]),
+        "ngp_factor_predict_long": (i32, [vp, i32, f64p, i32, f64p, i32, f64p, i32, f64p, f64p, f64p,
+                                          i32p]),
         "ngp_kernel_components": (i32, [KP, i32p, i32p, i32p, i32p, i32p]),
         "ngp_factor_components": (i32, [vp, i32p, KP, i32, f64p, f64p, f64p, f64p, i32p]),
         "ngp_kernel_terms": (i32, [KP, i32, i32, i32p, i32p, i32p, i32p, i32p, i32p, i32, f64p, i32]),
@@ -478,6 +481,29 @@ class Factor:
                                        dptr(lf), _nullable(mu), _nullable(sg), iptr(info)),
              "ngp_factor_nowcast")
         return dict(logml_base=lb, logml_full=lf, mu=mu, sigma=sg, info=info)
+
+    def predict_long(self, t_new, t_add=None, y_add=None, noise_on_new=True, want_sigma=True):
+        """One query for a horizon of up to ``NGP_MAX_LONG_HORIZON`` dates
+        (``ngp_factor_predict_long``): the dates are the panel of a triangular solve against the
+        resident L, not aux rows.  ``t_add`` [d] / ``y_add`` [D, d] as ``nowcast`` (None or empty:
+        plain predict).  Returns ``(mu [P, D, m], var [P, m], sigma [P, m, m] or None, info [P])``;
+        without ``want_sigma`` no m x m array is formed.  No weight update: ``nowcast`` with no
+        dates gives it."""
+        t_new = as_f64(t_new)
+        t_add = as_f64(t_add if t_add is not None else np.zeros(0))
+        d, m = t_add.size, t_new.size
+        y_add = as_f64(y_add).reshape(-1, d) if d else np.zeros((1, 0))
+        D = y_add.shape[0]
+        P = self.P
+        mu, var = np.empty((P, D, m)), np.empty((P, m))
+        sg = np.empty((P, m, m)) if want_sigma else None
+        info = np.zeros(P, dtype=np.int32)
+        _chk(load().ngp_factor_predict_long(self._h, d, dptr(t_add) if d else None, D,
+                                            dptr(y_add) if d else None, m,
+                                            dptr(t_new) if m else None, int(noise_on_new), dptr(mu),
+                                            dptr(var), _nullable(sg), iptr(info)),
+             "ngp_factor_predict_long")
+        return mu, var, sg, info
 
     def components(self, comps, t_new, want_sigma=True):
         """The joint posterior of every particle's additive parts (``ngp_factor_components``).

@@ -1327,6 +1327,30 @@ def predict_mvn(model: GPModel, ds, noise_on_new: bool = True) -> MixtureMVN:
     return predict_mvn_lockstep([model], ds, noise_on_new)[0]
 
 
+def _predict_marginals(model: GPModel, ds, noise_on_new: bool = True) -> "MixtureMarginals":
+    """``predict_mvn(model, ds).marginals()`` without the covariances where they are not needed: on
+    a horizon longer than one aux query carries, a model with a resident factor asks ONE long query
+    for means and variances alone (``Factor.predict_long`` with ``want_sigma=False``)."""
+    ds = list(ds)
+    t, _ = _group_obs([model])
+    fac = None
+    if (horizon_blocks(t.size, 0, len(ds)) is not None and distributed.world()[1] == 1
+            and not model.__dict__.get("_one_shot_predict", False)):
+        fac = model._factor()
+    if fac is None or not hasattr(fac, "predict_long"):
+        return predict_mvn(model, ds, noise_on_new).marginals(engine=model._eng())
+    t_new = model.ds_transform.apply(to_days(ds))
+    mu, var, _, info = fac.predict_long(t_new, noise_on_new=noise_on_new, want_sigma=False)
+    bad = np.flatnonzero(info)
+    if bad.size:
+        raise PosDefException(int(info[bad[0]]), int(bad[0]))
+    w, _ = distributed.normalize_log_weights(model.log_weights[:, None],
+                                             P_total=model.n_particles_total)
+    sl_ = model.y_transform.slope
+    return MixtureMarginals((mu[:, 0] - model.y_transform.intercept) / sl_, var / (sl_ * sl_),
+                            w[:, 0], engine=model._eng())
+
+
 def predict_mvn_lockstep(models: Sequence[GPModel], ds, noise_on_new: bool = True) -> List[MixtureMVN]:
     """``predict_mvn`` (reference src/forecasting.jl:46,66) of D models on the same dates: ONE
     engine call of P x D items (a single model goes through its resident factor), and in a
@@ -1356,6 +1380,10 @@ def predict_mvn_lockstep(models: Sequence[GPModel], ds, noise_on_new: bool = Tru
     blocks = horizon_blocks(t.size, 0, t_new.size)
     if blocks is None:
         mu, sigma, info, _ = call(t_new)
+    elif fac is not None and hasattr(fac, "predict_long"):
+        # longer than the aux rows carry: ONE query with the dates as the panel of a solve
+        mu, _, sigma, info = fac.predict_long(t_new, noise_on_new=noise_on_new)
+        mu = mu[:, 0]
     else:       # longer than one call carries: pairwise calls, joint covariance assembled
         mu, sigma, info, _ = predict_in_blocks(call, t_new, blocks)
     bad = np.flatnonzero(info)

@@ -1812,6 +1812,121 @@ extern "C" ngp_status ngp_factor_nowcast(ngp_factor *f, int32_t d, const double 
     return st;
 }
 
+// ---- long horizons ------------------------------------------------
+// The dates are the panel of a triangular solve against the resident L (ngp_long_kernels.h), not
+// aux rows: m is bounded by NGP_MAX_LONG_HORIZON and the device's memory, not by NGP_MAX_AUX.  The
+// particles are worked through in chunks sized to what the device holds.
+extern "C" ngp_status ngp_factor_predict_long(ngp_factor *f, int32_t d, const double *t_add,
+                                              int32_t D, const double *y_add, int32_t m,
+                                              const double *t_new, int32_t noise_on_new, double *mu,
+                                              double *var, double *sigma, int32_t *info) {
+    if (!f || !t_new || !mu || !var || m < 1 || d < 0) return NGP_ERR_ARG;
+    if (d > 0 && (D < 1 || !t_add || !y_add)) return NGP_ERR_ARG;
+    if (d == 0) D = 1;
+    if (m > NGP_MAX_LONG_HORIZON) return NGP_ERR_TOO_LARGE;
+    const int P = f->P, n = f->n, n0 = f->n0, tail = n - n0;
+    if ((int64_t)tail + d + 1 > NGP_MAX_AUX) return NGP_ERR_TOO_LARGE;
+    const int cc = tail + d;
+    std::vector<DevProgram> hp((size_t)P);
+    for (int i = 0; i < P; ++i) {
+        ngp_status st = compile_program(&f->kernels[(size_t)i], &hp[(size_t)i], nullptr);
+        if (st) return st;
+    }
+    LongGeom g{};
+    g.n0 = n0;
+    g.nb0 = f->nb0;
+    g.c = cc;
+    g.m = m;
+    g.D = D;
+    g.q1 = 1 + cc + m;
+    g.qpad = (g.q1 + LONG_TILE - 1) / LONG_TILE * LONG_TILE;
+    g.noise_on_new = noise_on_new ? 1 : 0;
+    g.y_shared = f->ldy ? 0 : 1;
+    g.want_sigma = sigma ? 1 : 0;
+    g.ld = n0;
+    g.L_stride = f->item_stride;
+    g.dinv_step = (int64_t)P * NB * NB;
+    // what travels up: programs | t0 | tp | y0 | yc
+    const int ny = g.y_shared ? 1 : P;
+    const size_t o_t0 = sizeof(DevProgram) * (size_t)P, o_tp = o_t0 + 8 * (size_t)n0,
+                 o_y0 = o_tp + 8 * (size_t)(cc + m), o_yc = o_y0 + 8 * (size_t)ny * n0,
+                 in_bytes = o_yc + 8 * (size_t)ny * D * cc;
+    std::vector<unsigned char> h_in(in_bytes);
+    std::memcpy(h_in.data(), hp.data(), o_t0);
+    {
+        double *h_t0 = reinterpret_cast<double *>(h_in.data() + o_t0);
+        double *h_tp = reinterpret_cast<double *>(h_in.data() + o_tp);
+        double *h_y0 = reinterpret_cast<double *>(h_in.data() + o_y0);
+        double *h_yc = reinterpret_cast<double *>(h_in.data() + o_yc);
+        std::copy(f->t.begin(), f->t.begin() + n0, h_t0);
+        std::copy(f->t.begin() + n0, f->t.end(), h_tp);
+        for (int a = 0; a < d; ++a) h_tp[tail + a] = t_add[a];
+        std::copy(t_new, t_new + m, h_tp + cc);
+        for (int b = 0; b < ny; ++b) {
+            const double *yb = f->y.data() + (size_t)b * n;
+            std::copy(yb, yb + n0, h_y0 + (size_t)b * n0);
+            for (int s = 0; s < D; ++s) {
+                double *dst = h_yc + ((size_t)b * D + s) * cc;
+                std::copy(yb + n0, yb + n, dst);
+                for (int a = 0; a < d; ++a) dst[tail + a] = y_add[(size_t)s * d + a];
+            }
+        }
+    }
+    // doubles of working storage and of outputs per item
+    const size_t cw = (size_t)cc + 1, mm = sigma ? (size_t)m * m : 0;
+    const size_t n_W = (size_t)g.qpad * n0, n_S = (size_t)g.q1 * cw, n_mu = (size_t)D * m;
+    const size_t item_bytes = 8 * (n_W + n_S + (size_t)g.q1 + (size_t)D * cc + n_mu + (size_t)m + mm) + 4;
+    ngp_ctx *c = f->ctx;
+    DevCall call(c);
+    if (call.status()) return call.status();
+    if ((size_t)P * item_bytes + in_bytes > c->mem_cap) c->refresh_mem_cap();
+    if (item_bytes + in_bytes > c->mem_cap) return NGP_ERR_TOO_LARGE;
+    const size_t Pc = std::min<size_t>(std::min<size_t>((size_t)P, MAX_CHUNK_ITEMS),
+                                       std::max<size_t>(1, (c->mem_cap - in_bytes) / item_bytes));
+    unsigned char *d_in = nullptr;
+    LongPtrs p{};
+    call.take(&d_in, in_bytes);
+    if (n0 > 0) call.take(&p.W, Pc * n_W);
+    call.take(&p.S, Pc * n_S).take(&p.dg, Pc * (size_t)g.q1).take(&p.z, Pc * (size_t)D * cc + 1);
+    call.take(&p.mu, Pc * n_mu).take(&p.var, Pc * (size_t)m).take(&p.info, Pc);
+    if (sigma) call.take(&p.sigma, Pc * mm);
+    call.up(d_in, h_in.data(), in_bytes);
+    const DevSpec sp = dev_spec(f->spec);
+    hipStream_t s = c->stream;
+    EventTimer &tm = call.tm;
+    for (size_t b0 = 0; b0 < (size_t)P && !call.status(); b0 += Pc) {
+        const size_t bc = std::min(Pc, (size_t)P - b0);
+        g.B = (int32_t)bc;
+        p.progs = reinterpret_cast<const DevProgram *>(d_in) + b0;
+        p.L = f->L ? f->L + b0 * (size_t)f->item_stride : nullptr;
+        p.dinv = f->dinv ? f->dinv + b0 * (size_t)(NB * NB) : nullptr;
+        p.finfo = n0 > 0 ? f->info + b0 : nullptr;   // without a main block create leaves it unwritten
+        p.t0 = reinterpret_cast<const double *>(d_in + o_t0);
+        p.tp = reinterpret_cast<const double *>(d_in + o_tp);
+        p.y0 = reinterpret_cast<const double *>(d_in + o_y0) + (g.y_shared ? 0 : b0 * (size_t)n0);
+        p.yc = reinterpret_cast<const double *>(d_in + o_yc) + (g.y_shared ? 0 : b0 * (size_t)D * cc);
+        const double dB = (double)bc, dq = (double)g.q1, dn = (double)n0;
+        const double wg_tiles = (double)((g.qpad + LONG_WG_TILE - 1) / LONG_WG_TILE);
+        call.timed(tm, 4, 0.0, 8.0 * dB * g.qpad * dn, [&] { launch_long(LONG_FILL, g, p, sp, s); });
+        call.timed(tm, 4, 0.0, 8.0 * dB * (dq * (double)cw + (double)mm), [&] { launch_long(LONG_SMALL, g, p, sp, s); });
+        // n0^2 q flops per item; L once per workgroup tile, the panel once in and once out, and —
+        // left-looking — block column j of the solved panel read back by every later step
+        call.timed(tm, 6, dB * dn * dn * dq,
+                   8.0 * dB * (wg_tiles * dn * dn / 2 + 2.0 * g.qpad * dn + g.qpad * dn * (g.nb0 - 1) / 2.0),
+                   [&] { launch_long(LONG_SOLVE, g, p, sp, s); });
+        call.timed(tm, 2, 0.0, 0.0, [&] { launch_long(LONG_GRAM, g, p, sp, s); });
+        call.timed(tm, 3, 0.0, 0.0, [&] {
+            launch_long(LONG_COND, g, p, sp, s);
+            launch_long(LONG_APPLY, g, p, sp, s);
+            launch_long(LONG_SIGMA, g, p, sp, s);
+        });
+        call.down(mu + b0 * n_mu, p.mu, 8 * bc * n_mu).down(var + b0 * (size_t)m, p.var, 8 * bc * (size_t)m);
+        if (sigma) call.down(sigma + b0 * mm, p.sigma, 8 * bc * mm);
+        if (info) call.down(info + b0, p.info, 4 * bc);
+    }
+    return call.sync();
+}
+
 // ---- additive decomposition ---------------------------------------
 // The components of a tree: its maximal non-Plus subtrees reached from the root through Plus nodes
 // only, left to right.  In postfix order a subtree is a contiguous slice of ops and of params.

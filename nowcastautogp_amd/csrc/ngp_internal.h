@@ -186,6 +186,42 @@ struct CompPtrs {
     int32_t       cmax;       // max C_b: the geometry's m is cmax * m
 };
 
+// ngp_factor_predict_long (ngp_long_kernels.h): the dates are the panel of a triangular solve
+// against the resident L, not aux rows of the factorisation
+constexpr int LONG_TILE = 64;          // panel columns a wave owns in the solve
+constexpr int LONG_WG_TILE = 256;      // panel columns of a workgroup: block row j of L is read once per such tile
+struct LongGeom {
+    int32_t B;             // items of the chunk
+    int32_t n0, nb0;       // the resident main block
+    int32_t c;             // conditioning points: tail (n - n0) + d appended
+    int32_t m, D;          // dates, scenarios
+    int32_t q1;            // panel rows: y', the c conditioning points, the m dates
+    int32_t qpad;          // q1 rounded up to a multiple of LONG_TILE
+    int32_t noise_on_new, y_shared, want_sigma, pad_;
+    int64_t ld;            // row stride of L and of the panel (= n0)
+    int64_t L_stride;      // elements per item in the factor storage
+    int64_t dinv_step;     // elements between the block inverses of consecutive block columns
+};
+struct LongPtrs {
+    const DevProgram *progs;   // [B]
+    const double *L;           // the chunk's first item in the resident factor
+    const double *dinv;        // block column 0, the chunk's first item
+    const int32_t *finfo;      // [B] the factor's status of create; null without a main block
+    const double *t0;          // [n0]
+    const double *tp;          // [c + m] tail, appended points, dates
+    const double *y0;          // [B or 1][n0]
+    const double *yc;          // [B or 1][D][c]
+    double *W;                 // [B][qpad][n0]
+    double *S;                 // [B][q1][c + 1]
+    double *dg;                // [B][q1]
+    double *z;                 // [B][D][c]
+    double *mu, *var, *sigma;  // [B][D][m], [B][m], [B][m][m] or null
+    int32_t *info;             // [B]
+};
+// step: 0 fill, 1 small blocks, 2 solve, 3 products of the rows, 4 conditioning block, 5 dates, 6 sigma
+enum { LONG_FILL = 0, LONG_SMALL, LONG_SOLVE, LONG_GRAM, LONG_COND, LONG_APPLY, LONG_SIGMA };
+void launch_long(int step, const LongGeom &g, const LongPtrs &p, const DevSpec &sp, hipStream_t s);
+
 // ---- short series in one launch (ngp_small_kernels.h) ------------------------------------
 constexpr int SM_WAVES = 8, SM_THREADS = 64 * SM_WAVES;   // two waves per SIMD: 256 VGPRs each
 constexpr int SM_NSLOT = 20;           // register blocks per wave (8 VGPRs each)

@@ -16,6 +16,7 @@
 //   ngp_col_kernels.h     chol_diag_kernel and the column kernels; ngp_small_kernels.h: short series
 //                         in one launch; ngp_mixture_kernels.h: mixture summaries;
 //                         ngp_component_kernels.h: fill and epilogue of ngp_factor_components;
+//                         ngp_long_kernels.h: ngp_factor_predict_long (the dates as a solve's panel);
 //                         ngp_path_kernels.h: functionals of whole sample paths
 //   this file             aux_update / aux_back_* / refine_gram_* (resident factor, Gram refinement),
 //                         diag_ahead, gram, epilogue, mixture sampling, the probe and stream kernels,
@@ -50,6 +51,7 @@
 #include "ngp_mixture_kernels.h"
 #include "ngp_tree_kernels.h"
 #include "ngp_component_kernels.h"
+#include "ngp_long_kernels.h"
 #include "ngp_grad_kernels.h"
 #include "ngp_hmc_kernels.h"
 
@@ -1124,6 +1126,43 @@ void launch_cov(const DevProgram *progs, int B, const double *t1, int n1, const 
     if (gx < 1) gx = 1;
     hipLaunchKernelGGL(cov_kernel, dim3(gx, B), dim3(256), 0, s, progs, t1, n1, t2, n2, add_diag,
                        out, sp);
+}
+
+void launch_long(int step, const LongGeom &g, const LongPtrs &p, const DevSpec &sp, hipStream_t s) {
+    auto blocks = [](long total) { return (int)std::max<long>(1, std::min<long>(4096, (total + 255) / 256)); };
+    const int nt = g.qpad / NB, ct = g.c / NB + 1;
+    const long small = (long)g.q1 * (g.c + 2) + (g.want_sigma ? (long)g.m * g.m : 0);
+    switch (step) {
+    case LONG_FILL:
+        if (g.n0 == 0) return;
+        hipLaunchKernelGGL(long_fill_kernel, dim3(blocks((long)g.qpad * g.n0), g.B), dim3(256), 0, s, g, p, sp);
+        return;
+    case LONG_SMALL:
+        hipLaunchKernelGGL(long_small_kernel, dim3(blocks(small), g.B), dim3(256), 0, s, g, p, sp);
+        return;
+    case LONG_SOLVE:
+        if (g.n0 == 0) return;
+        hipLaunchKernelGGL(long_solve_kernel, dim3((g.qpad + LONG_WG_TILE - 1) / LONG_WG_TILE, g.B),
+                           dim3(256), 0, s, g, p);
+        return;
+    case LONG_GRAM: {
+        if (g.n0 == 0) return;
+        const int npairs = g.want_sigma ? nt * (nt + 1) / 2 : ct * nt + (nt - ct);
+        hipLaunchKernelGGL(long_gram_kernel, dim3((npairs + 3) / 4, g.B), dim3(256), 0, s, g, p, npairs);
+        return;
+    }
+    case LONG_COND:
+        hipLaunchKernelGGL(long_cond_kernel, dim3(g.B), dim3(256),
+                           g.c <= LONG_COND_LDS ? 8 * (size_t)g.c * g.c : 0, s, g, p);
+        return;
+    case LONG_APPLY:
+        hipLaunchKernelGGL(long_apply_kernel, dim3((g.m + 63) / 64, g.B), dim3(64), 0, s, g, p, sp);
+        return;
+    case LONG_SIGMA:
+        if (!g.want_sigma) return;
+        hipLaunchKernelGGL(long_sigma_kernel, dim3(blocks((long)g.m * g.m), g.B), dim3(256), 0, s, g, p, sp);
+        return;
+    }
 }
 
 void launch_mfma_bench(double *out, int iters, int blocks, hipStream_t s) {

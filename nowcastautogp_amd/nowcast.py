@@ -367,11 +367,20 @@ def forecast_with_nowcasts(base_model: GPModel, nowcasts: Sequence[TData], forec
 
 
 def _nowcast_mixtures_batched(model, nowcasts, dates, ess_threshold):
+    w, means, covs, _, low, rng, sampler = _nowcast_mixtures_core(model, nowcasts, dates,
+                                                                  ess_threshold, True)
+    return w, means, covs, low, rng, sampler
+
+
+def _nowcast_mixtures_core(model, nowcasts, dates, ess_threshold, want_sigma):
     """All scenarios in one engine call: one factorisation per particle (src/forecasting.jl:133-155
     with n_mcmc = n_hmc = 0).  Returns the D scenario mixtures before anything is drawn: weights
     ``w`` [D, P] (not yet resampled), ``means`` [P, D, m], ``covs`` [P, m, m] shared by the
     scenarios of a particle, ``low`` [D] (scenarios whose ESS asks for resampling), the stream the
-    draws come from and the device sampler (None: the draws are made on the host)."""
+    draws come from and the device sampler (None: the draws are made on the host).  Between
+    ``covs`` and ``low`` it returns the per-date variances ``var`` [P, m]; without ``want_sigma`` a
+    horizon served by the long query (``Factor.predict_long``) forms no covariance at all and
+    ``covs`` is None."""
     t, y = model._obs()
     t_add = model.ds_transform.apply(autogp.to_days(list(nowcasts[0].ds)))
     y_add = np.stack([model.y_transform.apply(np.asarray(nc.y, dtype=np.float64))
@@ -389,6 +398,13 @@ def _nowcast_mixtures_batched(model, nowcasts, dates, ess_threshold):
     blocks = autogp.horizon_blocks(t.size, t_add.size, t_new.size)
     if blocks is None:
         out = call(t_new)[3]
+    elif fac is not None and hasattr(fac, "predict_long"):
+        # longer than the aux rows carry: the weight update from a query without dates, then ONE
+        # long query with the dates as the panel of a solve against the resident factor
+        first = fac.nowcast(t_add, y_add, t_new[:0], True)
+        mu_l, var_l, sg_l, info_l = fac.predict_long(t_new, t_add, y_add, True, want_sigma)
+        out = dict(first, mu=mu_l, sigma=sg_l, var=var_l,
+                   info=np.where(first["info"] != 0, first["info"], info_l))
     else:       # a horizon longer than one call carries: pairwise calls (autogp.predict_in_blocks)
         mu_all, sg_all, info_all, first = autogp.predict_in_blocks(call, t_new, blocks)
         out = dict(first, mu=mu_all, sigma=sg_all, info=info_all)
@@ -407,19 +423,29 @@ def _nowcast_mixtures_batched(model, nowcasts, dates, ess_threshold):
     _, ess, w_all = dist_.normalize_log_weights(logw, P_total=P, full=True)
     w = np.ascontiguousarray(w_all.T)                                         # [D, P]
     means = (out["mu"] - b) / s if m else np.zeros((logw.shape[0], D, 0))     # [P_local, D, m]
-    covs = out["sigma"] / (s * s) if m else np.zeros((logw.shape[0], 0, 0))
+    covs = None
+    if not m:
+        covs = np.zeros((logw.shape[0], 0, 0))
+    elif out["sigma"] is not None:
+        covs = out["sigma"] / (s * s)
+    var = out["var"] / (s * s) if out.get("var") is not None else np.einsum("pjj->pj", covs)
     if dist_.world()[1] > 1:        # the mixtures need every rank's components: one more
+        second = covs if covs is not None else var
         packed = np.concatenate([means.reshape(means.shape[0], -1),
-                                 covs.reshape(covs.shape[0], -1)], axis=1)
+                                 second.reshape(second.shape[0], -1)], axis=1)
         packed = dist_.all_gather_rows(packed, sizes=dist_.block_sizes(P))
         means = np.ascontiguousarray(packed[:, :D * m].reshape(P, D, m))
-        covs = np.ascontiguousarray(packed[:, D * m:].reshape(P, m, m))
+        if covs is not None:
+            covs = np.ascontiguousarray(packed[:, D * m:].reshape(P, m, m))
+            var = np.einsum("pjj->pj", covs)
+        else:
+            var = np.ascontiguousarray(packed[:, D * m:].reshape(P, m))
     low = ess < ess_threshold * P
     sampler = getattr(model._eng(), "mixture_sample", None)
     from ._abi import NGP_MAX_AUX
     if not 0 < m <= NGP_MAX_AUX:   # the device sampler's limit
         sampler = None
-    return w, means, covs, low, rng, sampler
+    return w, means, covs, var, low, rng, sampler
 
 
 def _forecast_with_nowcasts_batched(model, nowcasts, dates, draws, inv_transformation,
@@ -455,7 +481,7 @@ def forecast_mixture(model: GPModel, forecast_dates) -> "autogp.MixtureMarginals
     """The per-date marginals of the mixture ``forecast`` draws from (``predict_mvn`` of reference
     src/forecasting.jl:46), as an ``autogp.MixtureMarginals``: exact quantiles, CDF / PIT and CRPS
     instead of draws.  Consumes nothing from the model's random streams."""
-    return autogp.predict_mvn(model, list(forecast_dates)).marginals(engine=model._eng())
+    return autogp._predict_marginals(model, list(forecast_dates))
 
 
 def forecast_mixture_with_nowcasts(base_model: GPModel, nowcasts: Sequence[TData], forecast_dates, *,
@@ -481,8 +507,8 @@ def forecast_mixture_with_nowcasts(base_model: GPModel, nowcasts: Sequence[TData
     D = len(nowcasts)
     same_dates = all(list(nc.ds) == list(nowcasts[0].ds) for nc in nowcasts)
     if n_mcmc == 0 and n_hmc == 0 and same_dates and lockstep:
-        w, means, covs, low, rng, sampler = _nowcast_mixtures_batched(base_model, nowcasts, dates,
-                                                                      ess_threshold)
+        w, means, _, var, low, rng, sampler = _nowcast_mixtures_core(base_model, nowcasts, dates,
+                                                                     ess_threshold, False)
         P = w.shape[1]
         if sampler is not None:
             if low.any():
@@ -492,9 +518,7 @@ def forecast_mixture_with_nowcasts(base_model: GPModel, nowcasts: Sequence[TData
             for sc in np.flatnonzero(low):
                 w[sc] = np.bincount(rng.choice(P, size=P, p=w[sc]), minlength=P) / P
         m = len(dates)
-        # the scenarios of a particle share its covariance: [D P, m] from the diagonal, never the
-        # D P full matrices
-        var = np.einsum("pjj->pj", covs) if m else np.zeros((P, 0))
+        # the scenarios of a particle share its variances: [D P, m], never the D P full matrices
         return autogp.MixtureMarginals(
             np.ascontiguousarray(means.transpose(1, 0, 2)).reshape(D * P, m),
             np.broadcast_to(var[None], (D, P, m)).reshape(D * P, m),
