@@ -289,9 +289,29 @@ def comm_unique_id() -> bytes:
     return buf.raw
 
 
-class Comm:
+class _Handle:
+    """A handle of the C-ABI that lives inside a context (``self._h``, destroyed once by the
+    function ``_destroy`` names).  The handle points into its context: where ``_needs_ctx`` is
+    set, a context closed first (``self.ctx._h`` None) has already destroyed it."""
+    _destroy = ""
+    _needs_ctx = True
+
+    def close(self):
+        if self._h and (not self._needs_ctx or self.ctx._h is not None):
+            getattr(load(), self._destroy)(self._h)
+        self._h = None
+
+    def __del__(self):  # pragma: no cover
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Comm(_Handle):
     """The C-ABI's own communicator over RCCL (``ngp_comm``): the one exchange of the path for
     hosts without torch.distributed.  The Python mirror itself uses torch.distributed."""
+    _destroy = "ngp_comm_destroy"
 
     def __init__(self, ctx: "Context", uid: bytes, rank: int, world: int):
         h = C.c_void_p()
@@ -313,26 +333,67 @@ class Comm:
              "ngp_weights_allgather_normalize")
         return w_loc, w_all, ess, ln
 
-    def close(self):
-        if self._h is not None and self.ctx._h is not None:
-            load().ngp_comm_destroy(self._h)
-        self._h = None
-
-    def __del__(self):  # pragma: no cover
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 def _nullable(a: Optional[np.ndarray]):
     return dptr(a) if a is not None else None
 
 
-class GradJob:
+_u64p = C.POINTER(C.c_uint64)
+
+
+def _mixture_args(who, w, mu, sigma, seed, indep=None):
+    """The forecast mixture the sampler and the consumers of its paths take: w [S,P] with mu [P,S,m],
+    sigma [P,m,m] and one seed (shared components), or with mu [S,P,m], sigma [S,P,m,m] and S seeds
+    (independent mixtures; ``indep`` None: a ``seed`` that is a sequence says so) ->
+    (w, mu, sigma as float64, the seed(s) as a uint64 array, indep, S, P, m)."""
+    w, mu, sigma = as_f64(w), as_f64(mu), as_f64(sigma)
+    if indep is None:
+        indep = not np.isscalar(seed)
+        if w.ndim != 2 or mu.ndim != 3:
+            raise ValueError(f"{who}: w [S,P], mu [P,S,m] ([S,P,m] with S seeds)")
+    S, P = w.shape
+    m = mu.shape[2]
+    if indep:
+        if mu.shape != (S, P, m) or sigma.shape != (S, P, m, m) or len(seed) != S:
+            raise ValueError(f"{who}: w [S,P], mu [S,P,m], sigma [S,P,m,m], seeds [S]")
+    elif mu.shape != (P, S, m) or sigma.shape != (P, m, m):
+        raise ValueError(f"{who}: w [S,P], mu [P,S,m], sigma [P,m,m]")
+    sd = np.array([int(v) & (2**64 - 1) for v in (seed if indep else [seed])], dtype=np.uint64)
+    return w, mu, sigma, sd, indep, S, P, m
+
+
+def _inv_transform(inv):
+    """(kind, lam, offset, cap) -> NgpInvTransform"""
+    return NgpInvTransform(int(inv[0]), float(inv[1]), float(inv[2]), float(inv[3]))
+
+
+def _appended(t_add, y_add):
+    """The appended points t_add [d] and their scenarios y_add [D, d] (d = 0: one scenario of no
+    points) -> (d, D, t_add, y_add, pointer to t_add, pointer to y_add); NULL pointers for d = 0.
+    The caller keeps the arrays until the call has returned."""
+    t_add = as_f64(t_add)
+    d = t_add.size
+    y_add = as_f64(y_add).reshape(-1, d) if d else np.zeros((1, 0))
+    return d, y_add.shape[0], t_add, y_add, dptr(t_add) if d else None, dptr(y_add) if d else None
+
+
+def _per_particle(counts, m, mu, var, sg):
+    """The flat outputs of the component queries as per-particle lists: mu and var [C_p, ...],
+    sigma [C_p m, C_p m] (row = c m + j; sg None: None)."""
+    first = np.concatenate([[0], np.cumsum(counts)])
+    rows = counts.astype(np.int64) * m
+    soff = np.concatenate([[0], np.cumsum(rows ** 2)])
+    ps = range(counts.size)
+    return dict(mu=[mu[first[p]:first[p + 1]] for p in ps], var=[var[first[p]:first[p + 1]] for p in ps],
+                sigma=(None if sg is None else
+                       [sg[soff[p]:soff[p + 1]].reshape(int(rows[p]), int(rows[p])) for p in ps]))
+
+
+class GradJob(_Handle):
     """A gradient job whose trees, dates and observations stay on the device (``ngp_grad_stage``):
     ``run(ka)`` evaluates logml and gradient for the parameters ``ka`` holds NOW (the same trees —
     ``KernelArray.set_params`` between runs), sending nothing else across the bus."""
+    _destroy, _needs_ctx = "ngp_grad_job_destroy", False
 
     def __init__(self, ctx: "Context", handle, ka: KernelArray):
         self._ctx, self._h, self.n = ctx, handle, ka.n
@@ -395,20 +456,10 @@ class GradJob:
         return dict(general_items=int(out[0]), general_chunk=int(out[1]), toeplitz_items=int(out[2]),
                     toeplitz_chunk=int(out[3]), side_by_side=bool(out[4]))
 
-    def close(self):
-        if self._h:
-            load().ngp_grad_job_destroy(self._h)
-            self._h = None
 
-    def __del__(self):  # pragma: no cover
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class Job:
+class Job(_Handle):
     """A staged batch: inputs resident in HBM; ``run`` enqueues every kernel and waits."""
+    _destroy = "ngp_job_destroy"
 
     def __init__(self, ctx: "Context", handle, P: int, D: int, m: int, keep):
         self.ctx, self._h, self.P, self.D, self.m = ctx, handle, P, D, m
@@ -438,22 +489,11 @@ class Job:
              "ngp_job_mixed_stats")
         return dict(refine_steps=steps, refine_delta=delta, frac_f32=frac)
 
-    def close(self):
-        # the handle points into its context: a context closed first has already closed us
-        if self._h is not None and self.ctx._h is not None:
-            load().ngp_job_destroy(self._h)
-        self._h = None
 
-    def __del__(self):  # pragma: no cover
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class Factor:
+class Factor(_Handle):
     """Training covariances of P kernels factorised once and kept on the device (``ngp_factor``):
     every query sweeps only its appended / forecast rows through the resident L."""
+    _destroy = "ngp_factor_destroy"
 
     def __init__(self, ctx: "Context", handle, P: int):
         self.ctx, self._h, self.P = ctx, handle, P
@@ -466,20 +506,16 @@ class Factor:
 
     def nowcast(self, t_add, y_add, t_new, noise_on_new=True):
         """Same result dict as ``Context.nowcast_batch`` (``t_add`` empty: plain predict)."""
-        t_add, t_new = as_f64(t_add), as_f64(t_new)
-        d, m = t_add.size, t_new.size
-        y_add = as_f64(y_add).reshape(-1, d) if d else np.zeros((1, 0))
-        D = y_add.shape[0]
-        P = self.P
+        d, D, t_add, y_add, p_t, p_y = _appended(t_add, y_add)
+        t_new = as_f64(t_new)
+        m, P = t_new.size, self.P
         lb, lf = np.empty(P), np.empty((P, D))
         mu = np.empty((P, D, m)) if m else None
         sg = np.empty((P, m, m)) if m else None
         info = np.zeros(P, dtype=np.int32)
-        _chk(load().ngp_factor_nowcast(self._h, d, dptr(t_add) if d else None, D,
-                                       dptr(y_add) if d else None, m,
-                                       dptr(t_new) if m else None, int(noise_on_new), dptr(lb),
-                                       dptr(lf), _nullable(mu), _nullable(sg), iptr(info)),
-             "ngp_factor_nowcast")
+        _chk(load().ngp_factor_nowcast(self._h, d, p_t, D, p_y, m, dptr(t_new) if m else None,
+                                       int(noise_on_new), dptr(lb), dptr(lf), _nullable(mu),
+                                       _nullable(sg), iptr(info)), "ngp_factor_nowcast")
         return dict(logml_base=lb, logml_full=lf, mu=mu, sigma=sg, info=info)
 
     def predict_long(self, t_new, t_add=None, y_add=None, noise_on_new=True, want_sigma=True):
@@ -489,20 +525,15 @@ class Factor:
         plain predict).  Returns ``(mu [P, D, m], var [P, m], sigma [P, m, m] or None, info [P])``;
         without ``want_sigma`` no m x m array is formed.  No weight update: ``nowcast`` with no
         dates gives it."""
+        d, D, t_add, y_add, p_t, p_y = _appended(t_add if t_add is not None else np.zeros(0), y_add)
         t_new = as_f64(t_new)
-        t_add = as_f64(t_add if t_add is not None else np.zeros(0))
-        d, m = t_add.size, t_new.size
-        y_add = as_f64(y_add).reshape(-1, d) if d else np.zeros((1, 0))
-        D = y_add.shape[0]
-        P = self.P
+        m, P = t_new.size, self.P
         mu, var = np.empty((P, D, m)), np.empty((P, m))
         sg = np.empty((P, m, m)) if want_sigma else None
         info = np.zeros(P, dtype=np.int32)
-        _chk(load().ngp_factor_predict_long(self._h, d, dptr(t_add) if d else None, D,
-                                            dptr(y_add) if d else None, m,
-                                            dptr(t_new) if m else None, int(noise_on_new), dptr(mu),
-                                            dptr(var), _nullable(sg), iptr(info)),
-             "ngp_factor_predict_long")
+        _chk(load().ngp_factor_predict_long(self._h, d, p_t, D, p_y, m, dptr(t_new) if m else None,
+                                            int(noise_on_new), dptr(mu), dptr(var), _nullable(sg),
+                                            iptr(info)), "ngp_factor_predict_long")
         return mu, var, sg, info
 
     def components(self, comps, t_new, want_sigma=True):
@@ -525,14 +556,7 @@ class Factor:
         _chk(load().ngp_factor_components(self._h, iptr(counts), ka.arr, m, dptr(t_new) if m else None,
                                           dptr(mu), _nullable(sg), dptr(var), iptr(info)),
              "ngp_factor_components")
-        first = np.concatenate([[0], np.cumsum(counts)])
-        soff = np.concatenate([[0], np.cumsum(sizes)])
-        return dict(
-            mu=[mu[first[p]:first[p + 1]] for p in range(self.P)],
-            var=[var[first[p]:first[p + 1]] for p in range(self.P)],
-            sigma=([sg[soff[p]:soff[p + 1]].reshape(int(counts[p]) * m, int(counts[p]) * m)
-                    for p in range(self.P)] if want_sigma else None),
-            info=info)
+        return dict(**_per_particle(counts, m, mu, var, sg), info=info)
 
     def components_nowcast(self, comps, t_add, y_add, t_new, want_sigma=True):
         """``components`` conditioned on the appended points ``t_add`` [d] and the scenarios
@@ -541,10 +565,9 @@ class Factor:
         scenarios of a particle."""
         if len(comps) != self.P:
             raise ValueError("one list of component programs per particle")
-        t_add, t_new = as_f64(t_add), as_f64(t_new)
-        d, m = t_add.size, t_new.size
-        y_add = as_f64(y_add).reshape(-1, d) if d else np.zeros((1, 0))
-        D = y_add.shape[0]
+        d, D, t_add, y_add, p_t, p_y = _appended(t_add, y_add)
+        t_new = as_f64(t_new)
+        m = t_new.size
         counts = np.array([len(c) for c in comps], dtype=np.int32)
         ka = KernelArray([prog for c in comps for prog in c])
         tot = int(counts.sum())
@@ -554,32 +577,13 @@ class Factor:
         lf = np.empty((self.P, D))
         info = np.zeros(self.P, dtype=np.int32)
         _chk(load().ngp_factor_components_nowcast(
-            self._h, d, dptr(t_add) if d else None, D, dptr(y_add) if d else None, iptr(counts), ka.arr,
-            m, dptr(t_new) if m else None, dptr(lf), dptr(mu), _nullable(sg), dptr(var), iptr(info)),
-            "ngp_factor_components_nowcast")
-        first = np.concatenate([[0], np.cumsum(counts)])
-        soff = np.concatenate([[0], np.cumsum(sizes)])
-        return dict(
-            mu=[mu[first[p]:first[p + 1]] for p in range(self.P)],
-            var=[var[first[p]:first[p + 1]] for p in range(self.P)],
-            sigma=([sg[soff[p]:soff[p + 1]].reshape(int(counts[p]) * m, int(counts[p]) * m)
-                    for p in range(self.P)] if want_sigma else None),
-            logml_full=lf, info=info)
+            self._h, d, p_t, D, p_y, iptr(counts), ka.arr, m, dptr(t_new) if m else None, dptr(lf),
+            dptr(mu), _nullable(sg), dptr(var), iptr(info)), "ngp_factor_components_nowcast")
+        return dict(**_per_particle(counts, m, mu, var, sg), logml_full=lf, info=info)
 
     def predict(self, t_new, noise_on_new=True):
         r = self.nowcast(np.zeros(0), np.zeros((1, 0)), t_new, noise_on_new)
         return r["mu"][:, 0, :], r["sigma"], r["logml_full"][:, 0], r["info"]
-
-    def close(self):
-        if self._h is not None and self.ctx._h is not None:
-            load().ngp_factor_destroy(self._h)
-        self._h = None
-
-    def __del__(self):  # pragma: no cover
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 class Context:
@@ -662,17 +666,14 @@ class Context:
 
     def nowcast_batch(self, programs, t, y, t_add, y_add, t_new, noise_on_new=True):
         ka = KernelArray(programs)
-        t, y, t_add, t_new = as_f64(t), as_f64(y), as_f64(t_add), as_f64(t_new)
-        d, m = t_add.size, t_new.size
-        y_add = as_f64(y_add).reshape(-1, d) if d else np.zeros((1, 0))
-        D = y_add.shape[0]
+        t, y, t_new = as_f64(t), as_f64(y), as_f64(t_new)
+        d, D, t_add, y_add, p_t, p_y = _appended(t_add, y_add)
+        m = t_new.size
         lb, lf = np.empty(ka.n), np.empty((ka.n, D))
         mu = np.empty((ka.n, D, m)) if m else None
         sg = np.empty((ka.n, m, m)) if m else None
         info = np.zeros(ka.n, dtype=np.int32)
-        _chk(load().ngp_nowcast_batch(self._h, ka.n, ka.arr, t.size, dptr(t), dptr(y), d,
-                                      dptr(t_add) if d else None, D,
-                                      dptr(y_add) if d else None, m,
+        _chk(load().ngp_nowcast_batch(self._h, ka.n, ka.arr, t.size, dptr(t), dptr(y), d, p_t, D, p_y, m,
                                       dptr(t_new) if m else None, int(noise_on_new), dptr(lb),
                                       dptr(lf), _nullable(mu), _nullable(sg), iptr(info)),
              "ngp_nowcast_batch")
@@ -693,16 +694,12 @@ class Context:
         """S mixtures over the same P components, sampled on the device (``ngp_mixture_sample``):
         w [S,P], mu [P,S,m], sigma [P,m,m] -> (out [S,draws,m], comp [S,draws], info [P]);
         want_comp / want_info = False: NULL is passed for that output and None returned."""
-        w, mu, sigma = as_f64(w), as_f64(mu), as_f64(sigma)
-        S, P = w.shape
-        m = mu.shape[2]
-        if mu.shape != (P, S, m) or sigma.shape != (P, m, m):
-            raise ValueError("mixture_sample: w [S,P], mu [P,S,m], sigma [P,m,m]")
+        w, mu, sigma, sd, _, S, P, m = _mixture_args("mixture_sample", w, mu, sigma, seed, indep=False)
         out = np.empty((S, int(draws), m))
         comp = np.zeros((S, int(draws)), dtype=np.int32) if want_comp else None
         info = np.zeros(P, dtype=np.int32) if want_info else None
         _chk(load().ngp_mixture_sample(self._h, P, S, m, dptr(w), dptr(mu), dptr(sigma),
-                                       int(draws), C.c_uint64(int(seed) & (2**64 - 1)), dptr(out),
+                                       int(draws), C.c_uint64(int(sd[0])), dptr(out),
                                        iptr(comp) if want_comp else None,
                                        iptr(info) if want_info else None), "ngp_mixture_sample")
         return out, comp, info
@@ -712,18 +709,13 @@ class Context:
         """S independent mixtures of P components each (``ngp_mixture_sample_indep``): w [S,P],
         mu [S,P,m], sigma [S,P,m,m], seeds [S] -> (out [S,draws,m], comp [S,draws], info [S,P]);
         mixture s draws what ``mixture_sample`` with S = 1 and seed = seeds[s] draws."""
-        w, mu, sigma = as_f64(w), as_f64(mu), as_f64(sigma)
-        S, P = w.shape
-        m = mu.shape[2]
-        if mu.shape != (S, P, m) or sigma.shape != (S, P, m, m) or len(seeds) != S:
-            raise ValueError("mixture_sample_indep: w [S,P], mu [S,P,m], sigma [S,P,m,m], seeds [S]")
-        sd = np.array([int(v) & (2**64 - 1) for v in seeds], dtype=np.uint64)
+        w, mu, sigma, sd, _, S, P, m = _mixture_args("mixture_sample_indep", w, mu, sigma, seeds, indep=True)
         out = np.empty((S, int(draws), m))
         comp = np.zeros((S, int(draws)), dtype=np.int32) if want_comp else None
         info = np.zeros((S, P), dtype=np.int32) if want_info else None
         _chk(load().ngp_mixture_sample_indep(self._h, P, S, m, dptr(w), dptr(mu), dptr(sigma),
-                                             int(draws), sd.ctypes.data_as(C.POINTER(C.c_uint64)),
-                                             dptr(out), iptr(comp) if want_comp else None,
+                                             int(draws), sd.ctypes.data_as(_u64p), dptr(out),
+                                             iptr(comp) if want_comp else None,
                                              iptr(info) if want_info else None),
              "ngp_mixture_sample_indep")
         return out, comp, info
@@ -735,22 +727,12 @@ class Context:
         / ``mixture_sample_indep``; ``inv`` = (kind, lam, offset, cap); ``targets`` a sequence of
         (kind, j0, j1, thr); ``probs`` [Q] ->  dict(q [T,Q], mean [T], count [T], hist [T,m],
         values [T,N] or None, info)."""
-        w, mu, sigma = as_f64(w), as_f64(mu), as_f64(sigma)
-        indep = not np.isscalar(seed)
-        if w.ndim != 2 or mu.ndim != 3:
-            raise ValueError("mixture_path_targets: w [S,P], mu [P,S,m] ([S,P,m] with S seeds)")
-        S, P = w.shape
-        m = mu.shape[2]
-        if indep:
-            if mu.shape != (S, P, m) or sigma.shape != (S, P, m, m) or len(seed) != S:
-                raise ValueError("mixture_path_targets: w [S,P], mu [S,P,m], sigma [S,P,m,m], seeds [S]")
-        elif mu.shape != (P, S, m) or sigma.shape != (P, m, m):
-            raise ValueError("mixture_path_targets: w [S,P], mu [P,S,m], sigma [P,m,m]")
+        w, mu, sigma, sd, indep, S, P, m = _mixture_args("mixture_path_targets", w, mu, sigma, seed)
         probs = as_f64(probs).reshape(-1)
         T, Q, N = len(targets), probs.size, S * int(draws)
         tg = (NgpPathTarget * max(T, 1))(*[NgpPathTarget(int(k), int(j0), int(j1), float(thr))
                                            for k, j0, j1, thr in targets])
-        iv = NgpInvTransform(int(inv[0]), float(inv[1]), float(inv[2]), float(inv[3]))
+        iv = _inv_transform(inv)
         q, mean = np.empty((T, Q)), np.empty(T)
         count, hist = np.zeros(T, dtype=np.int64), np.zeros((T, m), dtype=np.int64)
         values = np.empty((T, N)) if want_values else None
@@ -758,15 +740,13 @@ class Context:
         i64p = C.POINTER(C.c_int64)
         tail = (C.byref(iv), T, tg, Q, dptr(probs), dptr(q), dptr(mean), count.ctypes.data_as(i64p),
                 hist.ctypes.data_as(i64p), dptr(values) if want_values else None, iptr(info))
+        head = (self._h, P, S, m, dptr(w), dptr(mu), dptr(sigma), int(draws))
         if indep:
-            sd = np.array([int(v) & (2**64 - 1) for v in seed], dtype=np.uint64)
-            _chk(load().ngp_mixture_path_targets_indep(
-                self._h, P, S, m, dptr(w), dptr(mu), dptr(sigma), int(draws),
-                sd.ctypes.data_as(C.POINTER(C.c_uint64)), *tail), "ngp_mixture_path_targets_indep")
+            _chk(load().ngp_mixture_path_targets_indep(*head, sd.ctypes.data_as(_u64p), *tail),
+                 "ngp_mixture_path_targets_indep")
         else:
-            _chk(load().ngp_mixture_path_targets(
-                self._h, P, S, m, dptr(w), dptr(mu), dptr(sigma), int(draws),
-                C.c_uint64(int(seed) & (2**64 - 1)), *tail), "ngp_mixture_path_targets")
+            _chk(load().ngp_mixture_path_targets(*head, C.c_uint64(int(sd[0])), *tail),
+                 "ngp_mixture_path_targets")
         return dict(q=q, mean=mean, count=count, hist=hist, values=values, info=info)
 
     @staticmethod
@@ -800,29 +780,19 @@ class Context:
         scalar: shared components; S seeds: independent mixtures) as ``mixture_path_targets``;
         ``inv`` = (kind, lam, offset, cap); y [m] on the original scale ->
         dict(es, term_obs, term_pair, info [W], chol_info)."""
-        w, mu, sigma, y = as_f64(w), as_f64(mu), as_f64(sigma), as_f64(y)
-        indep = not np.isscalar(seed)
-        if w.ndim != 2 or mu.ndim != 3:
-            raise ValueError("mixture_path_scores: w [S,P], mu [P,S,m] ([S,P,m] with S seeds)")
-        S, P = w.shape
-        m = mu.shape[2]
-        if indep:
-            if mu.shape != (S, P, m) or sigma.shape != (S, P, m, m) or len(seed) != S:
-                raise ValueError("mixture_path_scores: w [S,P], mu [S,P,m], sigma [S,P,m,m], seeds [S]")
-        elif mu.shape != (P, S, m) or sigma.shape != (P, m, m):
-            raise ValueError("mixture_path_scores: w [S,P], mu [P,S,m], sigma [P,m,m]")
+        w, mu, sigma, sd, indep, S, P, m = _mixture_args("mixture_path_scores", w, mu, sigma, seed)
+        y = as_f64(y)
         if y.shape != (m,):
             raise ValueError("mixture_path_scores: y [m]")
         win = self._windows(windows, "mixture_path_scores")
         W = win.shape[0]
-        sd = np.array([int(v) & (2**64 - 1) for v in (seed if indep else [seed])], dtype=np.uint64)
-        iv = NgpInvTransform(int(inv[0]), float(inv[1]), float(inv[2]), float(inv[3]))
+        iv = _inv_transform(inv)
         es, to, tp = np.empty(W), np.empty(W), np.empty(W)
         info = np.zeros(W, dtype=np.int32)
         cinfo = np.zeros((S, P) if indep else P, dtype=np.int32)
         _chk(load().ngp_mixture_path_scores(
             self._h, P, S, m, dptr(w), dptr(mu), dptr(sigma), int(indep), int(draws),
-            sd.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(iv), dptr(y), int(scale), float(shift),
+            sd.ctypes.data_as(_u64p), C.byref(iv), dptr(y), int(scale), float(shift),
             int(bool(fair)), W, iptr(win), dptr(es), dptr(to), dptr(tp), iptr(info), iptr(cinfo)),
             "ngp_mixture_path_scores")
         return dict(es=es, term_obs=to, term_pair=tp, info=info, chol_info=cinfo)
@@ -883,7 +853,7 @@ class Context:
         y = as_f64(y)
         if y.shape != (m,):
             raise ValueError("mixture_crps_mapped: y [m]")
-        iv = NgpInvTransform(int(inv[0]), float(inv[1]), float(inv[2]), float(inv[3]))
+        iv = _inv_transform(inv)
         out, mean, err = np.empty(m), np.empty(m), np.empty(m)
         info = np.zeros(m, dtype=np.int32)
         _chk(load().ngp_mixture_crps_mapped(self._h, C_, m, dptr(w), dptr(mu), dptr(var),

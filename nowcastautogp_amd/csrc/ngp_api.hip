@@ -3279,34 +3279,57 @@ extern "C" ngp_status ngp_weights_normalize_cols(int32_t P, int32_t D, const dou
     return NGP_OK;
 }
 
-// shared body of ngp_mixture_sample (seeds == nullptr: S mixtures over the SAME P components,
-// mu [P x S x m], sigma [P x m x m], one key) and ngp_mixture_sample_indep (seeds [S]: every
-// mixture has its own P components, mu [S x P x m], sigma [S x P x m x m], its own key)
-static ngp_status mixture_sample_impl(ngp_ctx *c, int32_t P, int32_t S, int32_t m, const double *w,
-                                      const double *mu, const double *sigma, int32_t draws,
-                                      uint64_t seed, const uint64_t *seeds, double *out,
-                                      int32_t *comp, int32_t *info) {
-    if (!c || !w || !mu || !sigma || !out || P <= 0 || S <= 0 || m <= 0 || draws <= 0)
-        return NGP_ERR_ARG;
-    if (m > NGP_MAX_AUX) return NGP_ERR_TOO_LARGE;
+// A forecast mixture as a caller hands it in: what the sampler and every consumer of its paths (the
+// trajectory targets, the path scores) take.  seeds == nullptr: S mixtures over the SAME P components,
+// mu [P x S x m], sigma [P x m x m], one key (seed); seeds [S]: every mixture has its own P components,
+// mu [S x P x m], sigma [S x P x m x m], its own key.  (MixStaged below: the per-date marginals.)
+struct MixInput {
+    int32_t P, S, m, draws;
+    const double *w, *mu, *sigma;
+    uint64_t seed; const uint64_t *seeds;   // one or the other
+    size_t blocks() const { return seeds ? (size_t)S * P : (size_t)P; }   // covariance blocks
+    size_t nw() const { return (size_t)S * P; }
+    size_t nmu() const { return nw() * (size_t)m; }
+    size_t nsg() const { return blocks() * (size_t)m * m; }
+    int64_t N() const { return (int64_t)S * draws; }                       // paths
+    // NGP_ERR_ARG and NGP_ERR_TOO_LARGE apart: the calls have checks of their own between the two
+    bool args_ok() const { return w && mu && sigma && P > 0 && S > 0 && m > 0 && draws > 0; }
+    // counts: the calls that index paths and blocks with 32 bits bound N and S P as well
+    bool too_large(bool counts) const { return m > NGP_MAX_AUX || (counts && (N() > INT32_MAX || nw() > INT32_MAX)); }
+    void up(DevCall &call, double *dw, double *dmu, double *dsg, uint64_t *dseeds) const {
+        call.up(dw, w, 8 * nw()).up(dmu, mu, 8 * nmu()).up(dsg, sigma, 8 * nsg());
+        if (seeds) call.up(dseeds, seeds, 8 * (size_t)S);
+    }
+    // a failed component (info [blocks()]: the Cholesky factorisations) that paths can come from,
+    // in its own mixture or, shared, in any of the S: nothing a call returns is free of it
+    bool tainted(const int32_t *info) const {
+        for (size_t k = 0; k < blocks(); ++k)
+            for (int32_t sc = 0; info[k] && sc < (seeds ? 1 : S); ++sc)
+                if (w[seeds ? k : (size_t)sc * P + k] > 0.0) return true;
+        return false;
+    }
+};
+
+// shared body of ngp_mixture_sample and ngp_mixture_sample_indep
+static ngp_status mixture_sample_impl(ngp_ctx *c, const MixInput &mix, double *out, int32_t *comp, int32_t *info) {
+    if (!c || !out || !mix.args_ok()) return NGP_ERR_ARG;
+    if (mix.too_large(false)) return NGP_ERR_TOO_LARGE;
     DevCall call(c);
-    const size_t ncomp_mats = seeds ? (size_t)S * P : (size_t)P;
-    const size_t nw = (size_t)S * P, nmu = (size_t)P * S * m, nsg = ncomp_mats * m * m,
-                 nout = (size_t)S * draws * m, ncomp = (size_t)S * draws;
+    const size_t nout = (size_t)mix.N() * mix.m, ncomp = (size_t)mix.N();
     double *dw = nullptr, *dmu = nullptr, *dsg = nullptr, *dout = nullptr;
     int32_t *dcomp = nullptr, *dinfo = nullptr;
     uint64_t *dseeds = nullptr;
-    call.take(&dw, nw).take(&dmu, nmu).take(&dsg, nsg).take(&dout, nout).take(&dcomp, ncomp)
-        .take(&dinfo, ncomp_mats);
-    if (seeds) call.take(&dseeds, (size_t)S);
-    call.up(dw, w, 8 * nw).up(dmu, mu, 8 * nmu).up(dsg, sigma, 8 * nsg);
-    if (seeds) call.up(dseeds, seeds, 8 * (size_t)S);
+    call.take(&dw, mix.nw()).take(&dmu, mix.nmu()).take(&dsg, mix.nsg()).take(&dout, nout).take(&dcomp, ncomp)
+        .take(&dinfo, mix.blocks());
+    if (mix.seeds) call.take(&dseeds, (size_t)mix.S);
+    mix.up(call, dw, dmu, dsg, dseeds);
     call.run([&] {
-            launch_mixture_sample(P, S, m, dw, dmu, dsg, draws, seed, dseeds, dout, dcomp, dinfo, c->stream);
+            launch_mixture_sample(mix.P, mix.S, mix.m, dw, dmu, dsg, mix.draws, mix.seed, dseeds, dout, dcomp,
+                                  dinfo, c->stream);
         })
         .down(out, dout, 8 * nout);
     if (comp) call.down(comp, dcomp, 4 * ncomp);
-    if (info) call.down(info, dinfo, 4 * ncomp_mats);
+    if (info) call.down(info, dinfo, 4 * mix.blocks());
     return call.sync();
 }
 
@@ -3316,7 +3339,7 @@ extern "C" ngp_status ngp_mixture_sample_indep(ngp_ctx *c, int32_t P, int32_t S,
                                                const uint64_t *seeds, double *out, int32_t *comp,
                                                int32_t *info) {
     if (!seeds) return NGP_ERR_ARG;
-    return mixture_sample_impl(c, P, S, m, w, mu, sigma, draws, 0, seeds, out, comp, info);
+    return mixture_sample_impl(c, MixInput{P, S, m, draws, w, mu, sigma, 0, seeds}, out, comp, info);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -3384,6 +3407,22 @@ bool probs_open_unit(const double *probs, int32_t n) {
 bool inv_transform_ok(const ngp_inv_transform *inv) {
     return inv->kind >= NGP_INV_IDENTITY && inv->kind <= NGP_INV_BOXCOX && std::isfinite(inv->lam) &&
            std::isfinite(inv->offset) && std::isfinite(inv->cap);
+}
+
+// the map as the calls that transform whole paths ask for it: Box-Cox with a positive cap
+bool path_inv_ok(const ngp_inv_transform *inv) {
+    return inv_transform_ok(inv) && (inv->kind != NGP_INV_BOXCOX || inv->cap > 0.0);
+}
+
+// observations on the scoring scale: an unknown scale, a shift not finite and non-negative; then the
+// caller's own size limits (too_large) BEFORE y is read; then a y not finite or with s(y) undefined
+ngp_status score_obs_check(int32_t scale, double shift, bool too_large, const double *y, int32_t m) {
+    if (scale != NGP_SCORE_NATURAL && scale != NGP_SCORE_LOG) return NGP_ERR_ARG;
+    if (!std::isfinite(shift) || shift < 0.0) return NGP_ERR_ARG;
+    if (too_large) return NGP_ERR_TOO_LARGE;
+    for (int32_t j = 0; j < m; ++j)
+        if (!std::isfinite(y[j]) || (scale == NGP_SCORE_LOG && !(y[j] + shift > 0.0))) return NGP_ERR_ARG;
+    return NGP_OK;
 }
 
 enum { MIX_CDF = 0, MIX_QUANTILES = 1, MIX_CRPS = 2 };
@@ -3462,17 +3501,12 @@ extern "C" ngp_status ngp_mixture_crps_mapped(ngp_ctx *c, int32_t C, int32_t m, 
                                               int32_t *info) {
     const ngp_inv_transform *inv = (const ngp_inv_transform *)inv_;
     if (!c || !inv || !y || !crps || !info || m < 1) return NGP_ERR_ARG;
-    if (scale != NGP_SCORE_NATURAL && scale != NGP_SCORE_LOG) return NGP_ERR_ARG;
-    if (!inv_transform_ok(inv) || !std::isfinite(shift) || !std::isfinite(tol) || shift < 0.0)
-        return NGP_ERR_ARG;
-    if (m > MIX_MAX_DATES) return NGP_ERR_TOO_LARGE;       // bounds the loop below
-    for (int32_t j = 0; j < m; ++j)
-        if (!std::isfinite(y[j]) || (scale == NGP_SCORE_LOG && !(y[j] + shift > 0.0)))
-            return NGP_ERR_ARG;
+    if (!inv_transform_ok(inv) || !std::isfinite(tol)) return NGP_ERR_ARG;
+    ngp_status st = score_obs_check(scale, shift, m > MIX_MAX_DATES, y, m);
+    if (st) return st;
     if (!(tol > 0.0)) tol = MIXMAP_DEFAULT_TOL;
     MixStaged h;
-    ngp_status st = mixture_stage(C, m, w, mu, var, info, &h);
-    if (st) return st;
+    if ((st = mixture_stage(C, m, w, mu, var, info, &h))) return st;
     const size_t Cn = (size_t)h.C;
     std::vector<double> rec((size_t)m * MIXMAP_REC, 0.0);   // (before the call: it outlives what reads and writes it)
     std::vector<MixMapPlan> work;
@@ -3578,16 +3612,14 @@ extern "C" ngp_status ngp_microbench_mixture_pairs(ngp_ctx *c, int32_t iters, do
 // The host validates, turns the levels into ranks (ascending, distinct: the select passes work
 // on those; q is filled per level from them), stages, launches and scatters the few results.
 namespace {
-ngp_status path_targets_impl(ngp_ctx *c, int32_t P, int32_t S, int32_t m, const double *w,
-                             const double *mu, const double *sigma, int32_t draws, uint64_t seed,
-                             const uint64_t *seeds, const ngp_inv_transform *inv, int32_t T,
+ngp_status path_targets_impl(ngp_ctx *c, const MixInput &mix, const ngp_inv_transform *inv, int32_t T,
                              const ngp_path_target *targets, int32_t Q, const double *probs,
                              double *q, double *mean, int64_t *count, int64_t *hist,
                              double *values, int32_t *info) {
-    if (!c || !w || !mu || !sigma || !inv || !targets || !probs || !q || !mean || !count || !hist ||
-        P <= 0 || S <= 0 || m <= 0 || draws < 1 || T < 1 || Q < 1)
+    const int32_t m = mix.m;
+    if (!c || !mix.args_ok() || !inv || !targets || !probs || !q || !mean || !count || !hist || T < 1 || Q < 1)
         return NGP_ERR_ARG;
-    if (!inv_transform_ok(inv) || (inv->kind == NGP_INV_BOXCOX && !(inv->cap > 0.0))) return NGP_ERR_ARG;
+    if (!path_inv_ok(inv)) return NGP_ERR_ARG;
     if (T > PATH_MAX_TARGETS || Q > PATH_MAX_LEVELS) return NGP_ERR_TOO_LARGE;   // bounds the loops below
     for (int32_t t = 0; t < T; ++t) {
         const ngp_path_target &tg = targets[t];
@@ -3596,8 +3628,8 @@ ngp_status path_targets_impl(ngp_ctx *c, int32_t P, int32_t S, int32_t m, const 
             return NGP_ERR_ARG;
     }
     if (!probs_open_unit(probs, Q)) return NGP_ERR_ARG;
-    const int64_t N = (int64_t)S * draws, Bn = seeds ? (int64_t)S * P : (int64_t)P;
-    if (m > NGP_MAX_AUX || N > INT32_MAX || (int64_t)S * P > INT32_MAX) return NGP_ERR_TOO_LARGE;
+    if (mix.too_large(true)) return NGP_ERR_TOO_LARGE;
+    const int64_t N = mix.N();
 
     // levels -> ranks, ascending and distinct; lvl[i]: where level i's rank sits among them
     std::vector<int64_t> rank_of(Q), ranks;
@@ -3611,15 +3643,15 @@ ngp_status path_targets_impl(ngp_ctx *c, int32_t P, int32_t S, int32_t m, const 
         if (targets[t].kind <= NGP_TARGET_DIFF) real.push_back(t);
 
     PathGeom g{};
-    g.P = P; g.S = S; g.m = m; g.draws = draws;
-    g.B = (int32_t)Bn;
-    g.indep = seeds ? 1 : 0;
+    g.P = mix.P; g.S = mix.S; g.m = m; g.draws = mix.draws;
+    g.B = (int32_t)mix.blocks();
+    g.indep = mix.seeds ? 1 : 0;
     g.PW = path_pw(m);
     g.T = T; g.Tr = (int32_t)real.size(); g.R = (int32_t)ranks.size();
     g.N = N;
-    const size_t Nn = (size_t)N, B = (size_t)Bn, Tn = (size_t)T, R = ranks.size(),
+    const size_t Nn = (size_t)N, B = mix.blocks(), Tn = (size_t)T, R = ranks.size(),
                  Tr = std::max<size_t>(real.size(), 1), slices = (size_t)path_slices(N);
-    const size_t nw = (size_t)S * P, nmu = (size_t)P * S * m, nsg = B * m * m;
+    const size_t nw = mix.nw(), nmu = mix.nmu(), nsg = mix.nsg();
 
     std::vector<int32_t> hinfo(B, 0);
     std::vector<double> hq(Tr * R, 0.0);
@@ -3635,7 +3667,7 @@ ngp_status path_targets_impl(ngp_ctx *c, int32_t P, int32_t S, int32_t m, const 
     ngp_path_target *dtargets = nullptr;
     PathBufs b{};
     call.take(&dw, nw).take(&dmu, nmu).take(&b.chol, nsg);
-    if (seeds) call.take(&dseeds, (size_t)S);
+    if (mix.seeds) call.take(&dseeds, (size_t)mix.S);
     call.take(&b.info, B).take(&b.bkt, Nn).take(&b.order, Nn).take(&b.rank, Nn).take(&b.cnt, B)
         .take(&b.off, B + 1).take(&b.wgoff, B + 1).take(&dtargets, Tn).take(&dreal, Tr).take(&dranks, R)
         .take(&b.values, Tn * Nn).take(&b.partial, Tn * slices).take(&b.mean, Tn).take(&b.count, Tn)
@@ -3644,12 +3676,11 @@ ngp_status path_targets_impl(ngp_ctx *c, int32_t P, int32_t S, int32_t m, const 
 
     b.w = dw; b.mu = dmu; b.seeds = dseeds; b.targets = dtargets; b.real = dreal; b.ranks = dranks;
 
-    call.up(dw, w, 8 * nw).up(dmu, mu, 8 * nmu).up(b.chol, sigma, 8 * nsg);
-    if (seeds) call.up(dseeds, seeds, 8 * (size_t)S);
+    mix.up(call, dw, dmu, b.chol, dseeds);
     call.up(dtargets, targets, sizeof(ngp_path_target) * Tn);
     if (!real.empty()) call.up(dreal, real.data(), 4 * real.size());
     call.up(dranks, ranks.data(), 8 * R)
-        .run([&] { return launch_path_targets(g, b, *inv, seed, c->stream); })
+        .run([&] { return launch_path_targets(g, b, *inv, mix.seed, c->stream); })
         .down(mean, b.mean, 8 * Tn)
         .down(count, b.count, 8 * Tn)
         .down(hist, b.hist, 8 * Tn * m);
@@ -3666,14 +3697,7 @@ ngp_status path_targets_impl(ngp_ctx *c, int32_t P, int32_t S, int32_t m, const 
             const size_t r = std::lower_bound(ranks.begin(), ranks.end(), rank_of[i]) - ranks.begin();
             q[(size_t)real[y] * Q + i] = hq[y * R + r];
         }
-    // a failed component that paths can come from: nothing the call returns is free of it
-    bool failed = false;
-    for (size_t k = 0; k < B && !failed; ++k) {
-        if (!hinfo[k]) continue;
-        if (seeds) failed = w[k] > 0.0;
-        else for (int32_t sc = 0; sc < S && !failed; ++sc) failed = w[(size_t)sc * P + k] > 0.0;
-    }
-    if (failed) {
+    if (mix.tainted(hinfo.data())) {
         for (size_t i = 0; i < Tn * (size_t)Q; ++i) q[i] = nan;
         for (size_t t = 0; t < Tn; ++t) { mean[t] = nan; count[t] = 0; }
         for (size_t i = 0; i < Tn * (size_t)m; ++i) hist[i] = 0;
@@ -3690,7 +3714,7 @@ extern "C" ngp_status ngp_mixture_path_targets(ngp_ctx *c, int32_t P, int32_t S,
                                                int32_t Q, const double *probs, double *q,
                                                double *mean, int64_t *count, int64_t *hist,
                                                double *values, int32_t *info) {
-    return path_targets_impl(c, P, S, m, w, mu, sigma, draws, seed, nullptr,
+    return path_targets_impl(c, MixInput{P, S, m, draws, w, mu, sigma, seed, nullptr},
                              (const ngp_inv_transform *)inv, T, (const ngp_path_target *)targets, Q,
                              probs, q, mean, count, hist, values, info);
 }
@@ -3705,7 +3729,7 @@ extern "C" ngp_status ngp_mixture_path_targets_indep(ngp_ctx *c, int32_t P, int3
                                                      int64_t *count, int64_t *hist, double *values,
                                                      int32_t *info) {
     if (!seeds) return NGP_ERR_ARG;
-    return path_targets_impl(c, P, S, m, w, mu, sigma, draws, 0, seeds,
+    return path_targets_impl(c, MixInput{P, S, m, draws, w, mu, sigma, 0, seeds},
                              (const ngp_inv_transform *)inv, T, (const ngp_path_target *)targets, Q,
                              probs, q, mean, count, hist, values, info);
 }
@@ -3717,40 +3741,30 @@ extern "C" ngp_status ngp_mixture_path_targets_indep(ngp_ctx *c, int32_t P, int3
 // The host validates, stages the paths (ensemble form) or has the sampler draw them into a device
 // buffer (mixture form), launches, and turns the two [W] totals into the scores.
 namespace {
-struct ScoreMixture {       // the mixture form's inputs (null for the ensemble form)
-    int32_t P, S, draws, indep;
-    const double *w, *mu, *sigma;
-    const uint64_t *seeds;
-    const ngp_inv_transform *inv;
-    int32_t *chol_info;
-};
-
 // what both forms ask of N, m, the windows and y; TOO_LARGE before any array is read
 ngp_status score_args(int64_t N, int32_t m, int32_t m_max, const double *y, int32_t scale, double shift,
                       int32_t fair, int32_t W, const int32_t *win, const double *es) {
     if (!y || !win || !es || N < 1 || m < 1 || W < 1) return NGP_ERR_ARG;
-    if (scale != NGP_SCORE_NATURAL && scale != NGP_SCORE_LOG) return NGP_ERR_ARG;
     if ((fair != 0 && fair != 1) || (fair == 1 && N < 2)) return NGP_ERR_ARG;
-    if (!std::isfinite(shift) || shift < 0.0) return NGP_ERR_ARG;
-    if (N > SCORE_MAX_PATHS || W > SCORE_MAX_WINDOWS || m > m_max) return NGP_ERR_TOO_LARGE;
+    const bool too_large = N > SCORE_MAX_PATHS || W > SCORE_MAX_WINDOWS || m > m_max;
+    if (ngp_status st = score_obs_check(scale, shift, too_large, y, m)) return st;
     for (int32_t w = 0; w < W; ++w)
         if (win[2 * w] < 0 || win[2 * w + 1] >= m || win[2 * w] > win[2 * w + 1]) return NGP_ERR_ARG;
-    for (int32_t j = 0; j < m; ++j)
-        if (!std::isfinite(y[j]) || (scale == NGP_SCORE_LOG && !(y[j] + shift > 0.0))) return NGP_ERR_ARG;
     return NGP_OK;
 }
 
-ngp_status scores_impl(ngp_ctx *c, int32_t N, int32_t m, const double *x, const ScoreMixture *mix,
-                       const double *y, int32_t scale, double shift, int32_t fair, int32_t W,
-                       const int32_t *win, double *es, double *term_obs, double *term_pair,
-                       int32_t *info) {
+// x: the ensemble form's paths; mix, inv, chol_info: the mixture form's inputs instead
+ngp_status scores_impl(ngp_ctx *c, int32_t N, int32_t m, const double *x, const double *y, int32_t scale,
+                       double shift, int32_t fair, int32_t W, const int32_t *win, double *es,
+                       double *term_obs, double *term_pair, int32_t *info, const MixInput *mix = nullptr,
+                       const ngp_inv_transform *inv = nullptr, int32_t *chol_info = nullptr) {
     const size_t Nn = (size_t)N, Wn = (size_t)W, nxm = Nn * (size_t)m;
     const size_t prow = (size_t)score_tile_pairs(N), orow = (size_t)score_slices(N);
     const size_t prow1 = (size_t)score_folded((int64_t)prow), orow1 = (size_t)score_folded((int64_t)orow);
     bool long_windows = false;
     for (int32_t w = 0; w < W; ++w) long_windows = long_windows || win[2 * w + 1] - win[2 * w] >= SCORE_FOLD;
-    const size_t B = mix ? (mix->indep ? (size_t)mix->S * mix->P : (size_t)mix->P) : 0;
-    const size_t nw = mix ? (size_t)mix->S * mix->P : 0, nmu = nw * (size_t)m, nsg = B * (size_t)m * m;
+    const size_t B = mix ? mix->blocks() : 0;
+    const size_t nw = mix ? mix->nw() : 0, nmu = mix ? mix->nmu() : 0, nsg = mix ? mix->nsg() : 0;
 
     std::vector<int32_t> hflag((size_t)m, 0), hcinfo(B, 0);
     std::vector<double> hobs(Wn, 0.0), hpair(Wn, 0.0);
@@ -3769,12 +3783,11 @@ ngp_status scores_impl(ngp_ctx *c, int32_t N, int32_t m, const double *x, const 
         .take(&b.obs[0], orow * Wn).take(&b.obs[1], orow1 * Wn);
     if (mix) {
         call.take(&dw, nw).take(&dmu, nmu).take(&dsg, nsg).take(&dcinfo, B);
-        if (mix->indep) call.take(&dseeds, (size_t)mix->S);
-        call.up(dw, mix->w, 8 * nw).up(dmu, mix->mu, 8 * nmu).up(dsg, mix->sigma, 8 * nsg);
-        if (mix->indep) call.up(dseeds, mix->seeds, 8 * (size_t)mix->S);
+        if (mix->seeds) call.take(&dseeds, (size_t)mix->S);
+        mix->up(call, dw, dmu, dsg, dseeds);
         call.run([&] {   // the sampler as ngp_mixture_sample launches it, its paths kept on the device
-            launch_mixture_sample(mix->P, mix->S, m, dw, dmu, dsg, mix->draws, mix->indep ? 0 : mix->seeds[0],
-                                  dseeds, dx, nullptr, dcinfo, c->stream);
+            launch_mixture_sample(mix->P, mix->S, m, dw, dmu, dsg, mix->draws, mix->seed, dseeds, dx, nullptr,
+                                  dcinfo, c->stream);
         });
     } else {
         call.up(dx, x, 8 * nxm);
@@ -3783,24 +3796,15 @@ ngp_status scores_impl(ngp_ctx *c, int32_t N, int32_t m, const double *x, const 
     const double *dobs = nullptr, *dpair = nullptr;
     call.up(dy, y, 8 * (size_t)m).up(dwin, win, 8 * Wn)
         .run([&] {
-            return launch_scores(N, m, W, long_windows, mix ? mix->inv : nullptr, scale, shift, b, &dobs,
-                                 &dpair, c->stream);
+            return launch_scores(N, m, W, long_windows, inv, scale, shift, b, &dobs, &dpair, c->stream);
         });
     if (call.status()) return call.status();
     call.down(hobs.data(), dobs, 8 * Wn).down(hpair.data(), dpair, 8 * Wn).down(hflag.data(), b.flag, 4 * (size_t)m);
     if (mix) call.down(hcinfo.data(), dcinfo, 4 * B);
     if (call.sync()) return call.status();
 
-    // a failed component that paths can come from: nothing the call returns is free of it
-    bool failed = false;
-    if (mix) {
-        if (mix->chol_info) std::copy(hcinfo.begin(), hcinfo.end(), mix->chol_info);
-        for (size_t k = 0; k < B && !failed; ++k) {
-            if (!hcinfo[k]) continue;
-            if (mix->indep) failed = mix->w[k] > 0.0;
-            else for (int32_t sc = 0; sc < mix->S && !failed; ++sc) failed = mix->w[(size_t)sc * mix->P + k] > 0.0;
-        }
-    }
+    if (chol_info) std::copy(hcinfo.begin(), hcinfo.end(), chol_info);
+    const bool failed = mix && mix->tainted(hcinfo.data());
     const double nan = std::nan("");
     const double pairs = fair ? 0.5 * (double)N * (double)(N - 1) : 0.5 * (double)N * (double)N;
     for (int32_t w = 0; w < W; ++w) {
@@ -3825,9 +3829,8 @@ extern "C" ngp_status ngp_ensemble_scores(ngp_ctx *c, int32_t N, int32_t m, cons
                                           int32_t W, const int32_t *win, double *es, double *term_obs,
                                           double *term_pair, int32_t *info) {
     if (!c || !x) return NGP_ERR_ARG;
-    const ngp_status st = score_args(N, m, SCORE_MAX_DATES, y, scale, shift, fair, W, win, es);
-    if (st) return st;
-    return scores_impl(c, N, m, x, nullptr, y, scale, shift, fair, W, win, es, term_obs, term_pair, info);
+    if (ngp_status st = score_args(N, m, SCORE_MAX_DATES, y, scale, shift, fair, W, win, es)) return st;
+    return scores_impl(c, N, m, x, y, scale, shift, fair, W, win, es, term_obs, term_pair, info);
 }
 
 extern "C" ngp_status ngp_mixture_path_scores(ngp_ctx *c, int32_t P, int32_t S, int32_t m,
@@ -3838,17 +3841,13 @@ extern "C" ngp_status ngp_mixture_path_scores(ngp_ctx *c, int32_t P, int32_t S, 
                                               double *es, double *term_obs, double *term_pair,
                                               int32_t *info, int32_t *chol_info) {
     const ngp_inv_transform *inv = (const ngp_inv_transform *)inv_;
-    if (!c || !w || !mu || !sigma || !seeds || !inv || P <= 0 || S <= 0 || m <= 0 || draws < 1 ||
-        (indep != 0 && indep != 1))
-        return NGP_ERR_ARG;
-    if (!inv_transform_ok(inv) || (inv->kind == NGP_INV_BOXCOX && !(inv->cap > 0.0))) return NGP_ERR_ARG;
-    const int64_t N = (int64_t)S * draws;
-    const ngp_status st = score_args(N, m, NGP_MAX_AUX, y, scale, shift, fair, W, win, es);
-    if (st) return st;
-    if ((int64_t)S * P > INT32_MAX) return NGP_ERR_TOO_LARGE;
-    const ScoreMixture mix{P, S, draws, indep, w, mu, sigma, seeds, inv, chol_info};
-    return scores_impl(c, (int32_t)N, m, nullptr, &mix, y, scale, shift, fair, W, win, es, term_obs,
-                       term_pair, info);
+    if (!c || !seeds || !inv || (indep != 0 && indep != 1)) return NGP_ERR_ARG;
+    const MixInput mix{P, S, m, draws, w, mu, sigma, indep ? 0 : seeds[0], indep ? seeds : nullptr};
+    if (!mix.args_ok() || !path_inv_ok(inv)) return NGP_ERR_ARG;
+    if (ngp_status st = score_args(mix.N(), m, NGP_MAX_AUX, y, scale, shift, fair, W, win, es)) return st;
+    if (mix.too_large(true)) return NGP_ERR_TOO_LARGE;
+    return scores_impl(c, (int32_t)mix.N(), m, nullptr, y, scale, shift, fair, W, win, es, term_obs, term_pair,
+                       info, &mix, inv, chol_info);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -3944,7 +3943,7 @@ ngp_status comb_run_one(ngp_ctx *c, ngp_comb_req &r) {
         if (r.gj) return grad_job_run_resident(r.gj, r.logml, r.grad, r.info);
         return logml_grad_direct(c, r.B, r.k, r.n, r.t, r.y, r.ldy, nullptr, r.logml, r.grad, r.info);
     default:
-        return mixture_sample_impl(c, r.P, 1, r.m, r.w, r.cmu, r.csigma, r.draws, r.seed, nullptr,
+        return mixture_sample_impl(c, MixInput{r.P, 1, r.m, r.draws, r.w, r.cmu, r.csigma, r.seed, nullptr},
                                    r.out, r.comp, r.info);
     }
 }
@@ -3965,9 +3964,8 @@ ngp_status comb_run_group(ngp_ctx *c, const std::vector<ngp_comb_req *> &grp, bo
             std::memcpy(sg.data() + a * P * m * m, grp[a]->csigma, 8 * P * m * m);
             seeds[a] = grp[a]->seed;
         }
-        const ngp_status st = mixture_sample_impl(c, r0.P, (int32_t)K, r0.m, w.data(), mu.data(), sg.data(),
-                                                  r0.draws, 0, seeds.data(), out.data(), comp.data(),
-                                                  info.data());
+        const MixInput mix{r0.P, (int32_t)K, r0.m, r0.draws, w.data(), mu.data(), sg.data(), 0, seeds.data()};
+        const ngp_status st = mixture_sample_impl(c, mix, out.data(), comp.data(), info.data());
         if (st) return st;
         for (size_t a = 0; a < K; ++a) {
             std::memcpy(grp[a]->out, out.data() + a * dr * m, 8 * dr * m);
@@ -4285,8 +4283,8 @@ extern "C" ngp_status ngp_mixture_sample(ngp_ctx *c, int32_t P, int32_t S, int32
     // S mixtures over shared components stay one call of their own; ONE mixture (what
     // predict_mvn(...) |> rand of a scenario task asks for, src/forecasting.jl:46-47) can share a
     // launch with other tasks' mixtures of the same shape
-    if (S != 1 || !c || !w || !mu || !sigma || !out || P <= 0 || m <= 0 || m > NGP_MAX_AUX || draws <= 0)
-        return mixture_sample_impl(c, P, S, m, w, mu, sigma, draws, seed, nullptr, out, comp, info);
+    const MixInput mix{P, S, m, draws, w, mu, sigma, seed, nullptr};
+    if (S != 1 || !c || !out || !mix.args_ok() || mix.too_large(false)) return mixture_sample_impl(c, mix, out, comp, info);
     ngp_comb_req r;
     r.kind = CK_MIXTURE;
     r.P = P; r.m = m; r.draws = draws; r.w = w;

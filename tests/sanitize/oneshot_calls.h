@@ -1,8 +1,8 @@
 // The one-shot device calls of the C-ABI at small fixed shapes: the table that oneshot_trace.cpp
 // records and oneshot_faults.cpp breaks.  A one-shot call takes the context, allocates a few device
 // blocks, copies up, launches, copies down, synchronises and gives the blocks back, all inside one
-// call.  The component queries need a resident factor: `setup` makes it and `teardown` destroys it,
-// outside of what is recorded or broken.
+// call.  The component and long-horizon queries need a resident factor: `setup` makes it and
+// `teardown` destroys it, outside of what is recorded or broken.
 #pragma once
 #include <cstdint>
 #include <functional>
@@ -89,6 +89,29 @@ struct Paths {
                                               count.data(), hist.data(),
                                               with_values ? values.data() : nullptr, info.data());
     }
+    // the paths scored on the natural scale, the fair estimator: one date, all dates
+    double y[m] = {0.75, 1.0, 1.25, 1.5, 1.75}, es[2], term_obs[2], term_pair[2];
+    int32_t win[4] = {2, 2, 0, m - 1}, winfo[2];
+    ngp_status scores(ngp_ctx *c, bool indep, bool with_chol_info) {
+        return ngp_mixture_path_scores(c, P, S, m, w.data(), mu.data(), indep ? sigma_indep.data() : sigma.data(),
+                                       indep ? 1 : 0, draws, seeds, &inv, y, NGP_SCORE_NATURAL, 0.0, 1, 2, win,
+                                       es, term_obs, term_pair, winfo, with_chol_info ? info.data() : nullptr);
+    }
+};
+
+// ---- the scores of paths the caller hands in: N = 16, m = 5, W = 2 (one date, all dates) --------
+struct Ens {
+    static constexpr int N = 16, m = 5, W = 2;
+    double x[N * m], y[m] = {0.75, 1.0, 1.25, 1.5, 1.75}, es[W], term_obs[W], term_pair[W];
+    int32_t win[2 * W] = {2, 2, 0, m - 1}, info[W];
+    Ens() {
+        for (int i = 0; i < N; ++i)
+            for (int j = 0; j < m; ++j) x[i * m + j] = 0.5 + 0.125 * ((i * 7 + j * 3) % 11);
+    }
+    ngp_status scores(ngp_ctx *c, bool log_scale) {
+        return ngp_ensemble_scores(c, N, m, x, y, log_scale ? NGP_SCORE_LOG : NGP_SCORE_NATURAL,
+                                   log_scale ? 0.5 : 0.0, log_scale ? 1 : 0, W, win, es, term_obs, term_pair, info);
+    }
 };
 
 // ---- the summaries: C = 5 with one zero weight, m = 7, K = Q = 3, one date with a bad component --
@@ -150,6 +173,14 @@ struct Comp {
         return ngp_factor_components_nowcast(f, d, t_add, D, y_add, counts, comps, m, t_new, lf, mu, sigma, var,
                                              info);
     }
+    // the long-horizon query of the same factor: m = 6 dates
+    static constexpr int mL = 6;
+    double t_long[mL], mu_long[P * D * mL], var_long[P * mL], sigma_long[P * mL * mL];
+    ngp_status predict_long(bool appended, bool with_sigma) {
+        for (int i = 0; i < mL; ++i) t_long[i] = (n + d + i) / 128.0;
+        return ngp_factor_predict_long(f, appended ? d : 0, t_add, D, y_add, mL, t_long, 0, mu_long, var_long,
+                                       with_sigma ? sigma_long : nullptr, info);
+    }
 };
 
 struct Probes {
@@ -165,6 +196,7 @@ inline std::vector<Entry> table() {
     static Paths pa;
     static Mix mx;
     static Comp cq;
+    static Ens en;
     static Probes pr;
     auto make = [](ngp_ctx *c) { return cq.create(c); };
     auto drop = [] { cq.destroy(); };
@@ -191,6 +223,16 @@ inline std::vector<Entry> table() {
         {"ngp_microbench_mfma_f64_detail", [](ngp_ctx *c) { return ngp_microbench_mfma_f64_detail(c, 1, 1, pr.r); }},
         {"ngp_microbench_mixture_pairs", [](ngp_ctx *c) { return ngp_microbench_mixture_pairs(c, 1, pr.r); }},
         {"ngp_microbench_hbm", [](ngp_ctx *c) { return ngp_microbench_hbm(c, 4096, pr.r, pr.r + 1); }},
+        {"ngp_ensemble_scores natural", [](ngp_ctx *c) { return en.scores(c, false); }},
+        {"ngp_ensemble_scores log shift", [](ngp_ctx *c) { return en.scores(c, true); }},
+        {"ngp_mixture_path_scores chol_info", [](ngp_ctx *c) { return pa.scores(c, false, true); }},
+        {"ngp_mixture_path_scores", [](ngp_ctx *c) { return pa.scores(c, false, false); }},
+        {"ngp_mixture_path_scores indep chol_info", [](ngp_ctx *c) { return pa.scores(c, true, true); }},
+        {"ngp_mixture_path_scores indep", [](ngp_ctx *c) { return pa.scores(c, true, false); }},
+        {"ngp_factor_predict_long d=0 sigma", [](ngp_ctx *) { return cq.predict_long(false, true); }, make, drop},
+        {"ngp_factor_predict_long d=0", [](ngp_ctx *) { return cq.predict_long(false, false); }, make, drop},
+        {"ngp_factor_predict_long d=2 sigma", [](ngp_ctx *) { return cq.predict_long(true, true); }, make, drop},
+        {"ngp_factor_predict_long d=2", [](ngp_ctx *) { return cq.predict_long(true, false); }, make, drop},
     };
 }
 

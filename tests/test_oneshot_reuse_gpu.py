@@ -3,9 +3,10 @@
 A one-shot call allocates its device blocks from the context's block cache and gives them back when
 it ends, so on a context that has served other calls every block a call gets is somebody else's old
 one: at least as large as asked, up to twice as large, and full of that call's data.  The sampler, the
-three summaries, the mapped CRPS, the trajectory targets and the covariance call (the small shapes of
-tests/sanitize/oneshot_calls.h) run on ONE context in one order, again in another order, and once
-each on a context of their own.  Each call's three results must be the same bytes, info arrays
+three summaries, the mapped CRPS, the trajectory targets, the covariance call, the scores of paths
+handed in and of paths drawn on the device, and the long-horizon query of a resident factor (the small
+shapes of tests/sanitize/oneshot_calls.h) run on ONE context in one order, again in another order, and
+once each on a context of their own.  Each call's three results must be the same bytes, info arrays
 included: a block handed out at the wrong size or type, or a read of a block the call did not fully
 write, shows as a difference."""
 import numpy as np
@@ -17,6 +18,7 @@ pytestmark = pytest.mark.gpu
 
 P, S, M, DRAWS = 3, 2, 5, 8
 C, MM, K = 5, 7, 3
+N_ENS, N_FAC, D_ADD, M_LONG = 16, 70, 2, 6
 
 
 def _inputs():
@@ -45,7 +47,15 @@ def _inputs():
         cprobs=[0.1, 0.5, 0.9], y=1.5 + 0.125 * np.arange(MM),
         progs=[([3], [0.3, 0.8], 0.05), ([2, 3, 7], [0.5, 0.1, 0.5, 0.2, 0.7], 0.02),
                ([3, 5, 6, 2, 7], [0.4, 0.6, 0.25, 0.2, 0.4, 0.5, 0.1, 0.5], 0.1)],
-        t1=[0.0, 0.125, 0.25, 0.5, 0.75], t2=[0.0625, 0.25, 0.875, 1.0])
+        t1=[0.0, 0.125, 0.25, 0.5, 0.75], t2=[0.0625, 0.25, 0.875, 1.0],
+        # the scores: 16 paths handed in, y [M], a window of one date and one of all dates
+        x_ens=0.5 + 0.125 * ((7 * np.arange(N_ENS)[:, None] + 3 * np.arange(M)[None, :]) % 11),
+        y_path=0.75 + 0.25 * np.arange(M), windows=[(2, 2), (0, M - 1)],
+        # the resident factor of the component entries: 2 particles, 70 points; 2 appended points in 2 scenarios
+        fprogs=[([3, 5, 6], [0.3, 0.8, 0.4, 0.25, 0.5], 0.05), ([2, 3, 7], [0.5, 0.1, 0.5, 0.2, 0.7], 0.02)],
+        ft=np.arange(N_FAC) / 128.0, fy=((np.arange(N_FAC) * 37) % 11) / 11.0 - 0.5,
+        t_add=(N_FAC + np.arange(D_ADD)) / 128.0, y_add=(0.1 * (np.arange(2 * D_ADD) % 3)).reshape(2, D_ADD),
+        t_long=(N_FAC + D_ADD + np.arange(M_LONG)) / 128.0)
 
 
 def _calls(a):
@@ -53,6 +63,23 @@ def _calls(a):
         r = ctx.mixture_path_targets(a["w"], mu, sigma, DRAWS, seed, a["inv"], a["targets"], a["probs"],
                                      want_values=True)
         return [r[k] for k in ("q", "mean", "count", "hist", "values", "info")]
+
+    def path_scores(ctx, seed, mu, sigma):
+        r = ctx.mixture_path_scores(a["w"], mu, sigma, DRAWS, seed, a["inv"], a["y_path"], a["windows"])
+        return [r[k] for k in ("es", "term_obs", "term_pair", "info", "chol_info")]
+
+    def ensemble_scores(ctx, scale, shift, fair):
+        r = ctx.ensemble_scores(a["x_ens"], a["y_path"], a["windows"], scale, shift, fair)
+        return [r[k] for k in ("es", "term_obs", "term_pair", "info")]
+
+    def predict_long(ctx, appended, want_sigma):
+        f = ctx.factor(a["fprogs"], a["ft"], a["fy"])
+        try:
+            r = f.predict_long(a["t_long"], a["t_add"] if appended else None, a["y_add"] if appended else None,
+                               noise_on_new=False, want_sigma=want_sigma)
+        finally:
+            f.close()
+        return [x for x in r if x is not None]
     return {
         "sample": lambda ctx: ctx.mixture_sample(a["w"], a["mu"], a["sigma"], DRAWS, 11),
         "sample_indep": lambda ctx: ctx.mixture_sample_indep(a["w"], a["mu_i"], a["sigma_i"], DRAWS, [7, 9]),
@@ -67,6 +94,14 @@ def _calls(a):
         "path_targets": lambda ctx: targets(ctx, 11, a["mu"], a["sigma"]),
         "path_targets_indep": lambda ctx: targets(ctx, [7, 9], a["mu_i"], a["sigma_i"]),
         "cov_batch": lambda ctx: [ctx.cov_batch(a["progs"], a["t1"], a["t2"], add_diag=True)],
+        "ensemble_scores natural": lambda ctx: ensemble_scores(ctx, _abi.NGP_SCORE_NATURAL, 0.0, False),
+        "ensemble_scores log": lambda ctx: ensemble_scores(ctx, _abi.NGP_SCORE_LOG, 0.5, True),
+        "path_scores": lambda ctx: path_scores(ctx, 11, a["mu"], a["sigma"]),
+        "path_scores_indep": lambda ctx: path_scores(ctx, [7, 9], a["mu_i"], a["sigma_i"]),
+        "predict_long d=0 sigma": lambda ctx: predict_long(ctx, False, True),
+        "predict_long d=0": lambda ctx: predict_long(ctx, False, False),
+        "predict_long d=2 sigma": lambda ctx: predict_long(ctx, True, True),
+        "predict_long d=2": lambda ctx: predict_long(ctx, True, False),
     }
 
 

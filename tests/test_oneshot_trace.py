@@ -3,10 +3,12 @@
 tests/sanitize/oneshot_trace.cpp walks the table of tests/sanitize/oneshot_calls.h through the C-ABI
 on the mock HIP runtime (tests/sanitize/mock_hip.cpp with its trace on): the covariance call, the
 sampler, the mixture summaries on both scales, the trajectory targets, the component queries of a
-resident factor, the self tests and the microbenchmarks, each at a small shape and each twice.  Every
+resident factor, the self tests and the microbenchmarks, the scores of paths handed in and of paths
+drawn on the device, the long-horizon query, each at a small shape and each twice; then the sampler,
+the targets and the path scores with invalid arguments, one line `call, fault: status` each.  Every
 copy (kind, bytes, stream), kernel launch (mangled name, grid, block, LDS bytes, stream, integer
 arguments) and event record of a call goes into one line, the number of records and their hash.
-The output must equal tests/golden/oneshot_trace_v1.txt byte for byte: the host code around these
+The output must equal tests/golden/oneshot_trace_v2.txt byte for byte: the host code around these
 calls may be rearranged, what it asks of the runtime on a successful call may not change.  To see
 WHAT moved, run the driver of two builds with --full and diff.  The golden file is regenerated only
 by a change that means to move a copy or a launch.  No GPU is involved."""
@@ -17,7 +19,7 @@ import pytest
 
 from tests.test_host_sanitizers import HIPCC, ROOT, build
 
-GOLDEN = os.path.join(ROOT, "tests", "golden", "oneshot_trace_v1.txt")
+GOLDEN = os.path.join(ROOT, "tests", "golden", "oneshot_trace_v2.txt")
 
 
 @pytest.mark.skipif(HIPCC is None, reason="no hipcc")
