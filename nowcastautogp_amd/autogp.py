@@ -959,9 +959,7 @@ class MixtureMVN:
             seed = int(self.rng.integers(0, 2**63 - 1))
             out, _, info = self.sampler(self.weights[None, :], self.means[:, None, :], self.covs,
                                         k, seed)
-            bad = np.flatnonzero(info)
-            if bad.size:
-                raise PosDefException(int(info[bad[0]]), int(bad[0]))
+            _raise_if_failed(info)
             return np.ascontiguousarray(out[0].T)
         comp = self.rng.choice(self.weights.size, size=k, p=self.weights)
         out = np.empty((m, k))
@@ -1341,9 +1339,7 @@ def _predict_marginals(model: GPModel, ds, noise_on_new: bool = True) -> "Mixtur
         return predict_mvn(model, ds, noise_on_new).marginals(engine=model._eng())
     t_new = model.ds_transform.apply(to_days(ds))
     mu, var, _, info = fac.predict_long(t_new, noise_on_new=noise_on_new, want_sigma=False)
-    bad = np.flatnonzero(info)
-    if bad.size:
-        raise PosDefException(int(info[bad[0]]), int(bad[0]))
+    _raise_if_failed(info)
     w, _ = distributed.normalize_log_weights(model.log_weights[:, None],
                                              P_total=model.n_particles_total)
     sl_ = model.y_transform.slope
@@ -1386,9 +1382,7 @@ def predict_mvn_lockstep(models: Sequence[GPModel], ds, noise_on_new: bool = Tru
         mu = mu[:, 0]
     else:       # longer than one call carries: pairwise calls, joint covariance assembled
         mu, sigma, info, _ = predict_in_blocks(call, t_new, blocks)
-    bad = np.flatnonzero(info)
-    if bad.size:
-        raise PosDefException(int(info[bad[0]]), int(bad[0]))
+    _raise_if_failed(info)
     m = t_new.size
     off = np.concatenate([[0], np.cumsum([len(mm.particles) for mm in models])])
     P_total = models[0].n_particles_total
@@ -1422,20 +1416,35 @@ def rand_lockstep(mixes: Sequence[MixtureMVN], draws: int, engine=None) -> List[
     """``rand(dist, draws)`` (reference src/forecasting.jl:47) for D mixtures: with the device
     sampler ONE call (``ngp_mixture_sample_indep``: mixture j keyed by the seed its own stream
     gives, so the draws are those of D separate ``rand`` calls); otherwise mixture by mixture."""
-    multi = getattr(engine, "mixture_sample_indep", None)
     k = int(draws)
-    m = mixes[0].means.shape[1]
-    P = mixes[0].means.shape[0]
-    if (multi is None or len(mixes) < 2 or k <= 1 or m == 0
-            or any(mx.sampler is None or mx.means.shape != (P, m) for mx in mixes)):
+    if not takes_independent_form(engine, mixes, k):
         return [mx.rand(k) for mx in mixes]
     seeds = [int(mx.rng.integers(0, 2**63 - 1)) for mx in mixes]
-    out, _, info = multi(np.stack([mx.weights for mx in mixes]), np.stack([mx.means for mx in mixes]),
-                         np.stack([mx.covs for mx in mixes]), k, seeds)
+    out, _, info = engine.mixture_sample_indep(
+        np.stack([mx.weights for mx in mixes]), np.stack([mx.means for mx in mixes]),
+        np.stack([mx.covs for mx in mixes]), k, seeds)
+    _raise_if_failed(info)
+    return [np.ascontiguousarray(out[j].T) for j in range(len(mixes))]
+
+
+def takes_independent_form(engine, mixes: Sequence[MixtureMVN], draws: int) -> bool:
+    """Whether ``draws`` draws from each of ``mixes`` are ONE call of the device's independent form
+    (``ngp_mixture_sample_indep`` and the targets / scores over it): the engine has it, there are
+    at least two mixtures and two draws, and every mixture has a sampler and the same (P, m)."""
+    P, m = mixes[0].means.shape
+    return (getattr(engine, "mixture_sample_indep", None) is not None and len(mixes) >= 2
+            and int(draws) > 1 and m > 0
+            and all(mx.sampler is not None and mx.means.shape == (P, m) for mx in mixes))
+
+
+def _raise_if_failed(info) -> None:
+    """``info``: a status per particle, [P] — or [S, P] from the independent forms — 0 or the pivot
+    that failed.  Raises ``PosDefException`` for the first failure with its particle (the flat
+    index; the last axis' for [S, P])."""
+    info = np.atleast_1d(info)
     bad = np.argwhere(info != 0)
     if bad.size:
-        raise PosDefException(int(info[tuple(bad[0])]), int(bad[0][1]))
-    return [np.ascontiguousarray(out[j].T) for j in range(len(mixes))]
+        raise PosDefException(int(info[tuple(bad[0])]), int(bad[0][-1]))
 
 
 # ---------------------------------------------------------------------------------------------
@@ -1684,9 +1693,7 @@ def predict_components(model: GPModel, ds, split: str = "plus") -> ComponentFore
     sigma = [np.zeros((len(ps) * m, len(ps) * m)) for ps in parts]
     for lo, hi in (blocks or [(0, m)]):
         o = fac.components(comps, t_new[lo:hi])
-        bad = np.flatnonzero(o["info"])
-        if bad.size:
-            raise PosDefException(int(o["info"][bad[0]]), int(bad[0]))
+        _raise_if_failed(o["info"])
         k = hi - lo
         for p in range(P):
             C = len(parts[p])
@@ -1847,18 +1854,14 @@ def _host_paths(engine, w, mu, sigma, draws: int, seed, inv_transformation):
     sampler = getattr(engine, "mixture_sample_indep" if indep else "mixture_sample", None)
     if sampler is not None:
         x, _, info = sampler(w, mu, sigma, int(draws), seed)
-        bad = np.argwhere(np.atleast_1d(info) != 0)
-        if bad.size:
-            raise PosDefException(int(info[tuple(bad[0])]), int(bad[0][-1]))
+        _raise_if_failed(info)
     elif indep and getattr(engine, "mixture_sample", None) is not None:
         # mixture s of the independent form IS a one-mixture call keyed by seeds[s]
         x = []
         for s in range(S):
             xs, _, info = engine.mixture_sample(w[s:s + 1], np.ascontiguousarray(mu[s][:, None, :]),
                                                 sigma[s], int(draws), seed[s])
-            if np.any(info):
-                k = int(np.flatnonzero(info)[0])
-                raise PosDefException(int(info[k]), k)
+            _raise_if_failed(info)
             x.append(xs[0])
         x = np.stack(x)
     elif indep:
@@ -1902,9 +1905,7 @@ def path_targets(mixes_or_arrays, targets, probs, draws: int, seed=None, inv_tra
     device = getattr(engine, "mixture_path_targets", None) if engine is not None else None
     if device is not None and inv is not None:
         o = device(w, mu, sigma, int(draws), seed, inv, tgs, probs, want_values)
-        bad = np.argwhere(np.atleast_1d(o["info"]) != 0)
-        if bad.size:
-            raise PosDefException(int(o["info"][tuple(bad[0])]), int(bad[0][-1]))
+        _raise_if_failed(o["info"])
         return PathTargets(tgs, probs, o["q"], o["mean"], o["count"], o["hist"], N, o["values"], True)
     x = _host_paths(engine, w, mu, sigma, int(draws), seed, inv_transformation)
     values = path_functionals(x, tgs)
@@ -2041,7 +2042,5 @@ def path_scores(mixes_or_arrays, y, draws: int, seed=None, inv_transformation=No
         raise ValueError("path_scores: y [dates]")
     win, single, longer = _score_windows(windows, m)
     o = device(w, mu, sigma, int(draws), seed, inv, y, win, _score_scale(scale), float(shift), bool(fair))
-    bad = np.argwhere(np.atleast_1d(o["chol_info"]) != 0)
-    if bad.size:
-        raise PosDefException(int(o["chol_info"][tuple(bad[0])]), int(bad[0][-1]))
+    _raise_if_failed(o["chol_info"])
     return EnsembleScores(win, o, single, longer, True)

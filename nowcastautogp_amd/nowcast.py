@@ -307,35 +307,33 @@ def forecast_with_nowcasts(base_model: GPModel, nowcasts: Sequence[TData], forec
     scenarios as concurrent tasks on that many threads — the reference's ``Threads.@spawn`` per
     scenario, src/forecasting.jl:131-132; the library combines their calls, include/ngp.h
     "concurrent callers") and ``hmc_config`` (leapfrog count / step size of the refinement moves;
-    AutoGP's defaults apply in the reference)."""
-    assert len(nowcasts) > 0, "nowcasts vector must not be empty"
-    assert not (n_mcmc > 0 and n_hmc == 0), \
-        "If n_mcmc > 0, n_hmc must also be > 0 for MCMC refinement"
-    assert 0.0 <= ess_threshold <= 1.0, "ess_threshold must be between 0 and 1"
-    assert forecast_n_hmc is None or forecast_n_hmc > 0, "forecast_n_hmc must be > 0 if specified"
-    dates = list(forecast_dates)
-    draws = int(forecast_draws_per_nowcast)
-    same_dates = all(list(nc.ds) == list(nowcasts[0].ds) for nc in nowcasts)
-    if n_mcmc == 0 and n_hmc == 0 and forecast_n_hmc is None and same_dates and lockstep:
-        return _forecast_with_nowcasts_batched(base_model, nowcasts, dates, draws,
-                                               inv_transformation, ess_threshold)
-    def clone():
-        return _clone_for_scenario(base_model)
-
-    if lockstep and same_dates:
-        models = _refined_clones_lockstep(base_model, nowcasts, n_mcmc, n_hmc, ess_threshold,
-                                          hmc_config)
-        results = forecast_lockstep(models, dates, draws, inv_transformation=inv_transformation,
+    AutoGP's defaults apply in the reference).  Everything up to the draws is the scenario pipeline
+    (``_Scenarios``); ``forecast_n_hmc`` and ``threads`` are this function's alone."""
+    sc = _Scenarios(base_model, nowcasts, forecast_dates, n_mcmc=n_mcmc, n_hmc=n_hmc,
+                    ess_threshold=ess_threshold, lockstep=lockstep, hmc_config=hmc_config,
+                    forecast_n_hmc=forecast_n_hmc)
+    dates, draws, D = sc.dates, int(forecast_draws_per_nowcast), len(nowcasts)
+    sc.run()
+    if sc.mode == "shared":
+        if sc.sampler is None:
+            return _apply(inv_transformation, sc.host_matrix(draws))
+        seed = sc.resample_for_device()
+        smp, _, info = sc.sampler(sc.w, sc.means, sc.covs, draws, seed)      # [D, draws, m]
+        autogp._raise_if_failed(info)
+        return _apply(inv_transformation, np.ascontiguousarray(smp.reshape(D * draws, len(dates)).T))
+    if sc.mode == "lockstep":
+        results = forecast_lockstep(sc.models, dates, draws, inv_transformation=inv_transformation,
                                     forecast_n_hmc=forecast_n_hmc, hmc_config=hmc_config)
         if verbose:
-            print(f"Nowcast scenarios: {len(results)}/{len(nowcasts)} (lockstep)")
+            print(f"Nowcast scenarios: {len(results)}/{D} (lockstep)")
         return np.hstack(results)
+
     def task(m, nc):      # the body of the reference's per-scenario task (src/forecasting.jl:133-155)
-        _refine_scenario(m, nc, n_mcmc, n_hmc, ess_threshold, hmc_config)
+        sc.refine(m, nc)
         return forecast(m, dates, draws, inv_transformation=inv_transformation,
                         forecast_n_hmc=forecast_n_hmc, hmc_config=hmc_config)
 
-    if threads is not None and int(threads) > 1 and len(nowcasts) > 1 and autogp.distributed.world()[1] == 1:
+    if threads is not None and int(threads) > 1 and D > 1 and autogp.distributed.world()[1] == 1:
         # Threads.@spawn per scenario (src/forecasting.jl:131-132).  The clones are made in scenario
         # order first (each takes its root from the base model's shared stream), then every task
         # works on its own clone with its own streams: the result does not depend on the schedule
@@ -343,7 +341,7 @@ def forecast_with_nowcasts(base_model: GPModel, nowcasts: Sequence[TData], forec
         # predictive call is the one-shot entry point (combinable), not a resident factor.
         import sys
         from concurrent.futures import ThreadPoolExecutor
-        models = [clone() for _ in nowcasts]
+        models = [sc.clone() for _ in nowcasts]
         for m in models:
             m._one_shot_predict = True
         # a task that comes back from the library needs the interpreter lock to go on; with the
@@ -356,125 +354,226 @@ def forecast_with_nowcasts(base_model: GPModel, nowcasts: Sequence[TData], forec
         finally:
             sys.setswitchinterval(old)
         if verbose:
-            print(f"Nowcast scenarios: {len(results)}/{len(nowcasts)} ({int(threads)} threads)")
+            print(f"Nowcast scenarios: {len(results)}/{D} ({int(threads)} threads)")
         return np.hstack(results)
     results = []
     for nc in nowcasts:   # one after another
-        results.append(task(clone(), nc))
+        results.append(task(sc.clone(), nc))
         if verbose:
-            print(f"Nowcast scenarios: {len(results)}/{len(nowcasts)}")
+            print(f"Nowcast scenarios: {len(results)}/{D}")
     return np.hstack(results)
 
 
-def _nowcast_mixtures_batched(model, nowcasts, dates, ess_threshold):
-    w, means, covs, _, low, rng, sampler = _nowcast_mixtures_core(model, nowcasts, dates,
-                                                                  ess_threshold, True)
-    return w, means, covs, low, rng, sampler
+class _Scenarios:
+    """The scenario pipeline: what the five ``*_with_nowcasts`` functions do before each consumes
+    the scenarios' mixtures in its own way (draw, marginals, components, targets, scores).  The
+    steps are written here once, in the order the random streams record them, which
+    is why from one snapshot and seed the five describe the same matrix of draws.
 
+    Construction asserts the arguments and chooses the ``mode``; it calls no engine and draws
+    nothing, so a function's own refusals come between it and ``run``:
 
-def _nowcast_mixtures_core(model, nowcasts, dates, ess_threshold, want_sigma):
-    """All scenarios in one engine call: one factorisation per particle (src/forecasting.jl:133-155
-    with n_mcmc = n_hmc = 0).  Returns the D scenario mixtures before anything is drawn: weights
-    ``w`` [D, P] (not yet resampled), ``means`` [P, D, m], ``covs`` [P, m, m] shared by the
-    scenarios of a particle, ``low`` [D] (scenarios whose ESS asks for resampling), the stream the
-    draws come from and the device sampler (None: the draws are made on the host).  Between
-    ``covs`` and ``low`` it returns the per-date variances ``var`` [P, m]; without ``want_sigma`` a
-    horizon served by the long query (``Factor.predict_long``) forms no covariance at all and
-    ``covs`` is None."""
-    t, y = model._obs()
-    t_add = model.ds_transform.apply(autogp.to_days(list(nowcasts[0].ds)))
-    y_add = np.stack([model.y_transform.apply(np.asarray(nc.y, dtype=np.float64))
-                      for nc in nowcasts])
-    t_new = model.ds_transform.apply(autogp.to_days(dates))
-    fac = model._factor()
+    ``"shared"`` (no refinement, the scenarios share their dates, ``lockstep``): ``run`` makes ONE
+    batched query, one factorisation per particle (src/forecasting.jl:133-155 with n_mcmc = n_hmc
+    = 0), and leaves the D mixtures before anything is drawn: weights ``w`` [D, P] (not yet
+    resampled), ``means`` [P, D, m], ``covs`` [P, m, m] and per-date variances ``var`` [P, m]
+    shared by the scenarios of a particle, ``low`` [D] (scenarios whose ESS asks for resampling),
+    ``rng`` (the stream the draws come from) and ``sampler`` (the device's; None: the draws are made
+    on the host).  Without ``want_sigma`` a horizon served by the long query
+    (``Factor.predict_long``) forms no covariance at all and ``covs`` is None.
 
-    def call(ts):
-        if fac is not None:
-            o = fac.nowcast(t_add, y_add, ts, True)
+    ``"lockstep"`` (refinement, shared dates, ``lockstep``): ``run`` leaves the D refined clones in
+    ``models``, the reference's D tasks as ONE ensemble of P x D items (src/forecasting.jl:131-149).
+
+    ``"loop"``: the reference's per-scenario loop.  Nothing happens in ``run``; ``mixtures`` clones,
+    refines and predicts scenario by scenario as it is consumed, so scenario s takes its root from
+    the base model's shared stream only after scenario s - 1 has drawn."""
+
+    def __init__(self, base_model: GPModel, nowcasts: Sequence[TData], forecast_dates, *,
+                 n_mcmc: int = 0, n_hmc: int = 0, ess_threshold: float = 0.0, lockstep: bool = True,
+                 hmc_config: Optional[dict] = None, forecast_n_hmc: Optional[int] = None):
+        assert len(nowcasts) > 0, "nowcasts vector must not be empty"
+        assert not (n_mcmc > 0 and n_hmc == 0), \
+            "If n_mcmc > 0, n_hmc must also be > 0 for MCMC refinement"
+        assert 0.0 <= ess_threshold <= 1.0, "ess_threshold must be between 0 and 1"
+        assert forecast_n_hmc is None or forecast_n_hmc > 0, "forecast_n_hmc must be > 0 if specified"
+        self.base, self.nowcasts, self.dates = base_model, nowcasts, list(forecast_dates)
+        self.n_mcmc, self.n_hmc, self.hmc_config = n_mcmc, n_hmc, hmc_config
+        self.ess_threshold = ess_threshold
+        self.same_dates = all(list(nc.ds) == list(nowcasts[0].ds) for nc in nowcasts)
+        if not (lockstep and self.same_dates):
+            self.mode = "loop"
+        elif n_mcmc == 0 and n_hmc == 0 and forecast_n_hmc is None:
+            self.mode = "shared"
         else:
-            o = model._eng().nowcast(model.programs(), t, y, t_add, y_add, ts, True)
-        return o["mu"], o["sigma"], o["info"], o
+            self.mode = "lockstep"
+        self._mixes = None
 
-    blocks = autogp.horizon_blocks(t.size, t_add.size, t_new.size)
-    if blocks is None:
-        out = call(t_new)[3]
-    elif fac is not None and hasattr(fac, "predict_long"):
-        # longer than the aux rows carry: the weight update from a query without dates, then ONE
-        # long query with the dates as the panel of a solve against the resident factor
-        first = fac.nowcast(t_add, y_add, t_new[:0], True)
-        mu_l, var_l, sg_l, info_l = fac.predict_long(t_new, t_add, y_add, True, want_sigma)
-        out = dict(first, mu=mu_l, sigma=sg_l, var=var_l,
-                   info=np.where(first["info"] != 0, first["info"], info_l))
-    else:       # a horizon longer than one call carries: pairwise calls (autogp.predict_in_blocks)
-        mu_all, sg_all, info_all, first = autogp.predict_in_blocks(call, t_new, blocks)
-        out = dict(first, mu=mu_all, sigma=sg_all, info=info_all)
-    bad = np.flatnonzero(out["info"])
-    if bad.size:
-        raise autogp.PosDefException(int(out["info"][bad[0]]), int(bad[0]))
-    s, b = model.y_transform.slope, model.y_transform.intercept
-    D = len(nowcasts)
-    m = len(dates)
-    P = model.n_particles_total
-    rng = model.rng_shared          # shared stream: every rank makes the same draws
-    # add_data! weight update for every scenario, normalised over ALL ranks' particles: one
-    # all-gather of [P_local, D] log-weights (the only collective of the weight update)
-    dist_ = autogp.distributed
-    logw = model.log_weights[:, None] + (out["logml_full"] - out["logml_base"][:, None])
-    _, ess, w_all = dist_.normalize_log_weights(logw, P_total=P, full=True)
-    w = np.ascontiguousarray(w_all.T)                                         # [D, P]
-    means = (out["mu"] - b) / s if m else np.zeros((logw.shape[0], D, 0))     # [P_local, D, m]
-    covs = None
-    if not m:
-        covs = np.zeros((logw.shape[0], 0, 0))
-    elif out["sigma"] is not None:
-        covs = out["sigma"] / (s * s)
-    var = out["var"] / (s * s) if out.get("var") is not None else np.einsum("pjj->pj", covs)
-    if dist_.world()[1] > 1:        # the mixtures need every rank's components: one more
-        second = covs if covs is not None else var
-        packed = np.concatenate([means.reshape(means.shape[0], -1),
-                                 second.reshape(second.shape[0], -1)], axis=1)
-        packed = dist_.all_gather_rows(packed, sizes=dist_.block_sizes(P))
-        means = np.ascontiguousarray(packed[:, :D * m].reshape(P, D, m))
-        if covs is not None:
-            covs = np.ascontiguousarray(packed[:, D * m:].reshape(P, m, m))
-            var = np.einsum("pjj->pj", covs)
+    def run(self, want_sigma: bool = True) -> None:
+        if self.mode == "shared":
+            self._weigh(want_sigma)
+        elif self.mode == "lockstep":
+            self.models = [self.clone() for _ in self.nowcasts]
+            autogp.add_data_lockstep(self.models, self.nowcasts[0].ds, [nc.y for nc in self.nowcasts],
+                                     base=self.base)
+            autogp.maybe_resample_lockstep(self.models,
+                                           self.ess_threshold * autogp.num_particles(self.base))
+            if self.n_mcmc > 0 and self.n_hmc > 0:
+                autogp.mcmc_structure_lockstep(self.models, self.n_mcmc, self.n_hmc, self.hmc_config)
+            elif self.n_mcmc == 0 and self.n_hmc > 0:
+                autogp.mcmc_parameters_lockstep(self.models, self.n_hmc, self.hmc_config)
+
+    # -- clones (modes "lockstep" and "loop") -------------------------------------------------------
+    def clone(self) -> GPModel:
+        # GPModel(deepcopy(Dict(base_model))) of the reference (src/forecasting.jl:128,133).  Every
+        # scenario is its own task with its own randomness there (:131-133); a clone that kept the
+        # snapshot's streams would repeat the first scenario's draws.  Splitting also advances the
+        # base model's shared stream, so a second call differs from the first.
+        return self.base.clone(root=int(self.base.rng_shared.integers(0, 2**62)))
+
+    def refine(self, m: GPModel, nc: TData) -> None:
+        """the body of the reference's per-scenario task up to its forecast (src/forecasting.jl:133-149)"""
+        autogp.add_data(m, nc.ds, nc.y)
+        autogp.maybe_resample(m, self.ess_threshold * autogp.num_particles(m))
+        if self.n_mcmc > 0 and self.n_hmc > 0:
+            autogp.mcmc_structure(m, self.n_mcmc, self.n_hmc, self.hmc_config)
+        elif self.n_mcmc == 0 and self.n_hmc > 0:
+            autogp.mcmc_parameters(m, self.n_hmc, self.hmc_config)
+
+    def mixtures(self):
+        """The scenarios' ``MixtureMVN``: a list from one ``predict_mvn_lockstep`` (made once) in
+        mode "lockstep", a generator in mode "loop"."""
+        if self.mode == "lockstep":
+            if self._mixes is None:
+                self._mixes = autogp.predict_mvn_lockstep(self.models, self.dates)
+            return self._mixes
+        return self._loop_mixtures()
+
+    def _loop_mixtures(self):
+        for nc in self.nowcasts:
+            mdl = self.clone()
+            self.refine(mdl, nc)
+            yield autogp.predict_mvn(mdl, self.dates)
+
+    # -- mode "shared": the batched query and the weight update -------------------------------------
+    def _weigh(self, want_sigma: bool) -> None:
+        model, nowcasts, dates = self.base, self.nowcasts, self.dates
+        t, y = model._obs()
+        t_add = model.ds_transform.apply(autogp.to_days(list(nowcasts[0].ds)))
+        y_add = np.stack([model.y_transform.apply(np.asarray(nc.y, dtype=np.float64))
+                          for nc in nowcasts])
+        t_new = model.ds_transform.apply(autogp.to_days(dates))
+        fac = model._factor()
+
+        def call(ts):
+            if fac is not None:
+                o = fac.nowcast(t_add, y_add, ts, True)
+            else:
+                o = model._eng().nowcast(model.programs(), t, y, t_add, y_add, ts, True)
+            return o["mu"], o["sigma"], o["info"], o
+
+        blocks = autogp.horizon_blocks(t.size, t_add.size, t_new.size)
+        if blocks is None:
+            out = call(t_new)[3]
+        elif fac is not None and hasattr(fac, "predict_long"):
+            # longer than the aux rows carry: the weight update from a query without dates, then ONE
+            # long query with the dates as the panel of a solve against the resident factor
+            first = fac.nowcast(t_add, y_add, t_new[:0], True)
+            mu_l, var_l, sg_l, info_l = fac.predict_long(t_new, t_add, y_add, True, want_sigma)
+            out = dict(first, mu=mu_l, sigma=sg_l, var=var_l,
+                       info=np.where(first["info"] != 0, first["info"], info_l))
+        else:       # a horizon longer than one call carries: pairwise calls (autogp.predict_in_blocks)
+            mu_all, sg_all, info_all, first = autogp.predict_in_blocks(call, t_new, blocks)
+            out = dict(first, mu=mu_all, sigma=sg_all, info=info_all)
+        autogp._raise_if_failed(out["info"])
+        s, b = model.y_transform.slope, model.y_transform.intercept
+        D = len(nowcasts)
+        m = len(dates)
+        P = model.n_particles_total
+        self.rng = model.rng_shared     # shared stream: every rank makes the same draws
+        # add_data! weight update for every scenario, normalised over ALL ranks' particles: one
+        # all-gather of [P_local, D] log-weights (the only collective of the weight update)
+        dist_ = autogp.distributed
+        logw = model.log_weights[:, None] + (out["logml_full"] - out["logml_base"][:, None])
+        _, ess, w_all = dist_.normalize_log_weights(logw, P_total=P, full=True)
+        self.w = np.ascontiguousarray(w_all.T)                                    # [D, P]
+        means = (out["mu"] - b) / s if m else np.zeros((logw.shape[0], D, 0))     # [P_local, D, m]
+        covs = None
+        if not m:
+            covs = np.zeros((logw.shape[0], 0, 0))
+        elif out["sigma"] is not None:
+            covs = out["sigma"] / (s * s)
+        var = out["var"] / (s * s) if out.get("var") is not None else np.einsum("pjj->pj", covs)
+        if dist_.world()[1] > 1:        # the mixtures need every rank's components: one more
+            second = covs if covs is not None else var
+            packed = np.concatenate([means.reshape(means.shape[0], -1),
+                                     second.reshape(second.shape[0], -1)], axis=1)
+            packed = dist_.all_gather_rows(packed, sizes=dist_.block_sizes(P))
+            means = np.ascontiguousarray(packed[:, :D * m].reshape(P, D, m))
+            if covs is not None:
+                covs = np.ascontiguousarray(packed[:, D * m:].reshape(P, m, m))
+                var = np.einsum("pjj->pj", covs)
+            else:
+                var = np.ascontiguousarray(packed[:, D * m:].reshape(P, m))
+        self.means, self.covs, self.var = means, covs, var
+        self.low = ess < self.ess_threshold * P
+        # (the device sampler takes at most NGP_MAX_AUX dates)
+        self.sampler = getattr(model._eng(), "mixture_sample", None) if 0 < m <= _abi.NGP_MAX_AUX else None
+
+    # -- mode "shared": maybe_resample! in its two recorded forms ------------------------------------
+    def resample_for_device(self) -> int:
+        """With a device sampler: ``maybe_resample!`` for ALL low scenarios in one multinomial
+        (ancestors ~ w, weights -> ancestor counts / P), then the seed of the ONE device call that
+        draws from all D mixtures.  The consumers that draw nothing (marginals, components) take
+        the seed all the same: it leaves the stream where the draws would."""
+        P = self.w.shape[1]
+        if self.low.any():
+            self.w[self.low] = self.rng.multinomial(P, self.w[self.low]) / P
+        return int(self.rng.integers(0, 2**63 - 1))
+
+    def _resampled(self, s: int) -> np.ndarray:
+        """``maybe_resample!`` of scenario s on the host: ancestors ~ w, weights -> counts / P"""
+        P = self.w.shape[1]
+        return np.bincount(self.rng.choice(P, size=P, p=self.w[s]), minlength=P) / P
+
+    def resample_without_draws(self) -> None:
+        """What the consumers that draw nothing do where ``forecast_with_nowcasts`` would draw: the
+        device form, or without a sampler the host form over the low scenarios alone (there
+        ``forecast_with_nowcasts`` interleaves every scenario's draws, so only the scenarios up to
+        the first resampled one have its weights)."""
+        if self.sampler is not None:
+            self.resample_for_device()
         else:
-            var = np.ascontiguousarray(packed[:, D * m:].reshape(P, m))
-    low = ess < ess_threshold * P
-    sampler = getattr(model._eng(), "mixture_sample", None)
-    from ._abi import NGP_MAX_AUX
-    if not 0 < m <= NGP_MAX_AUX:   # the device sampler's limit
-        sampler = None
-    return w, means, covs, var, low, rng, sampler
+            for s in np.flatnonzero(self.low):
+                self.w[s] = self._resampled(s)
 
+    # -- what forecast_with_nowcasts returns, where it is drawn on the host -------------------------
+    def host_matrix(self, draws: int) -> np.ndarray:
+        """[m, D draws] on the model's scale (column (s, d) at s draws + d).  "shared": scenario by
+        scenario, each resampled just before its own draws; "lockstep": ``rand_lockstep``;
+        "loop": ``rand`` of each scenario's mixture as it is made."""
+        if self.mode == "lockstep":
+            return np.hstack(autogp.rand_lockstep(self.mixtures(), draws, self.base._eng()))
+        if self.mode == "loop":
+            return np.hstack([mx.rand(draws) for mx in self.mixtures()])
+        res = np.empty((len(self.dates), len(self.nowcasts) * draws))
+        for s in range(len(self.nowcasts)):
+            wsc = self._resampled(s) if self.low[s] else self.w[s]
+            res[:, s * draws:(s + 1) * draws] = autogp.MixtureMVN(self.means[:, s, :], self.covs, wsc,
+                                                                  self.rng).rand(draws)
+        return res
 
-def _forecast_with_nowcasts_batched(model, nowcasts, dates, draws, inv_transformation,
-                                    ess_threshold):
-    w, means, covs, low, rng, sampler = _nowcast_mixtures_batched(model, nowcasts, dates,
-                                                                  ess_threshold)
-    D, P = w.shape
-    m = len(dates)
-    if sampler is not None:
-        # maybe_resample! for every scenario (ancestors ~ w, weights -> ancestor counts / P),
-        # then ONE device call that draws from all D mixtures
-        if low.any():
-            w[low] = rng.multinomial(P, w[low]) / P
-        seed = int(rng.integers(0, 2**63 - 1))
-        smp, _, info = sampler(w, means, covs, int(draws), seed)      # [D, draws, m]
-        bad = np.flatnonzero(info)
-        if bad.size:
-            raise autogp.PosDefException(int(info[bad[0]]), int(bad[0]))
-        res = smp.reshape(D * int(draws), m).T
-        return _apply(inv_transformation, np.ascontiguousarray(res))
-    res = np.empty((m, D * draws))
-    for sc in range(D):
-        wsc = w[sc]
-        if low[sc]:          # maybe_resample!: ancestors ~ w, weights -> uniform
-            anc = rng.choice(P, size=P, p=wsc)
-            wsc = np.bincount(anc, minlength=P) / P
-        mix = autogp.MixtureMVN(means[:, sc, :], covs, wsc, rng)
-        res[:, sc * draws:(sc + 1) * draws] = mix.rand(draws)
-    return _apply(inv_transformation, res)
+    def device_input(self, draws: int):
+        """``(mixes_or_arrays, seed)`` for ``autogp.path_targets`` / ``path_scores`` where
+        ``forecast_with_nowcasts`` draws in one device call — "shared" with a sampler: the arrays
+        and the seed after resampling; "lockstep" clones that take the independent form: their
+        mixtures, each keyed from its own stream — else None: ``host_matrix`` has the paths."""
+        if self.mode == "shared" and self.sampler is not None:
+            seed = self.resample_for_device()
+            return (self.w, self.means, self.covs), seed
+        if self.mode == "lockstep" and autogp.takes_independent_form(self.base._eng(), self.mixtures(), draws):
+            return self.mixtures(), None
+        return None
 
 
 def forecast_mixture(model: GPModel, forecast_dates) -> "autogp.MixtureMarginals":
@@ -491,49 +590,27 @@ def forecast_mixture_with_nowcasts(base_model: GPModel, nowcasts: Sequence[TData
     """The mixture ``forecast_with_nowcasts`` draws from, pooled over the scenarios (every scenario
     weighs 1 / D, as its equal share of the draws does), as an ``autogp.MixtureMarginals``.
 
-    Follows ``forecast_with_nowcasts`` step for step — same asserts, weight update, resampling with
-    the same use of the random streams, refinement moves — up to the point where that function
-    draws, so from the same snapshot and seed the draws of ``forecast_with_nowcasts`` are samples of
-    exactly the mixture returned here.  One exception: on the default path with an engine that has
+    The scenario pipeline (``_Scenarios``) up to the point where ``forecast_with_nowcasts`` draws,
+    so from the same snapshot and seed the draws of that function are samples of exactly the
+    mixture returned here.  One exception: on the default path with an engine that has
     no device sampler (or more forecast dates than it takes), ``forecast_with_nowcasts`` resamples
     a scenario AFTER it has drawn for the scenarios before it, so with ``ess_threshold > 0`` only
     the scenarios up to the first resampled one are the same there.  ``forecast_n_hmc`` (a new
     mixture before every draw) has no single mixture and is not taken."""
-    assert len(nowcasts) > 0, "nowcasts vector must not be empty"
-    assert not (n_mcmc > 0 and n_hmc == 0), \
-        "If n_mcmc > 0, n_hmc must also be > 0 for MCMC refinement"
-    assert 0.0 <= ess_threshold <= 1.0, "ess_threshold must be between 0 and 1"
-    dates = list(forecast_dates)
-    D = len(nowcasts)
-    same_dates = all(list(nc.ds) == list(nowcasts[0].ds) for nc in nowcasts)
-    if n_mcmc == 0 and n_hmc == 0 and same_dates and lockstep:
-        w, means, _, var, low, rng, sampler = _nowcast_mixtures_core(base_model, nowcasts, dates,
-                                                                     ess_threshold, False)
-        P = w.shape[1]
-        if sampler is not None:
-            if low.any():
-                w[low] = rng.multinomial(P, w[low]) / P
-            rng.integers(0, 2**63 - 1)      # the sampler's seed: leave the stream where the draws would
-        else:
-            for sc in np.flatnonzero(low):
-                w[sc] = np.bincount(rng.choice(P, size=P, p=w[sc]), minlength=P) / P
-        m = len(dates)
-        # the scenarios of a particle share its variances: [D P, m], never the D P full matrices
-        return autogp.MixtureMarginals(
-            np.ascontiguousarray(means.transpose(1, 0, 2)).reshape(D * P, m),
-            np.broadcast_to(var[None], (D, P, m)).reshape(D * P, m),
-            (w / D).reshape(D * P), engine=base_model._eng())
-    if lockstep and same_dates:
-        models = _refined_clones_lockstep(base_model, nowcasts, n_mcmc, n_hmc, ess_threshold,
-                                          hmc_config)
-        mixes = autogp.predict_mvn_lockstep(models, dates)
-    else:
-        mixes = []
-        for nc in nowcasts:
-            mdl = _clone_for_scenario(base_model)
-            _refine_scenario(mdl, nc, n_mcmc, n_hmc, ess_threshold, hmc_config)
-            mixes.append(autogp.predict_mvn(mdl, dates))
-    return autogp.MixtureMarginals.pool([mx.marginals(engine=base_model._eng()) for mx in mixes])
+    sc = _Scenarios(base_model, nowcasts, forecast_dates, n_mcmc=n_mcmc, n_hmc=n_hmc,
+                    ess_threshold=ess_threshold, lockstep=lockstep, hmc_config=hmc_config)
+    sc.run(want_sigma=False)
+    if sc.mode != "shared":
+        mixes = list(sc.mixtures())
+        return autogp.MixtureMarginals.pool([mx.marginals(engine=base_model._eng()) for mx in mixes])
+    sc.resample_without_draws()
+    D, P = sc.w.shape
+    m = len(sc.dates)
+    # the scenarios of a particle share its variances: [D P, m], never the D P full matrices
+    return autogp.MixtureMarginals(
+        np.ascontiguousarray(sc.means.transpose(1, 0, 2)).reshape(D * P, m),
+        np.broadcast_to(sc.var[None], (D, P, m)).reshape(D * P, m),
+        (sc.w / D).reshape(D * P), engine=base_model._eng())
 
 
 def forecast_components_with_nowcasts(base_model: GPModel, nowcasts: Sequence[TData], forecast_dates, *,
@@ -551,70 +628,58 @@ def forecast_components_with_nowcasts(base_model: GPModel, nowcasts: Sequence[TD
     Default mode only: the scenarios share their dates and no refinement moves are made (refined
     clones no longer share particles — call ``autogp.predict_components`` per clone for those).
     Single-rank runs only (``NotImplementedError`` in a sharded run, where ``predict_components``
-    per rank still works).  Weights and resampling are those of
-    ``forecast_mixture_with_nowcasts``' default path, with the same use of the random streams: from
-    the same snapshot and seed the two describe one mixture.
+    per rank still works).  Weights and resampling are the scenario pipeline's (``_Scenarios``), as
+    on ``forecast_mixture_with_nowcasts``' default path: from the same snapshot and seed the two
+    describe one mixture.
 
     The entries of the returned ``ComponentForecast`` are the pairs (s, p), scenario-major, with
     weight w[s][p] / D; ``sigma`` / ``var`` of (s, p) are the same array objects as particle p's
     (the scenarios of a particle share its covariance).  Original scale of y; ``split`` as
     ``autogp.decompose``."""
-    assert len(nowcasts) > 0, "nowcasts vector must not be empty"
-    assert 0.0 <= ess_threshold <= 1.0, "ess_threshold must be between 0 and 1"
-    if not all(list(nc.ds) == list(nowcasts[0].ds) for nc in nowcasts):
+    sc = _Scenarios(base_model, nowcasts, forecast_dates, ess_threshold=ess_threshold)
+    if not sc.same_dates:
         raise ValueError("forecast_components_with_nowcasts: the scenarios must share their dates")
     model = base_model
     fac = model._factor()
     if fac is None or not hasattr(fac, "components_nowcast"):
         raise RuntimeError("forecast_components_with_nowcasts needs the engine's resident factor "
                            "(ngp_factor_components_nowcast)")
-    dist_ = autogp.distributed
-    if dist_.world()[1] > 1:
+    if autogp.distributed.world()[1] > 1:
         raise NotImplementedError("forecast_components_with_nowcasts: single-rank runs only")
-    dates = list(forecast_dates)
     t, _ = model._obs()
     t_add = model.ds_transform.apply(autogp.to_days(list(nowcasts[0].ds)))
     # the appended points take rows beside the factor too: a particle whose terms fit without them
     # but not with them goes to the weaker split
-    from ._abi import NGP_MAX_AUX
-    parts = autogp.decompose(model, split, max_terms=NGP_MAX_AUX - t.size % 64 - t_add.size - 2)
+    parts = autogp.decompose(model, split, max_terms=_abi.NGP_MAX_AUX - t.size % 64 - t_add.size - 2)
     comps = [[gp.to_program(c.tree) + (0.0,) for c in ps] for ps in parts]
     y_add = np.stack([model.y_transform.apply(np.asarray(nc.y, dtype=np.float64)) for nc in nowcasts])
-    t_new = model.ds_transform.apply(autogp.to_days(dates))
+    t_new = model.ds_transform.apply(autogp.to_days(sc.dates))
     D, m, P = len(nowcasts), t_new.size, len(parts)
-    # weights, the scenarios to resample and the stream: the default path's own routine, so the
-    # log evidences are the bits of the very query it makes (they move in the last place with the
-    # number of forecast rows beside the factor)
-    w, _, _, low, rng, sampler = _nowcast_mixtures_batched(model, nowcasts, dates, ess_threshold)
+    # weights, the scenarios to resample and the stream: the pipeline's own query, so the log
+    # evidences are the bits of the very query the default path makes (they move in the last place
+    # with the number of forecast rows beside the factor)
+    sc.run()
     blocks = autogp.component_blocks(t.size, max(len(ps) for ps in parts), m, t_add.size)
     means = [np.empty((len(ps), D, m)) for ps in parts]
     var = [np.empty((len(ps), m)) for ps in parts]
     sigma = [np.zeros((len(ps) * m, len(ps) * m)) for ps in parts]
     for lo, hi in (blocks or [(0, m)]):
         o = fac.components_nowcast(comps, t_add, y_add, t_new[lo:hi])
-        bad = np.flatnonzero(o["info"])
-        if bad.size:
-            raise autogp.PosDefException(int(o["info"][bad[0]]), int(bad[0]))
+        autogp._raise_if_failed(o["info"])
         k = hi - lo
         for p in range(P):
             C = len(parts[p])
             means[p][:, :, lo:hi] = o["mu"][p]
             var[p][:, lo:hi] = o["var"][p]
             sigma[p].reshape(C, m, C, m)[:, lo:hi, :, lo:hi] = o["sigma"][p].reshape(C, k, C, k)
-    if sampler is not None:
-        if low.any():
-            w[low] = rng.multinomial(P, w[low]) / P
-        rng.integers(0, 2**63 - 1)      # the sampler's seed: leave the stream where the draws would
-    else:
-        for sc in np.flatnonzero(low):
-            w[sc] = np.bincount(rng.choice(P, size=P, p=w[sc]), minlength=P) / P
+    sc.resample_without_draws()
     inv = 1.0 / model.y_transform.slope           # y = (y_model - intercept) / slope
     var = [a * (inv * inv) for a in var]
     sigma = [a * (inv * inv) for a in sigma]
     return autogp.ComponentForecast(
-        [np.ascontiguousarray(means[p][:, sc, :]) * inv for sc in range(D) for p in range(P)],
+        [np.ascontiguousarray(means[p][:, s, :]) * inv for s in range(D) for p in range(P)],
         [sigma[p] for _ in range(D) for p in range(P)], [var[p] for _ in range(D) for p in range(P)],
-        (w / D).reshape(D * P),
+        (sc.w / D).reshape(D * P),
         [[c.kind for c in parts[p]] for _ in range(D) for p in range(P)],
         [[c.label for c in parts[p]] for _ in range(D) for p in range(P)],
         -model.y_transform.intercept * inv, blocks, engine=model._eng())
@@ -655,60 +720,24 @@ def forecast_targets_with_nowcasts(base_model: GPModel, nowcasts: Sequence[TData
                                    want_values: bool = False) -> "autogp.PathTargets":
     """``autogp.path_targets`` of the paths ``forecast_with_nowcasts`` returns.
 
-    Follows ``forecast_with_nowcasts`` step for step — same asserts, weight update, resampling, use
-    of the random streams and sampler seed — so from one snapshot and seed it summarises exactly
-    the matrix that function would return (column (s, d) is path s draws + d).  The default mode
+    The scenario pipeline (``_Scenarios``) with the sampler seed ``forecast_with_nowcasts`` takes,
+    so from one snapshot and seed it summarises exactly the matrix that function would return
+    (column (s, d) is path s draws + d).  The default mode
     (``n_mcmc = n_hmc = 0``) is one call over the shared components; lockstep-refined clones no
     longer share particles and go through the independent form.  ``forecast_n_hmc`` (a new mixture
     before every draw) is not taken; sharded runs raise ``NotImplementedError``."""
-    assert len(nowcasts) > 0, "nowcasts vector must not be empty"
-    assert not (n_mcmc > 0 and n_hmc == 0), \
-        "If n_mcmc > 0, n_hmc must also be > 0 for MCMC refinement"
-    assert 0.0 <= ess_threshold <= 1.0, "ess_threshold must be between 0 and 1"
+    sc = _Scenarios(base_model, nowcasts, forecast_dates, n_mcmc=n_mcmc, n_hmc=n_hmc,
+                    ess_threshold=ess_threshold, lockstep=lockstep, hmc_config=hmc_config)
     if autogp.distributed.world()[1] > 1:
         raise NotImplementedError("forecast_targets_with_nowcasts: single-rank runs only")
-    dates = list(forecast_dates)
     draws = int(forecast_draws_per_nowcast)
     eng = base_model._eng()
-    same_dates = all(list(nc.ds) == list(nowcasts[0].ds) for nc in nowcasts)
-    if n_mcmc == 0 and n_hmc == 0 and same_dates and lockstep:
-        w, means, covs, low, rng, sampler = _nowcast_mixtures_batched(base_model, nowcasts, dates,
-                                                                      ess_threshold)
-        P = w.shape[1]
-        if sampler is None:       # forecast_with_nowcasts draws these on the host, scenario by scenario
-            res = np.empty((len(dates), len(nowcasts) * draws))
-            for sc in range(len(nowcasts)):
-                wsc = w[sc]
-                if low[sc]:
-                    wsc = np.bincount(rng.choice(P, size=P, p=wsc), minlength=P) / P
-                res[:, sc * draws:(sc + 1) * draws] = autogp.MixtureMVN(means[:, sc, :], covs, wsc,
-                                                                        rng).rand(draws)
-            x = np.ascontiguousarray(res.T)
-            return _targets_of_paths(x if inv_transformation is None else _apply(inv_transformation, x),
-                                     targets, probs, want_values)
-        if low.any():
-            w[low] = rng.multinomial(P, w[low]) / P
-        seed = int(rng.integers(0, 2**63 - 1))
-        return autogp.path_targets((w, means, covs), targets, probs, draws, seed, inv_transformation,
+    sc.run()
+    on_device = sc.device_input(draws)
+    if on_device is not None:
+        return autogp.path_targets(on_device[0], targets, probs, draws, on_device[1], inv_transformation,
                                    engine=eng, want_values=want_values)
-    if lockstep and same_dates:
-        models = _refined_clones_lockstep(base_model, nowcasts, n_mcmc, n_hmc, ess_threshold,
-                                          hmc_config)
-        mixes = autogp.predict_mvn_lockstep(models, dates)
-        m, P = mixes[0].means.shape[1], mixes[0].means.shape[0]
-        if (getattr(eng, "mixture_sample_indep", None) is not None and len(mixes) >= 2 and draws > 1
-                and m > 0 and all(mx.sampler is not None and mx.means.shape == (P, m) for mx in mixes)):
-            return autogp.path_targets(mixes, targets, probs, draws, None, inv_transformation,
-                                       engine=eng, want_values=want_values)
-        x = np.hstack(autogp.rand_lockstep(mixes, draws, eng)).T
-    else:
-        cols = []
-        for nc in nowcasts:
-            mdl = _clone_for_scenario(base_model)
-            _refine_scenario(mdl, nc, n_mcmc, n_hmc, ess_threshold, hmc_config)
-            cols.append(autogp.predict_mvn(mdl, dates).rand(draws))
-        x = np.hstack(cols).T
-    x = np.ascontiguousarray(x)
+    x = np.ascontiguousarray(sc.host_matrix(draws).T)
     return _targets_of_paths(x if inv_transformation is None else _apply(inv_transformation, x),
                              targets, probs, want_values)
 
@@ -740,89 +769,21 @@ def forecast_scores_with_nowcasts(base_model: GPModel, nowcasts: Sequence[TData]
     [dates] (original scale): the sample CRPS per date and the energy score of the horizon
     (``windows`` None), or of the given windows of dates.
 
-    Follows ``forecast_targets_with_nowcasts`` step for step — same asserts, weight update,
-    resampling, use of the random streams and sampler seed — so from one snapshot and seed it
-    scores exactly the matrix ``forecast_with_nowcasts`` would return; where that function goes
+    The scenario pipeline (``_Scenarios``) with the sampler seed ``forecast_with_nowcasts`` takes,
+    so from one snapshot and seed it scores exactly the matrix that function would return; where it goes
     through the device the paths are drawn, mapped and scored there and never come back.
     ``forecast_n_hmc`` (a new mixture before every draw) is not taken: score those draws with
     ``score_forecast``.  Sharded runs raise ``NotImplementedError``."""
-    assert len(nowcasts) > 0, "nowcasts vector must not be empty"
-    assert not (n_mcmc > 0 and n_hmc == 0), \
-        "If n_mcmc > 0, n_hmc must also be > 0 for MCMC refinement"
-    assert 0.0 <= ess_threshold <= 1.0, "ess_threshold must be between 0 and 1"
+    sc = _Scenarios(base_model, nowcasts, forecast_dates, n_mcmc=n_mcmc, n_hmc=n_hmc,
+                    ess_threshold=ess_threshold, lockstep=lockstep, hmc_config=hmc_config)
     if autogp.distributed.world()[1] > 1:
         raise NotImplementedError("forecast_scores_with_nowcasts: single-rank runs only")
-    dates = list(forecast_dates)
     draws = int(forecast_draws_per_nowcast)
-    eng = base_model._eng()
-    kw = dict(windows=windows, scale=scale, shift=shift, fair=fair, engine=eng)
-
-    def of_host_paths(x):       # x [dates, N] on the model's scale, drawn on the host
-        x = np.ascontiguousarray(x)
-        return autogp.ensemble_scores(x if inv_transformation is None else _apply(inv_transformation, x),
-                                      y, **kw)
-
-    same_dates = all(list(nc.ds) == list(nowcasts[0].ds) for nc in nowcasts)
-    if n_mcmc == 0 and n_hmc == 0 and same_dates and lockstep:
-        w, means, covs, low, rng, sampler = _nowcast_mixtures_batched(base_model, nowcasts, dates,
-                                                                      ess_threshold)
-        P = w.shape[1]
-        if sampler is None:       # forecast_with_nowcasts draws these on the host, scenario by scenario
-            res = np.empty((len(dates), len(nowcasts) * draws))
-            for sc in range(len(nowcasts)):
-                wsc = w[sc]
-                if low[sc]:
-                    wsc = np.bincount(rng.choice(P, size=P, p=wsc), minlength=P) / P
-                res[:, sc * draws:(sc + 1) * draws] = autogp.MixtureMVN(means[:, sc, :], covs, wsc,
-                                                                        rng).rand(draws)
-            return of_host_paths(res)
-        if low.any():
-            w[low] = rng.multinomial(P, w[low]) / P
-        seed = int(rng.integers(0, 2**63 - 1))
-        return autogp.path_scores((w, means, covs), y, draws, seed, inv_transformation, **kw)
-    if lockstep and same_dates:
-        models = _refined_clones_lockstep(base_model, nowcasts, n_mcmc, n_hmc, ess_threshold,
-                                          hmc_config)
-        mixes = autogp.predict_mvn_lockstep(models, dates)
-        m, P = mixes[0].means.shape[1], mixes[0].means.shape[0]
-        if (getattr(eng, "mixture_sample_indep", None) is not None and len(mixes) >= 2 and draws > 1
-                and m > 0 and all(mx.sampler is not None and mx.means.shape == (P, m) for mx in mixes)):
-            return autogp.path_scores(mixes, y, draws, None, inv_transformation, **kw)
-        return of_host_paths(np.hstack(autogp.rand_lockstep(mixes, draws, eng)))
-    cols = []
-    for nc in nowcasts:
-        mdl = _clone_for_scenario(base_model)
-        _refine_scenario(mdl, nc, n_mcmc, n_hmc, ess_threshold, hmc_config)
-        cols.append(autogp.predict_mvn(mdl, dates).rand(draws))
-    return of_host_paths(np.hstack(cols))
-
-
-def _clone_for_scenario(base_model: GPModel) -> GPModel:
-    # GPModel(deepcopy(Dict(base_model))) of the reference (src/forecasting.jl:128,133).  Every
-    # scenario is its own task with its own randomness there (:131-133); a clone that kept the
-    # snapshot's streams would repeat the first scenario's draws.  Splitting also advances the
-    # base model's shared stream, so a second call differs from the first.
-    return base_model.clone(root=int(base_model.rng_shared.integers(0, 2**62)))
-
-
-def _refine_scenario(m: GPModel, nc: TData, n_mcmc, n_hmc, ess_threshold, hmc_config) -> None:
-    """the body of the reference's per-scenario task up to its forecast (src/forecasting.jl:133-149)"""
-    autogp.add_data(m, nc.ds, nc.y)
-    autogp.maybe_resample(m, ess_threshold * autogp.num_particles(m))
-    if n_mcmc > 0 and n_hmc > 0:
-        autogp.mcmc_structure(m, n_mcmc, n_hmc, hmc_config)
-    elif n_mcmc == 0 and n_hmc > 0:
-        autogp.mcmc_parameters(m, n_hmc, hmc_config)
-
-
-def _refined_clones_lockstep(base_model, nowcasts, n_mcmc, n_hmc, ess_threshold, hmc_config):
-    """the reference's D tasks as ONE ensemble of P x D items (src/forecasting.jl:131-149)"""
-    models = [_clone_for_scenario(base_model) for _ in nowcasts]
-    autogp.add_data_lockstep(models, nowcasts[0].ds, [nc.y for nc in nowcasts],
-                             base=base_model)
-    autogp.maybe_resample_lockstep(models, ess_threshold * autogp.num_particles(base_model))
-    if n_mcmc > 0 and n_hmc > 0:
-        autogp.mcmc_structure_lockstep(models, n_mcmc, n_hmc, hmc_config)
-    elif n_mcmc == 0 and n_hmc > 0:
-        autogp.mcmc_parameters_lockstep(models, n_hmc, hmc_config)
-    return models
+    kw = dict(windows=windows, scale=scale, shift=shift, fair=fair, engine=base_model._eng())
+    sc.run()
+    on_device = sc.device_input(draws)
+    if on_device is not None:
+        return autogp.path_scores(on_device[0], y, draws, on_device[1], inv_transformation, **kw)
+    x = np.ascontiguousarray(sc.host_matrix(draws))     # [dates, N] on the model's scale
+    return autogp.ensemble_scores(x if inv_transformation is None else _apply(inv_transformation, x),
+                                  y, **kw)

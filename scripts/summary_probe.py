@@ -83,7 +83,7 @@ def main():
         total[(C, m)] = q[0] + c[0] + p[0]
     if not a.skip_yardstick:
         # the device work of the first default-mode forecast_with_nowcasts at the headline size, call
-        # by call as the mirror makes them (nowcast._nowcast_mixtures_batched): factorise the 64
+        # by call as the mirror makes them (nowcast._Scenarios, mode "shared"): factorise the 64
         # particles, one nowcast query for the 200 scenarios, normalise the weights, 20 draws per
         # scenario from the device sampler — then the same forecast as exact summaries instead
         from nowcastautogp_amd import _lib
