@@ -838,6 +838,43 @@ ngp_status ngp_factor_predict_long(ngp_factor *f, int32_t d, const double *t_add
                                    int32_t m, const double *t_new, int32_t noise_on_new,
                                    double *mu, double *var, double *sigma, int32_t *info);
 
+/* ---- paths of a long horizon, drawn on the device -----------------------------------
+ * ngp_factor_sample_long draws from the S mixtures whose components are the long query's: with
+ * mu_p,s and sigma_p what ngp_factor_predict_long returns for the same d, t_add, D, y_add, m,
+ * t_new and noise_on_new, `out` is what the contract of ngp_mixture_sample (shared components)
+ * gives for (w, mu, sigma, draws, seed) — Philox4x32-10, counter (draw, scenario, block, 0), key =
+ * seed; block 0 picks the component against the fp64 running sum of w[s] (strict <, fallback
+ * P - 1); blocks 1 + j / 2 are Box-Muller pairs; x = mu_k,s + chol(sigma_k) z.  sigma never leaves
+ * the device: it is factorised in place, 64 columns at a time, on the fp64 matrix cores, and the
+ * paths are a triangular-matrix x panel product against normals staged once per path.
+ *   w         [S][P]          S = d > 0 ? D : 1; rows sum to 1
+ *   out       [S][draws][m]
+ *   comp      [S][draws]      the component of every path; may be NULL
+ *   mu        [P][S][m]       may be NULL; the bits ngp_factor_predict_long returns
+ *   var       [P][m]          may be NULL; likewise
+ *   info      [P]             may be NULL; as ngp_factor_predict_long
+ *   chol_info [P]             may be NULL; first non-positive pivot of chol(sigma_p), 1-based; 0:
+ *                             none.  A particle without weight in any scenario is not factorised
+ *                             and reports 0, as does one whose info > 0 (its sigma is NaN).
+ * A path picked from a particle with info > 0 or chol_info > 0 is NaN in every date; other paths
+ * are not affected.  A path's bits depend on (seed, scenario, draw, its particle) alone: not on
+ * `draws` (a call with fewer draws returns the first draws of a call with more), not on the paths
+ * it shares a tile with, not on how the particles or the paths are chunked by the memory.  Fixed
+ * summation orders, no floating-point atomics, bitwise reproducible from call to call.
+ * NGP_ERR_ARG: null f, t_new, w or out; m < 1; draws < 1; d < 0; d > 0 with D < 1 or null t_add /
+ * y_add.  NGP_ERR_TOO_LARGE: m > NGP_MAX_LONG_HORIZON, (n mod 64) + d + 1 > NGP_MAX_AUX,
+ * S draws > INT32_MAX — all before anything touches a device —, then what the device memory holds
+ * for the paths and ONE particle; a large P is never refused.  Runs under the factor's spec and
+ * the context's lock; not combined with concurrent callers.  Profile classes: the long query's,
+ * plus the pick, the grouping and the normals under 4, the factorisation of sigma under 1
+ * (diagonal blocks) and 6 (the rows below them), the product under 2.                        */
+ngp_status ngp_factor_sample_long(ngp_factor *f, int32_t d, const double *t_add,
+                                  int32_t D, const double *y_add,
+                                  int32_t m, const double *t_new, int32_t noise_on_new,
+                                  const double *w, int32_t draws, uint64_t seed,
+                                  double *out, int32_t *comp, double *mu, double *var,
+                                  int32_t *info, int32_t *chol_info);
+
 /* ---- measurement hooks -----------------------------------------------------
  * HIP-event timing of the kernels a job launches, on the stream they are
  * launched on.  Classes: 0 = chol_col_glds_kernel (fat steps: trailing-update

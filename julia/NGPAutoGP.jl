@@ -355,6 +355,34 @@ function predict_long(f::Factor, t_new::Vector{Float64};
 end
 
 """
+Paths of a long horizon drawn on the device (include/ngp.h `ngp_factor_sample_long`): the mixtures
+`w` (P x S, S = number of scenarios, 1 without appended points) over the components `predict_long`
+returns for the same query, under the contract of `mixture_sample`.  sigma never leaves the device.
+Returns `out` (m x draws x S), `comp` (draws x S, 0-based), `info` and `chol_info` (P); a path picked
+from a particle with `info > 0` or `chol_info > 0` is NaN.
+"""
+function sample_long(f::Factor, t_new::Vector{Float64}, w::Matrix{Float64}, draws::Integer,
+                     seed::UInt64;
+                     t_add::Vector{Float64} = Float64[],
+                     y_add::Matrix{Float64} = Matrix{Float64}(undef, 0, 1),
+                     noise_on_new::Bool = true)
+    P, d, D, m = f.P, length(t_add), max(size(y_add, 2), 1), length(t_new)
+    size(w) == (P, D) || throw(ArgumentError("w must be P x S"))
+    out = Array{Float64}(undef, m, draws, D)
+    comp = Matrix{Int32}(undef, draws, D)
+    info = zeros(Int32, P)
+    chol_info = zeros(Int32, P)
+    check(ccall((:ngp_factor_sample_long, LIBNGP), Int32,
+                (Ptr{Cvoid}, Int32, Ptr{Float64}, Int32, Ptr{Float64}, Int32, Ptr{Float64}, Int32,
+                 Ptr{Float64}, Int32, UInt64, Ptr{Float64}, Ptr{Int32}, Ptr{Float64}, Ptr{Float64},
+                 Ptr{Int32}, Ptr{Int32}),
+                f.h, d, t_add, D, y_add, m, t_new, noise_on_new, w, draws, seed, out, comp,
+                Ptr{Float64}(C_NULL), Ptr{Float64}(C_NULL), info, chol_info),
+          "ngp_factor_sample_long")
+    return (out = out, comp = comp, info = info, chol_info = chol_info)
+end
+
+"""
 The additive components of a program (include/ngp.h `ngp_kernel_components`): the maximal non-Plus
 subtrees under the root's Plus nodes, left to right, each a `Program` of its own.
 """

@@ -45,6 +45,7 @@ SYMBOLS = (
     "ngp_grad_job_hmc",
     "ngp_ensemble_scores", "ngp_mixture_path_scores",
     "ngp_factor_predict_long",
+    "ngp_factor_sample_long",
 )
 
 
@@ -127,6 +128,8 @@ def load():
         "ngp_factor_destroy": (None, [vp]),
         "ngp_factor_predict_long": (i32, [vp, i32, f64p, i32, f64p, i32, f64p, i32, f64p, f64p, f64p,
                                           i32p]),
+        "ngp_factor_sample_long": (i32, [vp, i32, f64p, i32, f64p, i32, f64p, i32, f64p, i32,
+                                         C.c_uint64, f64p, i32p, f64p, f64p, i32p, i32p]),
         "ngp_kernel_components": (i32, [KP, i32p, i32p, i32p, i32p, i32p]),
         "ngp_factor_components": (i32, [vp, i32p, KP, i32, f64p, f64p, f64p, f64p, i32p]),
         "ngp_kernel_terms": (i32, [KP, i32, i32, i32p, i32p, i32p, i32p, i32p, i32p, i32, f64p, i32]),
@@ -535,6 +538,34 @@ class Factor(_Handle):
                                             int(noise_on_new), dptr(mu), dptr(var), _nullable(sg),
                                             iptr(info)), "ngp_factor_predict_long")
         return mu, var, sg, info
+
+    def sample_long(self, t_new, w, draws, seed, t_add=None, y_add=None, noise_on_new=True,
+                    want_moments=False):
+        """Paths of a horizon of up to ``NGP_MAX_LONG_HORIZON`` dates drawn on the device
+        (``ngp_factor_sample_long``): the mixtures ``w`` [S, P] (S = D with appended points, else 1)
+        over the components ``predict_long`` returns for the same query, under the contract of
+        ``mixture_sample``.  sigma is formed, factorised and used on the device and never comes
+        back.  Returns ``(out [S, draws, m], comp [S, draws], info [P], chol_info [P])``, with
+        ``want_moments`` also ``mu [P, S, m]`` and ``var [P, m]`` (``predict_long``'s bits).  A path
+        picked from a particle with ``info > 0`` or ``chol_info > 0`` is NaN."""
+        d, D, t_add, y_add, p_t, p_y = _appended(t_add if t_add is not None else np.zeros(0), y_add)
+        t_new = as_f64(t_new)
+        m, P = t_new.size, self.P
+        w = np.ascontiguousarray(np.asarray(w, dtype=np.float64).reshape(-1, P))
+        if w.shape[0] != D:
+            raise ValueError(f"sample_long: {w.shape[0]} rows of weights for {D} scenarios")
+        draws = int(draws)
+        out = np.empty((D, max(draws, 0), m))
+        comp = np.zeros((D, max(draws, 0)), dtype=np.int32)
+        info, cinfo = np.zeros(P, dtype=np.int32), np.zeros(P, dtype=np.int32)
+        mu = np.empty((P, D, m)) if want_moments else None
+        var = np.empty((P, m)) if want_moments else None
+        _chk(load().ngp_factor_sample_long(self._h, d, p_t, D, p_y, m, dptr(t_new) if m else None,
+                                           int(noise_on_new), dptr(w), draws,
+                                           C.c_uint64(int(seed) & (2**64 - 1)), dptr(out),
+                                           iptr(comp), _nullable(mu), _nullable(var), iptr(info),
+                                           iptr(cinfo)), "ngp_factor_sample_long")
+        return (out, comp, info, cinfo, mu, var) if want_moments else (out, comp, info, cinfo)
 
     def components(self, comps, t_new, want_sigma=True):
         """The joint posterior of every particle's additive parts (``ngp_factor_components``).

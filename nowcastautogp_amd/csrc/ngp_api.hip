@@ -1816,23 +1816,39 @@ extern "C" ngp_status ngp_factor_nowcast(ngp_factor *f, int32_t d, const double 
 // The dates are the panel of a triangular solve against the resident L (ngp_long_kernels.h), not
 // aux rows: m is bounded by NGP_MAX_LONG_HORIZON and the device's memory, not by NGP_MAX_AUX.  The
 // particles are worked through in chunks sized to what the device holds.
-extern "C" ngp_status ngp_factor_predict_long(ngp_factor *f, int32_t d, const double *t_add,
-                                              int32_t D, const double *y_add, int32_t m,
-                                              const double *t_new, int32_t noise_on_new, double *mu,
-                                              double *var, double *sigma, int32_t *info) {
-    if (!f || !t_new || !mu || !var || m < 1 || d < 0) return NGP_ERR_ARG;
+//
+// What ngp_factor_predict_long and ngp_factor_sample_long (section 4.27) share: the checks of the
+// query, the panel's inputs, the geometry (long_stage), the working storage of a chunk (long_take)
+// and a chunk's launches up to sigma (long_launch).
+struct LongStage {
+    LongGeom g{};
+    std::vector<unsigned char> h_in;   // what travels up: programs | t0 | tp | y0 | yc
+    size_t o_t0 = 0, o_tp = 0, o_y0 = 0, o_yc = 0, in_bytes = 0;
+    size_t cw = 0, n_W = 0, n_S = 0, n_mu = 0;
+    size_t work_bytes = 0;             // working storage and outputs per item, sigma not counted
+    int cc = 0;
+    unsigned char *d_in = nullptr;
+    LongPtrs p{};
+};
+
+// sig_ld: the row stride sigma is formed with; 0: no sigma
+static ngp_status long_stage(ngp_factor *f, int32_t d, const double *t_add, int32_t &D,
+                             const double *y_add, int32_t m, const double *t_new,
+                             int32_t noise_on_new, int64_t sig_ld, LongStage &st) {
+    if (!f || !t_new || m < 1 || d < 0) return NGP_ERR_ARG;
     if (d > 0 && (D < 1 || !t_add || !y_add)) return NGP_ERR_ARG;
     if (d == 0) D = 1;
     if (m > NGP_MAX_LONG_HORIZON) return NGP_ERR_TOO_LARGE;
     const int P = f->P, n = f->n, n0 = f->n0, tail = n - n0;
     if ((int64_t)tail + d + 1 > NGP_MAX_AUX) return NGP_ERR_TOO_LARGE;
     const int cc = tail + d;
+    st.cc = cc;
     std::vector<DevProgram> hp((size_t)P);
     for (int i = 0; i < P; ++i) {
-        ngp_status st = compile_program(&f->kernels[(size_t)i], &hp[(size_t)i], nullptr);
-        if (st) return st;
+        ngp_status e = compile_program(&f->kernels[(size_t)i], &hp[(size_t)i], nullptr);
+        if (e) return e;
     }
-    LongGeom g{};
+    LongGeom &g = st.g;
     g.n0 = n0;
     g.nb0 = f->nb0;
     g.c = cc;
@@ -1842,16 +1858,20 @@ extern "C" ngp_status ngp_factor_predict_long(ngp_factor *f, int32_t d, const do
     g.qpad = (g.q1 + LONG_TILE - 1) / LONG_TILE * LONG_TILE;
     g.noise_on_new = noise_on_new ? 1 : 0;
     g.y_shared = f->ldy ? 0 : 1;
-    g.want_sigma = sigma ? 1 : 0;
+    g.want_sigma = sig_ld ? 1 : 0;
     g.ld = n0;
     g.L_stride = f->item_stride;
     g.dinv_step = (int64_t)P * NB * NB;
+    g.sig_ld = sig_ld;
+    g.sig_stride = sig_ld * sig_ld;
     // what travels up: programs | t0 | tp | y0 | yc
     const int ny = g.y_shared ? 1 : P;
     const size_t o_t0 = sizeof(DevProgram) * (size_t)P, o_tp = o_t0 + 8 * (size_t)n0,
                  o_y0 = o_tp + 8 * (size_t)(cc + m), o_yc = o_y0 + 8 * (size_t)ny * n0,
                  in_bytes = o_yc + 8 * (size_t)ny * D * cc;
-    std::vector<unsigned char> h_in(in_bytes);
+    st.o_t0 = o_t0, st.o_tp = o_tp, st.o_y0 = o_y0, st.o_yc = o_yc, st.in_bytes = in_bytes;
+    std::vector<unsigned char> &h_in = st.h_in;
+    h_in.resize(in_bytes);
     std::memcpy(h_in.data(), hp.data(), o_t0);
     {
         double *h_t0 = reinterpret_cast<double *>(h_in.data() + o_t0);
@@ -1873,58 +1893,218 @@ extern "C" ngp_status ngp_factor_predict_long(ngp_factor *f, int32_t d, const do
         }
     }
     // doubles of working storage and of outputs per item
-    const size_t cw = (size_t)cc + 1, mm = sigma ? (size_t)m * m : 0;
-    const size_t n_W = (size_t)g.qpad * n0, n_S = (size_t)g.q1 * cw, n_mu = (size_t)D * m;
-    const size_t item_bytes = 8 * (n_W + n_S + (size_t)g.q1 + (size_t)D * cc + n_mu + (size_t)m + mm) + 4;
+    st.cw = (size_t)cc + 1;
+    st.n_W = (size_t)g.qpad * n0, st.n_S = (size_t)g.q1 * st.cw, st.n_mu = (size_t)D * m;
+    st.work_bytes = 8 * (st.n_W + st.n_S + (size_t)g.q1 + (size_t)D * cc + st.n_mu + (size_t)m) + 4;
+    return NGP_OK;
+}
+
+// the inputs and the working storage of chunks of up to Pc items
+static void long_take(DevCall &call, const ngp_factor *f, LongStage &st, size_t Pc) {
+    const LongGeom &g = st.g;
+    LongPtrs &p = st.p;
+    call.take(&st.d_in, st.in_bytes);
+    if (g.n0 > 0) call.take(&p.W, Pc * st.n_W);
+    call.take(&p.S, Pc * st.n_S).take(&p.dg, Pc * (size_t)g.q1).take(&p.z, Pc * (size_t)g.D * st.cc + 1);
+    call.take(&p.mu, Pc * st.n_mu).take(&p.var, Pc * (size_t)g.m).take(&p.info, Pc);
+    if (g.want_sigma) call.take(&p.sigma, Pc * (size_t)g.sig_stride);
+    call.up(st.d_in, st.h_in.data(), st.in_bytes);
+    (void)f;
+}
+
+// items [b0, b0 + bc): the panel, its solve, the products, the conditioning block, means,
+// variances and (want_sigma) sigma, left in st.p
+static void long_launch(DevCall &call, ngp_factor *f, LongStage &st, size_t b0, size_t bc) {
+    LongGeom &g = st.g;
+    LongPtrs &p = st.p;
+    unsigned char *d_in = st.d_in;
+    const int n0 = g.n0, D = g.D, cc = st.cc;
+    const size_t cw = st.cw, mm = g.want_sigma ? (size_t)g.m * g.m : 0;
+    const DevSpec sp = dev_spec(f->spec);
+    hipStream_t s = f->ctx->stream;
+    EventTimer &tm = call.tm;
+    g.B = (int32_t)bc;
+    p.progs = reinterpret_cast<const DevProgram *>(d_in) + b0;
+    p.L = f->L ? f->L + b0 * (size_t)f->item_stride : nullptr;
+    p.dinv = f->dinv ? f->dinv + b0 * (size_t)(NB * NB) : nullptr;
+    p.finfo = n0 > 0 ? f->info + b0 : nullptr;   // without a main block create leaves it unwritten
+    p.t0 = reinterpret_cast<const double *>(d_in + st.o_t0);
+    p.tp = reinterpret_cast<const double *>(d_in + st.o_tp);
+    p.y0 = reinterpret_cast<const double *>(d_in + st.o_y0) + (g.y_shared ? 0 : b0 * (size_t)n0);
+    p.yc = reinterpret_cast<const double *>(d_in + st.o_yc) + (g.y_shared ? 0 : b0 * (size_t)D * cc);
+    const double dB = (double)bc, dq = (double)g.q1, dn = (double)n0;
+    const double wg_tiles = (double)((g.qpad + LONG_WG_TILE - 1) / LONG_WG_TILE);
+    call.timed(tm, 4, 0.0, 8.0 * dB * g.qpad * dn, [&] { launch_long(LONG_FILL, g, p, sp, s); });
+    call.timed(tm, 4, 0.0, 8.0 * dB * (dq * (double)cw + (double)mm), [&] { launch_long(LONG_SMALL, g, p, sp, s); });
+    // n0^2 q flops per item; L once per workgroup tile, the panel once in and once out, and —
+    // left-looking — block column j of the solved panel read back by every later step
+    call.timed(tm, 6, dB * dn * dn * dq,
+               8.0 * dB * (wg_tiles * dn * dn / 2 + 2.0 * g.qpad * dn + g.qpad * dn * (g.nb0 - 1) / 2.0),
+               [&] { launch_long(LONG_SOLVE, g, p, sp, s); });
+    call.timed(tm, 2, 0.0, 0.0, [&] { launch_long(LONG_GRAM, g, p, sp, s); });
+    call.timed(tm, 3, 0.0, 0.0, [&] {
+        launch_long(LONG_COND, g, p, sp, s);
+        launch_long(LONG_APPLY, g, p, sp, s);
+        launch_long(LONG_SIGMA, g, p, sp, s);
+    });
+}
+
+extern "C" ngp_status ngp_factor_predict_long(ngp_factor *f, int32_t d, const double *t_add,
+                                              int32_t D, const double *y_add, int32_t m,
+                                              const double *t_new, int32_t noise_on_new, double *mu,
+                                              double *var, double *sigma, int32_t *info) {
+    if (!mu || !var) return NGP_ERR_ARG;
+    LongStage st;
+    if (ngp_status e = long_stage(f, d, t_add, D, y_add, m, t_new, noise_on_new, sigma ? m : 0, st)) return e;
+    const LongPtrs &p = st.p;
+    const size_t P = (size_t)f->P, mm = sigma ? (size_t)m * m : 0, n_mu = st.n_mu, in_bytes = st.in_bytes;
+    const size_t item_bytes = st.work_bytes + 8 * mm;
     ngp_ctx *c = f->ctx;
     DevCall call(c);
     if (call.status()) return call.status();
-    if ((size_t)P * item_bytes + in_bytes > c->mem_cap) c->refresh_mem_cap();
+    if (P * item_bytes + in_bytes > c->mem_cap) c->refresh_mem_cap();
     if (item_bytes + in_bytes > c->mem_cap) return NGP_ERR_TOO_LARGE;
-    const size_t Pc = std::min<size_t>(std::min<size_t>((size_t)P, MAX_CHUNK_ITEMS),
+    const size_t Pc = std::min<size_t>(std::min<size_t>(P, MAX_CHUNK_ITEMS),
                                        std::max<size_t>(1, (c->mem_cap - in_bytes) / item_bytes));
-    unsigned char *d_in = nullptr;
-    LongPtrs p{};
-    call.take(&d_in, in_bytes);
-    if (n0 > 0) call.take(&p.W, Pc * n_W);
-    call.take(&p.S, Pc * n_S).take(&p.dg, Pc * (size_t)g.q1).take(&p.z, Pc * (size_t)D * cc + 1);
-    call.take(&p.mu, Pc * n_mu).take(&p.var, Pc * (size_t)m).take(&p.info, Pc);
-    if (sigma) call.take(&p.sigma, Pc * mm);
-    call.up(d_in, h_in.data(), in_bytes);
-    const DevSpec sp = dev_spec(f->spec);
-    hipStream_t s = c->stream;
-    EventTimer &tm = call.tm;
-    for (size_t b0 = 0; b0 < (size_t)P && !call.status(); b0 += Pc) {
-        const size_t bc = std::min(Pc, (size_t)P - b0);
-        g.B = (int32_t)bc;
-        p.progs = reinterpret_cast<const DevProgram *>(d_in) + b0;
-        p.L = f->L ? f->L + b0 * (size_t)f->item_stride : nullptr;
-        p.dinv = f->dinv ? f->dinv + b0 * (size_t)(NB * NB) : nullptr;
-        p.finfo = n0 > 0 ? f->info + b0 : nullptr;   // without a main block create leaves it unwritten
-        p.t0 = reinterpret_cast<const double *>(d_in + o_t0);
-        p.tp = reinterpret_cast<const double *>(d_in + o_tp);
-        p.y0 = reinterpret_cast<const double *>(d_in + o_y0) + (g.y_shared ? 0 : b0 * (size_t)n0);
-        p.yc = reinterpret_cast<const double *>(d_in + o_yc) + (g.y_shared ? 0 : b0 * (size_t)D * cc);
-        const double dB = (double)bc, dq = (double)g.q1, dn = (double)n0;
-        const double wg_tiles = (double)((g.qpad + LONG_WG_TILE - 1) / LONG_WG_TILE);
-        call.timed(tm, 4, 0.0, 8.0 * dB * g.qpad * dn, [&] { launch_long(LONG_FILL, g, p, sp, s); });
-        call.timed(tm, 4, 0.0, 8.0 * dB * (dq * (double)cw + (double)mm), [&] { launch_long(LONG_SMALL, g, p, sp, s); });
-        // n0^2 q flops per item; L once per workgroup tile, the panel once in and once out, and —
-        // left-looking — block column j of the solved panel read back by every later step
-        call.timed(tm, 6, dB * dn * dn * dq,
-                   8.0 * dB * (wg_tiles * dn * dn / 2 + 2.0 * g.qpad * dn + g.qpad * dn * (g.nb0 - 1) / 2.0),
-                   [&] { launch_long(LONG_SOLVE, g, p, sp, s); });
-        call.timed(tm, 2, 0.0, 0.0, [&] { launch_long(LONG_GRAM, g, p, sp, s); });
-        call.timed(tm, 3, 0.0, 0.0, [&] {
-            launch_long(LONG_COND, g, p, sp, s);
-            launch_long(LONG_APPLY, g, p, sp, s);
-            launch_long(LONG_SIGMA, g, p, sp, s);
-        });
+    long_take(call, f, st, Pc);
+    for (size_t b0 = 0; b0 < P && !call.status(); b0 += Pc) {
+        const size_t bc = std::min(Pc, P - b0);
+        long_launch(call, f, st, b0, bc);
         call.down(mu + b0 * n_mu, p.mu, 8 * bc * n_mu).down(var + b0 * (size_t)m, p.var, 8 * bc * (size_t)m);
         if (sigma) call.down(sigma + b0 * mm, p.sigma, 8 * bc * mm);
         if (info) call.down(info + b0, p.info, 4 * bc);
     }
     return call.sync();
+}
+
+// ---- paths of a long horizon ---------------------------------------
+// sigma of the long query stays on the device, [mpad x mpad] per particle with a unit diagonal in
+// the padding: factorised in place 64 columns at a time, then X = mu + L Z for the paths that
+// picked the particle, their normals staged once per path.  Particles go through in chunks sized
+// to the memory, and a chunk's paths in slices of the rows the staged normals have room for.
+extern "C" ngp_status ngp_factor_sample_long(ngp_factor *f, int32_t d, const double *t_add, int32_t D,
+                                             const double *y_add, int32_t m, const double *t_new,
+                                             int32_t noise_on_new, const double *w, int32_t draws,
+                                             uint64_t seed, double *out, int32_t *comp, double *mu,
+                                             double *var, int32_t *info, int32_t *chol_info) {
+    if (!f || !t_new || !w || !out || m < 1 || draws < 1 || d < 0) return NGP_ERR_ARG;
+    const int mpad = m > NGP_MAX_LONG_HORIZON ? 0 : (m + NB - 1) / NB * NB;
+    LongStage st;
+    if (ngp_status e = long_stage(f, d, t_add, D, y_add, m, t_new, noise_on_new, mpad, st)) return e;
+    const int S = D;                               // long_stage: D = 1 without appended points
+    if ((int64_t)S * draws > INT32_MAX) return NGP_ERR_TOO_LARGE;
+    const size_t P = (size_t)f->P, N = (size_t)S * draws, n_mu = st.n_mu;
+    LongSampleGeom sg{};
+    sg.P = (int32_t)P, sg.S = S, sg.draws = draws, sg.m = m;
+    sg.mpad = mpad, sg.nb = mpad / NB;
+    sg.N = (int64_t)N;
+    sg.stride = (int64_t)mpad * mpad;
+    // beside the particles' chunks: inputs, weights, picks, grouping, every path; then per item
+    // sigma, the block inverse, a log determinant nobody reads and the pivot report
+    const size_t row_bytes = 8 * (size_t)mpad;
+    const size_t fixed = st.in_bytes + 8 * (size_t)S * P + 8 * N + 8 * (P + 1) + 8 * N * (size_t)m;
+    const size_t item_bytes = st.work_bytes + 8 * (size_t)sg.stride + 8 * (size_t)(NB * NB) + 8 + 4;
+    constexpr size_t Z_MIN_ROWS = LS_WG_PATHS, Z_MAX_ROWS = (size_t)1 << 22;   // the latter bounds gridDim.y
+    const size_t z_least = row_bytes * (std::min(N, Z_MIN_ROWS) + NB);
+    ngp_ctx *c = f->ctx;
+    DevCall call(c);
+    if (call.status()) return call.status();
+    if (fixed + P * item_bytes + row_bytes * (N + NB) > c->mem_cap) c->refresh_mem_cap();
+    if (fixed + item_bytes + z_least > c->mem_cap) return NGP_ERR_TOO_LARGE;
+    // the staged normals: a quarter of the room, at least Z_MIN_ROWS paths, never the last item's share
+    const size_t room = c->mem_cap - fixed;
+    const size_t z_bytes = std::min(room - item_bytes, std::max(z_least, room / 4));
+    const size_t zcap = std::min(std::min(N, Z_MAX_ROWS), z_bytes / row_bytes - NB);
+    const size_t Pc = std::min<size_t>(std::min<size_t>(P, MAX_CHUNK_ITEMS),
+                                       std::max<size_t>(1, (room - row_bytes * (zcap + NB)) / item_bytes));
+    long_take(call, f, st, Pc);
+    const LongPtrs &p = st.p;
+    double *d_w = nullptr, *d_out = nullptr, *d_Z = nullptr, *d_dinv = nullptr, *d_logdet = nullptr;
+    int32_t *d_comp = nullptr, *d_order = nullptr, *d_cinfo = nullptr;
+    uint32_t *d_cnt = nullptr, *d_off = nullptr;
+    call.take(&d_w, (size_t)S * P).take(&d_comp, N).take(&d_order, N).take(&d_cnt, P).take(&d_off, P + 1);
+    call.take(&d_out, N * (size_t)m).take(&d_Z, (size_t)mpad * (zcap + NB));
+    call.take(&d_dinv, Pc * (size_t)(NB * NB)).take(&d_logdet, Pc).take(&d_cinfo, Pc);
+    call.up(d_w, w, 8 * (size_t)S * P);
+    hipStream_t s = c->stream;
+    EventTimer &tm = call.tm;
+    // the picks and how many paths each particle got: one round trip, the offsets are the host's
+    std::vector<uint32_t> cnt(P, 0u), off(P + 1, 0u);
+    std::vector<int32_t> hinfo(P, 0), hcinfo(P, 0);
+    call.timed(tm, 4, 0.0, 8.0 * (double)N + 4.0 * (double)N * (double)P, [&] {
+        launch_ls_pick(sg, d_w, seed, d_comp, s);
+        launch_ls_count(sg, d_comp, d_cnt, s);
+    });
+    call.down(cnt.data(), d_cnt, 4 * P);
+    if (comp) call.down(comp, d_comp, 4 * N);
+    if (call.wait()) return call.sync();
+    for (size_t k = 0; k < P; ++k) off[k + 1] = off[k] + (uint32_t)std::min<size_t>(cnt[k], N - off[k]);
+    call.up(d_off, off.data(), 4 * (P + 1));
+    call.timed(tm, 4, 0.0, 4.0 * (double)N * (double)P + 4.0 * (double)N,
+               [&] { launch_ls_group(sg, d_comp, d_off, d_order, s); });
+    // a particle is factorised when a scenario gives it weight (or, rows that do not sum to 1, the
+    // fallback of the pick fell on it)
+    std::vector<char> active(P, 0);
+    for (size_t k = 0; k < P; ++k) {
+        active[k] = off[k + 1] > off[k];
+        for (int sc = 0; sc < S && !active[k]; ++sc) active[k] = w[(size_t)sc * P + k] > 0.0;
+    }
+    for (size_t b0 = 0; b0 < P && !call.status(); b0 += Pc) {
+        const size_t bc = std::min(Pc, P - b0);
+        long_launch(call, f, st, b0, bc);
+        if (mu) call.down(mu + b0 * n_mu, p.mu, 8 * bc * n_mu);
+        if (var) call.down(var + b0 * (size_t)m, p.var, 8 * bc * (size_t)m);
+        call.down(hinfo.data() + b0, p.info, 4 * bc);
+        call.zero(d_cinfo, 4 * bc).zero(d_logdet, 8 * bc);
+        call.timed(tm, 4, 0.0, 8.0 * (double)bc * (double)(mpad - m) * (double)(m + mpad),
+                   [&] { launch_ls_pad(sg, p.sigma, (int)bc, s); });
+        LongSamplePtrs q{};
+        q.info = p.info, q.mu = p.mu, q.order = d_order, q.Z = d_Z, q.out = d_out;
+        // the factorisation, one launch sequence per run of active particles
+        for (size_t r0 = 0; r0 < bc;) {
+            if (!active[b0 + r0]) { ++r0; continue; }
+            size_t r1 = r0;
+            while (r1 < bc && active[b0 + r1]) ++r1;
+            const int B = (int)(r1 - r0);
+            q.sigma = p.sigma + r0 * (size_t)sg.stride;
+            q.dinv = d_dinv + r0 * (size_t)(NB * NB);
+            q.logdet = d_logdet + r0;
+            q.cinfo = d_cinfo + r0;
+            for (int j = 0; j < sg.nb; ++j) {
+                call.timed(tm, cost_diag(B, j, 0), [&] { launch_ls_diag(sg, q, B, j, s); });
+                if (j + 1 < sg.nb) call.timed(tm, cost_ls_panel(sg, B, j), [&] { launch_ls_panel(sg, q, B, j, s); });
+            }
+            r0 = r1;
+        }
+        q.sigma = p.sigma, q.dinv = d_dinv, q.logdet = d_logdet, q.cinfo = d_cinfo;
+        q.off = d_off + b0;
+        // the chunk's paths, a slice of sorted positions at a time
+        for (size_t z0 = off[b0]; z0 < off[b0 + bc] && !call.status(); z0 += zcap) {
+            const size_t zr = std::min(zcap, (size_t)off[b0 + bc] - z0);
+            size_t most = 0, waves = 0, wgs = 0;
+            for (size_t k = b0; k < b0 + bc; ++k) {
+                const size_t lo = std::max<size_t>(off[k], z0), hi = std::min<size_t>(off[k + 1], z0 + zr);
+                const size_t have = hi > lo ? hi - lo : 0;
+                most = std::max(most, have);
+                waves += (have + NB - 1) / NB;
+                wgs += (have + LS_WG_PATHS - 1) / LS_WG_PATHS;
+            }
+            call.timed(tm, 4, 0.0, row_bytes * (double)zr, [&] { launch_ls_normals(sg, seed, d_order, (int64_t)z0, (int64_t)zr, d_Z, s); });
+            call.timed(tm, cost_ls_draw(sg, (double)zr, (double)waves, (double)wgs), [&] {
+                launch_ls_draw(sg, q, (int)bc, (int64_t)z0, (int64_t)zr, (int)((most + LS_WG_PATHS - 1) / LS_WG_PATHS), s);
+            });
+        }
+        call.down(hcinfo.data() + b0, d_cinfo, 4 * bc);
+    }
+    call.down(out, d_out, 8 * N * (size_t)m);
+    const ngp_status e = call.sync();
+    if (e) return e;
+    for (size_t k = 0; k < P; ++k) {
+        if (info) info[k] = hinfo[k];
+        // a failed long query leaves NaN in sigma: its factorisation reports nothing of its own
+        if (chol_info) chol_info[k] = hinfo[k] > 0 ? 0 : hcinfo[k];
+    }
+    return NGP_OK;
 }
 
 // ---- additive decomposition ---------------------------------------

@@ -107,5 +107,21 @@ inline Cost cost_toep_back(int bc, int cc) {
 }
 inline Cost cost_toep_grad(const JobGeom &g, int bc) { return {11, 0.0, bc * 8.0 * 3.0 * (double)g.n0}; }
 inline Cost cost_contract(const JobGeom &g, int bc) { return {11, 0.0, bc * 8.0 * 0.5 * (double)g.n0 * g.n0}; }
+// ngp_factor_sample_long.  Block column jj of sigma's factorisation: the diagonal block is
+// cost_diag; the rows below it carry k = 64 jj products each and a 64-wide solve, block row jj of L
+// is read once per workgroup of four row blocks, a row block once in (k + 64 wide) and once out
+inline Cost cost_ls_panel(const LongSampleGeom &g, int bc, int jj) {
+    const double k = (double)jj * NB, rows = (double)(g.nb - jj - 1) * NB;
+    const double wgs = (double)((g.nb - jj - 1 + 3) / 4);
+    return {6, bc * (2.0 * NB * rows * k + rows * (double)NB * NB),
+            bc * 8.0 * (rows * k + wgs * NB * k + 2.0 * rows * NB + (double)NB * NB)};
+}
+// X = mu + L Z of `paths` paths in `waves` tiles of 64 and `wgs` workgroups: a wave multiplies 64
+// rows of L by its 64 paths over k = 64 (i + 1), summed over the row blocks K = mpad (mpad + 64) / 128;
+// the rows of L are read once per workgroup, those of Z once per wave, a path is written once
+inline Cost cost_ls_draw(const LongSampleGeom &g, double paths, double waves, double wgs) {
+    const double K = (double)g.mpad * ((double)g.mpad + NB) / (2.0 * NB);
+    return {2, 2.0 * waves * NB * NB * K, 8.0 * (wgs * NB * K + waves * NB * K + paths * (2.0 * g.m))};
+}
 
 }  // namespace ngp

@@ -201,6 +201,8 @@ struct LongGeom {
     int64_t ld;            // row stride of L and of the panel (= n0)
     int64_t L_stride;      // elements per item in the factor storage
     int64_t dinv_step;     // elements between the block inverses of consecutive block columns
+    int64_t sig_ld;        // row stride of an item's sigma (m; ngp_factor_sample_long: m rounded up to NB)
+    int64_t sig_stride;    // elements per item in sigma
 };
 struct LongPtrs {
     const DevProgram *progs;   // [B]
@@ -221,6 +223,46 @@ struct LongPtrs {
 // step: 0 fill, 1 small blocks, 2 solve, 3 products of the rows, 4 conditioning block, 5 dates, 6 sigma
 enum { LONG_FILL = 0, LONG_SMALL, LONG_SOLVE, LONG_GRAM, LONG_COND, LONG_APPLY, LONG_SIGMA };
 void launch_long(int step, const LongGeom &g, const LongPtrs &p, const DevSpec &sp, hipStream_t s);
+
+// ngp_factor_sample_long (ngp_long_sample_kernels.h): paths of a long horizon from the sigma the
+// long query leaves on the device.  sigma is stored [mpad x mpad] per item (mpad: m rounded up to
+// NB, the padding a unit diagonal), factorised in place 64 columns at a time, and the paths of a
+// particle are a lower-triangular x panel product against their staged normals.
+constexpr int LS_THREADS = 256;
+constexpr int LS_WG_PATHS = 256;       // paths of a workgroup of the product: four waves, 64 each
+struct LongSampleGeom {
+    int32_t P, S, draws, m;
+    int32_t mpad, nb;      // m rounded up to NB; mpad / NB
+    int64_t N;             // S draws
+    int64_t stride;        // elements per item in sigma: mpad mpad
+};
+struct LongSamplePtrs {
+    double *sigma;             // [B][mpad][mpad] the run's first item: sigma in, L out
+    double *dinv;              // [B][NB NB] inverse of the current diagonal block, MFMA strip order
+    double *logdet;            // [B] scratch of the diagonal step
+    int32_t *cinfo;            // [B] first non-positive pivot, 1-based; 0: none
+    const int32_t *info;       // [B] the long query's status
+    const double *mu;          // [B][S][m]
+    const uint32_t *off;       // [B + 1] first sorted position of each item's paths
+    const int32_t *order;      // [N] path (s draws + d) at each sorted position
+    const double *Z;           // [zrows + NB][mpad] normals of sorted positions zfirst ..
+    double *out;               // [N][m]
+};
+// pick: comp [N].  count: cnt [P].  group: order [N] from off [P + 1] (ascending path inside a group)
+void launch_ls_pick(const LongSampleGeom &g, const double *w, uint64_t seed, int32_t *comp, hipStream_t s);
+void launch_ls_count(const LongSampleGeom &g, const int32_t *comp, uint32_t *cnt, hipStream_t s);
+void launch_ls_group(const LongSampleGeom &g, const int32_t *comp, const uint32_t *off, int32_t *order,
+                     hipStream_t s);
+void launch_ls_normals(const LongSampleGeom &g, uint64_t seed, const int32_t *order, int64_t zfirst,
+                       int64_t zrows, double *Z, hipStream_t s);
+void launch_ls_pad(const LongSampleGeom &g, double *sigma, int B, hipStream_t s);
+// block column j of B items: the diagonal block (and its inverse), then the row blocks below it
+void launch_ls_diag(const LongSampleGeom &g, const LongSamplePtrs &p, int B, int j, hipStream_t s);
+void launch_ls_panel(const LongSampleGeom &g, const LongSamplePtrs &p, int B, int j, hipStream_t s);
+// paths of sorted positions [zfirst, zfirst + zrows) that belong to the B items; tiles: the
+// largest number of LS_WG_PATHS groups any of them needs
+void launch_ls_draw(const LongSampleGeom &g, const LongSamplePtrs &p, int B, int64_t zfirst, int64_t zrows,
+                    int tiles, hipStream_t s);
 
 // ---- short series in one launch (ngp_small_kernels.h) ------------------------------------
 constexpr int SM_WAVES = 8, SM_THREADS = 64 * SM_WAVES;   // two waves per SIMD: 256 VGPRs each

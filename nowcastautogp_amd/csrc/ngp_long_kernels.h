@@ -55,7 +55,7 @@ __global__ __launch_bounds__(256) void long_small_kernel(LongGeom g, LongPtrs p,
     const long nS = (long)g.q1 * cw, nD = g.q1, nG = g.want_sigma ? (long)g.m * g.m : 0;
     double *S = p.S + (long)item * nS;
     double *dg = p.dg + (long)item * nD;
-    double *Sg = g.want_sigma ? p.sigma + (long)item * g.m * g.m : nullptr;
+    double *Sg = g.want_sigma ? p.sigma + (long)item * g.sig_stride : nullptr;
     for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < nS + nD + nG; e += (long)gridDim.x * 256) {
         if (e < nS) {
             const int r = (int)(e / cw), j = (int)(e % cw);
@@ -71,7 +71,7 @@ __global__ __launch_bounds__(256) void long_small_kernel(LongGeom g, LongPtrs p,
         } else {
             const long x = e - nS - nD;
             const int i = (int)(x / g.m), j = (int)(x % g.m);
-            if (j <= i) Sg[x] = keval(P, sp, p.tp[g.c + i], p.tp[g.c + j]);
+            if (j <= i) Sg[(long)i * g.sig_ld + j] = keval(P, sp, p.tp[g.c + i], p.tp[g.c + j]);
         }
     }
 }
@@ -154,7 +154,7 @@ __global__ __launch_bounds__(256, 1) void long_gram_kernel(LongGeom g, LongPtrs 
     const int cw = g.c + 1;
     double *S = p.S + (long)item * g.q1 * cw;
     double *dg = p.dg + (long)item * g.q1;
-    double *Sg = g.want_sigma ? p.sigma + (long)item * g.m * g.m : nullptr;
+    double *Sg = g.want_sigma ? p.sigma + (long)item * g.sig_stride : nullptr;
     const int n16 = lane & 15, isub = lane >> 4;
     const int jj0 = 4 * (n16 >> 2) + isub;
 #pragma unroll
@@ -170,7 +170,7 @@ __global__ __launch_bounds__(256, 1) void long_gram_kernel(LongGeom g, LongPtrs 
                 if (rb == 0) S[(long)ra * cw] = v;
                 else if (rb <= g.c) S[(long)ra * cw + rb] -= v;
                 if (ra == rb && ra > g.c) dg[ra] -= v;
-                if (Sg && rb > g.c) Sg[(long)(ra - g.c - 1) * g.m + (rb - g.c - 1)] -= v;
+                if (Sg && rb > g.c) Sg[(long)(ra - g.c - 1) * g.sig_ld + (rb - g.c - 1)] -= v;
             }
 }
 
@@ -272,7 +272,7 @@ __global__ __launch_bounds__(256) void long_sigma_kernel(LongGeom g, LongPtrs p,
     const int item = blockIdx.y;
     const int c = g.c, cw = c + 1;
     const long total = (long)g.m * g.m;
-    double *Sg = p.sigma + (long)item * total;
+    double *Sg = p.sigma + (long)item * g.sig_stride;
     const double *S = p.S + (long)item * g.q1 * cw;
     const bool failed = p.info[item] > 0;
     const double nz = p.progs[item].noise + sp.jitter;
@@ -283,11 +283,11 @@ __global__ __launch_bounds__(256) void long_sigma_kernel(LongGeom g, LongPtrs p,
         if (failed) {
             s = __longlong_as_double(0x7ff8000000000000LL);
         } else {
-            s = long_schur_sub(Sg[e], S + (long)(c + 1 + i) * cw + 1, S + (long)(c + 1 + j) * cw + 1, c);
+            s = long_schur_sub(Sg[(long)i * g.sig_ld + j], S + (long)(c + 1 + i) * cw + 1, S + (long)(c + 1 + j) * cw + 1, c);
             if (i == j && g.noise_on_new) s += nz;
         }
-        Sg[e] = s;
-        Sg[(long)j * g.m + i] = s;
+        Sg[(long)i * g.sig_ld + j] = s;
+        Sg[(long)j * g.sig_ld + i] = s;
     }
 }
 

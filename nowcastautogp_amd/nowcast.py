@@ -260,12 +260,22 @@ def _apply(inv_transformation: Callable, a: np.ndarray) -> np.ndarray:
 
 def forecast(model: GPModel, forecast_dates, forecast_draws: int, *,
              inv_transformation: Callable = lambda y: y,
-             forecast_n_hmc: Optional[int] = None, hmc_config: Optional[dict] = None) -> np.ndarray:
+             forecast_n_hmc: Optional[int] = None, hmc_config: Optional[dict] = None,
+             device_paths: bool = False) -> np.ndarray:
     """Matrix (len(forecast_dates), forecast_draws) of samples (reference src/forecasting.jl:29-75).
     ``hmc_config`` (not in the reference's signature; AutoGP's default applies there): leapfrog
-    count and step size of the HMC moves, ``{"n_leapfrog": ..., "eps": ...}``."""
+    count and step size of the HMC moves, ``{"n_leapfrog": ..., "eps": ...}``.
+    ``device_paths`` (this module's own): a horizon beyond what one aux query carries is drawn on
+    the device from the resident factor in one call (``Factor.sample_long``, S = 1 with the model's
+    weights; one ``integers`` draw of the shared stream for its seed) instead of bringing every
+    particle's covariance to the host.  Where that does not apply — a short horizon,
+    ``forecast_n_hmc``, no resident factor with ``sample_long``, a sharded run — the existing path
+    runs, as with the default."""
     dates = list(forecast_dates)
-    if forecast_n_hmc is None:
+    long_x = _long_paths(model, dates, int(forecast_draws)) if device_paths and forecast_n_hmc is None else None
+    if long_x is not None:
+        draws = long_x
+    elif forecast_n_hmc is None:
         draws = autogp.predict_mvn(model, dates).rand(int(forecast_draws))
     else:
         draws = np.empty((len(dates), int(forecast_draws)))
@@ -273,6 +283,25 @@ def forecast(model: GPModel, forecast_dates, forecast_draws: int, *,
             autogp.mcmc_parameters(model, forecast_n_hmc, hmc_config)
             draws[:, i] = autogp.predict_mvn(model, dates).rand()
     return _apply(inv_transformation, draws)
+
+
+def _long_paths(model: GPModel, dates, draws: int) -> Optional[np.ndarray]:
+    """[m, draws] on the model's scale from ONE ``Factor.sample_long`` call (S = 1, no appended
+    points, the model's weights), or None where the device path does not apply."""
+    t, _ = model._obs()
+    t_new = model.ds_transform.apply(autogp.to_days(dates))
+    fac = model._factor()
+    if (autogp.horizon_blocks(t.size, 0, t_new.size) is None or fac is None
+            or not hasattr(fac, "sample_long") or autogp.distributed.world()[1] > 1):
+        return None
+    w, _ = autogp.distributed.normalize_log_weights(model.log_weights[:, None],
+                                                    P_total=model.n_particles_total)
+    seed = int(model.rng_shared.integers(0, 2**63 - 1))
+    out, _, info, cinfo = fac.sample_long(t_new, np.ascontiguousarray(w.T), draws, seed)
+    autogp._raise_if_failed(info)
+    autogp._raise_if_failed(cinfo)
+    x = (out[0] - model.y_transform.intercept) / model.y_transform.slope
+    return np.ascontiguousarray(x.T)
 
 
 def forecast_lockstep(models: Sequence[GPModel], forecast_dates, forecast_draws: int, *,
@@ -301,17 +330,21 @@ def forecast_with_nowcasts(base_model: GPModel, nowcasts: Sequence[TData], forec
                            n_hmc: int = 0, ess_threshold: float = 0.0,
                            forecast_n_hmc: Optional[int] = None, verbose: bool = False,
                            lockstep: bool = True, hmc_config: Optional[dict] = None,
-                           threads: Optional[int] = None) -> np.ndarray:
+                           threads: Optional[int] = None, device_paths: bool = False) -> np.ndarray:
     """reference src/forecasting.jl:117-167.  Three keywords are this module's own: ``lockstep``
     (False: the reference's per-scenario loop), ``threads`` (with ``lockstep=False``: the loop's
     scenarios as concurrent tasks on that many threads — the reference's ``Threads.@spawn`` per
     scenario, src/forecasting.jl:131-132; the library combines their calls, include/ngp.h
     "concurrent callers") and ``hmc_config`` (leapfrog count / step size of the refinement moves;
     AutoGP's defaults apply in the reference).  Everything up to the draws is the scenario pipeline
-    (``_Scenarios``); ``forecast_n_hmc`` and ``threads`` are this function's alone."""
+    (``_Scenarios``); ``forecast_n_hmc`` and ``threads`` are this function's alone.
+    ``device_paths``: a horizon beyond what one aux query carries is drawn on the device in one
+    ``Factor.sample_long`` call (``_Scenarios``, "device paths"); on a short horizon, in the
+    refinement modes, without a resident factor that has ``sample_long`` or with
+    ``lockstep=False`` the existing path runs, as with the default."""
     sc = _Scenarios(base_model, nowcasts, forecast_dates, n_mcmc=n_mcmc, n_hmc=n_hmc,
                     ess_threshold=ess_threshold, lockstep=lockstep, hmc_config=hmc_config,
-                    forecast_n_hmc=forecast_n_hmc)
+                    forecast_n_hmc=forecast_n_hmc, device_paths=device_paths)
     dates, draws, D = sc.dates, int(forecast_draws_per_nowcast), len(nowcasts)
     sc.run()
     if sc.mode == "shared":
@@ -382,6 +415,13 @@ class _Scenarios:
     on the host).  Without ``want_sigma`` a horizon served by the long query
     (``Factor.predict_long``) forms no covariance at all and ``covs`` is None.
 
+    Device paths (``device_paths=True``, mode "shared", a horizon beyond what one aux query carries,
+    a resident factor with ``sample_long``, a single rank): ``run`` makes the query without dates
+    for the weight update alone and asks ``predict_long`` for nothing; ``means``, ``covs`` and
+    ``var`` are None, ``sampler`` is None and ``long_sampler`` holds the query.  ``host_matrix``
+    then resamples in the device form (``resample_for_device``: the stream is used as on the
+    short-horizon device path) and draws every path in ONE ``Factor.sample_long`` call.
+
     ``"lockstep"`` (refinement, shared dates, ``lockstep``): ``run`` leaves the D refined clones in
     ``models``, the reference's D tasks as ONE ensemble of P x D items (src/forecasting.jl:131-149).
 
@@ -391,7 +431,8 @@ class _Scenarios:
 
     def __init__(self, base_model: GPModel, nowcasts: Sequence[TData], forecast_dates, *,
                  n_mcmc: int = 0, n_hmc: int = 0, ess_threshold: float = 0.0, lockstep: bool = True,
-                 hmc_config: Optional[dict] = None, forecast_n_hmc: Optional[int] = None):
+                 hmc_config: Optional[dict] = None, forecast_n_hmc: Optional[int] = None,
+                 device_paths: bool = False):
         assert len(nowcasts) > 0, "nowcasts vector must not be empty"
         assert not (n_mcmc > 0 and n_hmc == 0), \
             "If n_mcmc > 0, n_hmc must also be > 0 for MCMC refinement"
@@ -408,6 +449,7 @@ class _Scenarios:
         else:
             self.mode = "lockstep"
         self._mixes = None
+        self.device_paths, self.long_sampler = bool(device_paths), None
 
     def run(self, want_sigma: bool = True) -> None:
         if self.mode == "shared":
@@ -475,6 +517,11 @@ class _Scenarios:
         blocks = autogp.horizon_blocks(t.size, t_add.size, t_new.size)
         if blocks is None:
             out = call(t_new)[3]
+        elif (self.device_paths and fac is not None and hasattr(fac, "sample_long")
+              and autogp.distributed.world()[1] == 1):
+            # device paths: the weight update alone; sample_long forms the moments where it draws
+            out = dict(fac.nowcast(t_add, y_add, t_new[:0], True), mu=None, sigma=None, var=None)
+            self.long_sampler = (fac, t_new, t_add, y_add)
         elif fac is not None and hasattr(fac, "predict_long"):
             # longer than the aux rows carry: the weight update from a query without dates, then ONE
             # long query with the dates as the panel of a solve against the resident factor
@@ -497,6 +544,10 @@ class _Scenarios:
         logw = model.log_weights[:, None] + (out["logml_full"] - out["logml_base"][:, None])
         _, ess, w_all = dist_.normalize_log_weights(logw, P_total=P, full=True)
         self.w = np.ascontiguousarray(w_all.T)                                    # [D, P]
+        if self.long_sampler is not None:
+            self.means = self.covs = self.var = self.sampler = None
+            self.low = ess < self.ess_threshold * P
+            return
         means = (out["mu"] - b) / s if m else np.zeros((logw.shape[0], D, 0))     # [P_local, D, m]
         covs = None
         if not m:
@@ -541,7 +592,7 @@ class _Scenarios:
         device form, or without a sampler the host form over the low scenarios alone (there
         ``forecast_with_nowcasts`` interleaves every scenario's draws, so only the scenarios up to
         the first resampled one have its weights)."""
-        if self.sampler is not None:
+        if self.sampler is not None or self.long_sampler is not None:
             self.resample_for_device()
         else:
             for s in np.flatnonzero(self.low):
@@ -556,6 +607,14 @@ class _Scenarios:
             return np.hstack(autogp.rand_lockstep(self.mixtures(), draws, self.base._eng()))
         if self.mode == "loop":
             return np.hstack([mx.rand(draws) for mx in self.mixtures()])
+        if self.long_sampler is not None:
+            fac, t_new, t_add, y_add = self.long_sampler
+            seed = self.resample_for_device()
+            out, _, info, cinfo = fac.sample_long(t_new, self.w, draws, seed, t_add, y_add, True)
+            autogp._raise_if_failed(info)
+            autogp._raise_if_failed(cinfo)
+            tr = self.base.y_transform
+            return np.ascontiguousarray(((out - tr.intercept) / tr.slope).reshape(-1, t_new.size).T)
         res = np.empty((len(self.dates), len(self.nowcasts) * draws))
         for s in range(len(self.nowcasts)):
             wsc = self._resampled(s) if self.low[s] else self.w[s]
@@ -687,11 +746,19 @@ def forecast_components_with_nowcasts(base_model: GPModel, nowcasts: Sequence[TD
 
 def forecast_targets(model: GPModel, forecast_dates, targets, forecast_draws: int, *,
                      probs=(0.025, 0.25, 0.5, 0.75, 0.975), inv_transformation: Optional[Callable] = None,
-                     want_values: bool = False) -> "autogp.PathTargets":
+                     want_values: bool = False, device_paths: bool = False) -> "autogp.PathTargets":
     """Summaries of functionals of the paths ``forecast`` returns — totals over a window, the peak
     and its date, exceedance, change between two dates (``autogp.path_targets``) — from the same
     snapshot and seed exactly those paths, without bringing them to the host when the engine has
-    ``mixture_path_targets`` and the inverse is one of ``get_transformations``'."""
+    ``mixture_path_targets`` and the inverse is one of ``get_transformations``'.
+    ``device_paths``: as ``forecast``; the paths of a long horizon come back from
+    ``Factor.sample_long`` and are summarised by ``autogp.path_functionals`` (where it does not
+    apply the existing path runs)."""
+    long_x = _long_paths(model, list(forecast_dates), int(forecast_draws)) if device_paths else None
+    if long_x is not None:
+        x = np.ascontiguousarray(long_x.T)
+        return _targets_of_paths(x if inv_transformation is None else _apply(inv_transformation, x),
+                                 targets, probs, want_values)
     mix = autogp.predict_mvn(model, list(forecast_dates))
     eng = model._eng()
     if mix.sampler is None or int(forecast_draws) <= 1:    # the draws forecast() makes on the host
@@ -717,7 +784,8 @@ def forecast_targets_with_nowcasts(base_model: GPModel, nowcasts: Sequence[TData
                                    inv_transformation: Optional[Callable] = None, n_mcmc: int = 0,
                                    n_hmc: int = 0, ess_threshold: float = 0.0, lockstep: bool = True,
                                    hmc_config: Optional[dict] = None,
-                                   want_values: bool = False) -> "autogp.PathTargets":
+                                   want_values: bool = False,
+                                   device_paths: bool = False) -> "autogp.PathTargets":
     """``autogp.path_targets`` of the paths ``forecast_with_nowcasts`` returns.
 
     The scenario pipeline (``_Scenarios``) with the sampler seed ``forecast_with_nowcasts`` takes,
@@ -725,9 +793,13 @@ def forecast_targets_with_nowcasts(base_model: GPModel, nowcasts: Sequence[TData
     (column (s, d) is path s draws + d).  The default mode
     (``n_mcmc = n_hmc = 0``) is one call over the shared components; lockstep-refined clones no
     longer share particles and go through the independent form.  ``forecast_n_hmc`` (a new mixture
-    before every draw) is not taken; sharded runs raise ``NotImplementedError``."""
+    before every draw) is not taken; sharded runs raise ``NotImplementedError``.
+    ``device_paths``: as ``forecast_with_nowcasts`` — the paths of a long horizon are drawn in one
+    ``Factor.sample_long`` call and summarised by ``autogp.path_functionals``; where the conditions
+    do not hold the existing path runs."""
     sc = _Scenarios(base_model, nowcasts, forecast_dates, n_mcmc=n_mcmc, n_hmc=n_hmc,
-                    ess_threshold=ess_threshold, lockstep=lockstep, hmc_config=hmc_config)
+                    ess_threshold=ess_threshold, lockstep=lockstep, hmc_config=hmc_config,
+                    device_paths=device_paths)
     if autogp.distributed.world()[1] > 1:
         raise NotImplementedError("forecast_targets_with_nowcasts: single-rank runs only")
     draws = int(forecast_draws_per_nowcast)
@@ -764,7 +836,8 @@ def forecast_scores_with_nowcasts(base_model: GPModel, nowcasts: Sequence[TData]
                                   shift: float = 0.0, fair: bool = True,
                                   inv_transformation: Optional[Callable] = None, n_mcmc: int = 0,
                                   n_hmc: int = 0, ess_threshold: float = 0.0, lockstep: bool = True,
-                                  hmc_config: Optional[dict] = None) -> "autogp.EnsembleScores":
+                                  hmc_config: Optional[dict] = None,
+                                  device_paths: bool = False) -> "autogp.EnsembleScores":
     """``autogp.ensemble_scores`` of the paths ``forecast_with_nowcasts`` returns against ``y``
     [dates] (original scale): the sample CRPS per date and the energy score of the horizon
     (``windows`` None), or of the given windows of dates.
@@ -773,9 +846,13 @@ def forecast_scores_with_nowcasts(base_model: GPModel, nowcasts: Sequence[TData]
     so from one snapshot and seed it scores exactly the matrix that function would return; where it goes
     through the device the paths are drawn, mapped and scored there and never come back.
     ``forecast_n_hmc`` (a new mixture before every draw) is not taken: score those draws with
-    ``score_forecast``.  Sharded runs raise ``NotImplementedError``."""
+    ``score_forecast``.  Sharded runs raise ``NotImplementedError``.
+    ``device_paths``: as ``forecast_with_nowcasts`` — the paths of a long horizon are drawn in one
+    ``Factor.sample_long`` call and scored by ``autogp.ensemble_scores``; where the conditions do
+    not hold the existing path runs."""
     sc = _Scenarios(base_model, nowcasts, forecast_dates, n_mcmc=n_mcmc, n_hmc=n_hmc,
-                    ess_threshold=ess_threshold, lockstep=lockstep, hmc_config=hmc_config)
+                    ess_threshold=ess_threshold, lockstep=lockstep, hmc_config=hmc_config,
+                    device_paths=device_paths)
     if autogp.distributed.world()[1] > 1:
         raise NotImplementedError("forecast_scores_with_nowcasts: single-rank runs only")
     draws = int(forecast_draws_per_nowcast)
