@@ -1,4 +1,30 @@
 // ngp_api.hip — host side of libngp: contexts, staged jobs, launch schedule, C-ABI (include/ngp.h).
+//
+// One translation unit, as ngp_kernels.hip is on the device side.  The subsystems that nothing else
+// in the host layer depends on are one ngp_host_*.h each, included at the END of this file in
+// dependency order; the headers are not self-contained, and each says at its top what it holds and
+// what stands before it.  In the order of the text:
+//   this file            hip_status / HIPCHK, the page-locked pool and PinVec, ScopedEvent;
+//                        check_program, compile_program; ngp_ctx and its registry, WsPlan, EventTimer,
+//                        DevCall, dev_spec; the context's life cycle and switches; staged value jobs
+//                        (FillLists, ngp_job, factor_chunk, stage_general, refinement, ngp_job_*, the
+//                        *_stage calls, *_direct, ngp_nowcast_batch); the resident factor with its
+//                        long-horizon and component queries, ngp_kernel_components / _terms,
+//                        ngp_cov_batch; gradient jobs and the HMC trajectory
+//   ngp_host_mixture.h   the forecast mixture: weight normalisation, MixInput, sampler, summaries,
+//                        mapped CRPS, trajectory targets, ensemble and path scores — on the context
+//                        and DevCall alone: no job, factor or gradient code
+//   ngp_host_combine.h   flat combining, and the entry points that are requests (ngp_logml_batch,
+//                        ngp_predict_batch, ngp_logml_grad_batch, ngp_grad_job_run,
+//                        ngp_mixture_sample) — behind the value, gradient and mixture one-shot paths
+//                        it merges
+//   ngp_host_comm.h      the RCCL communicator, ngp_shard, all-gather and normalise — behind the
+//                        mixture's weight normalisation
+//   ngp_host_bench.h     microbenchmarks and MFMA layout self-tests — last, nothing needs it
+//
+// Host code of a new entry point goes with the subsystem whose state it runs on; a new subsystem gets
+// a header of its own, a line in this table and an include where its prerequisites allow.  A section
+// of this file that becomes a header moves as whole consecutive runs, no body edited.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -3416,1392 +3442,7 @@ static ngp_status logml_grad_direct(ngp_ctx *c, int32_t B, const ngp_kernel *ker
     return st;
 }
 
-// one column of a [P x ld]-strided log-weight matrix (ld = 1: a plain vector)
-static void weights_normalize_strided(int P, const double *logw, long ld, double *w_norm, long ldw,
-                                      double *ess, double *log_norm) {
-    // a particle whose factorisation failed carries -inf (or NaN after -inf - -inf): weight 0, it
-    // must not poison the others
-    double mx = -INFINITY;
-    for (int i = 0; i < P; ++i)
-        if (std::isfinite(logw[i * ld]) && logw[i * ld] > mx) mx = logw[i * ld];
-    if (!(mx > -INFINITY)) {
-        if (ess) *ess = NAN;
-        if (log_norm) *log_norm = -INFINITY;
-        if (w_norm) for (int i = 0; i < P; ++i) w_norm[i * ldw] = NAN;
-        return;
-    }
-    auto e = [&](int i) { return std::isfinite(logw[i * ld]) ? std::exp(logw[i * ld] - mx) : 0.0; };
-    double sum = 0.0;
-    for (int i = 0; i < P; ++i) sum += e(i);
-    double sq = 0.0;
-    for (int i = 0; i < P; ++i) {
-        const double w = e(i) / sum;
-        if (w_norm) w_norm[i * ldw] = w;
-        sq += w * w;
-    }
-    if (ess) *ess = 1.0 / sq;
-    if (log_norm) *log_norm = mx + std::log(sum);
-}
-
-extern "C" ngp_status ngp_weights_normalize(int32_t P, const double *logw, double *w_norm,
-                                            double *ess, double *log_norm) {
-    if (P <= 0 || !logw) return NGP_ERR_ARG;
-    weights_normalize_strided(P, logw, 1, w_norm, 1, ess, log_norm);
-    return NGP_OK;
-}
-
-extern "C" ngp_status ngp_weights_normalize_cols(int32_t P, int32_t D, const double *logw,
-                                                 double *w_norm, double *ess, double *log_norm) {
-    if (P <= 0 || D <= 0 || !logw) return NGP_ERR_ARG;
-    for (int s = 0; s < D; ++s)
-        weights_normalize_strided(P, logw + s, D, w_norm ? w_norm + s : nullptr, D,
-                                  ess ? ess + s : nullptr, log_norm ? log_norm + s : nullptr);
-    return NGP_OK;
-}
-
-// A forecast mixture as a caller hands it in: what the sampler and every consumer of its paths (the
-// trajectory targets, the path scores) take.  seeds == nullptr: S mixtures over the SAME P components,
-// mu [P x S x m], sigma [P x m x m], one key (seed); seeds [S]: every mixture has its own P components,
-// mu [S x P x m], sigma [S x P x m x m], its own key.  (MixStaged below: the per-date marginals.)
-struct MixInput {
-    int32_t P, S, m, draws;
-    const double *w, *mu, *sigma;
-    uint64_t seed; const uint64_t *seeds;   // one or the other
-    size_t blocks() const { return seeds ? (size_t)S * P : (size_t)P; }   // covariance blocks
-    size_t nw() const { return (size_t)S * P; }
-    size_t nmu() const { return nw() * (size_t)m; }
-    size_t nsg() const { return blocks() * (size_t)m * m; }
-    int64_t N() const { return (int64_t)S * draws; }                       // paths
-    // NGP_ERR_ARG and NGP_ERR_TOO_LARGE apart: the calls have checks of their own between the two
-    bool args_ok() const { return w && mu && sigma && P > 0 && S > 0 && m > 0 && draws > 0; }
-    // counts: the calls that index paths and blocks with 32 bits bound N and S P as well
-    bool too_large(bool counts) const { return m > NGP_MAX_AUX || (counts && (N() > INT32_MAX || nw() > INT32_MAX)); }
-    void up(DevCall &call, double *dw, double *dmu, double *dsg, uint64_t *dseeds) const {
-        call.up(dw, w, 8 * nw()).up(dmu, mu, 8 * nmu()).up(dsg, sigma, 8 * nsg());
-        if (seeds) call.up(dseeds, seeds, 8 * (size_t)S);
-    }
-    // a failed component (info [blocks()]: the Cholesky factorisations) that paths can come from,
-    // in its own mixture or, shared, in any of the S: nothing a call returns is free of it
-    bool tainted(const int32_t *info) const {
-        for (size_t k = 0; k < blocks(); ++k)
-            for (int32_t sc = 0; info[k] && sc < (seeds ? 1 : S); ++sc)
-                if (w[seeds ? k : (size_t)sc * P + k] > 0.0) return true;
-        return false;
-    }
-};
-
-// shared body of ngp_mixture_sample and ngp_mixture_sample_indep
-static ngp_status mixture_sample_impl(ngp_ctx *c, const MixInput &mix, double *out, int32_t *comp, int32_t *info) {
-    if (!c || !out || !mix.args_ok()) return NGP_ERR_ARG;
-    if (mix.too_large(false)) return NGP_ERR_TOO_LARGE;
-    DevCall call(c);
-    const size_t nout = (size_t)mix.N() * mix.m, ncomp = (size_t)mix.N();
-    double *dw = nullptr, *dmu = nullptr, *dsg = nullptr, *dout = nullptr;
-    int32_t *dcomp = nullptr, *dinfo = nullptr;
-    uint64_t *dseeds = nullptr;
-    call.take(&dw, mix.nw()).take(&dmu, mix.nmu()).take(&dsg, mix.nsg()).take(&dout, nout).take(&dcomp, ncomp)
-        .take(&dinfo, mix.blocks());
-    if (mix.seeds) call.take(&dseeds, (size_t)mix.S);
-    mix.up(call, dw, dmu, dsg, dseeds);
-    call.run([&] {
-            launch_mixture_sample(mix.P, mix.S, mix.m, dw, dmu, dsg, mix.draws, mix.seed, dseeds, dout, dcomp,
-                                  dinfo, c->stream);
-        })
-        .down(out, dout, 8 * nout);
-    if (comp) call.down(comp, dcomp, 4 * ncomp);
-    if (info) call.down(info, dinfo, 4 * mix.blocks());
-    return call.sync();
-}
-
-extern "C" ngp_status ngp_mixture_sample_indep(ngp_ctx *c, int32_t P, int32_t S, int32_t m,
-                                               const double *w, const double *mu,
-                                               const double *sigma, int32_t draws,
-                                               const uint64_t *seeds, double *out, int32_t *comp,
-                                               int32_t *info) {
-    if (!seeds) return NGP_ERR_ARG;
-    return mixture_sample_impl(c, MixInput{P, S, m, draws, w, mu, sigma, 0, seeds}, out, comp, info);
-}
-
-// ---------------------------------------------------------------------------------------
-// Summaries of a mixture's per-date marginals (ngp_mixture_cdf / _quantiles / _crps)
-//
-// The host pass validates, reports bad dates and restages the mixture for the kernels of
-// ngp_mixture_kernels.h: components of weight zero are dropped (they are to be ignored, bad values
-// included) and the rest goes DATE-MAJOR.  A date with a bad component is computed on harmless
-// stand-in values and comes out as NaN; nothing it holds reaches the arithmetic of another date.
-namespace {
-struct MixStaged {
-    int32_t C = 0;                       // components of positive weight
-    PinVec<double> w, mu, var;           // [C], [m][C], [m][C]
-    std::vector<char> bad;               // [m]
-};
-
-ngp_status mixture_stage(int32_t C, int32_t m, const double *w, const double *mu, const double *var,
-                         int32_t *info, MixStaged *out) {
-    if (!w || !mu || !var || !info || C < 1 || m < 1) return NGP_ERR_ARG;
-    if (C > MIX_MAX_COMPONENTS || m > MIX_MAX_DATES) return NGP_ERR_TOO_LARGE;
-    std::vector<int32_t> keep;
-    keep.reserve(C);
-    for (int32_t c = 0; c < C; ++c) {
-        if (!(w[c] >= 0.0) || !std::isfinite(w[c])) return NGP_ERR_ARG;
-        if (w[c] > 0.0) keep.push_back(c);
-    }
-    if (keep.empty()) return NGP_ERR_ARG;
-    const size_t Cn = keep.size();
-    out->C = (int32_t)Cn;
-    out->w.resize(Cn);
-    out->mu.resize(Cn * m);
-    out->var.resize(Cn * m);
-    out->bad.assign(m, 0);
-    for (int32_t j = 0; j < m; ++j) info[j] = 0;
-    for (size_t k = 0; k < Cn; ++k) {
-        const int32_t c = keep[k];
-        out->w[k] = w[c];
-        const double *mc = mu + (size_t)c * m, *vc = var + (size_t)c * m;
-        for (int32_t j = 0; j < m; ++j) {
-            const bool ok = std::isfinite(mc[j]) && std::isfinite(vc[j]) && vc[j] > 0.0;
-            if (!ok && !info[j]) info[j] = c + 1;      // components come in ascending order
-            out->mu[(size_t)j * Cn + k] = mc[j];
-            out->var[(size_t)j * Cn + k] = vc[j];
-        }
-    }
-    for (int32_t j = 0; j < m; ++j) {
-        if (!info[j]) continue;
-        out->bad[j] = 1;
-        for (size_t k = 0; k < Cn; ++k) {
-            out->mu[(size_t)j * Cn + k] = 0.0;
-            out->var[(size_t)j * Cn + k] = 1.0;
-        }
-    }
-    return NGP_OK;
-}
-
-// every level strictly inside (0, 1) (a NaN is not)
-bool probs_open_unit(const double *probs, int32_t n) {
-    for (int32_t i = 0; i < n; ++i)
-        if (!(probs[i] > 0.0 && probs[i] < 1.0)) return false;
-    return true;
-}
-
-// a known kind and finite parameters (what more a call asks of the map is checked at that call)
-bool inv_transform_ok(const ngp_inv_transform *inv) {
-    return inv->kind >= NGP_INV_IDENTITY && inv->kind <= NGP_INV_BOXCOX && std::isfinite(inv->lam) &&
-           std::isfinite(inv->offset) && std::isfinite(inv->cap);
-}
-
-// the map as the calls that transform whole paths ask for it: Box-Cox with a positive cap
-bool path_inv_ok(const ngp_inv_transform *inv) {
-    return inv_transform_ok(inv) && (inv->kind != NGP_INV_BOXCOX || inv->cap > 0.0);
-}
-
-// observations on the scoring scale: an unknown scale, a shift not finite and non-negative; then the
-// caller's own size limits (too_large) BEFORE y is read; then a y not finite or with s(y) undefined
-ngp_status score_obs_check(int32_t scale, double shift, bool too_large, const double *y, int32_t m) {
-    if (scale != NGP_SCORE_NATURAL && scale != NGP_SCORE_LOG) return NGP_ERR_ARG;
-    if (!std::isfinite(shift) || shift < 0.0) return NGP_ERR_ARG;
-    if (too_large) return NGP_ERR_TOO_LARGE;
-    for (int32_t j = 0; j < m; ++j)
-        if (!std::isfinite(y[j]) || (scale == NGP_SCORE_LOG && !(y[j] + shift > 0.0))) return NGP_ERR_ARG;
-    return NGP_OK;
-}
-
-enum { MIX_CDF = 0, MIX_QUANTILES = 1, MIX_CRPS = 2 };
-
-// pts: x [m x npts] (CDF), probs [npts] (quantiles), y [m] (CRPS, npts = 1); res [m x npts]
-ngp_status mixture_summary(ngp_ctx *c, int kind, int32_t C, int32_t m, const double *w,
-                           const double *mu, const double *var, int32_t npts, const double *pts,
-                           double *res, int32_t *info) {
-    if (!c || !pts || !res || npts < 1) return NGP_ERR_ARG;
-    if (npts > MIX_MAX_POINTS) return NGP_ERR_TOO_LARGE;
-    if (kind == MIX_QUANTILES && !probs_open_unit(pts, npts)) return NGP_ERR_ARG;
-    MixStaged h;
-    ngp_status st = mixture_stage(C, m, w, mu, var, info, &h);
-    if (st) return st;
-    const size_t Cn = (size_t)h.C, nres = (size_t)m * npts;
-    const size_t npin = kind == MIX_QUANTILES ? (size_t)npts : nres;
-    DevCall call(c);
-    hipStream_t s = c->stream;
-    double *dw = nullptr, *dmu = nullptr, *dvar = nullptr, *daux = nullptr, *dpts = nullptr,
-           *dres = nullptr;
-    // aux: inv [m][C] for the CDF and the quantiles, the slab of tile partials for the CRPS
-    const size_t naux = kind == MIX_CRPS ? (size_t)m * (size_t)mix_tile_pairs(h.C) : Cn * m;
-    call.take(&dw, Cn).take(&dmu, Cn * m).take(&dvar, Cn * m).take(&daux, naux).take(&dpts, npin)
-        .take(&dres, nres);
-    call.up(dw, h.w.data(), 8 * Cn)
-        .up(dmu, h.mu.data(), 8 * Cn * m)
-        .up(dvar, h.var.data(), 8 * Cn * m)
-        .up(dpts, pts, 8 * npin)
-        .run([&] {
-            if (kind == MIX_CRPS) {
-                launch_mixture_crps(h.C, m, dw, dmu, dvar, dpts, daux, dres, s);
-            } else {
-                launch_mixture_prep(dvar, daux, (int64_t)(Cn * m), s);
-                if (kind == MIX_CDF) launch_mixture_cdf(h.C, m, dw, dmu, daux, npts, dpts, dres, s);
-                else launch_mixture_quantiles(h.C, m, dw, dmu, daux, npts, dpts, dres, s);
-            }
-        })
-        .down(res, dres, 8 * nres);
-    if ((st = call.sync())) return st;
-    for (int32_t j = 0; j < m; ++j)
-        if (h.bad[j])
-            for (int32_t k = 0; k < npts; ++k) res[(size_t)j * npts + k] = std::nan("");
-    return NGP_OK;
-}
-}  // namespace
-
-extern "C" ngp_status ngp_mixture_cdf(ngp_ctx *c, int32_t C, int32_t m, const double *w,
-                                      const double *mu, const double *var, int32_t K,
-                                      const double *x, double *cdf, int32_t *info) {
-    return mixture_summary(c, MIX_CDF, C, m, w, mu, var, K, x, cdf, info);
-}
-
-extern "C" ngp_status ngp_mixture_quantiles(ngp_ctx *c, int32_t C, int32_t m, const double *w,
-                                            const double *mu, const double *var, int32_t Q,
-                                            const double *probs, double *q, int32_t *info) {
-    return mixture_summary(c, MIX_QUANTILES, C, m, w, mu, var, Q, probs, q, info);
-}
-
-extern "C" ngp_status ngp_mixture_crps(ngp_ctx *c, int32_t C, int32_t m, const double *w,
-                                       const double *mu, const double *var, const double *y,
-                                       double *crps, int32_t *info) {
-    return mixture_summary(c, MIX_CRPS, C, m, w, mu, var, 1, y, crps, info);
-}
-
-// ---------------------------------------------------------------------------------------
-// CRPS and mean after a monotone map (ngp_mixture_crps_mapped; ngp_mixture_mapped_kernels.h)
-//
-// The host validates, stages as the summaries above do, reads back one small record per date
-// (the scan kernel: range, boundaries of the map, the point where it crosses y), plans each date's
-// panels from its record alone and runs the panel and reduce kernels; dates whose error estimate
-// is above the tolerance go round again at half the width, alone, until the per-date cap.
-extern "C" ngp_status ngp_mixture_crps_mapped(ngp_ctx *c, int32_t C, int32_t m, const double *w,
-                                              const double *mu, const double *var, const void *inv_,
-                                              int32_t scale, double shift, const double *y,
-                                              double tol, double *crps, double *mean, double *err,
-                                              int32_t *info) {
-    const ngp_inv_transform *inv = (const ngp_inv_transform *)inv_;
-    if (!c || !inv || !y || !crps || !info || m < 1) return NGP_ERR_ARG;
-    if (!inv_transform_ok(inv) || !std::isfinite(tol)) return NGP_ERR_ARG;
-    ngp_status st = score_obs_check(scale, shift, m > MIX_MAX_DATES, y, m);
-    if (st) return st;
-    if (!(tol > 0.0)) tol = MIXMAP_DEFAULT_TOL;
-    MixStaged h;
-    if ((st = mixture_stage(C, m, w, mu, var, info, &h))) return st;
-    const size_t Cn = (size_t)h.C;
-    std::vector<double> rec((size_t)m * MIXMAP_REC, 0.0);   // (before the call: it outlives what reads and writes it)
-    std::vector<MixMapPlan> work;
-    std::vector<double> res;
-    DevCall call(c);
-    hipStream_t s = c->stream;
-    double *dw = nullptr, *dmu = nullptr, *dvar = nullptr, *dinv = nullptr, *dy = nullptr,
-           *drec = nullptr;
-    call.take(&dw, Cn).take(&dmu, Cn * m).take(&dvar, Cn * m).take(&dinv, Cn * m).take(&dy, (size_t)m)
-        .take(&drec, (size_t)m * MIXMAP_REC);
-    call.up(dw, h.w.data(), 8 * Cn)
-        .up(dmu, h.mu.data(), 8 * Cn * m)
-        .up(dvar, h.var.data(), 8 * Cn * m)
-        .up(dy, y, 8 * (size_t)m)
-        .run([&] {
-            launch_mixture_prep(dvar, dinv, (int64_t)(Cn * m), s);
-            launch_mixmap_scan(h.C, m, *inv, scale, shift, dw, dmu, dinv, dy, drec, s);
-        })
-        .down(rec.data(), drec, 8 * rec.size());
-    if ((st = call.sync())) return st;
-
-    const double nan = std::nan("");
-    work.reserve(m);
-    for (int32_t j = 0; j < m; ++j) {
-        crps[j] = nan;
-        if (mean) mean[j] = nan;
-        if (err) err[j] = nan;
-        if (h.bad[j]) continue;
-        if (rec[(size_t)j * MIXMAP_REC + MIXMAP_REC_FLAG] != 0.0) {
-            info[j] = NGP_INFO_NOT_FINITE;
-            continue;
-        }
-        work.push_back(mixmap_plan(j, &rec[(size_t)j * MIXMAP_REC]));
-    }
-    while (!work.empty()) {
-        const size_t nw = work.size();
-        int32_t maxp = 1;
-        for (const MixMapPlan &p : work) maxp = std::max(maxp, p.npanels);
-        DevCall round(call);                               // this width's buffers, given back below
-        MixMapPlan *dplan = nullptr;
-        double *dslab = nullptr, *dres = nullptr;
-        round.take(&dplan, nw).take(&dslab, nw * (size_t)maxp * 3).take(&dres, nw * 3);
-        res.assign(nw * 3, 0.0);
-        round.up(dplan, work.data(), nw * sizeof(MixMapPlan))
-            .run([&] {
-                launch_mixmap_panels(h.C, (int)nw, maxp, *inv, scale, shift, dplan, dw, dmu, dinv, dslab,
-                                     dres, s);
-            })
-            .down(res.data(), dres, 8 * res.size());
-        if ((st = round.sync())) return st;
-        std::vector<MixMapPlan> next;
-        for (size_t k = 0; k < nw; ++k) {
-            const int32_t j = work[k].date;
-            const double *r = &rec[(size_t)j * MIXMAP_REC];
-            const double cj = res[k * 3] + r[MIXMAP_REC_CLIP], ej = res[k * 3 + 1];
-            const double mj = r[MIXMAP_REC_PSI0] + res[k * 3 + 2];
-            if (!std::isfinite(cj) || !std::isfinite(mj) || !std::isfinite(ej)) {
-                info[j] = NGP_INFO_NOT_FINITE;             // the outputs stay NaN
-                continue;
-            }
-            const bool done = ej <= tol * std::fabs(cj);
-            if (!done && mixmap_refine(&work[k])) {
-                next.push_back(work[k]);
-                continue;
-            }
-            crps[j] = cj;
-            if (mean) mean[j] = mj;
-            if (err) err[j] = ej;
-            if (!done) info[j] = NGP_INFO_NOT_CONVERGED;
-        }
-        work.swap(next);
-    }
-    return NGP_OK;
-}
-
-// pair terms of the CRPS cross sum per second with the operands in registers (no loads, no LDS):
-// the ceiling mix_crps_pairs_kernel is measured against (scripts/summary_probe.py)
-extern "C" ngp_status ngp_microbench_mixture_pairs(ngp_ctx *c, int32_t iters, double *pairs_per_s) {
-    if (!c || !pairs_per_s || iters <= 0) return NGP_ERR_ARG;
-    DevCall call(c);
-    const int blocks = 256 * 8;
-    double *out = nullptr;
-    call.take(&out, (size_t)blocks * 256);
-    ScopedEvent a, b;
-    call.run([&] {
-            launch_mixture_pair_rate(iters, blocks, out, c->stream);  // warm-up
-            return hipEventRecord(a, c->stream);
-        })
-        .run([&] {
-            launch_mixture_pair_rate(iters, blocks, out, c->stream);
-            return hipEventRecord(b, c->stream);
-        });
-    if (call.sync()) return call.status();
-    float ms = 0.f;
-    HIPCHK(hipEventElapsedTime(&ms, a, b));
-    *pairs_per_s = (double)blocks * 256.0 * (double)iters / ((double)ms * 1e-3);
-    return NGP_OK;
-}
-
-// ---------------------------------------------------------------------------------------
-// Trajectory targets (ngp_mixture_path_targets / _indep; kernels: ngp_path_kernels.h)
-//
-// The host validates, turns the levels into ranks (ascending, distinct: the select passes work
-// on those; q is filled per level from them), stages, launches and scatters the few results.
-namespace {
-ngp_status path_targets_impl(ngp_ctx *c, const MixInput &mix, const ngp_inv_transform *inv, int32_t T,
-                             const ngp_path_target *targets, int32_t Q, const double *probs,
-                             double *q, double *mean, int64_t *count, int64_t *hist,
-                             double *values, int32_t *info) {
-    const int32_t m = mix.m;
-    if (!c || !mix.args_ok() || !inv || !targets || !probs || !q || !mean || !count || !hist || T < 1 || Q < 1)
-        return NGP_ERR_ARG;
-    if (!path_inv_ok(inv)) return NGP_ERR_ARG;
-    if (T > PATH_MAX_TARGETS || Q > PATH_MAX_LEVELS) return NGP_ERR_TOO_LARGE;   // bounds the loops below
-    for (int32_t t = 0; t < T; ++t) {
-        const ngp_path_target &tg = targets[t];
-        if (tg.kind < NGP_TARGET_SUM || tg.kind > NGP_TARGET_EXCEED || tg.j0 < 0 || tg.j1 >= m ||
-            tg.j0 > tg.j1 || !std::isfinite(tg.thr))
-            return NGP_ERR_ARG;
-    }
-    if (!probs_open_unit(probs, Q)) return NGP_ERR_ARG;
-    if (mix.too_large(true)) return NGP_ERR_TOO_LARGE;
-    const int64_t N = mix.N();
-
-    // levels -> ranks, ascending and distinct; lvl[i]: where level i's rank sits among them
-    std::vector<int64_t> rank_of(Q), ranks;
-    for (int32_t i = 0; i < Q; ++i)
-        rank_of[i] = std::min<int64_t>(std::max<int64_t>((int64_t)std::ceil(probs[i] * (double)N), 1), N);
-    ranks = rank_of;
-    std::sort(ranks.begin(), ranks.end());
-    ranks.erase(std::unique(ranks.begin(), ranks.end()), ranks.end());
-    std::vector<int32_t> real;
-    for (int32_t t = 0; t < T; ++t)
-        if (targets[t].kind <= NGP_TARGET_DIFF) real.push_back(t);
-
-    PathGeom g{};
-    g.P = mix.P; g.S = mix.S; g.m = m; g.draws = mix.draws;
-    g.B = (int32_t)mix.blocks();
-    g.indep = mix.seeds ? 1 : 0;
-    g.PW = path_pw(m);
-    g.T = T; g.Tr = (int32_t)real.size(); g.R = (int32_t)ranks.size();
-    g.N = N;
-    const size_t Nn = (size_t)N, B = mix.blocks(), Tn = (size_t)T, R = ranks.size(),
-                 Tr = std::max<size_t>(real.size(), 1), slices = (size_t)path_slices(N);
-    const size_t nw = mix.nw(), nmu = mix.nmu(), nsg = mix.nsg();
-
-    std::vector<int32_t> hinfo(B, 0);
-    std::vector<double> hq(Tr * R, 0.0);
-    DevCall call(c);
-    if (call.status()) return call.status();
-    c->refresh_mem_cap();
-    if ((double)(8 * Tn + 12) * (double)Nn + 8.0 * (double)(nw + nmu + nsg) > (double)c->mem_cap)
-        return NGP_ERR_TOO_LARGE;
-    double *dw = nullptr, *dmu = nullptr;
-    uint64_t *dseeds = nullptr;
-    int64_t *dranks = nullptr;
-    int32_t *dreal = nullptr;
-    ngp_path_target *dtargets = nullptr;
-    PathBufs b{};
-    call.take(&dw, nw).take(&dmu, nmu).take(&b.chol, nsg);
-    if (mix.seeds) call.take(&dseeds, (size_t)mix.S);
-    call.take(&b.info, B).take(&b.bkt, Nn).take(&b.order, Nn).take(&b.rank, Nn).take(&b.cnt, B)
-        .take(&b.off, B + 1).take(&b.wgoff, B + 1).take(&dtargets, Tn).take(&dreal, Tr).take(&dranks, R)
-        .take(&b.values, Tn * Nn).take(&b.partial, Tn * slices).take(&b.mean, Tn).take(&b.count, Tn)
-        .take(&b.hist, Tn * m).take(&b.prefix, Tr * R).take(&b.gpre, Tr * R).take(&b.krem, Tr * R)
-        .take(&b.grp, Tr * R).take(&b.ng, Tr).take(&b.ghist, Tr * R * 256).take(&b.q, Tr * R);
-
-    b.w = dw; b.mu = dmu; b.seeds = dseeds; b.targets = dtargets; b.real = dreal; b.ranks = dranks;
-
-    mix.up(call, dw, dmu, b.chol, dseeds);
-    call.up(dtargets, targets, sizeof(ngp_path_target) * Tn);
-    if (!real.empty()) call.up(dreal, real.data(), 4 * real.size());
-    call.up(dranks, ranks.data(), 8 * R)
-        .run([&] { return launch_path_targets(g, b, *inv, mix.seed, c->stream); })
-        .down(mean, b.mean, 8 * Tn)
-        .down(count, b.count, 8 * Tn)
-        .down(hist, b.hist, 8 * Tn * m);
-    if (!real.empty()) call.down(hq.data(), b.q, 8 * real.size() * R);
-    if (values) call.down(values, b.values, 8 * Tn * Nn);
-    call.down(hinfo.data(), b.info, 4 * B);
-    if (call.sync()) return call.status();
-
-    if (info) std::copy(hinfo.begin(), hinfo.end(), info);
-    const double nan = std::nan("");
-    for (size_t i = 0; i < Tn * (size_t)Q; ++i) q[i] = nan;
-    for (size_t y = 0; y < real.size(); ++y)
-        for (int32_t i = 0; i < Q; ++i) {
-            const size_t r = std::lower_bound(ranks.begin(), ranks.end(), rank_of[i]) - ranks.begin();
-            q[(size_t)real[y] * Q + i] = hq[y * R + r];
-        }
-    if (mix.tainted(hinfo.data())) {
-        for (size_t i = 0; i < Tn * (size_t)Q; ++i) q[i] = nan;
-        for (size_t t = 0; t < Tn; ++t) { mean[t] = nan; count[t] = 0; }
-        for (size_t i = 0; i < Tn * (size_t)m; ++i) hist[i] = 0;
-        if (values) for (size_t i = 0; i < Tn * Nn; ++i) values[i] = nan;
-    }
-    return NGP_OK;
-}
-}  // namespace
-
-extern "C" ngp_status ngp_mixture_path_targets(ngp_ctx *c, int32_t P, int32_t S, int32_t m,
-                                               const double *w, const double *mu,
-                                               const double *sigma, int32_t draws, uint64_t seed,
-                                               const void *inv, int32_t T, const void *targets,
-                                               int32_t Q, const double *probs, double *q,
-                                               double *mean, int64_t *count, int64_t *hist,
-                                               double *values, int32_t *info) {
-    return path_targets_impl(c, MixInput{P, S, m, draws, w, mu, sigma, seed, nullptr},
-                             (const ngp_inv_transform *)inv, T, (const ngp_path_target *)targets, Q,
-                             probs, q, mean, count, hist, values, info);
-}
-
-extern "C" ngp_status ngp_mixture_path_targets_indep(ngp_ctx *c, int32_t P, int32_t S, int32_t m,
-                                                     const double *w, const double *mu,
-                                                     const double *sigma, int32_t draws,
-                                                     const uint64_t *seeds,
-                                                     const void *inv, int32_t T,
-                                                     const void *targets, int32_t Q,
-                                                     const double *probs, double *q, double *mean,
-                                                     int64_t *count, int64_t *hist, double *values,
-                                                     int32_t *info) {
-    if (!seeds) return NGP_ERR_ARG;
-    return path_targets_impl(c, MixInput{P, S, m, draws, w, mu, sigma, 0, seeds},
-                             (const ngp_inv_transform *)inv, T, (const ngp_path_target *)targets, Q,
-                             probs, q, mean, count, hist, values, info);
-}
-
-// ---------------------------------------------------------------------------------------
-// Energy score and sample CRPS of paths (ngp_ensemble_scores / ngp_mixture_path_scores; kernels:
-// ngp_score_kernels.h)
-//
-// The host validates, stages the paths (ensemble form) or has the sampler draw them into a device
-// buffer (mixture form), launches, and turns the two [W] totals into the scores.
-namespace {
-// what both forms ask of N, m, the windows and y; TOO_LARGE before any array is read
-ngp_status score_args(int64_t N, int32_t m, int32_t m_max, const double *y, int32_t scale, double shift,
-                      int32_t fair, int32_t W, const int32_t *win, const double *es) {
-    if (!y || !win || !es || N < 1 || m < 1 || W < 1) return NGP_ERR_ARG;
-    if ((fair != 0 && fair != 1) || (fair == 1 && N < 2)) return NGP_ERR_ARG;
-    const bool too_large = N > SCORE_MAX_PATHS || W > SCORE_MAX_WINDOWS || m > m_max;
-    if (ngp_status st = score_obs_check(scale, shift, too_large, y, m)) return st;
-    for (int32_t w = 0; w < W; ++w)
-        if (win[2 * w] < 0 || win[2 * w + 1] >= m || win[2 * w] > win[2 * w + 1]) return NGP_ERR_ARG;
-    return NGP_OK;
-}
-
-// x: the ensemble form's paths; mix, inv, chol_info: the mixture form's inputs instead
-ngp_status scores_impl(ngp_ctx *c, int32_t N, int32_t m, const double *x, const double *y, int32_t scale,
-                       double shift, int32_t fair, int32_t W, const int32_t *win, double *es,
-                       double *term_obs, double *term_pair, int32_t *info, const MixInput *mix = nullptr,
-                       const ngp_inv_transform *inv = nullptr, int32_t *chol_info = nullptr) {
-    const size_t Nn = (size_t)N, Wn = (size_t)W, nxm = Nn * (size_t)m;
-    const size_t prow = (size_t)score_tile_pairs(N), orow = (size_t)score_slices(N);
-    const size_t prow1 = (size_t)score_folded((int64_t)prow), orow1 = (size_t)score_folded((int64_t)orow);
-    bool long_windows = false;
-    for (int32_t w = 0; w < W; ++w) long_windows = long_windows || win[2 * w + 1] - win[2 * w] >= SCORE_FOLD;
-    const size_t B = mix ? mix->blocks() : 0;
-    const size_t nw = mix ? mix->nw() : 0, nmu = mix ? mix->nmu() : 0, nsg = mix ? mix->nsg() : 0;
-
-    std::vector<int32_t> hflag((size_t)m, 0), hcinfo(B, 0);
-    std::vector<double> hobs(Wn, 0.0), hpair(Wn, 0.0);
-    DevCall call(c);
-    if (call.status()) return call.status();
-    c->refresh_mem_cap();
-    if (8.0 * ((double)nxm * 2.0 + (double)Wn * (double)(prow + prow1 + orow + orow1) +
-               (double)(nw + nmu + nsg)) > (double)c->mem_cap)
-        return NGP_ERR_TOO_LARGE;
-    ScoreBufs b{};
-    double *dx = nullptr, *dy = nullptr, *dw = nullptr, *dmu = nullptr, *dsg = nullptr;
-    int32_t *dwin = nullptr, *dcinfo = nullptr;
-    uint64_t *dseeds = nullptr;
-    call.take(&dx, nxm).take(&dy, (size_t)m).take(&b.u, nxm).take(&b.v, (size_t)m).take(&b.flag, (size_t)m)
-        .take(&dwin, 2 * Wn).take(&b.pair[0], prow * Wn).take(&b.pair[1], prow1 * Wn)
-        .take(&b.obs[0], orow * Wn).take(&b.obs[1], orow1 * Wn);
-    if (mix) {
-        call.take(&dw, nw).take(&dmu, nmu).take(&dsg, nsg).take(&dcinfo, B);
-        if (mix->seeds) call.take(&dseeds, (size_t)mix->S);
-        mix->up(call, dw, dmu, dsg, dseeds);
-        call.run([&] {   // the sampler as ngp_mixture_sample launches it, its paths kept on the device
-            launch_mixture_sample(mix->P, mix->S, m, dw, dmu, dsg, mix->draws, mix->seed, dseeds, dx, nullptr,
-                                  dcinfo, c->stream);
-        });
-    } else {
-        call.up(dx, x, 8 * nxm);
-    }
-    b.x = dx; b.y = dy; b.win = dwin;
-    const double *dobs = nullptr, *dpair = nullptr;
-    call.up(dy, y, 8 * (size_t)m).up(dwin, win, 8 * Wn)
-        .run([&] {
-            return launch_scores(N, m, W, long_windows, inv, scale, shift, b, &dobs, &dpair, c->stream);
-        });
-    if (call.status()) return call.status();
-    call.down(hobs.data(), dobs, 8 * Wn).down(hpair.data(), dpair, 8 * Wn).down(hflag.data(), b.flag, 4 * (size_t)m);
-    if (mix) call.down(hcinfo.data(), dcinfo, 4 * B);
-    if (call.sync()) return call.status();
-
-    if (chol_info) std::copy(hcinfo.begin(), hcinfo.end(), chol_info);
-    const bool failed = mix && mix->tainted(hcinfo.data());
-    const double nan = std::nan("");
-    const double pairs = fair ? 0.5 * (double)N * (double)(N - 1) : 0.5 * (double)N * (double)N;
-    for (int32_t w = 0; w < W; ++w) {
-        bool bad = failed;
-        for (int32_t j = win[2 * w]; j <= win[2 * w + 1] && !bad; ++j) bad = hflag[j] != 0;
-        // finite values whose differences overflow when squared (1e155 and beyond; the largest finite
-        // double a Box-Cox image is capped at): the window has no finite score either
-        bad = bad || !std::isfinite(hobs[w]) || !std::isfinite(hpair[w]);
-        const double to = bad ? nan : hobs[w] / (double)N;
-        const double tp = bad ? nan : hpair[w] / pairs;
-        es[w] = bad ? nan : to - 0.5 * tp;
-        if (term_obs) term_obs[w] = to;
-        if (term_pair) term_pair[w] = tp;
-        if (info) info[w] = bad ? NGP_INFO_NOT_FINITE : 0;
-    }
-    return NGP_OK;
-}
-}  // namespace
-
-extern "C" ngp_status ngp_ensemble_scores(ngp_ctx *c, int32_t N, int32_t m, const double *x,
-                                          const double *y, int32_t scale, double shift, int32_t fair,
-                                          int32_t W, const int32_t *win, double *es, double *term_obs,
-                                          double *term_pair, int32_t *info) {
-    if (!c || !x) return NGP_ERR_ARG;
-    if (ngp_status st = score_args(N, m, SCORE_MAX_DATES, y, scale, shift, fair, W, win, es)) return st;
-    return scores_impl(c, N, m, x, y, scale, shift, fair, W, win, es, term_obs, term_pair, info);
-}
-
-extern "C" ngp_status ngp_mixture_path_scores(ngp_ctx *c, int32_t P, int32_t S, int32_t m,
-                                              const double *w, const double *mu, const double *sigma,
-                                              int32_t indep, int32_t draws, const uint64_t *seeds,
-                                              const void *inv_, const double *y, int32_t scale,
-                                              double shift, int32_t fair, int32_t W, const int32_t *win,
-                                              double *es, double *term_obs, double *term_pair,
-                                              int32_t *info, int32_t *chol_info) {
-    const ngp_inv_transform *inv = (const ngp_inv_transform *)inv_;
-    if (!c || !seeds || !inv || (indep != 0 && indep != 1)) return NGP_ERR_ARG;
-    const MixInput mix{P, S, m, draws, w, mu, sigma, indep ? 0 : seeds[0], indep ? seeds : nullptr};
-    if (!mix.args_ok() || !path_inv_ok(inv)) return NGP_ERR_ARG;
-    if (ngp_status st = score_args(mix.N(), m, NGP_MAX_AUX, y, scale, shift, fair, W, win, es)) return st;
-    if (mix.too_large(true)) return NGP_ERR_TOO_LARGE;
-    return scores_impl(c, (int32_t)mix.N(), m, nullptr, y, scale, shift, fair, W, win, es, term_obs, term_pair,
-                       info, &mix, inv, chol_info);
-}
-
-// ---------------------------------------------------------------------------------------
-// Combining concurrent callers (flat combining)
-//
-// The reference enters the boundary from one task per nowcast scenario (Threads.@spawn,
-// src/forecasting.jl:131-159): D tasks, each with the P particles of its own clone, all on the same
-// dates.  Serialised on the context they are D calls of P items — the small-batch regime D times
-// over.  Here a one-shot call (ngp_logml_batch, ngp_predict_batch, ngp_logml_grad_batch,
-// ngp_mixture_sample with S = 1) is a REQUEST: it joins `pending`; whoever finds nobody serving takes
-// everything that is pending, sorts it into groups of compatible requests — same entry point, same
-// series length, bytewise identical dates (a hash, then memcmp), same forecast dates / flags — and
-// runs every group as ONE launch sequence over the concatenated items with per-item observation
-// rows (the `ldy = n` form every entry point already has; a group of one takes the unchanged
-// one-shot path), scatters the results and wakes the callers.  No timer and no extra thread:
-// requests pile up by themselves while the device is busy with the previous sequence.  A server
-// that has finished its own request hands the role to the first waiter, so nobody serves forever.
-// Requests that are not compatible run in arrival order, as before; staged jobs, resident factors
-// and the collective do not combine (they take ctx->mu as they always did).
-// A merged group that fails as a whole (device memory, a HIP error) is re-run request by request,
-// so every caller gets the status its own call would have had.
-// ---------------------------------------------------------------------------------------
-enum { CK_LOGML = 0, CK_PREDICT = 1, CK_GRAD = 2, CK_MIXTURE = 3 };
-struct ngp_comb_req {
-    int kind = CK_LOGML;
-    // CK_LOGML / CK_PREDICT / CK_GRAD
-    int32_t B = 0, n = 0, m = 0, noise_on_new = 0;
-    const ngp_kernel *k = nullptr;
-    const double *t = nullptr, *y = nullptr, *t_new = nullptr;
-    int64_t ldy = 0;
-    double *logml = nullptr, *grad = nullptr, *mu = nullptr, *sigma = nullptr;
-    int32_t *info = nullptr;
-    ngp_grad_job *gj = nullptr;   // CK_GRAD from ngp_grad_job_run: alone it runs on its resident inputs
-    GradRoute route;              // CK_GRAD: the job's staged spec and switches, or (one-shot calls) the
-                                  // context's when the batch is served (comb_execute)
-    // CK_MIXTURE (one mixture of P components: ngp_mixture_sample with S = 1)
-    int32_t P = 0, draws = 0;
-    const double *w = nullptr, *cmu = nullptr, *csigma = nullptr;
-    uint64_t seed = 0;
-    double *out = nullptr;
-    int32_t *comp = nullptr;
-    // what must be equal for two requests to share a launch sequence, hashed by the caller
-    uint64_t key = 0;
-    ngp_status st = NGP_OK;
-    bool done = false;
-    std::condition_variable cv;
-};
-
-namespace {
-
-inline uint64_t fnv_words(uint64_t h, const void *p, size_t bytes) {
-    const unsigned char *b = (const unsigned char *)p;
-    size_t i = 0;
-    for (; i + 8 <= bytes; i += 8) {
-        uint64_t w;
-        std::memcpy(&w, b + i, 8);
-        h = (h ^ w) * 0x100000001b3ull;
-        h ^= h >> 29;
-    }
-    for (; i < bytes; ++i) h = (h ^ b[i]) * 0x100000001b3ull;
-    return h;
-}
-
-uint64_t comb_key(const ngp_comb_req &r) {
-    uint64_t h = 0xcbf29ce484222325ull;
-    const int32_t head[6] = {r.kind, r.n, r.m, r.noise_on_new, r.P, r.draws};
-    h = fnv_words(h, head, sizeof(head));
-    if (r.kind != CK_MIXTURE) {
-        h = fnv_words(h, r.t, 8 * (size_t)r.n);
-        if (r.m > 0) h = fnv_words(h, r.t_new, 8 * (size_t)r.m);
-    }
-    return h;
-}
-
-bool comb_same(const ngp_comb_req &a, const ngp_comb_req &b) {
-    if (a.kind != b.kind || a.key != b.key || a.n != b.n || a.m != b.m ||
-        a.noise_on_new != b.noise_on_new || a.P != b.P || a.draws != b.draws)
-        return false;
-    if (a.kind == CK_MIXTURE) return true;
-    if (a.kind == CK_GRAD && !grad_route_same(a.route, b.route)) return false;
-    if (std::memcmp(a.t, b.t, 8 * (size_t)a.n) != 0) return false;
-    return a.m == 0 || std::memcmp(a.t_new, b.t_new, 8 * (size_t)a.m) == 0;
-}
-
-// the request alone: the one-shot path as it always was
-ngp_status comb_run_one(ngp_ctx *c, ngp_comb_req &r) {
-    switch (r.kind) {
-    case CK_LOGML: return logml_direct(c, r.B, r.k, r.n, r.t, r.y, r.ldy, r.logml, r.info);
-    case CK_PREDICT:
-        return predict_direct(c, r.B, r.k, r.n, r.t, r.y, r.ldy, r.m, r.t_new, r.noise_on_new, r.mu,
-                              r.sigma, r.logml, r.info);
-    case CK_GRAD:
-        if (r.gj) return grad_job_run_resident(r.gj, r.logml, r.grad, r.info);
-        return logml_grad_direct(c, r.B, r.k, r.n, r.t, r.y, r.ldy, nullptr, r.logml, r.grad, r.info);
-    default:
-        return mixture_sample_impl(c, MixInput{r.P, 1, r.m, r.draws, r.w, r.cmu, r.csigma, r.seed, nullptr},
-                                   r.out, r.comp, r.info);
-    }
-}
-
-// a group of compatible requests as ONE call; the results go back to every request's own arrays
-ngp_status comb_run_group(ngp_ctx *c, const std::vector<ngp_comb_req *> &grp, bool *shared_k) {
-    const ngp_comb_req &r0 = *grp[0];
-    *shared_k = false;
-    if (r0.kind == CK_MIXTURE) {
-        // K mixtures of P components each = ngp_mixture_sample_indep with one seed per request
-        const size_t K = grp.size(), P = (size_t)r0.P, m = (size_t)r0.m, dr = (size_t)r0.draws;
-        std::vector<double> w(K * P), mu(K * P * m), sg(K * P * m * m), out(K * dr * m);
-        std::vector<uint64_t> seeds(K);
-        std::vector<int32_t> comp(K * dr), info(K * P);
-        for (size_t a = 0; a < K; ++a) {
-            std::memcpy(w.data() + a * P, grp[a]->w, 8 * P);
-            std::memcpy(mu.data() + a * P * m, grp[a]->cmu, 8 * P * m);
-            std::memcpy(sg.data() + a * P * m * m, grp[a]->csigma, 8 * P * m * m);
-            seeds[a] = grp[a]->seed;
-        }
-        const MixInput mix{r0.P, (int32_t)K, r0.m, r0.draws, w.data(), mu.data(), sg.data(), 0, seeds.data()};
-        const ngp_status st = mixture_sample_impl(c, mix, out.data(), comp.data(), info.data());
-        if (st) return st;
-        for (size_t a = 0; a < K; ++a) {
-            std::memcpy(grp[a]->out, out.data() + a * dr * m, 8 * dr * m);
-            if (grp[a]->comp) std::memcpy(grp[a]->comp, comp.data() + a * dr, 4 * dr);
-            if (grp[a]->info) std::memcpy(grp[a]->info, info.data() + a * P, 4 * P);
-        }
-        return NGP_OK;
-    }
-    // ---- the scenario tasks of the reference's DEFAULT mode (n_mcmc = n_hmc = 0, src/forecasting.jl:120):
-    // every task holds a clone of the same model — the same trees and parameters — on the same
-    // dates, and its observations differ from the others' only in the appended nowcast points
-    // (src/create_nowcast_data.jl:36-37).  K does not depend on y: such a group is ONE factorisation
-    // per particle with the tasks' appended observations as scenarios — the shared-K form of
-    // ngp_nowcast_batch (SURVEY.md section 8d "dedupe rule") — instead of one per (particle, task).
-    // Recognised, not assumed: same kernels byte for byte, one y per request, a common prefix of the
-    // observations up to a few last points.  Not under ngp_set_batch_invariant (another route to the
-    // same numbers: equal to rounding, not bit for bit).
-    bool invariant;
-    {
-        std::lock_guard<std::mutex> lk(c->mu);
-        invariant = c->invariant;
-    }
-    if ((r0.kind == CK_LOGML || r0.kind == CK_PREDICT) && !invariant) {
-        constexpr int SHARED_K_MAX_TAIL = 16;
-        bool same = true;
-        for (size_t a = 1; a < grp.size() && same; ++a) {
-            const ngp_comb_req &r = *grp[a];
-            same = r.B == r0.B && r.ldy == 0 && r0.ldy == 0;
-            for (int b = 0; same && b < r.B; ++b) {
-                const ngp_kernel &ka = r0.k[b], &kb = r.k[b];
-                same = ka.n_ops == kb.n_ops && ka.n_params == kb.n_params && ka.noise == kb.noise &&
-                       std::memcmp(ka.ops, kb.ops, 4 * (size_t)ka.n_ops) == 0 &&
-                       (ka.n_params == 0 || std::memcmp(ka.params, kb.params, 8 * (size_t)ka.n_params) == 0);
-            }
-        }
-        int npre = r0.n;   // observations every request shares
-        for (size_t a = 1; a < grp.size() && same; ++a) {
-            int i = 0;
-            while (i < npre && grp[a]->y[i] == r0.y[i]) ++i;
-            npre = i;
-        }
-        int dt = std::max(r0.n - npre, 1);
-        npre = r0.n - dt;
-        if (same && grp[0]->ldy == 0 && dt <= SHARED_K_MAX_TAIL && npre >= 1 &&
-            (npre % NB) + dt + r0.m + 1 <= NGP_MAX_AUX) {
-            const size_t P = (size_t)r0.B, D = grp.size(), m = (size_t)r0.m;
-            std::vector<double> yadd(D * (size_t)dt), lf(P * D), mu(P * D * m), sg(P * m * m);
-            std::vector<int32_t> info(P);
-            for (size_t a = 0; a < D; ++a) std::memcpy(yadd.data() + a * dt, grp[a]->y + npre, 8 * (size_t)dt);
-            ngp_job *job = nullptr;
-            ngp_status st = stage_general(c, (int)P, r0.k, npre, r0.t, r0.y, 0, dt, r0.t + npre, (int)D,
-                                          yadd.data(), 0, r0.m, r0.t_new, r0.noise_on_new, &job);
-            if (!st) {
-                st = ngp_job_run(job);
-                if (!st) st = ngp_job_fetch(job, nullptr, lf.data(), m ? mu.data() : nullptr,
-                                            m ? sg.data() : nullptr, info.data());
-                ngp_job_destroy(job);
-            }
-            if (st) return st;
-            for (size_t a = 0; a < D; ++a) {
-                ngp_comb_req *r = grp[a];
-                for (size_t b = 0; b < P; ++b) {
-                    if (r->logml) r->logml[b] = lf[b * D + a];
-                    if (m && r->mu) std::memcpy(r->mu + b * m, mu.data() + (b * D + a) * m, 8 * m);
-                }
-                if (m && r->sigma) std::memcpy(r->sigma, sg.data(), 8 * P * m * m);
-                if (r->info) std::memcpy(r->info, info.data(), 4 * P);
-            }
-            *shared_k = true;
-            return NGP_OK;
-        }
-    }
-    size_t Bt = 0;
-    for (const ngp_comb_req *r : grp) Bt += (size_t)r->B;
-    if (Bt > (size_t)0x7fffffff) return NGP_ERR_TOO_LARGE;
-    std::vector<ngp_kernel> ks;
-    std::vector<const double *> rows;
-    ks.reserve(Bt);
-    rows.reserve(Bt);
-    for (const ngp_comb_req *r : grp)
-        for (int b = 0; b < r->B; ++b) {
-            ks.push_back(r->k[b]);
-            rows.push_back(r->y + (int64_t)b * r->ldy);
-        }
-    std::vector<double> lm(Bt);
-    std::vector<int32_t> info(Bt);
-    if (r0.kind == CK_GRAD) {
-        size_t ng = 0;
-        for (const ngp_kernel &k : ks) ng += (size_t)k.n_params + 1;
-        std::vector<double> grad(ng);
-        // under the members' own spec and switches (comb_same), not the context's current ones: a
-        // job keeps what it was staged under whatever ngp_set_spec did since
-        const ngp_status st = logml_grad_direct(c, (int32_t)Bt, ks.data(), r0.n, r0.t, nullptr, 0,
-                                                rows.data(), lm.data(), grad.data(), info.data(),
-                                                &r0.route);
-        if (st) return st;
-        size_t b0 = 0, g0 = 0;
-        for (ngp_comb_req *r : grp) {
-            size_t len = 0;
-            for (int b = 0; b < r->B; ++b) len += (size_t)r->k[b].n_params + 1;
-            std::memcpy(r->grad, grad.data() + g0, 8 * len);
-            if (r->logml) std::memcpy(r->logml, lm.data() + b0, 8 * (size_t)r->B);
-            if (r->info) std::memcpy(r->info, info.data() + b0, 4 * (size_t)r->B);
-            b0 += (size_t)r->B;
-            g0 += len;
-        }
-        return NGP_OK;
-    }
-    const size_t m = (size_t)r0.m;
-    std::vector<double> mu(Bt * m), sg(Bt * m * m);
-    static const double dummy = 0.0;
-    ngp_job *job = nullptr;
-    ngp_status st = stage_general(c, (int)Bt, ks.data(), r0.n, r0.t, nullptr, 0, 0, &dummy, 1, &dummy, 0,
-                                  r0.m, r0.t_new, r0.noise_on_new, &job, rows.data());
-    if (st) return st;
-    st = ngp_job_run(job);
-    if (!st) st = ngp_job_fetch(job, nullptr, lm.data(), m ? mu.data() : nullptr,
-                                m ? sg.data() : nullptr, info.data());
-    ngp_job_destroy(job);
-    if (st) return st;
-    size_t b0 = 0;
-    for (ngp_comb_req *r : grp) {
-        const size_t B = (size_t)r->B;
-        if (r->logml) std::memcpy(r->logml, lm.data() + b0, 8 * B);
-        if (r->info) std::memcpy(r->info, info.data() + b0, 4 * B);
-        if (m && r->mu) std::memcpy(r->mu, mu.data() + b0 * m, 8 * B * m);
-        if (m && r->sigma) std::memcpy(r->sigma, sg.data() + b0 * m * m, 8 * B * m * m);
-        b0 += B;
-    }
-    return NGP_OK;
-}
-
-// everything one server took from `pending`: groups in order of their first member's arrival
-void comb_execute(ngp_ctx *c, const std::vector<ngp_comb_req *> &batch, int64_t stats[6]) {
-    {
-        // one-shot gradient calls run under the context's spec and switches as they are now (as
-        // they would alone); a staged job brought its own (ngp_grad_job_run)
-        std::lock_guard<std::mutex> lk(c->mu);
-        const GradRoute now = grad_route_of(c);
-        for (ngp_comb_req *r : batch)
-            if (r->kind == CK_GRAD && !r->gj) r->route = now;
-    }
-    std::vector<char> taken(batch.size(), 0);
-    for (size_t i = 0; i < batch.size(); ++i) {
-        if (taken[i]) continue;
-        std::vector<ngp_comb_req *> grp{batch[i]};
-        taken[i] = 1;
-        for (size_t j = i + 1; j < batch.size(); ++j)
-            if (!taken[j] && comb_same(*batch[i], *batch[j])) {
-                grp.push_back(batch[j]);
-                taken[j] = 1;
-            }
-        stats[0] += (int64_t)grp.size();
-        if (grp.size() > 1) {
-            bool shared_k = false;
-            const ngp_status st = comb_run_group(c, grp, &shared_k);
-            if (st == NGP_OK) {
-                for (ngp_comb_req *r : grp) r->st = NGP_OK;
-                if (shared_k) stats[4] += (int64_t)grp.size();
-                stats[1] += 1;
-                stats[2] = std::max<int64_t>(stats[2], (int64_t)grp.size());
-                stats[3] += (int64_t)grp.size();
-                continue;
-            }
-        }
-        for (ngp_comb_req *r : grp) {   // alone, or the merged call failed: each for itself
-            r->st = comb_run_one(c, *r);
-            stats[1] += 1;
-            stats[2] = std::max<int64_t>(stats[2], 1);
-        }
-    }
-}
-
-// A caller that finds nobody serving, but whose predecessors came in company, gives that company
-// this long to arrive before it serves (tasks that were woken together by the previous sequence do
-// their host work and come back within microseconds of each other: without the wait the first one
-// back runs alone and the convoy alternates 1, T-1, 1, T-1 ...).  Bounded, and never paid twice in
-// vain: a wait that ends short of the expected company lowers the expectation to what did arrive,
-// so a caller that is alone waits at most once after a concurrent phase and never otherwise.
-constexpr int COMB_LINGER_US = 200;
-
-ngp_status combine_submit(ngp_ctx *c, ngp_comb_req &r) {
-    r.key = comb_key(r);   // outside the lock: 16 KB of dates at n = 2048
-    std::unique_lock<std::mutex> q(c->qmu);
-    if (!c->combine_on) {
-        q.unlock();
-        return comb_run_one(c, r);
-    }
-    c->pending.push_back(&r);
-    c->comb_arrival.notify_all();
-    // Invariant: a request that is not done is either in `pending` or in the batch of the one
-    // serving thread (combining == true).  So a thread that finds nobody serving finds its own
-    // request in `pending`.
-    while (!r.done) {
-        if (c->combining) {
-            r.cv.wait(q);
-            continue;
-        }
-        c->combining = true;
-        if (c->combine_linger && c->pending.size() < c->comb_expect) {
-            const auto deadline = std::chrono::steady_clock::now() + std::chrono::microseconds(COMB_LINGER_US);
-            (void)c->comb_arrival.wait_until(q, deadline, [&] { return c->pending.size() >= c->comb_expect; });
-        }
-        std::vector<ngp_comb_req *> batch;
-        batch.swap(c->pending);
-        c->comb_expect = std::max<size_t>(batch.size(), 1);
-        q.unlock();
-        int64_t stats[6] = {0, 0, 0, 0, 0, 0};
-        comb_execute(c, batch, stats);
-        q.lock();
-        c->comb_stats[0] += stats[0];
-        c->comb_stats[1] += stats[1];
-        c->comb_stats[2] = std::max(c->comb_stats[2], stats[2]);
-        c->comb_stats[3] += stats[3];
-        c->comb_stats[4] += stats[4];
-        // (qmu is held from `done = true` to the notify: a woken caller cannot leave — and take its
-        // request off its stack — before this loop is through with it)
-        for (ngp_comb_req *x : batch) {
-            x->done = true;
-            if (x != &r) x->cv.notify_one();
-        }
-        c->combining = false;
-        // what arrived meanwhile is served by its first waiter, not by this thread
-        if (!c->pending.empty()) c->pending.front()->cv.notify_one();
-    }
-    return r.st;
-}
-
-}  // namespace
-
-extern "C" ngp_status ngp_set_combining(ngp_ctx *c, int32_t on) {
-    if (!c) return NGP_ERR_ARG;
-    std::lock_guard<std::mutex> lk(c->qmu);
-    c->combine_on = on != 0;
-    c->combine_linger = on != 2;   // 2: combine what is pending, never wait for company
-    return NGP_OK;
-}
-
-extern "C" ngp_status ngp_combine_stats(ngp_ctx *c, int64_t *out6, int32_t reset) {
-    if (!c || !out6) return NGP_ERR_ARG;
-    std::lock_guard<std::mutex> lk(c->qmu);
-    for (int i = 0; i < 6; ++i) out6[i] = c->comb_stats[i];
-    if (reset) for (int i = 0; i < 6; ++i) c->comb_stats[i] = 0;
-    return NGP_OK;
-}
-
-// Arguments the merged form could not carry (null arrays, a malformed tree, empty sizes) never
-// join a group: the direct path reports them exactly as before.
-static bool comb_value_args_ok(ngp_ctx *c, int32_t B, const ngp_kernel *k, int32_t n, const double *t,
-                               const double *y) {
-    if (!c || !k || !t || !y || B <= 0 || n <= 0) return false;
-    for (int i = 0; i < B; ++i)
-        if (check_program(&k[i]) != NGP_OK) return false;
-    return true;
-}
-
-extern "C" ngp_status ngp_logml_batch(ngp_ctx *c, int32_t B, const ngp_kernel *k, int32_t n,
-                                      const double *t, const double *y, int64_t ldy, double *logml,
-                                      int32_t *info) {
-    if (!comb_value_args_ok(c, B, k, n, t, y)) return logml_direct(c, B, k, n, t, y, ldy, logml, info);
-    ngp_comb_req r;
-    r.kind = CK_LOGML;
-    r.B = B; r.k = k; r.n = n; r.t = t; r.y = y; r.ldy = ldy;
-    r.logml = logml; r.info = info;
-    return combine_submit(c, r);
-}
-
-extern "C" ngp_status ngp_predict_batch(ngp_ctx *c, int32_t B, const ngp_kernel *k, int32_t n,
-                                        const double *t, const double *y, int64_t ldy, int32_t m,
-                                        const double *t_new, int32_t noise_on_new, double *mu,
-                                        double *sigma, double *logml, int32_t *info) {
-    if (!comb_value_args_ok(c, B, k, n, t, y) || m <= 0 || !t_new)
-        return predict_direct(c, B, k, n, t, y, ldy, m, t_new, noise_on_new, mu, sigma, logml, info);
-    ngp_comb_req r;
-    r.kind = CK_PREDICT;
-    r.B = B; r.k = k; r.n = n; r.t = t; r.y = y; r.ldy = ldy;
-    r.m = m; r.t_new = t_new; r.noise_on_new = noise_on_new ? 1 : 0;
-    r.mu = mu; r.sigma = sigma; r.logml = logml; r.info = info;
-    return combine_submit(c, r);
-}
-
-extern "C" ngp_status ngp_logml_grad_batch(ngp_ctx *c, int32_t B, const ngp_kernel *kernels,
-                                           int32_t n, const double *t, const double *y,
-                                           int64_t ldy, double *logml, double *grad,
-                                           int32_t *info) {
-    if (!grad || !comb_value_args_ok(c, B, kernels, n, t, y))
-        return logml_grad_direct(c, B, kernels, n, t, y, ldy, nullptr, logml, grad, info);
-    ngp_comb_req r;
-    r.kind = CK_GRAD;
-    r.B = B; r.k = kernels; r.n = n; r.t = t; r.y = y; r.ldy = ldy;
-    r.logml = logml; r.grad = grad; r.info = info;
-    return combine_submit(c, r);
-}
-
-// A resident job that still has the one-shot form of its inputs (small jobs) is a gradient request
-// like any other: with company it shares one call over everybody's items, alone it runs on its
-// resident inputs.
-extern "C" ngp_status ngp_grad_job_run(ngp_grad_job *j, double *logml, double *grad, int32_t *info) {
-    if (!j || !grad) return NGP_ERR_ARG;
-    if (j->h_k.empty()) return grad_job_run_resident(j, logml, grad, info);
-    ngp_comb_req r;
-    r.kind = CK_GRAD;
-    r.gj = j;
-    r.route = j->route;
-    r.B = j->B; r.k = j->h_k.data(); r.n = j->n; r.t = j->h_t.data();
-    r.y = j->h_y.data(); r.ldy = j->h_ldy;
-    r.logml = logml; r.grad = grad; r.info = info;
-    return combine_submit(j->ctx, r);
-}
-
-extern "C" ngp_status ngp_mixture_sample(ngp_ctx *c, int32_t P, int32_t S, int32_t m,
-                                         const double *w, const double *mu, const double *sigma,
-                                         int32_t draws, uint64_t seed, double *out, int32_t *comp,
-                                         int32_t *info) {
-    // S mixtures over shared components stay one call of their own; ONE mixture (what
-    // predict_mvn(...) |> rand of a scenario task asks for, src/forecasting.jl:46-47) can share a
-    // launch with other tasks' mixtures of the same shape
-    const MixInput mix{P, S, m, draws, w, mu, sigma, seed, nullptr};
-    if (S != 1 || !c || !out || !mix.args_ok() || mix.too_large(false)) return mixture_sample_impl(c, mix, out, comp, info);
-    ngp_comb_req r;
-    r.kind = CK_MIXTURE;
-    r.P = P; r.m = m; r.draws = draws; r.w = w;
-    r.cmu = mu; r.csigma = sigma;
-    r.seed = seed; r.out = out; r.comp = comp; r.info = info;
-    return combine_submit(c, r);
-}
-
-// ---------------------------------------------------------------------------------------
-// The one collective of the path (north_star: RCCL over xGMI only for the particle-weight
-// normalisation / resample reduction), for hosts that bring no collective library of their own
-// (the Julia shim; the Python mirror uses torch.distributed, whose "nccl" backend is this same
-// RCCL).  librccl is opened at run time: the library has no link-time dependency on it and the
-// entry points answer NGP_ERR_UNAVAILABLE when it is not installed.
-// ---------------------------------------------------------------------------------------
-namespace {
-struct RcclUid { char internal[128]; };   // ncclUniqueId (rccl.h: NCCL_UNIQUE_ID_BYTES = 128)
-struct RcclApi {
-    void *handle = nullptr;
-    int (*GetUniqueId)(RcclUid *) = nullptr;
-    int (*CommInitRank)(void **, int, RcclUid, int) = nullptr;
-    int (*CommDestroy)(void *) = nullptr;
-    int (*AllGather)(const void *, void *, size_t, int, void *, hipStream_t) = nullptr;
-    bool ok = false;
-};
-RcclApi load_rccl() {
-    RcclApi r;
-    // The RCCL that belongs to the HIP runtime THIS library is bound to, by path: a host process may
-    // hold a second ROCm stack (PyTorch wheels bundle libamdhip64 / libhsa-runtime64 / librccl; when
-    // torch is imported after libngp both stacks are mapped), and a bare dlopen("librccl.so.1")
-    // then returns the copy already loaded — tied to the other, uninitialised runtime
-    // ("no ROCm-capable device", scripts/rccl_probe.py).  The directory of the libamdhip64 that
-    // resolved our own HIP calls decides.
-    std::vector<std::string> names;
-    Dl_info di{};
-    if (dladdr((void *)&hipGetDeviceCount, &di) && di.dli_fname) {
-        std::string dir(di.dli_fname);
-        const size_t slash = dir.rfind('/');
-        if (slash != std::string::npos) {
-            dir.resize(slash + 1);
-            names.push_back(dir + "librccl.so.1");
-            names.push_back(dir + "librccl.so");
-        }
-    }
-    for (const char *nm : {"librccl.so.1", "librccl.so", "/opt/rocm/lib/librccl.so.1"}) names.push_back(nm);
-    for (const std::string &name : names) {
-        r.handle = dlopen(name.c_str(), RTLD_NOW | RTLD_LOCAL);
-        if (r.handle) break;
-    }
-    if (!r.handle) return r;
-    r.GetUniqueId = (decltype(r.GetUniqueId))dlsym(r.handle, "ncclGetUniqueId");
-    r.CommInitRank = (decltype(r.CommInitRank))dlsym(r.handle, "ncclCommInitRank");
-    r.CommDestroy = (decltype(r.CommDestroy))dlsym(r.handle, "ncclCommDestroy");
-    r.AllGather = (decltype(r.AllGather))dlsym(r.handle, "ncclAllGather");
-    r.ok = r.GetUniqueId && r.CommInitRank && r.CommDestroy && r.AllGather;
-    return r;
-}
-const RcclApi &rccl() {
-    static const RcclApi api = load_rccl();
-    return api;
-}
-constexpr int RCCL_FLOAT64 = 8;   // ncclFloat64 (rccl.h)
-}  // namespace
-
-struct ngp_comm {
-    ngp_ctx *ctx = nullptr;
-    void *comm = nullptr;
-    int rank = 0, world = 1;
-    // send / receive buffers of the all-gather, grow-only: after the first call of a shape no
-    // rank allocates inside a collective (an allocation that fails on ONE rank would leave its
-    // peers waiting in the all-gather)
-    void *d_send = nullptr, *d_recv = nullptr;
-    size_t cap = 0;   // doubles per rank
-};
-
-extern "C" ngp_status ngp_comm_unique_id(void *id128) {
-    if (!id128) return NGP_ERR_ARG;
-    if (!rccl().ok) return NGP_ERR_UNAVAILABLE;
-    RcclUid uid{};
-    if (rccl().GetUniqueId(&uid) != 0) return NGP_ERR_UNAVAILABLE;
-    std::memcpy(id128, uid.internal, sizeof(uid.internal));
-    return NGP_OK;
-}
-
-extern "C" ngp_status ngp_comm_create(ngp_ctx *c, const void *id128, int32_t rank, int32_t world,
-                                      ngp_comm **out) {
-    if (!c || !id128 || !out || world <= 0 || rank < 0 || rank >= world) return NGP_ERR_ARG;
-    *out = nullptr;
-    if (!rccl().ok) return NGP_ERR_UNAVAILABLE;
-    std::lock_guard<std::mutex> lk(c->mu);
-    HIPCHK(hipSetDevice(c->device));
-    RcclUid uid{};
-    std::memcpy(uid.internal, id128, sizeof(uid.internal));
-    ngp_comm *m = new (std::nothrow) ngp_comm();
-    if (!m) return NGP_ERR_TOO_LARGE;
-    m->ctx = c;
-    m->rank = rank;
-    m->world = world;
-    // RCCL allocates its own device buffers, and after a large job most of the device can sit in
-    // the caching allocators of this process: they are given back BEFORE the one attempt.  (The
-    // initialisation is a collective — a rank that retried it alone after a failure would pair
-    // with nobody, its peers having returned from the first attempt or still waiting inside it.)
-    c->drop_cache();
-    c->ws_drop();
-    ngp_ctx::drop_other_caches(c);
-    if (rccl().CommInitRank(&m->comm, world, uid, rank) != 0) {
-        (void)hipGetLastError();
-        delete m;
-        return NGP_ERR_UNAVAILABLE;
-    }
-    *out = m;
-    return NGP_OK;
-}
-
-extern "C" void ngp_comm_destroy(ngp_comm *m) {
-    if (!m) return;
-    if (m->comm && rccl().ok) {
-        (void)hipSetDevice(m->ctx->device);
-        (void)rccl().CommDestroy(m->comm);
-    }
-    {
-        std::lock_guard<std::mutex> lk(m->ctx->mu);
-        m->ctx->release(m->d_send);
-        m->ctx->release(m->d_recv);
-    }
-    delete m;
-}
-
-extern "C" ngp_status ngp_shard(int32_t P_total, int32_t world, int32_t rank, int32_t *first,
-                                int32_t *rows) {
-    if (P_total < 0 || world <= 0 || rank < 0 || rank >= world) return NGP_ERR_ARG;
-    const int base = P_total / world, rem = P_total % world;
-    if (first) *first = rank * base + std::min(rank, rem);
-    if (rows) *rows = base + (rank < rem ? 1 : 0);
-    return NGP_OK;
-}
-
-// The host half of the exchange: `padded` holds what an all-gather of equally sized, zero-padded
-// shards delivers — world blocks of pmax x D doubles, pmax = the largest shard (rank 0's), block r =
-// rank r's rows then padding — and comes out as the P_total x D normalised weights.  Exported so that
-// a host with a collective of its own (MPI.jl, Julia's Distributed, torch.distributed) pads,
-// gathers with that, and normalises exactly as ngp_weights_allgather_normalize does.
-extern "C" ngp_status ngp_weights_unpad_normalize(int32_t P_total, int32_t world, int32_t D,
-                                                  const double *padded, double *w_all, double *ess,
-                                                  double *log_norm) {
-    if (!padded || P_total <= 0 || D <= 0 || world <= 0 || P_total < world) return NGP_ERR_ARG;
-    auto rows_of = [&](int r) { int32_t v = 0; (void)ngp_shard(P_total, world, r, nullptr, &v); return (size_t)v; };
-    auto first_of = [&](int r) { int32_t v = 0; (void)ngp_shard(P_total, world, r, &v, nullptr); return (size_t)v; };
-    const size_t cnt = rows_of(0) * (size_t)D;
-    std::vector<double> lw((size_t)P_total * D), wn((size_t)P_total * D);
-    for (int r = 0; r < world; ++r)
-        std::memcpy(lw.data() + first_of(r) * D, padded + (size_t)r * cnt, 8 * rows_of(r) * D);
-    for (int sidx = 0; sidx < D; ++sidx)
-        weights_normalize_strided(P_total, lw.data() + sidx, D, wn.data() + sidx, D,
-                                  ess ? ess + sidx : nullptr, log_norm ? log_norm + sidx : nullptr);
-    if (w_all) std::memcpy(w_all, wn.data(), 8 * wn.size());
-    return NGP_OK;
-}
-
-extern "C" ngp_status ngp_weights_allgather_normalize(ngp_comm *m, int32_t P_total, int32_t D,
-                                                      const double *logw_local, double *w_local,
-                                                      double *w_all, double *ess,
-                                                      double *log_norm) {
-    if (!m || !logw_local || P_total <= 0 || D <= 0 || P_total < m->world) return NGP_ERR_ARG;
-    // block partition of the particles over the ranks, remainder to the low ranks (ngp_shard: the
-    // partition nowcastautogp_amd.distributed.shard and the Julia shim use)
-    auto rows_of = [&](int r) { int32_t v = 0; (void)ngp_shard(P_total, m->world, r, nullptr, &v); return (int)v; };
-    auto first_of = [&](int r) { int32_t v = 0; (void)ngp_shard(P_total, m->world, r, &v, nullptr); return (int)v; };
-    const int mine = rows_of(m->rank), pmax = rows_of(0);
-    ngp_ctx *c = m->ctx;
-    std::vector<double> h_all;
-    DevCall call(c);   // for the lock, the device and the copies: the buffers are the communicator's
-    if (call.status()) return call.status();
-    hipStream_t s = c->stream;
-    // ragged shards: every rank sends pmax rows (its own, then padding).  The buffers stay with the
-    // communicator; every rank sees the same (P_total, D), so they grow on all ranks in the same
-    // call — and a rank that cannot grow them has left the collective for good: any non-zero
-    // return of this function is FATAL for the communicator (its peers may be inside the
-    // all-gather), destroy it and start over.
-    const size_t cnt = (size_t)pmax * D;
-    if (cnt > m->cap) {
-        void *a = nullptr, *b = nullptr;
-        ngp_status st;
-        if ((st = c->alloc(&a, 8 * cnt)) || (st = c->alloc(&b, 8 * cnt * (size_t)m->world))) {
-            c->release(a);
-            return st;
-        }
-        c->release(m->d_send);
-        c->release(m->d_recv);
-        m->d_send = a;
-        m->d_recv = b;
-        m->cap = cnt;
-    }
-    void *d_send = m->d_send, *d_recv = m->d_recv;
-    h_all.resize(cnt * (size_t)m->world);
-    int rc = 0;
-    call.run([&] { return hipMemsetAsync(d_send, 0, 8 * cnt, s); })
-        .up(d_send, logw_local, 8 * (size_t)mine * D)
-        .run([&] { rc = rccl().AllGather(d_send, d_recv, cnt, RCCL_FLOAT64, m->comm, s); });
-    if (rc == 0) call.down(h_all.data(), d_recv, 8 * h_all.size());
-    const ngp_status gathered = call.sync();
-    if (rc != 0) return NGP_ERR_UNAVAILABLE;
-    if (gathered) return gathered;
-    // compact the padded shards to [P_total x D], then the columns as ngp_weights_normalize_cols
-    std::vector<double> wn((size_t)P_total * D);
-    const ngp_status st = ngp_weights_unpad_normalize(P_total, m->world, D, h_all.data(), wn.data(), ess, log_norm);
-    if (st) return st;
-    if (w_all) std::memcpy(w_all, wn.data(), 8 * wn.size());
-    if (w_local)
-        std::memcpy(w_local, wn.data() + (size_t)first_of(m->rank) * D, 8 * (size_t)mine * D);
-    return NGP_OK;
-}
-
-// ---------------------------------------------------------------------------------------
-// microbenchmarks / self tests
-// ---------------------------------------------------------------------------------------
-extern "C" ngp_status ngp_microbench_mfma_f64(ngp_ctx *c, int32_t iters, double *tflops) {
-    if (!c || !tflops || iters <= 0) return NGP_ERR_ARG;
-    DevCall call(c);
-    iters = (iters + 3) / 4 * 4;
-    const int blocks = 256 * 4;  // 4 workgroups of 4 waves per CU
-    double *out = nullptr;
-    call.take(&out, (size_t)blocks * 256);
-    ScopedEvent a, b;
-    call.run([&] {
-            launch_mfma_bench(out, iters, blocks, c->stream);  // warm-up
-            return hipEventRecord(a, c->stream);
-        })
-        .run([&] {
-            launch_mfma_bench(out, iters, blocks, c->stream);
-            return hipEventRecord(b, c->stream);
-        });
-    if (call.sync()) return call.status();
-    float ms = 0.f;
-    HIPCHK(hipEventElapsedTime(&ms, a, b));
-    *tflops = (double)blocks * 4.0 * (double)iters * 2048.0 / ((double)ms * 1e-3) * 1e-12;
-    return NGP_OK;
-}
-
-// out[0] TFLOP/s (wall), out[1] median shader cycles per MFMA per wave, out[2] median effective
-// shader clock in GHz (s_memtime / s_memrealtime), out[3] waves per SIMD used
-extern "C" ngp_status ngp_microbench_mfma_f64_detail(ngp_ctx *c, int32_t iters,
-                                                     int32_t blocks_per_cu, double *out) {
-    if (!c || !out || iters <= 0 || blocks_per_cu <= 0 || blocks_per_cu > 8) return NGP_ERR_ARG;
-    iters = (iters + 3) / 4 * 4;
-    const int blocks = 256 * blocks_per_cu;
-    const int waves = blocks * 4;
-    std::vector<unsigned long long> h(2 * (size_t)waves);
-    DevCall call(c);
-    unsigned long long *stamps = nullptr;
-    call.take(&stamps, 2 * (size_t)waves);
-    ScopedEvent a, b;
-    call.run([&] {
-            launch_mfma_bench_detail(stamps, iters, blocks, c->stream);
-            return hipEventRecord(a, c->stream);
-        })
-        .run([&] {
-            launch_mfma_bench_detail(stamps, iters, blocks, c->stream);
-            return hipEventRecord(b, c->stream);
-        })
-        .down(h.data(), stamps, sizeof(unsigned long long) * h.size());
-    if (call.sync()) return call.status();
-    float ms = 0.f;
-    HIPCHK(hipEventElapsedTime(&ms, a, b));
-    std::vector<double> cyc((size_t)waves), ghz((size_t)waves);
-    for (int w = 0; w < waves; ++w) {
-        cyc[(size_t)w] = (double)h[2 * (size_t)w] / (double)iters;
-        ghz[(size_t)w] = (double)h[2 * (size_t)w] / ((double)h[2 * (size_t)w + 1] * 10.0);
-    }
-    std::nth_element(cyc.begin(), cyc.begin() + waves / 2, cyc.end());
-    std::nth_element(ghz.begin(), ghz.begin() + waves / 2, ghz.end());
-    out[0] = (double)waves * (double)iters * 2048.0 / ((double)ms * 1e-3) * 1e-12;
-    out[1] = cyc[(size_t)waves / 2];
-    out[2] = ghz[(size_t)waves / 2];
-    out[3] = (double)blocks_per_cu;
-    return NGP_OK;
-}
-
-extern "C" ngp_status ngp_microbench_hbm(ngp_ctx *c, int64_t bytes, double *write_gbs,
-                                         double *copy_gbs) {
-    if (!c || bytes < 4096) return NGP_ERR_ARG;
-    DevCall call(c);
-    const int64_t n = bytes / 16 * 2;
-    double *a = nullptr, *b = nullptr;
-    call.take(&a, (size_t)n).take(&b, (size_t)n);
-    ScopedEvent e0, e1, e2;
-    call.run([&] {
-            launch_stream_write(a, n, c->stream);
-            launch_stream_copy(b, a, n, c->stream);
-            return hipEventRecord(e0, c->stream);
-        })
-        .run([&] {
-            launch_stream_write(a, n, c->stream);
-            return hipEventRecord(e1, c->stream);
-        })
-        .run([&] {
-            launch_stream_copy(b, a, n, c->stream);
-            return hipEventRecord(e2, c->stream);
-        });
-    if (call.sync()) return call.status();
-    float w = 0.f, cp = 0.f;
-    HIPCHK(hipEventElapsedTime(&w, e0, e1));
-    HIPCHK(hipEventElapsedTime(&cp, e1, e2));
-    if (write_gbs) *write_gbs = (double)n * 8.0 / ((double)w * 1e-3) * 1e-9;
-    if (copy_gbs) *copy_gbs = 2.0 * (double)n * 8.0 / ((double)cp * 1e-3) * 1e-9;
-    return NGP_OK;
-}
-
-// D[0:256]   = A(16x4) B(4x16) through one v_mfma_f64_16x16x4_f64 using the operand maps the
-//              kernels assume
-// D[256:512] = the same product through four DPP-rotated v_mfma_f64_4x4x4_4b_f64 + the gather back
-//              to the 16x16x4 C/D layout (the fast path of the k-loops)
-// The caller compares both with A @ B on asymmetric data — tests/test_gpu_parity.py.
-extern "C" ngp_status ngp_selftest_mfma_layout(ngp_ctx *c, const double *A, const double *Bm,
-                                               double *D) {
-    if (!c || !A || !Bm || !D) return NGP_ERR_ARG;
-    DevCall call(c);
-    double *da = nullptr, *db = nullptr, *dd = nullptr;
-    call.take(&da, 64).take(&db, 64).take(&dd, 512);
-    call.up(da, A, 64 * 8)
-        .up(db, Bm, 64 * 8)
-        .run([&] { launch_mfma_layout_probe(da, db, dd, c->stream); })
-        .down(D, dd, 512 * 8);
-    return call.sync();
-}
-
-// D (32 x 32, row-major) = A (32 x 2) B (2 x 32) through one v_mfma_f32_32x32x2_f32 with the operand
-// and result maps the mixed-precision k-loop assumes; the caller compares with A @ B.
-extern "C" ngp_status ngp_selftest_mfma_f32_layout(ngp_ctx *c, const float *A, const float *Bm,
-                                                   float *D) {
-    if (!c || !A || !Bm || !D) return NGP_ERR_ARG;
-    DevCall call(c);
-    float *da = nullptr, *db = nullptr, *dd = nullptr;
-    call.take(&da, 64).take(&db, 64).take(&dd, 1024);
-    call.up(da, A, 64 * 4)
-        .up(db, Bm, 64 * 4)
-        .run([&] { launch_mfma_f32_probe(da, db, dd, c->stream); })
-        .down(D, dd, 1024 * 4);
-    return call.sync();
-}
+#include "ngp_host_mixture.h"
+#include "ngp_host_combine.h"
+#include "ngp_host_comm.h"
+#include "ngp_host_bench.h"

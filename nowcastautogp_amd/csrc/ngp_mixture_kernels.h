@@ -2,7 +2,7 @@
 // (ngp_mixture_cdf / ngp_mixture_quantiles / ngp_mixture_crps, include/ngp.h).
 //
 // The host stages a mixture DATE-MAJOR with its zero-weight components dropped: w [C], and per date
-// j the rows mu [j][C], var [j][C] (ngp_api.hip mixture_stage).  Everything here works on one date
+// j the rows mu [j][C], var [j][C] (ngp_host_mixture.h mixture_stage).  Everything here works on one date
 // at a time and never looks at m, so a date's bits do not depend on which other dates travel with
 // it.  All of it is fp64 VALU work bound by erf / exp / sqrt, not by memory: a date is 24 C bytes.
 //
