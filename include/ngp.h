@@ -875,6 +875,43 @@ ngp_status ngp_factor_sample_long(ngp_factor *f, int32_t d, const double *t_add,
                                   double *out, int32_t *comp, double *mu, double *var,
                                   int32_t *info, int32_t *chol_info);
 
+/* ---- the decomposition over a long horizon ------------------------------------------
+ * ngp_factor_components_nowcast carries its C_p m component rows as aux rows, so (n mod 64) + d +
+ * 1 + C_p m <= NGP_MAX_AUX: 42 dates per call at C_p = 3 with a tail of 63.
+ * ngp_factor_components_long is the same decomposition (the same formulas, no noise term
+ * anywhere) in the panel form of ngp_factor_predict_long: the panel of the ONE triangular solve
+ * against the resident L holds, per particle, C_max groups of date rows, group c filled under the
+ * particle's c-th component program.  A daily grid over a year is one query.
+ *   d, t_add, D, y_add    as ngp_factor_predict_long; with d = 0, D, t_add and y_add are ignored;
+ *                         S = d > 0 ? D : 1 scenarios
+ *   comp_count, comps     as ngp_factor_components (not checked to sum to the kernel; a
+ *                         component's `noise` is ignored)
+ *   mu    [sum C_p][S][m] the layout of ngp_factor_components_nowcast
+ *   cross per particle [C_p][C_p][m], packed back to back; always written.  cross[c][c'][j] =
+ *         Sigma_c,c'[j, j], the covariance of parts c and c' at the SAME date: its c = c' planes are
+ *         the variances, and the variance of any sum of parts at a date is the sum of its entries —
+ *         C^2 m numbers where sigma has (C m)^2.  Exactly symmetric in (c, c').
+ *   sigma per particle [C_p m][C_p m] (row = c m + j), packed back to back; may be NULL: no
+ *         (C m)^2 object is then formed, on the device or on the bus; mu and cross have the same
+ *         bits either way.  cross is its same-date diagonal bit for bit.  Exactly symmetric.
+ *   info  [P] as ngp_factor_predict_long; may be NULL.  An item with info > 0 is NaN in all its
+ *         outputs; other items are not affected.
+ * Limits (NGP_ERR_TOO_LARGE, before anything touches a device): m <= NGP_MAX_LONG_HORIZON,
+ * (n mod 64) + d + 1 <= NGP_MAX_AUX, and with sigma max_p C_p m <= NGP_MAX_LONG_HORIZON (also
+ * C_p <= 65,534); then what the device memory holds for ONE particle — the particles are worked
+ * through in chunks sized to the memory, a large P is never refused.
+ * NGP_ERR_ARG: null f, comp_count, comps, t_new, mu or cross; m < 1; C_p < 1; d < 0; d > 0 with
+ * D < 1 or null t_add / y_add.  NGP_ERR_PROGRAM: a malformed component.  All before device work.
+ * Runs under the factor's spec and the context's lock; not combined with concurrent callers.
+ * Bitwise reproducible from call to call (fixed summation orders, no floating-point atomics); a
+ * particle's outputs depend neither on the other particles of the call nor on how the memory
+ * chunks them.  Profile classes: those of ngp_factor_predict_long (fill and small blocks 4, solve
+ * 6, products of rows 2, conditioning block and per-date algebra 3).                           */
+ngp_status ngp_factor_components_long(ngp_factor *f, int32_t d, const double *t_add, int32_t D,
+                                      const double *y_add, const int32_t *comp_count,
+                                      const ngp_kernel *comps, int32_t m, const double *t_new,
+                                      double *mu, double *cross, double *sigma, int32_t *info);
+
 /* ---- measurement hooks -----------------------------------------------------
  * HIP-event timing of the kernels a job launches, on the stream they are
  * launched on.  Classes: 0 = chol_col_glds_kernel (fat steps: trailing-update

@@ -491,6 +491,45 @@ function components_nowcast(f::Factor, comps::Vector{Vector{Program}}, t_add::Ve
             logml_full = lf, info = info)
 end
 
+"""
+`components_nowcast` over a horizon of up to `NGP_MAX_LONG_HORIZON` dates in ONE query (include/ngp.h
+`ngp_factor_components_long`): the component rows are groups of the panel of `predict_long`'s solve,
+not aux rows.  `t_add` / `y_add` as `predict_long` (empty: no appended points).  Returns per particle
+`mu` (m x S x C_p), `cross` (m x C_p x C_p: the covariance of two parts at the same date, its c = c'
+planes the variances) and, with `want_sigma`, `sigma` (C_p m x C_p m); without it nothing of that size
+is formed and `sigma` is `nothing`.
+"""
+function components_long(f::Factor, comps::Vector{Vector{Program}}, t_new::Vector{Float64};
+                         t_add::Vector{Float64} = Float64[],
+                         y_add::Matrix{Float64} = Matrix{Float64}(undef, 0, 1),
+                         want_sigma::Bool = false)
+    length(comps) == f.P || throw(ArgumentError("one vector of component programs per particle"))
+    d, D, m = length(t_add), max(size(y_add, 2), 1), length(t_new)
+    counts = Int32[length(c) for c in comps]
+    flat = reduce(vcat, comps)
+    mu = Array{Float64}(undef, m, D, length(flat))
+    csz = [Int(c)^2 * m for c in counts]
+    sizes = [(Int(c) * m)^2 for c in counts]
+    cr = Vector{Float64}(undef, sum(csz))
+    sg = want_sigma ? Vector{Float64}(undef, sum(sizes)) : nothing
+    info = zeros(Int32, f.P)
+    GC.@preserve flat begin
+        ks = kernels(flat)
+        check(ccall((:ngp_factor_components_long, LIBNGP), Int32,
+                    (Ptr{Cvoid}, Int32, Ptr{Float64}, Int32, Ptr{Float64}, Ptr{Int32}, Ptr{NgpKernel}, Int32,
+                     Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}),
+                    f.h, d, t_add, D, y_add, counts, ks, m, t_new, mu, cr,
+                    want_sigma ? pointer(sg) : Ptr{Float64}(C_NULL), info),
+              "ngp_factor_components_long")
+    end
+    first = cumsum(vcat(0, Int.(counts))); coff = cumsum(vcat(0, csz)); soff = cumsum(vcat(0, sizes))
+    return (mu = [mu[:, :, first[p]+1:first[p+1]] for p in 1:f.P],
+            cross = [reshape(cr[coff[p]+1:coff[p+1]], m, Int(counts[p]), Int(counts[p])) for p in 1:f.P],
+            sigma = want_sigma ? [reshape(sg[soff[p]+1:soff[p+1]], Int(counts[p]) * m, Int(counts[p]) * m)
+                                  for p in 1:f.P] : nothing,
+            info = info)
+end
+
 "Draws from S mixtures over the same components on the device (include/ngp.h `ngp_mixture_sample`)."
 function mixture_sample(c::Context, w::Matrix{Float64},        # P x S  (column = scenario)
                         mu::Array{Float64,3},                   # m x S x P

@@ -46,6 +46,7 @@ SYMBOLS = (
     "ngp_ensemble_scores", "ngp_mixture_path_scores",
     "ngp_factor_predict_long",
     "ngp_factor_sample_long",
+    "ngp_factor_components_long",
 )
 
 
@@ -135,6 +136,8 @@ def load():
         "ngp_kernel_terms": (i32, [KP, i32, i32, i32p, i32p, i32p, i32p, i32p, i32p, i32, f64p, i32]),
         "ngp_factor_components_nowcast": (i32, [vp, i32, f64p, i32, f64p, i32p, KP, i32, f64p, f64p,
                                                 f64p, f64p, f64p, i32p]),
+        "ngp_factor_components_long": (i32, [vp, i32, f64p, i32, f64p, i32p, KP, i32, f64p, f64p,
+                                             f64p, f64p, i32p]),
         "ngp_mixture_sample": (i32, [vp, i32, i32, i32, f64p, f64p, f64p, i32, C.c_uint64, f64p,
                                      i32p, i32p]),
         "ngp_mixture_cdf": (i32, [vp, i32, i32, f64p, f64p, f64p, i32, f64p, f64p, i32p]),
@@ -611,6 +614,40 @@ class Factor(_Handle):
             self._h, d, p_t, D, p_y, iptr(counts), ka.arr, m, dptr(t_new) if m else None, dptr(lf),
             dptr(mu), _nullable(sg), dptr(var), iptr(info)), "ngp_factor_components_nowcast")
         return dict(**_per_particle(counts, m, mu, var, sg), logml_full=lf, info=info)
+
+    def components_long(self, comps, t_new, t_add=None, y_add=None, want_sigma=False):
+        """The decomposition over a horizon of up to ``NGP_MAX_LONG_HORIZON`` dates in one query
+        (``ngp_factor_components_long``): ``components_nowcast`` in the panel form of
+        ``predict_long``.  Returns a dict of per-particle lists: ``mu`` [C_p, S, m] (S = D with
+        appended points, else 1), ``cross`` [C_p, C_p, m] — the covariance of two parts at the same
+        date; its c = c' planes are the variances —, ``sigma`` [C_p m, C_p m] (None without
+        ``want_sigma``: nothing of that size is then formed) and ``info`` [P]."""
+        if len(comps) != self.P:
+            raise ValueError("one list of component programs per particle")
+        d, D, t_add, y_add, p_t, p_y = _appended(t_add if t_add is not None else np.zeros(0), y_add)
+        t_new = as_f64(t_new)
+        m = t_new.size
+        counts = np.array([len(c) for c in comps], dtype=np.int32)
+        ka = KernelArray([prog for c in comps for prog in c])
+        tot = int(counts.sum())
+        c64 = counts.astype(np.int64)
+        mu = np.empty((tot, D, m))
+        cr = np.empty(int((c64 ** 2).sum()) * m)
+        sg = np.empty(int(((c64 * m) ** 2).sum())) if want_sigma else None
+        info = np.zeros(self.P, dtype=np.int32)
+        _chk(load().ngp_factor_components_long(
+            self._h, d, p_t, D, p_y, iptr(counts), ka.arr, m, dptr(t_new) if m else None, dptr(mu),
+            dptr(cr), _nullable(sg), iptr(info)), "ngp_factor_components_long")
+        first = np.concatenate([[0], np.cumsum(c64)])
+        o_cr = np.concatenate([[0], np.cumsum(c64 ** 2 * m)])
+        o_sg = np.concatenate([[0], np.cumsum((c64 * m) ** 2)])
+        P = self.P
+        return dict(
+            mu=[mu[first[p]:first[p + 1]] for p in range(P)],
+            cross=[cr[o_cr[p]:o_cr[p + 1]].reshape(counts[p], counts[p], m) for p in range(P)],
+            sigma=[sg[o_sg[p]:o_sg[p + 1]].reshape(counts[p] * m, counts[p] * m) for p in range(P)]
+            if want_sigma else None,
+            info=info)
 
     def predict(self, t_new, noise_on_new=True):
         r = self.nowcast(np.zeros(0), np.zeros((1, 0)), t_new, noise_on_new)

@@ -1603,8 +1603,12 @@ class ComponentForecast:
     ORIGINAL scale of y (what ``predict_components`` returns):
 
         means[p]  [C_p, m]          posterior mean of part c
-        sigma[p]  [C_p m, C_p m]    joint covariance of the parts, row = c m + j
+        sigma[p]  [C_p m, C_p m]    joint covariance of the parts, row = c m + j; None when the
+                                    forecast carries ``cross`` alone
         var[p]    [C_p, m]          its diagonal (always there)
+        cross                       None, or per particle [C_p, C_p, m]: the covariance of parts c, c'
+                                    at the SAME date (``ngp_factor_components_long``) — all that
+                                    ``grouped`` reads
         weights   [P]               particle weights
         kinds[p], labels[p]         per part: "trend" / "seasonal" / "other", the printed sub-kernel
         offset                      the constant of the y-transform: it belongs to no part, the
@@ -1616,8 +1620,9 @@ class ComponentForecast:
     The parts are the latent functions; observation noise is a part of its own (the remainder) and
     appears nowhere here."""
 
-    def __init__(self, means, sigma, var, weights, kinds, labels, offset, date_blocks=None, engine=None):
-        self.means, self.sigma, self.var = means, sigma, var
+    def __init__(self, means, sigma, var, weights, kinds, labels, offset, date_blocks=None, engine=None,
+                 cross=None):
+        self.means, self.sigma, self.var, self.cross = means, sigma, var, cross
         self.weights = np.asarray(weights, dtype=np.float64)
         self.kinds, self.labels, self.offset = kinds, labels, float(offset)
         self.date_blocks, self.engine = date_blocks, engine
@@ -1644,7 +1649,10 @@ class ComponentForecast:
                     atom += self.weights[p]
                     continue
                 C, m = self.means[p].shape
-                blocks = np.einsum("ajbj->abj", self.sigma[p].reshape(C, m, C, m))   # same-date entries
+                if self.cross is not None:
+                    blocks = self.cross[p]
+                else:
+                    blocks = np.einsum("ajbj->abj", self.sigma[p].reshape(C, m, C, m))   # same-date entries
                 mus.append(self.means[p][idx].sum(axis=0))
                 vs.append(blocks[np.ix_(idx, idx)].sum(axis=(0, 1)))
                 ws.append(self.weights[p])
@@ -1672,12 +1680,33 @@ def component_blocks(n_obs: int, c_max: int, m: int, d: int = 0):
     return [(lo, min(lo + per, m)) for lo in range(0, m, per)]
 
 
-def predict_components(model: GPModel, ds, split: str = "plus") -> ComponentForecast:
+def long_component_forecast(model: GPModel, parts, o, weights) -> ComponentForecast:
+    """The ``ComponentForecast`` of one ``components_long`` result ``o`` on the original scale:
+    ``means[p]`` is [C_p, S, m] as the query returns it, ``var`` the c = c' planes of ``cross``,
+    ``sigma`` None unless the query formed it."""
+    _raise_if_failed(o["info"])
+    inv = 1.0 / model.y_transform.slope           # y = (y_model - intercept) / slope
+    cross = [a * (inv * inv) for a in o["cross"]]
+    var = [np.ascontiguousarray(np.einsum("ccj->cj", a)) for a in cross]
+    sigma = [a * (inv * inv) for a in o["sigma"]] if o["sigma"] is not None else [None] * len(parts)
+    return ComponentForecast([a * inv for a in o["mu"]], sigma, var, weights,
+                             [[c.kind for c in ps] for ps in parts], [[c.label for c in ps] for ps in parts],
+                             -model.y_transform.intercept * inv, None, engine=model._eng(), cross=cross)
+
+
+def predict_components(model: GPModel, ds, split: str = "plus", one_query: bool = False,
+                       want_sigma: bool = False) -> ComponentForecast:
     """The additive decomposition of the model's forecast on the dates ``ds``: ONE query of the
     model's resident factor (``ngp_factor_components``) per block of dates — no refit on a
     sub-kernel, which would not be conditioned on the same K.  Needs an engine with resident
     factors (there is no host path).  In a sharded run every rank gets its own particles' parts,
-    with their globally normalised weights.  ``split``: as ``decompose``."""
+    with their globally normalised weights.  ``split``: as ``decompose``.
+
+    ``one_query=True`` (with a factor that has ``components_long``): ONE call whatever the horizon
+    (``ngp_factor_components_long``); ``date_blocks`` is None, the forecast carries ``cross``,
+    ``var`` is its diagonal planes and ``sigma`` is the full joint covariance with ``want_sigma``,
+    else None per particle.  ``want_sigma`` has no effect on the default path, which always returns
+    its block-diagonal ``sigma``."""
     fac = model._factor()
     if fac is None or not hasattr(fac, "components"):
         raise RuntimeError("predict_components needs the engine's resident factor (ngp_factor_components)")
@@ -1686,6 +1715,12 @@ def predict_components(model: GPModel, ds, split: str = "plus") -> ComponentFore
     t, _ = model._obs()
     t_new = model.ds_transform.apply(to_days(list(ds)))
     m = t_new.size
+    if one_query and hasattr(fac, "components_long"):
+        w, _ = distributed.normalize_log_weights(model.log_weights[:, None],
+                                                 P_total=model.n_particles_total)
+        o = fac.components_long(comps, t_new, want_sigma=want_sigma)
+        o = dict(o, mu=[a[:, 0, :] for a in o["mu"]])
+        return long_component_forecast(model, parts, o, w[:, 0])
     blocks = component_blocks(t.size, max(len(ps) for ps in parts), m)
     P = len(parts)
     means = [np.empty((len(ps), m)) for ps in parts]

@@ -1938,17 +1938,12 @@ static void long_take(DevCall &call, const ngp_factor *f, LongStage &st, size_t 
     (void)f;
 }
 
-// items [b0, b0 + bc): the panel, its solve, the products, the conditioning block, means,
-// variances and (want_sigma) sigma, left in st.p
-static void long_launch(DevCall &call, ngp_factor *f, LongStage &st, size_t b0, size_t bc) {
+// the chunk's size and where its items' inputs and their part of the resident factor are
+static void long_bind(const ngp_factor *f, LongStage &st, size_t b0, size_t bc) {
     LongGeom &g = st.g;
     LongPtrs &p = st.p;
     unsigned char *d_in = st.d_in;
     const int n0 = g.n0, D = g.D, cc = st.cc;
-    const size_t cw = st.cw, mm = g.want_sigma ? (size_t)g.m * g.m : 0;
-    const DevSpec sp = dev_spec(f->spec);
-    hipStream_t s = f->ctx->stream;
-    EventTimer &tm = call.tm;
     g.B = (int32_t)bc;
     p.progs = reinterpret_cast<const DevProgram *>(d_in) + b0;
     p.L = f->L ? f->L + b0 * (size_t)f->item_stride : nullptr;
@@ -1958,15 +1953,34 @@ static void long_launch(DevCall &call, ngp_factor *f, LongStage &st, size_t b0, 
     p.tp = reinterpret_cast<const double *>(d_in + st.o_tp);
     p.y0 = reinterpret_cast<const double *>(d_in + st.o_y0) + (g.y_shared ? 0 : b0 * (size_t)n0);
     p.yc = reinterpret_cast<const double *>(d_in + st.o_yc) + (g.y_shared ? 0 : b0 * (size_t)D * cc);
-    const double dB = (double)bc, dq = (double)g.q1, dn = (double)n0;
+}
+
+// n0^2 q flops per item; L once per workgroup tile, the panel once in and once out, and —
+// left-looking — block column j of the solved panel read back by every later step
+static void long_solve(DevCall &call, const LongStage &st, const DevSpec &sp, hipStream_t s) {
+    const LongGeom &g = st.g;
+    const double dB = (double)g.B, dq = (double)g.q1, dn = (double)g.n0;
     const double wg_tiles = (double)((g.qpad + LONG_WG_TILE - 1) / LONG_WG_TILE);
+    call.timed(call.tm, 6, dB * dn * dn * dq,
+               8.0 * dB * (wg_tiles * dn * dn / 2 + 2.0 * g.qpad * dn + g.qpad * dn * (g.nb0 - 1) / 2.0),
+               [&] { launch_long(LONG_SOLVE, g, st.p, sp, s); });
+}
+
+// items [b0, b0 + bc): the panel, its solve, the products, the conditioning block, means,
+// variances and (want_sigma) sigma, left in st.p
+static void long_launch(DevCall &call, ngp_factor *f, LongStage &st, size_t b0, size_t bc) {
+    long_bind(f, st, b0, bc);
+    const LongGeom &g = st.g;
+    const LongPtrs &p = st.p;
+    const int n0 = g.n0;
+    const size_t cw = st.cw, mm = g.want_sigma ? (size_t)g.m * g.m : 0;
+    const DevSpec sp = dev_spec(f->spec);
+    hipStream_t s = f->ctx->stream;
+    EventTimer &tm = call.tm;
+    const double dB = (double)bc, dq = (double)g.q1, dn = (double)n0;
     call.timed(tm, 4, 0.0, 8.0 * dB * g.qpad * dn, [&] { launch_long(LONG_FILL, g, p, sp, s); });
     call.timed(tm, 4, 0.0, 8.0 * dB * (dq * (double)cw + (double)mm), [&] { launch_long(LONG_SMALL, g, p, sp, s); });
-    // n0^2 q flops per item; L once per workgroup tile, the panel once in and once out, and —
-    // left-looking — block column j of the solved panel read back by every later step
-    call.timed(tm, 6, dB * dn * dn * dq,
-               8.0 * dB * (wg_tiles * dn * dn / 2 + 2.0 * g.qpad * dn + g.qpad * dn * (g.nb0 - 1) / 2.0),
-               [&] { launch_long(LONG_SOLVE, g, p, sp, s); });
+    long_solve(call, st, sp, s);
     call.timed(tm, 2, 0.0, 0.0, [&] { launch_long(LONG_GRAM, g, p, sp, s); });
     call.timed(tm, 3, 0.0, 0.0, [&] {
         launch_long(LONG_COND, g, p, sp, s);
@@ -2427,6 +2441,105 @@ extern "C" ngp_status ngp_factor_components_nowcast(ngp_factor *f, int32_t d, co
     if (d < 0 || D < 1 || (d > 0 && (!t_add || !y_add))) return NGP_ERR_ARG;
     return components_query(f, d, t_add, D, y_add, comp_count, comps, m, t_new, logml_full, mu, sigma,
                             var, info);
+}
+
+// ---- the decomposition over a long horizon ---------------------------
+// The long query's staging, chunks, solve and conditioning block (long_stage, long_take,
+// long_bind, long_solve); the panel carries cmax groups of date rows, each padded to LONG_TILE, and
+// every panel row has a row of S (ngp_long_component_kernels.h).
+extern "C" ngp_status ngp_factor_components_long(ngp_factor *f, int32_t d, const double *t_add,
+                                                 int32_t D, const double *y_add,
+                                                 const int32_t *comp_count, const ngp_kernel *comps,
+                                                 int32_t m, const double *t_new, double *mu,
+                                                 double *cross, double *sigma, int32_t *info) {
+    if (!comp_count || !comps || !mu || !cross) return NGP_ERR_ARG;
+    LongStage st;
+    if (ngp_status e = long_stage(f, d, t_add, D, y_add, m, t_new, 0, 0, st)) return e;
+    const size_t P = (size_t)f->P;
+    std::vector<int32_t> first(P + 1, 0);
+    std::vector<int64_t> cr_off(P + 1, 0), sig_off(P + 1, 0);
+    int64_t cmax = 0;
+    for (size_t b = 0; b < P; ++b) {
+        const int64_t cb = comp_count[b];
+        if (cb < 1) return NGP_ERR_ARG;
+        if (cb > 65534 || (sigma && cb * m > NGP_MAX_LONG_HORIZON)) return NGP_ERR_TOO_LARGE;
+        if (first[b] + cb > INT32_MAX) return NGP_ERR_TOO_LARGE;
+        first[b + 1] = (int32_t)(first[b] + cb);
+        cr_off[b + 1] = cr_off[b] + cb * cb;
+        sig_off[b + 1] = sig_off[b] + cb * m * cb * m;
+        cmax = std::max(cmax, cb);
+    }
+    const size_t ncomp = (size_t)first[P];
+    std::vector<DevProgram> hp(ncomp);
+    for (size_t i = 0; i < ncomp; ++i)
+        if (ngp_status e = compile_program(&comps[i], &hp[i], nullptr)) return e;
+    LongCompGeom cg{};
+    cg.m = m;
+    cg.mpad = (m + LONG_TILE - 1) / LONG_TILE * LONG_TILE;
+    cg.cmax = (int32_t)cmax;
+    cg.hpad = (1 + st.cc + LONG_TILE - 1) / LONG_TILE * LONG_TILE;
+    if (cg.hpad + cmax * cg.mpad > INT32_MAX / 2) return NGP_ERR_TOO_LARGE;
+    LongGeom &g = st.g;
+    g.q1 = g.qpad = cg.hpad + (int32_t)cmax * cg.mpad;
+    g.want_sigma = sigma ? 1 : 0;
+    const size_t S = (size_t)g.D, um = (size_t)m, uc = (size_t)cmax;
+    st.n_W = (size_t)g.qpad * g.n0, st.n_S = (size_t)g.q1 * st.cw, st.n_mu = uc * S * um;
+    const size_t n_cr = uc * uc * um, n_sig = sigma ? n_cr * um : 0;
+    const size_t item_bytes = 8 * (st.n_W + st.n_S + S * st.cc + st.n_mu + n_cr + n_sig) + 4;
+    const size_t o_first = sizeof(DevProgram) * ncomp, o_cr = (o_first + 4 * first.size() + 7) & ~(size_t)7,
+                 o_sig = o_cr + 8 * cr_off.size(), cin_bytes = o_sig + 8 * sig_off.size();
+    std::vector<unsigned char> h_cin(cin_bytes);
+    std::memcpy(h_cin.data(), hp.data(), o_first);
+    std::memcpy(h_cin.data() + o_first, first.data(), 4 * first.size());
+    std::memcpy(h_cin.data() + o_cr, cr_off.data(), 8 * cr_off.size());
+    std::memcpy(h_cin.data() + o_sig, sig_off.data(), 8 * sig_off.size());
+    const size_t in_bytes = st.in_bytes + cin_bytes;
+    ngp_ctx *c = f->ctx;
+    DevCall call(c);
+    if (call.status()) return call.status();
+    if (P * item_bytes + in_bytes > c->mem_cap) c->refresh_mem_cap();
+    if (item_bytes + in_bytes > c->mem_cap) return NGP_ERR_TOO_LARGE;
+    const size_t Pc = std::min<size_t>(std::min<size_t>(P, MAX_CHUNK_ITEMS),
+                                       std::max<size_t>(1, (c->mem_cap - in_bytes) / item_bytes));
+    LongPtrs &p = st.p;
+    LongCompPtrs cp{};
+    unsigned char *d_cin = nullptr;
+    call.take(&st.d_in, st.in_bytes).take(&d_cin, cin_bytes);
+    if (g.n0 > 0) call.take(&p.W, Pc * st.n_W);
+    call.take(&p.S, Pc * st.n_S).take(&p.z, Pc * S * st.cc + 1).take(&p.info, Pc);
+    call.take(&cp.mu, Pc * st.n_mu).take(&cp.cross, Pc * n_cr);
+    if (sigma) call.take(&cp.sigma, Pc * n_sig);
+    call.up(st.d_in, st.h_in.data(), st.in_bytes).up(d_cin, h_cin.data(), cin_bytes);
+    const DevSpec sp = dev_spec(f->spec);
+    hipStream_t s = c->stream;
+    EventTimer &tm = call.tm;
+    for (size_t b0 = 0; b0 < P && !call.status(); b0 += Pc) {
+        const size_t bc = std::min(Pc, P - b0), b1 = b0 + bc;
+        long_bind(f, st, b0, bc);
+        cp.progs = reinterpret_cast<const DevProgram *>(d_cin) + first[b0];
+        cp.first = reinterpret_cast<const int32_t *>(d_cin + o_first) + b0;
+        cp.cr_off = reinterpret_cast<const int64_t *>(d_cin + o_cr) + b0;
+        cp.sig_off = reinterpret_cast<const int64_t *>(d_cin + o_sig) + b0;
+        const size_t nc = (size_t)(first[b1] - first[b0]), ncr = (size_t)(cr_off[b1] - cr_off[b0]) * um,
+                     nsg = sigma ? (size_t)(sig_off[b1] - sig_off[b0]) : 0;
+        const double dB = (double)bc;
+        call.timed(tm, 4, 0.0, 8.0 * dB * g.qpad * (double)g.n0, [&] { launch_long_comp(LCOMP_FILL, g, p, cg, cp, sp, s); });
+        call.timed(tm, 4, 0.0, 8.0 * (dB * cg.hpad * (double)st.cw + (double)nc * um * (double)st.cw + (double)ncr + (double)nsg / 2),
+                   [&] { launch_long_comp(LCOMP_SMALL, g, p, cg, cp, sp, s); });
+        long_solve(call, st, sp, s);
+        call.timed(tm, 2, 0.0, 0.0, [&] { launch_long_comp(LCOMP_GRAM, g, p, cg, cp, sp, s); });
+        call.timed(tm, 3, 0.0, 0.0, [&] {
+            launch_long(LONG_COND, g, p, sp, s);
+            launch_long_comp(LCOMP_APPLY, g, p, cg, cp, sp, s);
+            launch_long_comp(LCOMP_CROSS, g, p, cg, cp, sp, s);
+            launch_long_comp(LCOMP_SIGMA, g, p, cg, cp, sp, s);
+        });
+        call.down(mu + (size_t)first[b0] * S * um, cp.mu, 8 * nc * S * um);
+        call.down(cross + (size_t)cr_off[b0] * um, cp.cross, 8 * ncr);
+        if (sigma) call.down(sigma + sig_off[b0], cp.sigma, 8 * nsg);
+        if (info) call.down(info + b0, p.info, 4 * bc);
+    }
+    return call.sync();
 }
 
 extern "C" void ngp_factor_destroy(ngp_factor *f) {

@@ -224,6 +224,35 @@ struct LongPtrs {
 enum { LONG_FILL = 0, LONG_SMALL, LONG_SOLVE, LONG_GRAM, LONG_COND, LONG_APPLY, LONG_SIGMA };
 void launch_long(int step, const LongGeom &g, const LongPtrs &p, const DevSpec &sp, hipStream_t s);
 
+// ngp_factor_components_long (ngp_long_component_kernels.h): the long query's panel with the m date
+// rows replaced by cmax groups of date rows, group c of an item filled under its c-th component
+// program.  The LongGeom of the call has q1 = qpad = hpad + cmax mpad (every panel row is a row of S
+// too), LongPtrs::tp holds the conditioning points and the m dates once, dg / mu / var / sigma of
+// LongPtrs stay null.
+struct LongCompGeom {
+    int32_t m, mpad;       // dates per component; m rounded up to LONG_TILE: the rows of a group
+    int32_t cmax;          // groups of the panel: the call's largest C_p
+    int32_t hpad;          // y' and the c conditioning rows, rounded up to LONG_TILE: group c starts
+                           // at row hpad + c mpad, so date i of every group sits at the same place of
+                           // its 64-row tile
+};
+struct LongCompPtrs {
+    const DevProgram *progs;   // the component programs of the chunk's first item onward
+    // running sums over the particles of the CALL, entry 0 = the chunk's first item: an item's place
+    // in the chunk's outputs is its entry minus entry 0
+    const int32_t *first;      // [B + 1] C_b
+    const int64_t *cr_off;     // [B + 1] C_b^2
+    const int64_t *sig_off;    // [B + 1] (C_b m)^2
+    double *mu;                // [sum C_b][D][m]
+    double *cross;             // per item [C_b][C_b][m]
+    double *sigma;             // per item [C_b m][C_b m], or null
+};
+// step: 0 fill, 1 small blocks, 2 products of the rows, 3 means, 4 cross, 5 sigma; the solve and the
+// conditioning block are launch_long's
+enum { LCOMP_FILL = 0, LCOMP_SMALL, LCOMP_GRAM, LCOMP_APPLY, LCOMP_CROSS, LCOMP_SIGMA };
+void launch_long_comp(int step, const LongGeom &g, const LongPtrs &p, const LongCompGeom &cg,
+                      const LongCompPtrs &cp, const DevSpec &sp, hipStream_t s);
+
 // ngp_factor_sample_long (ngp_long_sample_kernels.h): paths of a long horizon from the sigma the
 // long query leaves on the device.  sigma is stored [mpad x mpad] per item (mpad: m rounded up to
 // NB, the padding a unit diagonal), factorised in place 64 columns at a time, and the paths of a

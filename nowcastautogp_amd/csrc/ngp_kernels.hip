@@ -18,6 +18,7 @@
 //                         ngp_component_kernels.h: fill and epilogue of ngp_factor_components;
 //                         ngp_long_kernels.h: ngp_factor_predict_long (the dates as a solve's panel);
 //                         ngp_long_sample_kernels.h: ngp_factor_sample_long (paths from its sigma);
+//                         ngp_long_component_kernels.h: ngp_factor_components_long (component rows in its panel);
 //                         ngp_path_kernels.h: functionals of whole sample paths
 //   this file             aux_update / aux_back_* / refine_gram_* (resident factor, Gram refinement),
 //                         diag_ahead, gram, epilogue, mixture sampling, the probe and stream kernels,
@@ -53,6 +54,7 @@
 #include "ngp_tree_kernels.h"
 #include "ngp_component_kernels.h"
 #include "ngp_long_kernels.h"
+#include "ngp_long_component_kernels.h"
 #include "ngp_grad_kernels.h"
 #include "ngp_hmc_kernels.h"
 
@@ -1163,6 +1165,45 @@ void launch_long(int step, const LongGeom &g, const LongPtrs &p, const DevSpec &
     case LONG_SIGMA:
         if (!g.want_sigma) return;
         hipLaunchKernelGGL(long_sigma_kernel, dim3(blocks((long)g.m * g.m), g.B), dim3(256), 0, s, g, p, sp);
+        return;
+    }
+}
+
+void launch_long_comp(int step, const LongGeom &g, const LongPtrs &p, const LongCompGeom &cg,
+                      const LongCompPtrs &cp, const DevSpec &sp, hipStream_t s) {
+    auto blocks = [](long total) { return (int)std::max<long>(1, std::min<long>(4096, (total + 255) / 256)); };
+    const int nt = g.qpad / NB, ht = cg.hpad / NB, mt = cg.mpad / NB, groups = 1 + cg.cmax;
+    const int gpairs = cg.cmax * (cg.cmax + 1) / 2;
+    const long wid = (long)cg.cmax * cg.m;
+    switch (step) {
+    case LCOMP_FILL:
+        if (g.n0 == 0) return;
+        hipLaunchKernelGGL(lcomp_fill_kernel, dim3(blocks((long)std::max(cg.hpad, cg.mpad) * g.n0), g.B, groups),
+                           dim3(256), 0, s, g, p, cg, cp, sp);
+        return;
+    case LCOMP_SMALL:
+        hipLaunchKernelGGL(lcomp_small_kernel,
+                           dim3(blocks(std::max<long>((long)cg.hpad * (g.c + 1),
+                                                      (long)cg.m * (g.c + 2 + cg.cmax + (g.want_sigma ? wid : 0)))),
+                                g.B, groups),
+                           dim3(256), 0, s, g, p, cg, cp, sp);
+        return;
+    case LCOMP_GRAM: {
+        if (g.n0 == 0) return;
+        const int npairs = g.want_sigma ? nt * (nt + 1) / 2 : ht * nt + gpairs * mt;
+        hipLaunchKernelGGL(lcomp_gram_kernel, dim3((npairs + 3) / 4, g.B), dim3(256), 0, s, g, p, cg, cp, npairs);
+        return;
+    }
+    case LCOMP_APPLY:
+        hipLaunchKernelGGL(lcomp_apply_kernel, dim3((cg.m + 63) / 64, g.B, cg.cmax), dim3(64), 0, s, g, p, cg, cp);
+        return;
+    case LCOMP_CROSS:
+        hipLaunchKernelGGL(lcomp_cross_kernel, dim3((cg.m + 63) / 64, g.B, std::min(gpairs, 65535)), dim3(64), 0, s,
+                           g, p, cg, cp);
+        return;
+    case LCOMP_SIGMA:
+        if (!g.want_sigma) return;
+        hipLaunchKernelGGL(lcomp_sigma_kernel, dim3(blocks(wid * wid), g.B), dim3(256), 0, s, g, p, cg, cp);
         return;
     }
 }

@@ -672,9 +672,15 @@ def forecast_mixture_with_nowcasts(base_model: GPModel, nowcasts: Sequence[TData
         (sc.w / D).reshape(D * P), engine=base_model._eng())
 
 
+# the most terms a particle is split into for ``forecast_components_with_nowcasts(one_query=True)``:
+# the long query holds C^2 m numbers per particle, not C m rows beside the factor
+LONG_COMPONENT_TERMS = 256
+
+
 def forecast_components_with_nowcasts(base_model: GPModel, nowcasts: Sequence[TData], forecast_dates, *,
-                                      split: str = "changepoint",
-                                      ess_threshold: float = 0.0) -> "autogp.ComponentForecast":
+                                      split: str = "changepoint", ess_threshold: float = 0.0,
+                                      one_query: bool = False,
+                                      want_sigma: bool = False) -> "autogp.ComponentForecast":
     """Which part of the nowcast-conditioned forecast is trend, which is season: the additive
     decomposition (``autogp.predict_components``) of the mixture ``forecast_mixture_with_nowcasts``
     returns on its default path.  The parts come from ONE query of the resident factor per block
@@ -694,7 +700,13 @@ def forecast_components_with_nowcasts(base_model: GPModel, nowcasts: Sequence[TD
     The entries of the returned ``ComponentForecast`` are the pairs (s, p), scenario-major, with
     weight w[s][p] / D; ``sigma`` / ``var`` of (s, p) are the same array objects as particle p's
     (the scenarios of a particle share its covariance).  Original scale of y; ``split`` as
-    ``autogp.decompose``."""
+    ``autogp.decompose``.
+
+    ``one_query=True`` (with a factor that has ``components_long``): the parts come from ONE call
+    whatever the horizon (``ngp_factor_components_long``), as in ``autogp.predict_components``:
+    ``date_blocks`` is None, the forecast carries ``cross``, ``sigma`` is full with ``want_sigma``,
+    else None.  The terms of a particle are then capped at ``LONG_COMPONENT_TERMS``, not at the
+    rows left beside the factor."""
     sc = _Scenarios(base_model, nowcasts, forecast_dates, ess_threshold=ess_threshold)
     if not sc.same_dates:
         raise ValueError("forecast_components_with_nowcasts: the scenarios must share their dates")
@@ -709,7 +721,9 @@ def forecast_components_with_nowcasts(base_model: GPModel, nowcasts: Sequence[TD
     t_add = model.ds_transform.apply(autogp.to_days(list(nowcasts[0].ds)))
     # the appended points take rows beside the factor too: a particle whose terms fit without them
     # but not with them goes to the weaker split
-    parts = autogp.decompose(model, split, max_terms=_abi.NGP_MAX_AUX - t.size % 64 - t_add.size - 2)
+    long_query = one_query and hasattr(fac, "components_long")
+    parts = autogp.decompose(model, split, max_terms=LONG_COMPONENT_TERMS if long_query else
+                             _abi.NGP_MAX_AUX - t.size % 64 - t_add.size - 2)
     comps = [[gp.to_program(c.tree) + (0.0,) for c in ps] for ps in parts]
     y_add = np.stack([model.y_transform.apply(np.asarray(nc.y, dtype=np.float64)) for nc in nowcasts])
     t_new = model.ds_transform.apply(autogp.to_days(sc.dates))
@@ -718,6 +732,15 @@ def forecast_components_with_nowcasts(base_model: GPModel, nowcasts: Sequence[TD
     # evidences are the bits of the very query the default path makes (they move in the last place
     # with the number of forecast rows beside the factor)
     sc.run()
+    if long_query:
+        o = fac.components_long(comps, t_new, t_add, y_add, want_sigma=want_sigma)
+        sc.resample_without_draws()
+        one = autogp.long_component_forecast(model, parts, o, np.ones(P))
+        return autogp.ComponentForecast(
+            [np.ascontiguousarray(one.means[p][:, s, :]) for s in range(D) for p in range(P)],
+            [one.sigma[p] for _ in range(D) for p in range(P)], [one.var[p] for _ in range(D) for p in range(P)],
+            (sc.w / D).reshape(D * P), one.kinds * D, one.labels * D, one.offset, None,
+            engine=model._eng(), cross=[one.cross[p] for _ in range(D) for p in range(P)])
     blocks = autogp.component_blocks(t.size, max(len(ps) for ps in parts), m, t_add.size)
     means = [np.empty((len(ps), D, m)) for ps in parts]
     var = [np.empty((len(ps), m)) for ps in parts]
