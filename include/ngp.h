@@ -912,6 +912,37 @@ ngp_status ngp_factor_components_long(ngp_factor *f, int32_t d, const double *t_
                                       const ngp_kernel *comps, int32_t m, const double *t_new,
                                       double *mu, double *cross, double *sigma, int32_t *info);
 
+/* ---- hindcasts: the forecasts of one resident factor at many forecast origins ---------
+ * What would this fitted model have forecast knowing only the first c observations?  The leading
+ * c x c block of the resident Cholesky factor is the factor of the first c observations, so after
+ * the ONE triangular solve of ngp_factor_predict_long every prefix of a date's solved panel row is
+ * a forecast origin: the means and variances of R origins x m dates are running sums along the
+ * rows (and on through the small conditioning block of the tail), not R factorisations.
+ *   cut   [R]        strictly increasing, 1 <= cut <= n: origin r knows the first cut[r]
+ *                    observations of the factor, in the order it was created with
+ *   t_new [m], noise_on_new   as ngp_factor_predict_long (no appended points: d = 0)
+ *   mu, var [P][R][m]  the predictive of the particle's GP conditioned on those observations alone;
+ *                    the jitter and noise conventions of ngp_factor_predict_long
+ *   logml [P][R]     log p(y_1:cut[r] | particle); may be NULL
+ *   info  [P]        as ngp_factor_predict_long; may be NULL.  An item with info > 0 is NaN in all
+ *                    its outputs; other items are not affected.
+ * To rounding, origin r is ngp_factor_predict_long (d = 0) and ngp_factor_logml of a factor created
+ * on the first cut[r] observations, and cut = n is this factor's own long query and logml (not bit
+ * for bit: the running sums and the products on the matrix cores add in different orders).
+ * Bitwise reproducible from call to call; an origin's outputs do not depend on which other origins
+ * share the call, a particle's neither on the other particles nor on how the memory chunks them
+ * (every sum runs k ascending, no floating-point atomics).
+ * NGP_ERR_ARG: null f, cut, t_new, mu or var; R < 1; m < 1; a cut outside 1..n or not strictly
+ * increasing.  NGP_ERR_TOO_LARGE: R > NGP_MAX_ORIGINS, m > NGP_MAX_LONG_HORIZON, (n mod 64) + 1 >
+ * NGP_MAX_AUX; then what the device memory holds for ONE particle — a large P is never refused.
+ * All before anything touches a device.  Runs under the factor's spec and the context's lock; not
+ * combined with concurrent callers.  Profile classes: those of ngp_factor_predict_long, the passes
+ * over the origins and the evidence under 3.                                                   */
+#define NGP_MAX_ORIGINS 1024
+ngp_status ngp_factor_predict_origins(ngp_factor *f, int32_t R, const int32_t *cut,
+                                      int32_t m, const double *t_new, int32_t noise_on_new,
+                                      double *mu, double *var, double *logml, int32_t *info);
+
 /* ---- measurement hooks -----------------------------------------------------
  * HIP-event timing of the kernels a job launches, on the stream they are
  * launched on.  Classes: 0 = chol_col_glds_kernel (fat steps: trailing-update

@@ -355,6 +355,27 @@ function predict_long(f::Factor, t_new::Vector{Float64};
 end
 
 """
+Hindcasts from the resident factor (include/ngp.h `ngp_factor_predict_origins`): origin r knows the
+first `cuts[r]` observations (strictly increasing, 1 .. n).  One query: the means and variances are
+running sums along the solved panel rows of `predict_long`, no factorisation per origin.  Returns
+`mu`, `var` (m x R x P), `logml` (R x P: log p(y_1:cuts[r])) and `info` (P).
+"""
+function predict_origins(f::Factor, cuts::Vector{Int32}, t_new::Vector{Float64};
+                         noise_on_new::Bool = true)
+    P, R, m = f.P, length(cuts), length(t_new)
+    mu = Array{Float64}(undef, m, R, P)
+    var = Array{Float64}(undef, m, R, P)
+    logml = Matrix{Float64}(undef, R, P)
+    info = zeros(Int32, P)
+    check(ccall((:ngp_factor_predict_origins, LIBNGP), Int32,
+                (Ptr{Cvoid}, Int32, Ptr{Int32}, Int32, Ptr{Float64}, Int32,
+                 Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}),
+                f.h, R, cuts, m, t_new, noise_on_new, mu, var, logml, info),
+          "ngp_factor_predict_origins")
+    return (mu = mu, var = var, logml = logml, info = info)
+end
+
+"""
 Paths of a long horizon drawn on the device (include/ngp.h `ngp_factor_sample_long`): the mixtures
 `w` (P x S, S = number of scenarios, 1 without appended points) over the components `predict_long`
 returns for the same query, under the contract of `mixture_sample`.  sigma never leaves the device.

@@ -15,6 +15,7 @@ NGP_MAX_PARAMS = 96
 NGP_MAX_STACK = 16
 NGP_MAX_AUX = 192
 NGP_MAX_LONG_HORIZON = 4096
+NGP_MAX_ORIGINS = 1024
 NGP_SPLIT_PLUS, NGP_SPLIT_CHANGEPOINT, NGP_SPLIT_TIMES = 0, 1, 2   # ngp_kernel_terms flags, or-ed
 NGP_NUM_KERNEL_CLASSES = 14
 NGP_PREC_F64, NGP_PREC_MIXED = 0, 1

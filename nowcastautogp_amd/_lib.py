@@ -47,6 +47,7 @@ SYMBOLS = (
     "ngp_factor_predict_long",
     "ngp_factor_sample_long",
     "ngp_factor_components_long",
+    "ngp_factor_predict_origins",
 )
 
 
@@ -138,6 +139,7 @@ def load():
                                                 f64p, f64p, f64p, i32p]),
         "ngp_factor_components_long": (i32, [vp, i32, f64p, i32, f64p, i32p, KP, i32, f64p, f64p,
                                              f64p, f64p, i32p]),
+        "ngp_factor_predict_origins": (i32, [vp, i32, i32p, i32, f64p, i32, f64p, f64p, f64p, i32p]),
         "ngp_mixture_sample": (i32, [vp, i32, i32, i32, f64p, f64p, f64p, i32, C.c_uint64, f64p,
                                      i32p, i32p]),
         "ngp_mixture_cdf": (i32, [vp, i32, i32, f64p, f64p, f64p, i32, f64p, f64p, i32p]),
@@ -648,6 +650,24 @@ class Factor(_Handle):
             sigma=[sg[o_sg[p]:o_sg[p + 1]].reshape(counts[p] * m, counts[p] * m) for p in range(P)]
             if want_sigma else None,
             info=info)
+
+    def predict_origins(self, cuts, t_new, noise_on_new=True):
+        """The forecasts of R forecast origins in one query (``ngp_factor_predict_origins``): origin
+        r knows the first ``cuts[r]`` observations (strictly increasing, 1 .. n).  Returns
+        ``(mu [P, R, m], var [P, R, m], logml [P, R], info [P])``: per origin what ``predict_long``
+        and ``logml`` of a factor on that prefix give, to rounding."""
+        cuts = np.ascontiguousarray(cuts, dtype=np.int32).reshape(-1)
+        t_new = as_f64(t_new)
+        R, m = cuts.size, t_new.size
+        mu = np.empty((self.P, R, m))
+        var = np.empty((self.P, R, m))
+        lm = np.empty((self.P, R))
+        info = np.zeros(self.P, dtype=np.int32)
+        _chk(load().ngp_factor_predict_origins(
+            self._h, R, iptr(cuts) if R else None, m, dptr(t_new) if m else None,
+            1 if noise_on_new else 0, dptr(mu), dptr(var), dptr(lm), iptr(info)),
+            "ngp_factor_predict_origins")
+        return mu, var, lm, info
 
     def predict(self, t_new, noise_on_new=True):
         r = self.nowcast(np.zeros(0), np.zeros((1, 0)), t_new, noise_on_new)

@@ -1347,6 +1347,99 @@ def _predict_marginals(model: GPModel, ds, noise_on_new: bool = True) -> "Mixtur
                             w[:, 0], engine=model._eng())
 
 
+def origin_counts(model: GPModel, origins) -> np.ndarray:
+    """Forecast origins as observation counts in the factor's order: an integer is a count, a date
+    means "the data up to and including that date".  Refuses (``ValueError``) observed dates that
+    are not strictly increasing in that order, a count outside 1 .. n and a date before the first
+    observation; a date past the last observation is the whole series."""
+    idx = np.sort(model._perm[:model.n_obs])
+    days = model.days[idx]
+    if days.size < 1 or np.any(np.diff(days) <= 0):
+        raise ValueError("predict_origins: the observed dates must be strictly increasing in the "
+                         "order the model holds them, so that a prefix is what was known at a date")
+    out = []
+    for o in list(origins):
+        if isinstance(o, (int, np.integer)) and not isinstance(o, bool):
+            c = int(o)
+            if not 1 <= c <= days.size:
+                raise ValueError(f"predict_origins: origin {c} is not a count in 1 .. {days.size}")
+        else:
+            c = int(np.searchsorted(days, to_days([o])[0], side="right"))
+            if c < 1:
+                raise ValueError(f"predict_origins: origin {o} lies before the first observation")
+        out.append(c)
+    if not out:
+        raise ValueError("predict_origins: at least one origin")
+    return np.asarray(out, dtype=np.int32)
+
+
+def origin_log_weights(log_weights, logml, logml_n):
+    """log w_p(r) = log w_p + log p(y_1:c_r | p) - log p(y_1:n | p): what the fitted weights would
+    have been at origin r had the particles been the same.  ``logml`` [P, R], ``logml_n`` [P]."""
+    return np.stack([_advance_weights(np.asarray(log_weights, dtype=np.float64), logml[:, r], logml_n)
+                     for r in range(logml.shape[1])], axis=1)
+
+
+def _host_origins(model: GPModel, cuts, t_new, noise_on_new):
+    """one ``engine.predict`` per origin on the prefix (in blocks of dates where one call does not
+    carry them all; only the marginals are kept)"""
+    from ._abi import NGP_MAX_AUX
+    eng, progs = model._eng(), model.programs()
+    t, y = model._obs()
+    P, m = len(progs), t_new.size
+    mu, var = np.empty((P, cuts.size, m)), np.empty((P, cuts.size, m))
+    lm = np.empty((P, cuts.size))
+    for r, c in enumerate(cuts):
+        blk = max(1, NGP_MAX_AUX - (int(c) % 64) - 1)
+        for lo in range(0, m, blk):
+            a, sg, l, info = eng.predict(progs, t[:c], y[:c], t_new[lo:lo + blk], noise_on_new)
+            _raise_if_failed(info)
+            mu[:, r, lo:lo + blk] = a
+            var[:, r, lo:lo + blk] = np.einsum("pjj->pj", sg)
+            lm[:, r] = l
+    return mu, var, lm
+
+
+def predict_origins(model: GPModel, origins, ds, noise_on_new: bool = True, weights: str = "fitted"):
+    """Hindcasts of a fitted model: what would it have forecast for the dates ``ds`` knowing only
+    the data up to each origin (``origin_counts``)?  The particles — structures and parameters —
+    are the fitted ones; only the data they are conditioned on is cut.  Returns
+    ``(marginals, ess)``: a ``MixtureMarginals`` over ``ds`` per origin and the effective sample
+    size per origin.
+
+    ``weights="fitted"`` keeps the model's weights; ``"origin"`` reweights each particle by the
+    evidence of the prefix (``origin_log_weights``).  A model with a resident factor asks ONE device
+    query for all origins (``Factor.predict_origins``: running sums along the solved panel of the
+    long query, no factorisation per origin); any other engine is asked one ``predict`` per origin
+    on the prefix."""
+    if weights not in ("fitted", "origin"):
+        raise ValueError('predict_origins: weights "fitted" or "origin"')
+    cuts = origin_counts(model, origins)
+    n = model.n_obs
+    # the device call wants strictly increasing cuts; the whole series rides along for "origin"
+    uniq, back = np.unique(np.concatenate([cuts, [n]]) if weights == "origin" else cuts,
+                           return_inverse=True)
+    uniq = uniq.astype(np.int32)
+    t_new = model.ds_transform.apply(to_days(list(ds)))
+    fac = None
+    if distributed.world()[1] == 1 and not model.__dict__.get("_one_shot_predict", False):
+        fac = model._factor()
+    if fac is not None and hasattr(fac, "predict_origins"):
+        mu, var, lm, info = fac.predict_origins(uniq, t_new, noise_on_new)
+        _raise_if_failed(info)
+    else:
+        mu, var, lm = _host_origins(model, uniq, t_new, noise_on_new)
+    R = cuts.size
+    logw = np.repeat(np.asarray(model.log_weights, dtype=np.float64)[:, None], R, axis=1)
+    if weights == "origin":
+        logw = origin_log_weights(model.log_weights, lm[:, back[:R]], lm[:, back[R]])
+    w, ess = distributed.normalize_log_weights(logw, P_total=model.n_particles_total)
+    sl_, ic = model.y_transform.slope, model.y_transform.intercept
+    eng = model._eng()
+    return ([MixtureMarginals((mu[:, back[r]] - ic) / sl_, var[:, back[r]] / (sl_ * sl_), w[:, r],
+                              engine=eng) for r in range(R)], np.asarray(ess, dtype=np.float64))
+
+
 def predict_mvn_lockstep(models: Sequence[GPModel], ds, noise_on_new: bool = True) -> List[MixtureMVN]:
     """``predict_mvn`` (reference src/forecasting.jl:46,66) of D models on the same dates: ONE
     engine call of P x D items (a single model goes through its resident factor), and in a

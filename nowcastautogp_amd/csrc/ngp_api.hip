@@ -2542,6 +2542,71 @@ extern "C" ngp_status ngp_factor_components_long(ngp_factor *f, int32_t d, const
     return call.sync();
 }
 
+// ---- hindcasts at many forecast origins ------------------------------
+// The long query without appended points (long_stage, long_bind, long_solve, the unchanged fill,
+// small blocks, products and conditioning block); the dates' means and variances are read off the
+// solved panel at every prefix the call asks for (ngp_long_origin_kernels.h).
+extern "C" ngp_status ngp_factor_predict_origins(ngp_factor *f, int32_t R, const int32_t *cut,
+                                                 int32_t m, const double *t_new,
+                                                 int32_t noise_on_new, double *mu, double *var,
+                                                 double *logml, int32_t *info) {
+    if (!f || !cut || !t_new || !mu || !var || R < 1 || m < 1) return NGP_ERR_ARG;
+    if (R > NGP_MAX_ORIGINS) return NGP_ERR_TOO_LARGE;
+    for (int32_t r = 0; r < R; ++r)
+        if (cut[r] < 1 || cut[r] > f->n || (r > 0 && cut[r] <= cut[r - 1])) return NGP_ERR_ARG;
+    LongStage st;
+    int32_t D = 1;
+    if (ngp_status e = long_stage(f, 0, nullptr, D, nullptr, m, t_new, noise_on_new, 0, st)) return e;
+    LongGeom &g = st.g;
+    LongOriginGeom og{};
+    og.R = R;
+    og.R0 = (int32_t)(std::upper_bound(cut, cut + R, g.n0) - cut);
+    const size_t P = (size_t)f->P, uR = (size_t)R, n_out = uR * (size_t)m;
+    st.work_bytes = 8 * (st.n_W + st.n_S + (size_t)g.q1 + (size_t)st.cc + 2 * n_out + uR) + 4;
+    const size_t item_bytes = st.work_bytes, cut_bytes = 4 * uR, in_bytes = st.in_bytes + cut_bytes;
+    ngp_ctx *c = f->ctx;
+    DevCall call(c);
+    if (call.status()) return call.status();
+    if (P * item_bytes + in_bytes > c->mem_cap) c->refresh_mem_cap();
+    if (item_bytes + in_bytes > c->mem_cap) return NGP_ERR_TOO_LARGE;
+    const size_t Pc = std::min<size_t>(std::min<size_t>(P, MAX_CHUNK_ITEMS),
+                                       std::max<size_t>(1, (c->mem_cap - in_bytes) / item_bytes));
+    LongPtrs &p = st.p;
+    LongOriginPtrs op{};
+    int32_t *d_cut = nullptr;
+    call.take(&st.d_in, st.in_bytes).take(&d_cut, uR);
+    if (g.n0 > 0) call.take(&p.W, Pc * st.n_W);
+    call.take(&p.S, Pc * st.n_S).take(&p.dg, Pc * (size_t)g.q1).take(&p.z, Pc * (size_t)st.cc + 1).take(&p.info, Pc);
+    call.take(&op.mu, Pc * n_out).take(&op.var, Pc * n_out);
+    if (logml) call.take(&op.logml, Pc * uR);
+    call.up(st.d_in, st.h_in.data(), st.in_bytes).up(d_cut, cut, cut_bytes);
+    op.cut = d_cut;
+    const DevSpec sp = dev_spec(f->spec);
+    hipStream_t s = c->stream;
+    EventTimer &tm = call.tm;
+    for (size_t b0 = 0; b0 < P && !call.status(); b0 += Pc) {
+        const size_t bc = std::min(Pc, P - b0);
+        long_bind(f, st, b0, bc);
+        const double dB = (double)bc, dq = (double)g.q1, dn = (double)g.n0;
+        call.timed(tm, 4, 0.0, 8.0 * dB * g.qpad * dn, [&] { launch_long(LONG_FILL, g, p, sp, s); });
+        call.timed(tm, 4, 0.0, 8.0 * dB * dq * (double)st.cw, [&] { launch_long(LONG_SMALL, g, p, sp, s); });
+        long_solve(call, st, sp, s);
+        // one read of the solved date rows, two stores per origin inside the main block and date
+        call.timed(tm, 3, 2.0 * dB * (double)m * dn, 8.0 * dB * ((double)g.qpad * dn + 2.0 * og.R0 * (double)m),
+                   [&] { launch_long_origin(LORG_MAIN, g, p, og, op, sp, s); });
+        call.timed(tm, 2, 0.0, 0.0, [&] { launch_long(LONG_GRAM, g, p, sp, s); });
+        call.timed(tm, 3, 0.0, 0.0, [&] {
+            launch_long(LONG_COND, g, p, sp, s);
+            launch_long_origin(LORG_TAIL, g, p, og, op, sp, s);
+            launch_long_origin(LORG_LOGML, g, p, og, op, sp, s);
+        });
+        call.down(mu + b0 * n_out, op.mu, 8 * bc * n_out).down(var + b0 * n_out, op.var, 8 * bc * n_out);
+        if (logml) call.down(logml + b0 * uR, op.logml, 8 * bc * uR);
+        if (info) call.down(info + b0, p.info, 4 * bc);
+    }
+    return call.sync();
+}
+
 extern "C" void ngp_factor_destroy(ngp_factor *f) {
     if (!f) return;
     {

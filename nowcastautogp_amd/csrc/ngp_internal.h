@@ -253,6 +253,23 @@ enum { LCOMP_FILL = 0, LCOMP_SMALL, LCOMP_GRAM, LCOMP_APPLY, LCOMP_CROSS, LCOMP_
 void launch_long_comp(int step, const LongGeom &g, const LongPtrs &p, const LongCompGeom &cg,
                       const LongCompPtrs &cp, const DevSpec &sp, hipStream_t s);
 
+// ngp_factor_predict_origins (ngp_long_origin_kernels.h): the long query without appended points,
+// read at R prefixes of the observations.  LongPtrs::mu / var / sigma stay null.
+struct LongOriginGeom {
+    int32_t R;             // origins
+    int32_t R0;            // of them inside the main block (cut <= n0): the cuts are sorted
+};
+struct LongOriginPtrs {
+    const int32_t *cut;    // [R] strictly increasing, 1 .. n
+    double *mu, *var;      // [B][R][m]
+    double *logml;         // [B][R], or null
+};
+// step: 0 origins inside the main block (between the solve and the products of the rows), 1 origins
+// in the conditioning block, 2 evidence (both behind the conditioning block)
+enum { LORG_MAIN = 0, LORG_TAIL, LORG_LOGML };
+void launch_long_origin(int step, const LongGeom &g, const LongPtrs &p, const LongOriginGeom &og,
+                        const LongOriginPtrs &op, const DevSpec &sp, hipStream_t s);
+
 // ngp_factor_sample_long (ngp_long_sample_kernels.h): paths of a long horizon from the sigma the
 // long query leaves on the device.  sigma is stored [mpad x mpad] per item (mpad: m rounded up to
 // NB, the padding a unit diagonal), factorised in place 64 columns at a time, and the paths of a

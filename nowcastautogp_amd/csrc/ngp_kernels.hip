@@ -19,6 +19,7 @@
 //                         ngp_long_kernels.h: ngp_factor_predict_long (the dates as a solve's panel);
 //                         ngp_long_sample_kernels.h: ngp_factor_sample_long (paths from its sigma);
 //                         ngp_long_component_kernels.h: ngp_factor_components_long (component rows in its panel);
+//                         ngp_long_origin_kernels.h: ngp_factor_predict_origins (prefixes of its solved rows);
 //                         ngp_path_kernels.h: functionals of whole sample paths
 //   this file             aux_update / aux_back_* / refine_gram_* (resident factor, Gram refinement),
 //                         diag_ahead, gram, epilogue, mixture sampling, the probe and stream kernels,
@@ -55,6 +56,7 @@
 #include "ngp_component_kernels.h"
 #include "ngp_long_kernels.h"
 #include "ngp_long_component_kernels.h"
+#include "ngp_long_origin_kernels.h"
 #include "ngp_grad_kernels.h"
 #include "ngp_hmc_kernels.h"
 
@@ -1204,6 +1206,23 @@ void launch_long_comp(int step, const LongGeom &g, const LongPtrs &p, const Long
     case LCOMP_SIGMA:
         if (!g.want_sigma) return;
         hipLaunchKernelGGL(lcomp_sigma_kernel, dim3(blocks(wid * wid), g.B), dim3(256), 0, s, g, p, cg, cp);
+        return;
+    }
+}
+
+void launch_long_origin(int step, const LongGeom &g, const LongPtrs &p, const LongOriginGeom &og,
+                        const LongOriginPtrs &op, const DevSpec &sp, hipStream_t s) {
+    switch (step) {
+    case LORG_MAIN:
+        if (g.n0 == 0 || og.R0 == 0) return;
+        hipLaunchKernelGGL(lorg_main_kernel, dim3((g.m + 63) / 64, g.B), dim3(64), 0, s, g, p, og, op, sp);
+        return;
+    case LORG_TAIL:
+        hipLaunchKernelGGL(lorg_tail_kernel, dim3((g.m + 63) / 64, g.B), dim3(64), 0, s, g, p, og, op, sp);
+        return;
+    case LORG_LOGML:
+        if (!op.logml) return;
+        hipLaunchKernelGGL(lorg_logml_kernel, dim3(g.B), dim3(256), 0, s, g, p, og, op);
         return;
     }
 }

@@ -39,7 +39,8 @@ GPConfig = gp.GPConfig
 __all__ = ["TData", "GPModel", "GPConfig", "create_transformed_data", "make_and_fit_model",
            "forecast", "forecast_with_nowcasts", "create_nowcast_data", "forecast_mixture",
            "forecast_mixture_with_nowcasts", "get_transformations", "forecast_targets",
-           "forecast_targets_with_nowcasts", "score_forecast", "forecast_scores_with_nowcasts"]
+           "forecast_targets_with_nowcasts", "score_forecast", "forecast_scores_with_nowcasts",
+           "hindcast"]
 
 
 class TData:
@@ -640,6 +641,92 @@ def forecast_mixture(model: GPModel, forecast_dates) -> "autogp.MixtureMarginals
     src/forecasting.jl:46), as an ``autogp.MixtureMarginals``: exact quantiles, CDF / PIT and CRPS
     instead of draws.  Consumes nothing from the model's random streams."""
     return autogp._predict_marginals(model, list(forecast_dates))
+
+
+class Hindcast:
+    """Forecast skill by report date and horizon of ONE fitted model (``hindcast``).
+
+        origins    [R] observation counts: origin r knows the first ``origins[r]`` observations
+        horizons   [H] steps ahead, 1 = the next observation after the origin
+        dates      [R][H] the date forecast at (origin, horizon); None past the last observation
+        observed   [R, H] what was observed there, on the scale the model was given; NaN past it
+        marginals  [R] ``autogp.MixtureMarginals`` of origin r over ``union_dates``
+        ess        [R] effective sample size of the weights used at each origin
+
+    ``crps()``, ``pit()`` and ``quantile(levels)`` are [R, H] ([R, H, Q]) tables from the exact
+    ``MixtureMarginals`` methods, NaN where there is nothing to score.  With the
+    ``inv_transformation`` the hindcast was asked with (an inverse of ``get_transformations``) the
+    CRPS is the exact one on the natural scale and the quantiles are mapped back."""
+
+    def __init__(self, origins, horizons, dates, observed, marginals, ess, union_dates, cols,
+                 inv_transformation=None):
+        self.origins, self.horizons, self.dates, self.observed = origins, horizons, dates, observed
+        self.marginals, self.ess, self.union_dates = marginals, ess, union_dates
+        self._cols, self.inv_transformation = cols, inv_transformation
+
+    def _table(self, fn, extra=()):
+        """fn(marginals over the origin's existing dates, their observations) -> [k, ...]"""
+        R, H = self._cols.shape
+        out = np.full((R, H) + tuple(extra), np.nan)
+        for r, mix in enumerate(self.marginals):
+            have = np.flatnonzero(self._cols[r] >= 0)
+            if have.size:
+                c = self._cols[r, have]
+                sub = autogp.MixtureMarginals(mix.means[:, c], mix.variances[:, c], mix.weights,
+                                              engine=mix.engine)
+                out[r, have] = fn(sub, self.observed[r, have])
+        return out
+
+    def crps(self):
+        inv = self.inv_transformation
+        if inv is None:
+            return self._table(lambda mix, y: mix.crps(y))
+        return self._table(lambda mix, y: mix.crps(_apply(inv, y), inv_transformation=inv, scale="natural"))
+
+    def pit(self):
+        return self._table(lambda mix, y: mix.pit(y))
+
+    def quantile(self, levels):
+        lv = np.atleast_1d(np.asarray(levels, dtype=np.float64))
+        kw = {} if self.inv_transformation is None else {"inv_transformation": self.inv_transformation}
+        return self._table(lambda mix, y: mix.quantile(lv, **kw), (lv.size,))
+
+
+def hindcast_columns(cuts, horizons, n: int):
+    """Observation cut + h - 1 (0-based) is what origin ``cut`` forecasts h steps ahead.  Returns
+    the sorted union of those below n and ``cols`` [R, H]: where each entry sits in the union, -1
+    past the last observation."""
+    cuts = np.asarray(cuts, dtype=np.int64).reshape(-1)
+    hz = np.asarray(horizons, dtype=np.int64).reshape(-1)
+    if hz.size < 1 or np.any(hz < 1):
+        raise ValueError("hindcast: horizons are steps ahead, 1 or more")
+    obs = cuts[:, None] + hz[None, :] - 1
+    union = np.unique(obs[obs < n])
+    cols = np.where(obs < n, np.searchsorted(union, np.minimum(obs, n - 1)), -1)
+    return union, cols
+
+
+def hindcast(model: GPModel, report_dates, horizons, *, inv_transformation: Optional[Callable] = None,
+             weights: str = "fitted") -> Hindcast:
+    """How good have this fitted model's forecasts been?  For every report date (an observation
+    count, or a date meaning "the data up to and including") and every horizon h the forecast of
+    the h-th observation after it from the data before it alone — the table of the reference's
+    "forecast skill by report date" figures (docs/vignettes/setting-priors.jl:166-171) with the
+    fitted particles held fixed instead of refitted.  ONE device query on the union of the dates
+    (``autogp.predict_origins``), gathered to [report date, horizon]."""
+    cuts = autogp.origin_counts(model, report_dates)
+    n = model.n_obs
+    hz = np.asarray(horizons, dtype=np.int64).reshape(-1)
+    union, cols = hindcast_columns(cuts, hz, n)
+    if union.size < 1:
+        raise ValueError("hindcast: every (report date, horizon) lies past the last observation")
+    idx = np.sort(model._perm[:n])
+    union_dates = [model.ds[i] for i in idx[union]]
+    mixes, ess = autogp.predict_origins(model, [int(c) for c in cuts], union_dates, weights=weights)
+    y_union = np.asarray(model.y, dtype=np.float64)[idx[union]]
+    observed = np.where(cols >= 0, y_union[np.maximum(cols, 0)], np.nan)
+    dates = [[union_dates[c] if c >= 0 else None for c in row] for row in cols]
+    return Hindcast(cuts, hz, dates, observed, mixes, ess, union_dates, cols, inv_transformation)
 
 
 def forecast_mixture_with_nowcasts(base_model: GPModel, nowcasts: Sequence[TData], forecast_dates, *,
