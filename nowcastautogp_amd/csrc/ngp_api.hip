@@ -1838,183 +1838,214 @@ extern "C" ngp_status ngp_factor_nowcast(ngp_factor *f, int32_t d, const double 
     return st;
 }
 
-// ---- long horizons ------------------------------------------------
+// ---- long horizons (DESIGN.md sections 4.25, 4.27 - 4.29) -----------------------------------
 // The dates are the panel of a triangular solve against the resident L (ngp_long_kernels.h), not
 // aux rows: m is bounded by NGP_MAX_LONG_HORIZON and the device's memory, not by NGP_MAX_AUX.  The
 // particles are worked through in chunks sized to what the device holds.
 //
-// What ngp_factor_predict_long and ngp_factor_sample_long (section 4.27) share: the checks of the
-// query, the panel's inputs, the geometry (long_stage), the working storage of a chunk (long_take)
-// and a chunk's launches up to sigma (long_launch).
-struct LongStage {
-    LongGeom g{};
-    std::vector<unsigned char> h_in;   // what travels up: programs | t0 | tp | y0 | yc
-    size_t o_t0 = 0, o_tp = 0, o_y0 = 0, o_yc = 0, in_bytes = 0;
-    size_t cw = 0, n_W = 0, n_S = 0, n_mu = 0;
-    size_t work_bytes = 0;             // working storage and outputs per item, sigma not counted
-    int cc = 0;
-    unsigned char *d_in = nullptr;
-    LongPtrs p{};
+// The four entry points share the checks (long_check), the geometry and inputs (long_stage), one
+// list of the query's device blocks (LongStage::blocks: bytes per item, takes and uploads are read
+// off it) and the run on the device (LongRun: sizing, takes, chunks, a chunk's launches in their one
+// order).  An entry point reads: checks, geometry, blocks, per chunk its own steps and downloads.
+struct LongBlock {
+    void **p;               // null: counted, not taken
+    bool per_item;          // `bytes` for every item of a chunk, or for the call
+    size_t bytes, spare;    // spare: taken behind the last item, not counted
+    const void *host;       // copied up once the blocks are taken
 };
 
-// sig_ld: the row stride sigma is formed with; 0: no sigma
-static ngp_status long_stage(ngp_factor *f, int32_t d, const double *t_add, int32_t &D,
-                             const double *y_add, int32_t m, const double *t_new,
-                             int32_t noise_on_new, int64_t sig_ld, LongStage &st) {
+struct LongStage {
+    LongGeom g{};
+    LongPtrs p{};
+    std::vector<unsigned char> h_in;   // what travels up: programs | t0 | tp | y0 | yc
+    size_t o_t0 = 0, o_tp = 0, o_y0 = 0, o_yc = 0;
+    unsigned char *d_in = nullptr;
+    size_t cw = 0;                     // the row of S: y' and the conditioning points
+    std::vector<LongBlock> blocks;     // in the order they are taken (and given back)
+    template <class T> LongStage &per_call(T **q, size_t count, const void *host = nullptr) {
+        blocks.push_back({reinterpret_cast<void **>(q), false, sizeof(T) * count, 0, host});
+        return *this;
+    }
+    template <class T> LongStage &per_item(T **q, size_t count, size_t spare = 0) {
+        blocks.push_back({reinterpret_cast<void **>(q), true, sizeof(T) * count, sizeof(T) * spare, nullptr});
+        return *this;
+    }
+    // the panel, the small blocks, the dates' diagonal (where the layout has one) and the u_s (an
+    // empty z still has an address)
+    LongStage &work_blocks(bool has_dg = true) {
+        if (g.n0 > 0) per_item(&p.W, (size_t)g.qpad * g.n0);
+        per_item(&p.S, (size_t)g.q1 * cw);
+        if (has_dg) per_item(&p.dg, (size_t)g.q1);
+        return per_item(&p.z, (size_t)g.D * g.c, 1);
+    }
+    size_t bytes(bool per_item) const {
+        size_t n = 0;
+        for (const LongBlock &b : blocks) n += b.per_item == per_item ? b.bytes : 0;
+        return n;
+    }
+};
+
+static ngp_status long_check(const ngp_factor *f, int32_t d, const double *t_add, int32_t D,
+                             const double *y_add, int32_t m, const double *t_new) {
     if (!f || !t_new || m < 1 || d < 0) return NGP_ERR_ARG;
     if (d > 0 && (D < 1 || !t_add || !y_add)) return NGP_ERR_ARG;
-    if (d == 0) D = 1;
     if (m > NGP_MAX_LONG_HORIZON) return NGP_ERR_TOO_LARGE;
-    const int P = f->P, n = f->n, n0 = f->n0, tail = n - n0;
-    if ((int64_t)tail + d + 1 > NGP_MAX_AUX) return NGP_ERR_TOO_LARGE;
-    const int cc = tail + d;
-    st.cc = cc;
-    std::vector<DevProgram> hp((size_t)P);
-    for (int i = 0; i < P; ++i) {
-        ngp_status e = compile_program(&f->kernels[(size_t)i], &hp[(size_t)i], nullptr);
-        if (e) return e;
-    }
-    LongGeom &g = st.g;
-    g.n0 = n0;
-    g.nb0 = f->nb0;
-    g.c = cc;
-    g.m = m;
-    g.D = D;
-    g.q1 = 1 + cc + m;
-    g.qpad = (g.q1 + LONG_TILE - 1) / LONG_TILE * LONG_TILE;
-    g.noise_on_new = noise_on_new ? 1 : 0;
-    g.y_shared = f->ldy ? 0 : 1;
-    g.want_sigma = sig_ld ? 1 : 0;
-    g.ld = n0;
-    g.L_stride = f->item_stride;
-    g.dinv_step = (int64_t)P * NB * NB;
-    g.sig_ld = sig_ld;
-    g.sig_stride = sig_ld * sig_ld;
-    // what travels up: programs | t0 | tp | y0 | yc
-    const int ny = g.y_shared ? 1 : P;
-    const size_t o_t0 = sizeof(DevProgram) * (size_t)P, o_tp = o_t0 + 8 * (size_t)n0,
-                 o_y0 = o_tp + 8 * (size_t)(cc + m), o_yc = o_y0 + 8 * (size_t)ny * n0,
-                 in_bytes = o_yc + 8 * (size_t)ny * D * cc;
-    st.o_t0 = o_t0, st.o_tp = o_tp, st.o_y0 = o_y0, st.o_yc = o_yc, st.in_bytes = in_bytes;
-    std::vector<unsigned char> &h_in = st.h_in;
-    h_in.resize(in_bytes);
-    std::memcpy(h_in.data(), hp.data(), o_t0);
-    {
-        double *h_t0 = reinterpret_cast<double *>(h_in.data() + o_t0);
-        double *h_tp = reinterpret_cast<double *>(h_in.data() + o_tp);
-        double *h_y0 = reinterpret_cast<double *>(h_in.data() + o_y0);
-        double *h_yc = reinterpret_cast<double *>(h_in.data() + o_yc);
-        std::copy(f->t.begin(), f->t.begin() + n0, h_t0);
-        std::copy(f->t.begin() + n0, f->t.end(), h_tp);
-        for (int a = 0; a < d; ++a) h_tp[tail + a] = t_add[a];
-        std::copy(t_new, t_new + m, h_tp + cc);
-        for (int b = 0; b < ny; ++b) {
-            const double *yb = f->y.data() + (size_t)b * n;
-            std::copy(yb, yb + n0, h_y0 + (size_t)b * n0);
-            for (int s = 0; s < D; ++s) {
-                double *dst = h_yc + ((size_t)b * D + s) * cc;
-                std::copy(yb + n0, yb + n, dst);
-                for (int a = 0; a < d; ++a) dst[tail + a] = y_add[(size_t)s * d + a];
-            }
-        }
-    }
-    // doubles of working storage and of outputs per item
-    st.cw = (size_t)cc + 1;
-    st.n_W = (size_t)g.qpad * n0, st.n_S = (size_t)g.q1 * st.cw, st.n_mu = (size_t)D * m;
-    st.work_bytes = 8 * (st.n_W + st.n_S + (size_t)g.q1 + (size_t)D * cc + st.n_mu + (size_t)m) + 4;
+    if ((int64_t)(f->n - f->n0) + d + 1 > NGP_MAX_AUX) return NGP_ERR_TOO_LARGE;
     return NGP_OK;
 }
 
-// the inputs and the working storage of chunks of up to Pc items
-static void long_take(DevCall &call, const ngp_factor *f, LongStage &st, size_t Pc) {
-    const LongGeom &g = st.g;
-    LongPtrs &p = st.p;
-    call.take(&st.d_in, st.in_bytes);
-    if (g.n0 > 0) call.take(&p.W, Pc * st.n_W);
-    call.take(&p.S, Pc * st.n_S).take(&p.dg, Pc * (size_t)g.q1).take(&p.z, Pc * (size_t)g.D * st.cc + 1);
-    call.take(&p.mu, Pc * st.n_mu).take(&p.var, Pc * (size_t)g.m).take(&p.info, Pc);
-    if (g.want_sigma) call.take(&p.sigma, Pc * (size_t)g.sig_stride);
-    call.up(st.d_in, st.h_in.data(), st.in_bytes);
-    (void)f;
-}
-
-// the chunk's size and where its items' inputs and their part of the resident factor are
-static void long_bind(const ngp_factor *f, LongStage &st, size_t b0, size_t bc) {
+// A query long_check has passed: its geometry and its inputs, the first of its blocks.
+// groups = 0: the panel is y', the conditioning rows and the m dates, padded to LONG_TILE as a
+// whole; groups = C: the head and each of C groups of date rows are padded on their own (4.28).
+// sig_ld: the row stride LongPtrs::sigma is formed with (0: it is not); want_sigma: the kernels
+// form a sigma, LongPtrs' or the entry point's own.
+static ngp_status long_stage(const ngp_factor *f, int32_t d, const double *t_add, int32_t D,
+                             const double *y_add, int32_t m, const double *t_new, int32_t noise_on_new,
+                             int32_t groups, int64_t sig_ld, bool want_sigma, LongStage &st) {
+    if (d == 0) D = 1;
+    const int P = f->P, n = f->n, n0 = f->n0, tail = n - n0, cc = tail + d;
+    std::vector<DevProgram> hp((size_t)P);
+    for (int i = 0; i < P; ++i)
+        if (ngp_status e = compile_program(&f->kernels[(size_t)i], &hp[(size_t)i], nullptr)) return e;
+    auto padded = [](int32_t rows) { return (rows + LONG_TILE - 1) / LONG_TILE * LONG_TILE; };
     LongGeom &g = st.g;
-    LongPtrs &p = st.p;
-    unsigned char *d_in = st.d_in;
-    const int n0 = g.n0, D = g.D, cc = st.cc;
-    g.B = (int32_t)bc;
-    p.progs = reinterpret_cast<const DevProgram *>(d_in) + b0;
-    p.L = f->L ? f->L + b0 * (size_t)f->item_stride : nullptr;
-    p.dinv = f->dinv ? f->dinv + b0 * (size_t)(NB * NB) : nullptr;
-    p.finfo = n0 > 0 ? f->info + b0 : nullptr;   // without a main block create leaves it unwritten
-    p.t0 = reinterpret_cast<const double *>(d_in + st.o_t0);
-    p.tp = reinterpret_cast<const double *>(d_in + st.o_tp);
-    p.y0 = reinterpret_cast<const double *>(d_in + st.o_y0) + (g.y_shared ? 0 : b0 * (size_t)n0);
-    p.yc = reinterpret_cast<const double *>(d_in + st.o_yc) + (g.y_shared ? 0 : b0 * (size_t)D * cc);
+    g.n0 = n0, g.nb0 = f->nb0, g.c = cc, g.m = m, g.D = D;
+    g.q1 = groups ? padded(1 + cc) + groups * padded(m) : 1 + cc + m;   // 65,534 groups of 4,096 fit
+    g.qpad = padded(g.q1);
+    g.noise_on_new = noise_on_new ? 1 : 0, g.y_shared = f->ldy ? 0 : 1, g.want_sigma = want_sigma ? 1 : 0;
+    g.ld = n0, g.L_stride = f->item_stride, g.dinv_step = (int64_t)P * NB * NB;
+    g.sig_ld = sig_ld, g.sig_stride = sig_ld * sig_ld;
+    const int ny = g.y_shared ? 1 : P;
+    st.o_t0 = sizeof(DevProgram) * (size_t)P, st.o_tp = st.o_t0 + 8 * (size_t)n0;
+    st.o_y0 = st.o_tp + 8 * (size_t)(cc + m), st.o_yc = st.o_y0 + 8 * (size_t)ny * n0;
+    std::vector<unsigned char> &h_in = st.h_in;
+    h_in.resize(st.o_yc + 8 * (size_t)ny * D * cc);
+    std::memcpy(h_in.data(), hp.data(), st.o_t0);
+    auto at = [&](size_t o) { return reinterpret_cast<double *>(h_in.data() + o); };
+    double *h_t0 = at(st.o_t0), *h_tp = at(st.o_tp), *h_y0 = at(st.o_y0), *h_yc = at(st.o_yc);
+    std::copy(f->t.begin(), f->t.begin() + n0, h_t0);
+    std::copy(f->t.begin() + n0, f->t.end(), h_tp);
+    for (int a = 0; a < d; ++a) h_tp[tail + a] = t_add[a];
+    std::copy(t_new, t_new + m, h_tp + cc);
+    for (int b = 0; b < ny; ++b) {
+        const double *yb = f->y.data() + (size_t)b * n;
+        std::copy(yb, yb + n0, h_y0 + (size_t)b * n0);
+        for (int s = 0; s < D; ++s) {
+            double *dst = h_yc + ((size_t)b * D + s) * cc;
+            std::copy(yb + n0, yb + n, dst);
+            for (int a = 0; a < d; ++a) dst[tail + a] = y_add[(size_t)s * d + a];
+        }
+    }
+    st.cw = (size_t)cc + 1;
+    st.per_call(&st.d_in, h_in.size(), h_in.data());
+    return NGP_OK;
 }
 
-// n0^2 q flops per item; L once per workgroup tile, the panel once in and once out, and —
-// left-looking — block column j of the solved panel read back by every later step
-static void long_solve(DevCall &call, const LongStage &st, const DevSpec &sp, hipStream_t s) {
-    const LongGeom &g = st.g;
-    const double dB = (double)g.B, dq = (double)g.q1, dn = (double)g.n0;
-    const double wg_tiles = (double)((g.qpad + LONG_WG_TILE - 1) / LONG_WG_TILE);
-    call.timed(call.tm, 6, dB * dn * dn * dq,
-               8.0 * dB * (wg_tiles * dn * dn / 2 + 2.0 * g.qpad * dn + g.qpad * dn * (g.nb0 - 1) / 2.0),
-               [&] { launch_long(LONG_SOLVE, g, st.p, sp, s); });
+// the context's cap, refreshed when a call of `whole` bytes would not fit the remembered one
+static size_t long_cap(ngp_ctx *c, size_t whole) {
+    if (whole > c->mem_cap) c->refresh_mem_cap();
+    return c->mem_cap;
 }
 
-// items [b0, b0 + bc): the panel, its solve, the products, the conditioning block, means,
-// variances and (want_sigma) sigma, left in st.p
-static void long_launch(DevCall &call, ngp_factor *f, LongStage &st, size_t b0, size_t bc) {
-    long_bind(f, st, b0, bc);
-    const LongGeom &g = st.g;
-    const LongPtrs &p = st.p;
-    const int n0 = g.n0;
-    const size_t cw = st.cw, mm = g.want_sigma ? (size_t)g.m * g.m : 0;
-    const DevSpec sp = dev_spec(f->spec);
-    hipStream_t s = f->ctx->stream;
-    EventTimer &tm = call.tm;
-    const double dB = (double)bc, dq = (double)g.q1, dn = (double)n0;
-    call.timed(tm, 4, 0.0, 8.0 * dB * g.qpad * dn, [&] { launch_long(LONG_FILL, g, p, sp, s); });
-    call.timed(tm, 4, 0.0, 8.0 * dB * (dq * (double)cw + (double)mm), [&] { launch_long(LONG_SMALL, g, p, sp, s); });
-    long_solve(call, st, sp, s);
-    call.timed(tm, 2, 0.0, 0.0, [&] { launch_long(LONG_GRAM, g, p, sp, s); });
-    call.timed(tm, 3, 0.0, 0.0, [&] {
-        launch_long(LONG_COND, g, p, sp, s);
-        launch_long(LONG_APPLY, g, p, sp, s);
-        launch_long(LONG_SIGMA, g, p, sp, s);
-    });
-}
+// the slots of a chunk's launches an entry point may fill itself (LongRun::launch)
+enum { LONG_OWN_FILL, LONG_OWN_SMALL, LONG_OWN_AFTER_SOLVE, LONG_OWN_PRODUCTS, LONG_OWN_FINISH };
+static bool long_plain(int) { return false; }
+
+// A long query on the device: the call's scope, the chunk size, the takes and uploads (open), the
+// chunks with their pointers (next), a chunk's launches (launch) and its pivot reports (info_down).
+struct LongRun {
+    ngp_factor *f;
+    LongStage &st;
+    DevCall call;
+    const DevSpec sp;
+    hipStream_t s;
+    size_t Pc = 0;
+    LongRun(ngp_factor *f_, LongStage &st_)
+        : f(f_), st(st_), call(f_->ctx), sp(dev_spec(f_->spec)), s(f_->ctx->stream) {}
+    // reserved: bytes beside the declared blocks.  A call whose single item does not fit is refused.
+    ngp_status open(size_t reserved = 0) {
+        if (call.status()) return call.status();
+        const size_t P = (size_t)f->P, fixed = st.bytes(false) + reserved, item = st.bytes(true);
+        const size_t cap = long_cap(f->ctx, fixed + P * item);
+        if (fixed + item > cap) return NGP_ERR_TOO_LARGE;
+        Pc = std::min<size_t>(std::min<size_t>(P, MAX_CHUNK_ITEMS), std::max<size_t>(1, (cap - fixed) / item));
+        for (const LongBlock &b : st.blocks)
+            if (b.p) call.take(reinterpret_cast<unsigned char **>(b.p), (b.per_item ? Pc : 1) * b.bytes + b.spare);
+        for (const LongBlock &b : st.blocks)
+            if (b.host) call.up(*b.p, b.host, b.bytes);
+        return NGP_OK;
+    }
+    // the items of the chunk at b0 (0: no more, or the call has failed), its inputs and its part of
+    // the resident factor bound
+    size_t next(size_t b0) {
+        if (b0 >= (size_t)f->P || call.status()) return 0;
+        const size_t bc = std::min(Pc, (size_t)f->P - b0);
+        LongGeom &g = st.g;
+        LongPtrs &p = st.p;
+        unsigned char *d_in = st.d_in;
+        g.B = (int32_t)bc;
+        p.progs = reinterpret_cast<const DevProgram *>(d_in) + b0;
+        p.L = f->L ? f->L + b0 * (size_t)f->item_stride : nullptr;
+        p.dinv = f->dinv ? f->dinv + b0 * (size_t)(NB * NB) : nullptr;
+        p.finfo = g.n0 > 0 ? f->info + b0 : nullptr;   // without a main block create leaves it unwritten
+        p.t0 = reinterpret_cast<const double *>(d_in + st.o_t0);
+        p.tp = reinterpret_cast<const double *>(d_in + st.o_tp);
+        p.y0 = reinterpret_cast<const double *>(d_in + st.o_y0) + (g.y_shared ? 0 : b0 * (size_t)g.n0);
+        p.yc = reinterpret_cast<const double *>(d_in + st.o_yc) + (g.y_shared ? 0 : b0 * (size_t)g.D * g.c);
+        return bc;
+    }
+    double small_bytes() const {   // what the plain query's small blocks write
+        return 8.0 * st.g.B * ((double)st.g.q1 * (double)st.cw + (st.g.want_sigma ? (double)st.g.m * st.g.m : 0.0));
+    }
+    // The bound chunk's launches: panel, small blocks, solve, [a step behind the solve, where `after`
+    // has a class], products, conditioning block and what is read off it.  own(slot): the entry point
+    // launches that slot itself and says so; the plain query's kernels otherwise.
+    template <class Own> void launch(Own own, double small_b, Cost after = Cost{-1, 0.0, 0.0}) {
+        const LongGeom &g = st.g;
+        const LongPtrs &p = st.p;
+        EventTimer &tm = call.tm;
+        const double dB = (double)g.B, dq = (double)g.q1, dn = (double)g.n0;
+        call.timed(tm, 4, 0.0, 8.0 * dB * g.qpad * dn, [&] { if (!own(LONG_OWN_FILL)) launch_long(LONG_FILL, g, p, sp, s); });
+        call.timed(tm, 4, 0.0, small_b, [&] { if (!own(LONG_OWN_SMALL)) launch_long(LONG_SMALL, g, p, sp, s); });
+        // n0^2 q flops per item; L once per workgroup tile, the panel once in and once out, and —
+        // left-looking — block column j of the solved panel read back by every later step
+        const double wg_tiles = (double)((g.qpad + LONG_WG_TILE - 1) / LONG_WG_TILE);
+        call.timed(tm, 6, dB * dn * dn * dq,
+                   8.0 * dB * (wg_tiles * dn * dn / 2 + 2.0 * g.qpad * dn + g.qpad * dn * (g.nb0 - 1) / 2.0),
+                   [&] { launch_long(LONG_SOLVE, g, p, sp, s); });
+        if (after.cls >= 0) call.timed(tm, after, [&] { own(LONG_OWN_AFTER_SOLVE); });
+        call.timed(tm, 2, 0.0, 0.0, [&] { if (!own(LONG_OWN_PRODUCTS)) launch_long(LONG_GRAM, g, p, sp, s); });
+        call.timed(tm, 3, 0.0, 0.0, [&] {
+            launch_long(LONG_COND, g, p, sp, s);
+            if (own(LONG_OWN_FINISH)) return;
+            launch_long(LONG_APPLY, g, p, sp, s);
+            launch_long(LONG_SIGMA, g, p, sp, s);
+        });
+    }
+    void info_down(int32_t *info, size_t b0) { if (info) call.down(info + b0, st.p.info, 4 * (size_t)st.g.B); }
+};
 
 extern "C" ngp_status ngp_factor_predict_long(ngp_factor *f, int32_t d, const double *t_add,
                                               int32_t D, const double *y_add, int32_t m,
                                               const double *t_new, int32_t noise_on_new, double *mu,
                                               double *var, double *sigma, int32_t *info) {
     if (!mu || !var) return NGP_ERR_ARG;
+    if (ngp_status e = long_check(f, d, t_add, D, y_add, m, t_new)) return e;
     LongStage st;
-    if (ngp_status e = long_stage(f, d, t_add, D, y_add, m, t_new, noise_on_new, sigma ? m : 0, st)) return e;
-    const LongPtrs &p = st.p;
-    const size_t P = (size_t)f->P, mm = sigma ? (size_t)m * m : 0, n_mu = st.n_mu, in_bytes = st.in_bytes;
-    const size_t item_bytes = st.work_bytes + 8 * mm;
-    ngp_ctx *c = f->ctx;
-    DevCall call(c);
-    if (call.status()) return call.status();
-    if (P * item_bytes + in_bytes > c->mem_cap) c->refresh_mem_cap();
-    if (item_bytes + in_bytes > c->mem_cap) return NGP_ERR_TOO_LARGE;
-    const size_t Pc = std::min<size_t>(std::min<size_t>(P, MAX_CHUNK_ITEMS),
-                                       std::max<size_t>(1, (c->mem_cap - in_bytes) / item_bytes));
-    long_take(call, f, st, Pc);
-    for (size_t b0 = 0; b0 < P && !call.status(); b0 += Pc) {
-        const size_t bc = std::min(Pc, P - b0);
-        long_launch(call, f, st, b0, bc);
-        call.down(mu + b0 * n_mu, p.mu, 8 * bc * n_mu).down(var + b0 * (size_t)m, p.var, 8 * bc * (size_t)m);
-        if (sigma) call.down(sigma + b0 * mm, p.sigma, 8 * bc * mm);
-        if (info) call.down(info + b0, p.info, 4 * bc);
+    if (ngp_status e = long_stage(f, d, t_add, D, y_add, m, t_new, noise_on_new, 0, sigma ? m : 0, sigma, st)) return e;
+    LongPtrs &p = st.p;
+    const size_t um = (size_t)m, n_mu = (size_t)st.g.D * um, mm = sigma ? um * um : 0;
+    st.work_blocks().per_item(&p.mu, n_mu).per_item(&p.var, um).per_item(&p.info, 1);
+    if (sigma) st.per_item(&p.sigma, mm);
+    LongRun run(f, st);
+    if (ngp_status e = run.open()) return e;
+    for (size_t b0 = 0, bc; (bc = run.next(b0)); b0 += bc) {
+        run.launch(long_plain, run.small_bytes());
+        run.call.down(mu + b0 * n_mu, p.mu, 8 * bc * n_mu).down(var + b0 * um, p.var, 8 * bc * um);
+        if (sigma) run.call.down(sigma + b0 * mm, p.sigma, 8 * bc * mm);
+        run.info_down(info, b0);
     }
-    return call.sync();
+    return run.call.sync();
 }
 
 // ---- paths of a long horizon ---------------------------------------
@@ -2027,46 +2058,43 @@ extern "C" ngp_status ngp_factor_sample_long(ngp_factor *f, int32_t d, const dou
                                              int32_t noise_on_new, const double *w, int32_t draws,
                                              uint64_t seed, double *out, int32_t *comp, double *mu,
                                              double *var, int32_t *info, int32_t *chol_info) {
-    if (!f || !t_new || !w || !out || m < 1 || draws < 1 || d < 0) return NGP_ERR_ARG;
-    const int mpad = m > NGP_MAX_LONG_HORIZON ? 0 : (m + NB - 1) / NB * NB;
+    if (!w || !out || draws < 1) return NGP_ERR_ARG;
+    if (ngp_status e = long_check(f, d, t_add, D, y_add, m, t_new)) return e;
+    const int mpad = (m + NB - 1) / NB * NB;
     LongStage st;
-    if (ngp_status e = long_stage(f, d, t_add, D, y_add, m, t_new, noise_on_new, mpad, st)) return e;
-    const int S = D;                               // long_stage: D = 1 without appended points
+    if (ngp_status e = long_stage(f, d, t_add, D, y_add, m, t_new, noise_on_new, 0, mpad, true, st)) return e;
+    const int S = st.g.D;                          // 1 without appended points
     if ((int64_t)S * draws > INT32_MAX) return NGP_ERR_TOO_LARGE;
-    const size_t P = (size_t)f->P, N = (size_t)S * draws, n_mu = st.n_mu;
+    const size_t P = (size_t)f->P, N = (size_t)S * draws, um = (size_t)m, n_mu = (size_t)S * um;
     LongSampleGeom sg{};
     sg.P = (int32_t)P, sg.S = S, sg.draws = draws, sg.m = m;
     sg.mpad = mpad, sg.nb = mpad / NB;
-    sg.N = (int64_t)N;
-    sg.stride = (int64_t)mpad * mpad;
-    // beside the particles' chunks: inputs, weights, picks, grouping, every path; then per item
-    // sigma, the block inverse, a log determinant nobody reads and the pivot report
-    const size_t row_bytes = 8 * (size_t)mpad;
-    const size_t fixed = st.in_bytes + 8 * (size_t)S * P + 8 * N + 8 * (P + 1) + 8 * N * (size_t)m;
-    const size_t item_bytes = st.work_bytes + 8 * (size_t)sg.stride + 8 * (size_t)(NB * NB) + 8 + 4;
-    constexpr size_t Z_MIN_ROWS = LS_WG_PATHS, Z_MAX_ROWS = (size_t)1 << 22;   // the latter bounds gridDim.y
-    const size_t z_least = row_bytes * (std::min(N, Z_MIN_ROWS) + NB);
-    ngp_ctx *c = f->ctx;
-    DevCall call(c);
-    if (call.status()) return call.status();
-    if (fixed + P * item_bytes + row_bytes * (N + NB) > c->mem_cap) c->refresh_mem_cap();
-    if (fixed + item_bytes + z_least > c->mem_cap) return NGP_ERR_TOO_LARGE;
-    // the staged normals: a quarter of the room, at least Z_MIN_ROWS paths, never the last item's share
-    const size_t room = c->mem_cap - fixed;
-    const size_t z_bytes = std::min(room - item_bytes, std::max(z_least, room / 4));
-    const size_t zcap = std::min(std::min(N, Z_MAX_ROWS), z_bytes / row_bytes - NB);
-    const size_t Pc = std::min<size_t>(std::min<size_t>(P, MAX_CHUNK_ITEMS),
-                                       std::max<size_t>(1, (room - row_bytes * (zcap + NB)) / item_bytes));
-    long_take(call, f, st, Pc);
+    sg.N = (int64_t)N, sg.stride = (int64_t)mpad * mpad;
+    // weights, picks, grouping, every path (and the four bytes by which the chunk's size has always
+    // overcounted them); per item also sigma, block inverse, an unread log determinant, pivot report
     const LongPtrs &p = st.p;
     double *d_w = nullptr, *d_out = nullptr, *d_Z = nullptr, *d_dinv = nullptr, *d_logdet = nullptr;
     int32_t *d_comp = nullptr, *d_order = nullptr, *d_cinfo = nullptr;
     uint32_t *d_cnt = nullptr, *d_off = nullptr;
-    call.take(&d_w, (size_t)S * P).take(&d_comp, N).take(&d_order, N).take(&d_cnt, P).take(&d_off, P + 1);
-    call.take(&d_out, N * (size_t)m).take(&d_Z, (size_t)mpad * (zcap + NB));
-    call.take(&d_dinv, Pc * (size_t)(NB * NB)).take(&d_logdet, Pc).take(&d_cinfo, Pc);
-    call.up(d_w, w, 8 * (size_t)S * P);
-    hipStream_t s = c->stream;
+    st.work_blocks().per_item(&st.p.mu, n_mu).per_item(&st.p.var, um).per_item(&st.p.info, 1);
+    st.per_item(&st.p.sigma, (size_t)sg.stride).per_call(&d_w, (size_t)S * P, w).per_call(&d_comp, N);
+    st.per_call(&d_order, N).per_call(&d_cnt, P).per_call((uint32_t **)nullptr, 1).per_call(&d_off, P + 1);
+    st.per_call(&d_out, N * um).per_item(&d_dinv, (size_t)(NB * NB)).per_item(&d_logdet, 1).per_item(&d_cinfo, 1);
+    LongRun run(f, st);
+    DevCall &call = run.call;
+    if (call.status()) return call.status();
+    // the staged normals: a quarter of the room, at least Z_MIN_ROWS paths, never the last item's share
+    const size_t row_bytes = 8 * (size_t)mpad, fixed = st.bytes(false), item_bytes = st.bytes(true);
+    constexpr size_t Z_MIN_ROWS = LS_WG_PATHS, Z_MAX_ROWS = (size_t)1 << 22;   // the latter bounds gridDim.y
+    const size_t z_least = row_bytes * (std::min(N, Z_MIN_ROWS) + NB);
+    const size_t cap = long_cap(f->ctx, fixed + P * item_bytes + row_bytes * (N + NB));
+    if (fixed + item_bytes + z_least > cap) return NGP_ERR_TOO_LARGE;
+    const size_t room = cap - fixed;
+    const size_t z_bytes = std::min(room - item_bytes, std::max(z_least, room / 4));
+    const size_t zcap = std::min(std::min(N, Z_MAX_ROWS), z_bytes / row_bytes - NB);
+    if (ngp_status e = run.open(row_bytes * (zcap + NB))) return e;
+    call.take(&d_Z, (size_t)mpad * (zcap + NB));
+    hipStream_t s = run.s;
     EventTimer &tm = call.tm;
     // the picks and how many paths each particle got: one round trip, the offsets are the host's
     std::vector<uint32_t> cnt(P, 0u), off(P + 1, 0u);
@@ -2089,12 +2117,12 @@ extern "C" ngp_status ngp_factor_sample_long(ngp_factor *f, int32_t d, const dou
         active[k] = off[k + 1] > off[k];
         for (int sc = 0; sc < S && !active[k]; ++sc) active[k] = w[(size_t)sc * P + k] > 0.0;
     }
-    for (size_t b0 = 0; b0 < P && !call.status(); b0 += Pc) {
-        const size_t bc = std::min(Pc, P - b0);
-        long_launch(call, f, st, b0, bc);
+    for (size_t b0 = 0, bc; (bc = run.next(b0)); b0 += bc) {
+        run.launch(long_plain, run.small_bytes());
         if (mu) call.down(mu + b0 * n_mu, p.mu, 8 * bc * n_mu);
-        if (var) call.down(var + b0 * (size_t)m, p.var, 8 * bc * (size_t)m);
-        call.down(hinfo.data() + b0, p.info, 4 * bc);
+        if (var) call.down(var + b0 * um, p.var, 8 * bc * um);
+        run.info_down(hinfo.data(), b0);
+        // the chunk's sigma padded and factorised, then its paths drawn
         call.zero(d_cinfo, 4 * bc).zero(d_logdet, 8 * bc);
         call.timed(tm, 4, 0.0, 8.0 * (double)bc * (double)(mpad - m) * (double)(m + mpad),
                    [&] { launch_ls_pad(sg, p.sigma, (int)bc, s); });
@@ -2136,7 +2164,7 @@ extern "C" ngp_status ngp_factor_sample_long(ngp_factor *f, int32_t d, const dou
         }
         call.down(hcinfo.data() + b0, d_cinfo, 4 * bc);
     }
-    call.down(out, d_out, 8 * N * (size_t)m);
+    call.down(out, d_out, 8 * N * um);
     const ngp_status e = call.sync();
     if (e) return e;
     for (size_t k = 0; k < P; ++k) {
@@ -2444,17 +2472,16 @@ extern "C" ngp_status ngp_factor_components_nowcast(ngp_factor *f, int32_t d, co
 }
 
 // ---- the decomposition over a long horizon ---------------------------
-// The long query's staging, chunks, solve and conditioning block (long_stage, long_take,
-// long_bind, long_solve); the panel carries cmax groups of date rows, each padded to LONG_TILE, and
-// every panel row has a row of S (ngp_long_component_kernels.h).
+// The long query (LongStage, LongRun) with its own panel layout: cmax groups of date rows, each
+// padded to LONG_TILE, and every panel row has a row of S (ngp_long_component_kernels.h).  Fill,
+// small blocks, products and what follows the conditioning block are its own kernels.
 extern "C" ngp_status ngp_factor_components_long(ngp_factor *f, int32_t d, const double *t_add,
                                                  int32_t D, const double *y_add,
                                                  const int32_t *comp_count, const ngp_kernel *comps,
                                                  int32_t m, const double *t_new, double *mu,
                                                  double *cross, double *sigma, int32_t *info) {
     if (!comp_count || !comps || !mu || !cross) return NGP_ERR_ARG;
-    LongStage st;
-    if (ngp_status e = long_stage(f, d, t_add, D, y_add, m, t_new, 0, 0, st)) return e;
+    if (ngp_status e = long_check(f, d, t_add, D, y_add, m, t_new)) return e;
     const size_t P = (size_t)f->P;
     std::vector<int32_t> first(P + 1, 0);
     std::vector<int64_t> cr_off(P + 1, 0), sig_off(P + 1, 0);
@@ -2473,19 +2500,16 @@ extern "C" ngp_status ngp_factor_components_long(ngp_factor *f, int32_t d, const
     std::vector<DevProgram> hp(ncomp);
     for (size_t i = 0; i < ncomp; ++i)
         if (ngp_status e = compile_program(&comps[i], &hp[i], nullptr)) return e;
+    LongStage st;
+    if (ngp_status e = long_stage(f, d, t_add, D, y_add, m, t_new, 0, (int32_t)cmax, 0, sigma, st)) return e;
+    const LongGeom &g = st.g;
     LongCompGeom cg{};
     cg.m = m;
     cg.mpad = (m + LONG_TILE - 1) / LONG_TILE * LONG_TILE;
     cg.cmax = (int32_t)cmax;
-    cg.hpad = (1 + st.cc + LONG_TILE - 1) / LONG_TILE * LONG_TILE;
-    if (cg.hpad + cmax * cg.mpad > INT32_MAX / 2) return NGP_ERR_TOO_LARGE;
-    LongGeom &g = st.g;
-    g.q1 = g.qpad = cg.hpad + (int32_t)cmax * cg.mpad;
-    g.want_sigma = sigma ? 1 : 0;
+    cg.hpad = g.q1 - cg.cmax * cg.mpad;
     const size_t S = (size_t)g.D, um = (size_t)m, uc = (size_t)cmax;
-    st.n_W = (size_t)g.qpad * g.n0, st.n_S = (size_t)g.q1 * st.cw, st.n_mu = uc * S * um;
     const size_t n_cr = uc * uc * um, n_sig = sigma ? n_cr * um : 0;
-    const size_t item_bytes = 8 * (st.n_W + st.n_S + S * st.cc + st.n_mu + n_cr + n_sig) + 4;
     const size_t o_first = sizeof(DevProgram) * ncomp, o_cr = (o_first + 4 * first.size() + 7) & ~(size_t)7,
                  o_sig = o_cr + 8 * cr_off.size(), cin_bytes = o_sig + 8 * sig_off.size();
     std::vector<unsigned char> h_cin(cin_bytes);
@@ -2493,59 +2517,49 @@ extern "C" ngp_status ngp_factor_components_long(ngp_factor *f, int32_t d, const
     std::memcpy(h_cin.data() + o_first, first.data(), 4 * first.size());
     std::memcpy(h_cin.data() + o_cr, cr_off.data(), 8 * cr_off.size());
     std::memcpy(h_cin.data() + o_sig, sig_off.data(), 8 * sig_off.size());
-    const size_t in_bytes = st.in_bytes + cin_bytes;
-    ngp_ctx *c = f->ctx;
-    DevCall call(c);
-    if (call.status()) return call.status();
-    if (P * item_bytes + in_bytes > c->mem_cap) c->refresh_mem_cap();
-    if (item_bytes + in_bytes > c->mem_cap) return NGP_ERR_TOO_LARGE;
-    const size_t Pc = std::min<size_t>(std::min<size_t>(P, MAX_CHUNK_ITEMS),
-                                       std::max<size_t>(1, (c->mem_cap - in_bytes) / item_bytes));
-    LongPtrs &p = st.p;
+    const LongPtrs &p = st.p;
     LongCompPtrs cp{};
     unsigned char *d_cin = nullptr;
-    call.take(&st.d_in, st.in_bytes).take(&d_cin, cin_bytes);
-    if (g.n0 > 0) call.take(&p.W, Pc * st.n_W);
-    call.take(&p.S, Pc * st.n_S).take(&p.z, Pc * S * st.cc + 1).take(&p.info, Pc);
-    call.take(&cp.mu, Pc * st.n_mu).take(&cp.cross, Pc * n_cr);
-    if (sigma) call.take(&cp.sigma, Pc * n_sig);
-    call.up(st.d_in, st.h_in.data(), st.in_bytes).up(d_cin, h_cin.data(), cin_bytes);
-    const DevSpec sp = dev_spec(f->spec);
-    hipStream_t s = c->stream;
-    EventTimer &tm = call.tm;
-    for (size_t b0 = 0; b0 < P && !call.status(); b0 += Pc) {
-        const size_t bc = std::min(Pc, P - b0), b1 = b0 + bc;
-        long_bind(f, st, b0, bc);
+    st.per_call(&d_cin, cin_bytes, h_cin.data()).work_blocks(false).per_item(&st.p.info, 1);
+    st.per_item(&cp.mu, uc * S * um).per_item(&cp.cross, n_cr);
+    if (sigma) st.per_item(&cp.sigma, n_sig);
+    LongRun run(f, st);
+    if (ngp_status e = run.open()) return e;
+    const DevSpec &sp = run.sp;
+    hipStream_t s = run.s;
+    auto own = [&](int slot) {   // every slot but the one behind the solve, which it has not
+        if (slot == LONG_OWN_FILL) launch_long_comp(LCOMP_FILL, g, p, cg, cp, sp, s);
+        if (slot == LONG_OWN_SMALL) launch_long_comp(LCOMP_SMALL, g, p, cg, cp, sp, s);
+        if (slot == LONG_OWN_PRODUCTS) launch_long_comp(LCOMP_GRAM, g, p, cg, cp, sp, s);
+        if (slot == LONG_OWN_FINISH) {
+            launch_long_comp(LCOMP_APPLY, g, p, cg, cp, sp, s);
+            launch_long_comp(LCOMP_CROSS, g, p, cg, cp, sp, s);
+            launch_long_comp(LCOMP_SIGMA, g, p, cg, cp, sp, s);
+        }
+        return true;
+    };
+    for (size_t b0 = 0, bc; (bc = run.next(b0)); b0 += bc) {
+        const size_t b1 = b0 + bc;
         cp.progs = reinterpret_cast<const DevProgram *>(d_cin) + first[b0];
         cp.first = reinterpret_cast<const int32_t *>(d_cin + o_first) + b0;
         cp.cr_off = reinterpret_cast<const int64_t *>(d_cin + o_cr) + b0;
         cp.sig_off = reinterpret_cast<const int64_t *>(d_cin + o_sig) + b0;
+        // the chunk's components, elements of cross and of sigma
         const size_t nc = (size_t)(first[b1] - first[b0]), ncr = (size_t)(cr_off[b1] - cr_off[b0]) * um,
                      nsg = sigma ? (size_t)(sig_off[b1] - sig_off[b0]) : 0;
-        const double dB = (double)bc;
-        call.timed(tm, 4, 0.0, 8.0 * dB * g.qpad * (double)g.n0, [&] { launch_long_comp(LCOMP_FILL, g, p, cg, cp, sp, s); });
-        call.timed(tm, 4, 0.0, 8.0 * (dB * cg.hpad * (double)st.cw + (double)nc * um * (double)st.cw + (double)ncr + (double)nsg / 2),
-                   [&] { launch_long_comp(LCOMP_SMALL, g, p, cg, cp, sp, s); });
-        long_solve(call, st, sp, s);
-        call.timed(tm, 2, 0.0, 0.0, [&] { launch_long_comp(LCOMP_GRAM, g, p, cg, cp, sp, s); });
-        call.timed(tm, 3, 0.0, 0.0, [&] {
-            launch_long(LONG_COND, g, p, sp, s);
-            launch_long_comp(LCOMP_APPLY, g, p, cg, cp, sp, s);
-            launch_long_comp(LCOMP_CROSS, g, p, cg, cp, sp, s);
-            launch_long_comp(LCOMP_SIGMA, g, p, cg, cp, sp, s);
-        });
-        call.down(mu + (size_t)first[b0] * S * um, cp.mu, 8 * nc * S * um);
-        call.down(cross + (size_t)cr_off[b0] * um, cp.cross, 8 * ncr);
-        if (sigma) call.down(sigma + sig_off[b0], cp.sigma, 8 * nsg);
-        if (info) call.down(info + b0, p.info, 4 * bc);
+        run.launch(own, 8.0 * ((double)bc * cg.hpad * (double)st.cw + (double)nc * um * (double)st.cw + (double)ncr + (double)nsg / 2));
+        run.call.down(mu + (size_t)first[b0] * S * um, cp.mu, 8 * nc * S * um);
+        run.call.down(cross + (size_t)cr_off[b0] * um, cp.cross, 8 * ncr);
+        if (sigma) run.call.down(sigma + sig_off[b0], cp.sigma, 8 * nsg);
+        run.info_down(info, b0);
     }
-    return call.sync();
+    return run.call.sync();
 }
 
 // ---- hindcasts at many forecast origins ------------------------------
-// The long query without appended points (long_stage, long_bind, long_solve, the unchanged fill,
-// small blocks, products and conditioning block); the dates' means and variances are read off the
-// solved panel at every prefix the call asks for (ngp_long_origin_kernels.h).
+// The long query without appended points, unchanged up to the conditioning block; the dates' means
+// and variances are read off the solved panel at every prefix the call asks for, the main block's
+// right behind the solve (ngp_long_origin_kernels.h).
 extern "C" ngp_status ngp_factor_predict_origins(ngp_factor *f, int32_t R, const int32_t *cut,
                                                  int32_t m, const double *t_new,
                                                  int32_t noise_on_new, double *mu, double *var,
@@ -2554,57 +2568,41 @@ extern "C" ngp_status ngp_factor_predict_origins(ngp_factor *f, int32_t R, const
     if (R > NGP_MAX_ORIGINS) return NGP_ERR_TOO_LARGE;
     for (int32_t r = 0; r < R; ++r)
         if (cut[r] < 1 || cut[r] > f->n || (r > 0 && cut[r] <= cut[r - 1])) return NGP_ERR_ARG;
+    if (ngp_status e = long_check(f, 0, nullptr, 1, nullptr, m, t_new)) return e;
     LongStage st;
-    int32_t D = 1;
-    if (ngp_status e = long_stage(f, 0, nullptr, D, nullptr, m, t_new, noise_on_new, 0, st)) return e;
-    LongGeom &g = st.g;
+    if (ngp_status e = long_stage(f, 0, nullptr, 1, nullptr, m, t_new, noise_on_new, 0, 0, false, st)) return e;
+    const LongGeom &g = st.g;
+    const LongPtrs &p = st.p;
     LongOriginGeom og{};
     og.R = R;
     og.R0 = (int32_t)(std::upper_bound(cut, cut + R, g.n0) - cut);
-    const size_t P = (size_t)f->P, uR = (size_t)R, n_out = uR * (size_t)m;
-    st.work_bytes = 8 * (st.n_W + st.n_S + (size_t)g.q1 + (size_t)st.cc + 2 * n_out + uR) + 4;
-    const size_t item_bytes = st.work_bytes, cut_bytes = 4 * uR, in_bytes = st.in_bytes + cut_bytes;
-    ngp_ctx *c = f->ctx;
-    DevCall call(c);
-    if (call.status()) return call.status();
-    if (P * item_bytes + in_bytes > c->mem_cap) c->refresh_mem_cap();
-    if (item_bytes + in_bytes > c->mem_cap) return NGP_ERR_TOO_LARGE;
-    const size_t Pc = std::min<size_t>(std::min<size_t>(P, MAX_CHUNK_ITEMS),
-                                       std::max<size_t>(1, (c->mem_cap - in_bytes) / item_bytes));
-    LongPtrs &p = st.p;
     LongOriginPtrs op{};
     int32_t *d_cut = nullptr;
-    call.take(&st.d_in, st.in_bytes).take(&d_cut, uR);
-    if (g.n0 > 0) call.take(&p.W, Pc * st.n_W);
-    call.take(&p.S, Pc * st.n_S).take(&p.dg, Pc * (size_t)g.q1).take(&p.z, Pc * (size_t)st.cc + 1).take(&p.info, Pc);
-    call.take(&op.mu, Pc * n_out).take(&op.var, Pc * n_out);
-    if (logml) call.take(&op.logml, Pc * uR);
-    call.up(st.d_in, st.h_in.data(), st.in_bytes).up(d_cut, cut, cut_bytes);
+    const size_t uR = (size_t)R, n_out = uR * (size_t)m;
+    st.per_call(&d_cut, uR, cut).work_blocks().per_item(&st.p.info, 1);
+    st.per_item(&op.mu, n_out).per_item(&op.var, n_out);
+    st.per_item(logml ? &op.logml : (double **)nullptr, uR);   // counted also when nobody asks for it
+    LongRun run(f, st);
+    if (ngp_status e = run.open()) return e;
     op.cut = d_cut;
-    const DevSpec sp = dev_spec(f->spec);
-    hipStream_t s = c->stream;
-    EventTimer &tm = call.tm;
-    for (size_t b0 = 0; b0 < P && !call.status(); b0 += Pc) {
-        const size_t bc = std::min(Pc, P - b0);
-        long_bind(f, st, b0, bc);
-        const double dB = (double)bc, dq = (double)g.q1, dn = (double)g.n0;
-        call.timed(tm, 4, 0.0, 8.0 * dB * g.qpad * dn, [&] { launch_long(LONG_FILL, g, p, sp, s); });
-        call.timed(tm, 4, 0.0, 8.0 * dB * dq * (double)st.cw, [&] { launch_long(LONG_SMALL, g, p, sp, s); });
-        long_solve(call, st, sp, s);
-        // one read of the solved date rows, two stores per origin inside the main block and date
-        call.timed(tm, 3, 2.0 * dB * (double)m * dn, 8.0 * dB * ((double)g.qpad * dn + 2.0 * og.R0 * (double)m),
-                   [&] { launch_long_origin(LORG_MAIN, g, p, og, op, sp, s); });
-        call.timed(tm, 2, 0.0, 0.0, [&] { launch_long(LONG_GRAM, g, p, sp, s); });
-        call.timed(tm, 3, 0.0, 0.0, [&] {
-            launch_long(LONG_COND, g, p, sp, s);
-            launch_long_origin(LORG_TAIL, g, p, og, op, sp, s);
-            launch_long_origin(LORG_LOGML, g, p, og, op, sp, s);
-        });
-        call.down(mu + b0 * n_out, op.mu, 8 * bc * n_out).down(var + b0 * n_out, op.var, 8 * bc * n_out);
-        if (logml) call.down(logml + b0 * uR, op.logml, 8 * bc * uR);
-        if (info) call.down(info + b0, p.info, 4 * bc);
+    auto own = [&](int slot) {
+        if (slot == LONG_OWN_AFTER_SOLVE) launch_long_origin(LORG_MAIN, g, p, og, op, run.sp, run.s);
+        if (slot == LONG_OWN_FINISH) {
+            launch_long_origin(LORG_TAIL, g, p, og, op, run.sp, run.s);
+            launch_long_origin(LORG_LOGML, g, p, og, op, run.sp, run.s);
+        }
+        return slot == LONG_OWN_AFTER_SOLVE || slot == LONG_OWN_FINISH;
+    };
+    for (size_t b0 = 0, bc; (bc = run.next(b0)); b0 += bc) {
+        // behind the solve: one read of the solved date rows, two stores per origin and date
+        run.launch(own, run.small_bytes(),
+                   Cost{3, 2.0 * (double)bc * (double)m * (double)g.n0,
+                        8.0 * (double)bc * ((double)g.qpad * (double)g.n0 + 2.0 * og.R0 * (double)m)});
+        run.call.down(mu + b0 * n_out, op.mu, 8 * bc * n_out).down(var + b0 * n_out, op.var, 8 * bc * n_out);
+        if (logml) run.call.down(logml + b0 * uR, op.logml, 8 * bc * uR);
+        run.info_down(info, b0);
     }
-    return call.sync();
+    return run.call.sync();
 }
 
 extern "C" void ngp_factor_destroy(ngp_factor *f) {

@@ -1134,17 +1134,19 @@ void launch_cov(const DevProgram *progs, int B, const double *t1, int n1, const 
                        out, sp);
 }
 
+// the workgroups of a long-horizon kernel whose threads stride over `total` elements
+static int long_blocks(long total) { return (int)std::max<long>(1, std::min<long>(4096, (total + 255) / 256)); }
+
 void launch_long(int step, const LongGeom &g, const LongPtrs &p, const DevSpec &sp, hipStream_t s) {
-    auto blocks = [](long total) { return (int)std::max<long>(1, std::min<long>(4096, (total + 255) / 256)); };
     const int nt = g.qpad / NB, ct = g.c / NB + 1;
     const long small = (long)g.q1 * (g.c + 2) + (g.want_sigma ? (long)g.m * g.m : 0);
     switch (step) {
     case LONG_FILL:
         if (g.n0 == 0) return;
-        hipLaunchKernelGGL(long_fill_kernel, dim3(blocks((long)g.qpad * g.n0), g.B), dim3(256), 0, s, g, p, sp);
+        hipLaunchKernelGGL(long_fill_kernel, dim3(long_blocks((long)g.qpad * g.n0), g.B), dim3(256), 0, s, g, p, sp);
         return;
     case LONG_SMALL:
-        hipLaunchKernelGGL(long_small_kernel, dim3(blocks(small), g.B), dim3(256), 0, s, g, p, sp);
+        hipLaunchKernelGGL(long_small_kernel, dim3(long_blocks(small), g.B), dim3(256), 0, s, g, p, sp);
         return;
     case LONG_SOLVE:
         if (g.n0 == 0) return;
@@ -1166,26 +1168,25 @@ void launch_long(int step, const LongGeom &g, const LongPtrs &p, const DevSpec &
         return;
     case LONG_SIGMA:
         if (!g.want_sigma) return;
-        hipLaunchKernelGGL(long_sigma_kernel, dim3(blocks((long)g.m * g.m), g.B), dim3(256), 0, s, g, p, sp);
+        hipLaunchKernelGGL(long_sigma_kernel, dim3(long_blocks((long)g.m * g.m), g.B), dim3(256), 0, s, g, p, sp);
         return;
     }
 }
 
 void launch_long_comp(int step, const LongGeom &g, const LongPtrs &p, const LongCompGeom &cg,
                       const LongCompPtrs &cp, const DevSpec &sp, hipStream_t s) {
-    auto blocks = [](long total) { return (int)std::max<long>(1, std::min<long>(4096, (total + 255) / 256)); };
     const int nt = g.qpad / NB, ht = cg.hpad / NB, mt = cg.mpad / NB, groups = 1 + cg.cmax;
     const int gpairs = cg.cmax * (cg.cmax + 1) / 2;
     const long wid = (long)cg.cmax * cg.m;
     switch (step) {
     case LCOMP_FILL:
         if (g.n0 == 0) return;
-        hipLaunchKernelGGL(lcomp_fill_kernel, dim3(blocks((long)std::max(cg.hpad, cg.mpad) * g.n0), g.B, groups),
+        hipLaunchKernelGGL(lcomp_fill_kernel, dim3(long_blocks((long)std::max(cg.hpad, cg.mpad) * g.n0), g.B, groups),
                            dim3(256), 0, s, g, p, cg, cp, sp);
         return;
     case LCOMP_SMALL:
         hipLaunchKernelGGL(lcomp_small_kernel,
-                           dim3(blocks(std::max<long>((long)cg.hpad * (g.c + 1),
+                           dim3(long_blocks(std::max<long>((long)cg.hpad * (g.c + 1),
                                                       (long)cg.m * (g.c + 2 + cg.cmax + (g.want_sigma ? wid : 0)))),
                                 g.B, groups),
                            dim3(256), 0, s, g, p, cg, cp, sp);
@@ -1205,7 +1206,7 @@ void launch_long_comp(int step, const LongGeom &g, const LongPtrs &p, const Long
         return;
     case LCOMP_SIGMA:
         if (!g.want_sigma) return;
-        hipLaunchKernelGGL(lcomp_sigma_kernel, dim3(blocks(wid * wid), g.B), dim3(256), 0, s, g, p, cg, cp);
+        hipLaunchKernelGGL(lcomp_sigma_kernel, dim3(long_blocks(wid * wid), g.B), dim3(256), 0, s, g, p, cg, cp);
         return;
     }
 }

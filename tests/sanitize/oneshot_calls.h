@@ -4,6 +4,7 @@
 // call.  The component and long-horizon queries need a resident factor: `setup` makes it and
 // `teardown` destroys it, outside of what is recorded or broken.
 #pragma once
+#include <algorithm>
 #include <cstdint>
 #include <functional>
 #include <string>
@@ -181,6 +182,132 @@ struct Comp {
         return ngp_factor_predict_long(f, appended ? d : 0, t_add, D, y_add, mL, t_long, 0, mu_long, var_long,
                                        with_sigma ? sigma_long : nullptr, info);
     }
+    // its paths (4 draws; the second particle without weight when nothing is appended), its
+    // decomposition (counts 2 | 1) and its hindcasts either side of the main block's end
+    static constexpr int drawsL = 4, RL = 5;
+    double wL0[P] = {1.0, 0.0}, wL2[D * P] = {0.5, 0.5, 0.25, 0.75}, out_long[D * drawsL * mL];
+    double cmu_long[3 * D * mL], cross_long[5 * mL], csigma_long[5 * mL * mL];
+    double omu_long[P * RL * mL], ovar_long[P * RL * mL], logml_long[P * RL];
+    int32_t cutL[RL] = {1, 63, 64, 65, n}, comp_long[D * drawsL], cinfo_long[P];
+    void dates() { for (int i = 0; i < mL; ++i) t_long[i] = (n + d + i) / 128.0; }
+    ngp_status sample_long(bool appended) {
+        dates();
+        return ngp_factor_sample_long(f, appended ? d : 0, t_add, D, y_add, mL, t_long, 1, appended ? wL2 : wL0,
+                                      drawsL, 17u, out_long, comp_long, mu_long, var_long, info, cinfo_long);
+    }
+    ngp_status components_long(bool appended, bool with_sigma) {
+        dates();
+        return ngp_factor_components_long(f, appended ? d : 0, t_add, D, y_add, counts, comps, mL, t_long, cmu_long,
+                                          cross_long, with_sigma ? csigma_long : nullptr, info);
+    }
+    ngp_status predict_origins(bool with_logml) {
+        dates();
+        return ngp_factor_predict_origins(f, RL, cutL, mL, t_long, 0, omu_long, ovar_long,
+                                          with_logml ? logml_long : nullptr, info);
+    }
+};
+
+// ---- the long-horizon family: a resident factor of P = 3 with a main block and a tail (n = 191:
+// 128 + 63) or without a main block (n = 20); d = 0, and d = 2 with D = 3 --------------------------
+struct Long {
+    static constexpr int P = 3, d = 2, D = 3, NC = 6, NC2 = 1 + 9 + 4;   // sum C_p, sum C_p^2
+    // Plus(Plus(Linear, Periodic), SqExp) | Times(Plus(Linear, Periodic), SqExp) |
+    // Plus(ChangePoint(Plus(SqExp, Constant), Periodic), GammaExp)
+    int32_t ops0[5] = {2, 5, 6, 3, 6}, ops1[5] = {2, 5, 6, 3, 7}, ops2[7] = {3, 1, 6, 5, 8, 4, 6};
+    double par0[8] = {0.2, 0.1, 0.5, 0.9, 0.3, 0.7, 0.21, 0.4};
+    double par1[8] = {0.1, 0.3, 0.8, 1.1, 0.21, 0.4, 0.3, 0.6};
+    double par2[11] = {0.2, 0.5, 0.25, 1.0, 0.3, 0.3, 0.5, 0.1, 0.3, 1.5, 0.2};
+    int32_t lin[1] = {2}, per[1] = {5}, se[1] = {3};
+    ngp_kernel ks[P], comps[NC];
+    int32_t counts[P] = {1, 3, 2};
+    int n, m, draws, R;
+    std::vector<double> t, y, t_add, y_add, t_new;
+    std::vector<int32_t> cut;
+    // d = 0: the middle particle has no weight; d = 2: the last one has none in any scenario
+    double w0[P] = {0.5, 0.0, 0.5}, w2[D * P] = {0.5, 0.5, 0.0, 1.0, 0.0, 0.0, 0.25, 0.75, 0.0};
+    // every output of a call lies in `host` between two guard bands (cover(), below)
+    static constexpr size_t GUARD = 32;
+    std::vector<double> host;
+    std::vector<int32_t> ihost;
+    double *mu = nullptr, *var = nullptr, *sigma = nullptr, *out = nullptr, *cross = nullptr, *logml = nullptr;
+    int32_t *info = nullptr, *cinfo = nullptr, *comp = nullptr;
+    ngp_factor *f = nullptr;
+    Long(int n_, int m_, int draws_ = 4) : n(n_), m(m_), draws(draws_), t(n_), y(n_), t_add(d), y_add(D * d), t_new(m_) {
+        ks[0] = {5, 8, ops0, par0, 0.05};
+        ks[1] = {5, 8, ops1, par1, 0.02};
+        ks[2] = {7, 11, ops2, par2, 0.1};
+        comps[0] = ks[0];
+        comps[1] = {1, 3, lin, par1, 0.0};
+        comps[2] = {1, 3, per, par1 + 3, 0.0};
+        comps[3] = {1, 2, se, par1 + 6, 0.0};
+        comps[4] = {5, 8, ops2, par2, 0.0};          // ChangePoint(Plus(SqExp, Constant), Periodic)
+        comps[5] = {1, 3, ops2 + 5, par2 + 8, 0.0};  // GammaExp
+        for (int i = 0; i < n; ++i) { t[i] = i / 256.0; y[i] = ((i * 37) % 11) / 11.0 - 0.5; }
+        for (int i = 0; i < d; ++i) t_add[i] = (n + i) / 256.0;
+        for (int i = 0; i < D * d; ++i) y_add[i] = 0.1 * (i % 3);
+        for (int i = 0; i < m; ++i) t_new[i] = (n + d + i) / 256.0;
+        // origins either side of the main block's end (and of its first block row)
+        for (int c : {1, 64, 127, 128, 129, 191}) if (c <= n) cut.push_back(c);
+        if (cut.back() != n) cut.push_back(n);
+        R = (int)cut.size();
+        const size_t um = (size_t)m, nd[6] = {(size_t)std::max(NC * D, P * R) * um, (size_t)P * R * um, (size_t)NC2 * um * um,
+                                              (size_t)D * draws * um, (size_t)NC2 * um, (size_t)P * R};
+        size_t at = GUARD;
+        double **pd[6] = {&mu, &var, &sigma, &out, &cross, &logml};
+        for (size_t k : nd) at += k + GUARD;
+        host.assign(at, 0.0);
+        at = GUARD;
+        for (int k = 0; k < 6; ++k) { *pd[k] = host.data() + at; at += nd[k] + GUARD; }
+        ihost.assign(4 * GUARD + 2 * P + (size_t)D * draws, 0);
+        info = ihost.data() + GUARD;
+        cinfo = info + P + GUARD;
+        comp = cinfo + P + GUARD;
+    }
+    ngp_status create(ngp_ctx *c) { return ngp_factor_create(c, P, ks, n, t.data(), y.data(), 0, &f); }
+    void destroy() { ngp_factor_destroy(f); f = nullptr; }
+    ngp_status predict_long(bool appended, bool with_sigma) {
+        return ngp_factor_predict_long(f, appended ? d : 0, t_add.data(), D, y_add.data(), m, t_new.data(), 1, mu,
+                                       var, with_sigma ? sigma : nullptr, info);
+    }
+    ngp_status sample_long(bool appended, bool extras = true) {
+        return ngp_factor_sample_long(f, appended ? d : 0, t_add.data(), D, y_add.data(), m, t_new.data(), 1,
+                                      appended ? w2 : w0, draws, 17u, out, extras ? comp : nullptr,
+                                      extras ? mu : nullptr, extras ? var : nullptr, extras ? info : nullptr,
+                                      extras ? cinfo : nullptr);
+    }
+    ngp_status components_long(bool appended, bool with_sigma) {
+        return ngp_factor_components_long(f, appended ? d : 0, t_add.data(), D, y_add.data(), counts, comps, m,
+                                          t_new.data(), mu, cross, with_sigma ? sigma : nullptr, info);
+    }
+    ngp_status predict_origins(bool with_logml) {
+        return ngp_factor_predict_origins(f, R, cut.data(), m, t_new.data(), 1, mu, var, with_logml ? logml : nullptr,
+                                          info);
+    }
+    // The downloads of a call land at host offsets that depend on the chunk; the trace does not show
+    // them.  cover(call, ...) fills everything with a sentinel, runs the call and counts the elements of
+    // the named outputs (pointer, length) that are not 0 afterwards — the mock's device memory is zeroed
+    // and its copies are memcpy — plus the elements outside them that lost the sentinel.
+    struct Span { const void *p; size_t n; };
+    long cover(const std::function<ngp_status()> &call, const std::vector<Span> &written, ngp_status *st) {
+        const double ds = 7.5;
+        const int32_t is = 0x5a5a5a5a;
+        std::vector<char> dw(host.size(), 0), iw(ihost.size(), 0);
+        for (const Span &s : written) {
+            const double *pdbl = static_cast<const double *>(s.p);
+            const int32_t *pint = static_cast<const int32_t *>(s.p);
+            if (pdbl >= host.data() && pdbl < host.data() + host.size())
+                std::fill_n(dw.begin() + (pdbl - host.data()), s.n, 1);
+            else
+                std::fill_n(iw.begin() + (pint - ihost.data()), s.n, 1);
+        }
+        std::fill(host.begin(), host.end(), ds);
+        std::fill(ihost.begin(), ihost.end(), is);
+        *st = call();
+        long bad = 0;
+        for (size_t i = 0; i < host.size(); ++i) bad += dw[i] ? host[i] != 0.0 : host[i] != ds;
+        for (size_t i = 0; i < ihost.size(); ++i) bad += iw[i] ? ihost[i] != 0 : ihost[i] != is;
+        return bad;
+    }
 };
 
 struct Probes {
@@ -233,7 +360,39 @@ inline std::vector<Entry> table() {
         {"ngp_factor_predict_long d=0", [](ngp_ctx *) { return cq.predict_long(false, false); }, make, drop},
         {"ngp_factor_predict_long d=2 sigma", [](ngp_ctx *) { return cq.predict_long(true, true); }, make, drop},
         {"ngp_factor_predict_long d=2", [](ngp_ctx *) { return cq.predict_long(true, false); }, make, drop},
+        {"ngp_factor_sample_long d=0", [](ngp_ctx *) { return cq.sample_long(false); }, make, drop},
+        {"ngp_factor_sample_long d=2", [](ngp_ctx *) { return cq.sample_long(true); }, make, drop},
+        {"ngp_factor_components_long d=0", [](ngp_ctx *) { return cq.components_long(false, false); }, make, drop},
+        {"ngp_factor_components_long d=2 sigma", [](ngp_ctx *) { return cq.components_long(true, true); }, make, drop},
+        {"ngp_factor_predict_origins logml", [](ngp_ctx *) { return cq.predict_origins(true); }, make, drop},
+        {"ngp_factor_predict_origins", [](ngp_ctx *) { return cq.predict_origins(false); }, make, drop},
     };
+}
+
+// the long-horizon family on the two factors of Long: n = 191 with m = 70 dates (two blocks of sigma
+// for the sampler), n = 20 with m = 6
+inline std::vector<Entry> long_table() {
+    static Long l191(191, 70), l20(20, 6);
+    std::vector<Entry> all;
+    for (Long *lp : {&l191, &l20}) {
+        Long &l = *lp;
+        auto make = [&l](ngp_ctx *c) { return l.create(c); };
+        auto drop = [&l] { l.destroy(); };
+        const std::string at = " n=" + std::to_string(l.n);
+        auto add = [&](const char *name, std::function<ngp_status()> call) {
+            all.push_back({name + at, [call](ngp_ctx *) { return call(); }, make, drop});
+        };
+        add("ngp_factor_sample_long d=0", [&l] { return l.sample_long(false); });
+        add("ngp_factor_sample_long d=2 D=3", [&l] { return l.sample_long(true); });
+        add("ngp_factor_sample_long d=2 D=3 out alone", [&l] { return l.sample_long(true, false); });
+        add("ngp_factor_components_long d=0 sigma", [&l] { return l.components_long(false, true); });
+        add("ngp_factor_components_long d=0", [&l] { return l.components_long(false, false); });
+        add("ngp_factor_components_long d=2 D=3 sigma", [&l] { return l.components_long(true, true); });
+        add("ngp_factor_components_long d=2 D=3", [&l] { return l.components_long(true, false); });
+        add("ngp_factor_predict_origins logml", [&l] { return l.predict_origins(true); });
+        add("ngp_factor_predict_origins", [&l] { return l.predict_origins(false); });
+    }
+    return all;
 }
 
 }  // namespace oneshot

@@ -90,7 +90,9 @@ static void allocation_failure(const oneshot::Entry &e) {
 }
 
 int main() {
-    for (const oneshot::Entry &e : oneshot::table()) {
+    std::vector<oneshot::Entry> calls = oneshot::table();
+    for (const oneshot::Entry &e : oneshot::long_table()) calls.push_back(e);
+    for (const oneshot::Entry &e : calls) {
         copy_failures(e);
         allocation_failure(e);
     }

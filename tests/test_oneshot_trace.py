@@ -4,11 +4,15 @@ tests/sanitize/oneshot_trace.cpp walks the table of tests/sanitize/oneshot_calls
 on the mock HIP runtime (tests/sanitize/mock_hip.cpp with its trace on): the covariance call, the
 sampler, the mixture summaries on both scales, the trajectory targets, the component queries of a
 resident factor, the self tests and the microbenchmarks, the scores of paths handed in and of paths
-drawn on the device, the long-horizon query, each at a small shape and each twice; then the sampler,
-the targets and the path scores with invalid arguments, one line `call, fault: status` each.  Every
+drawn on the device, the four long-horizon calls (prediction, paths, decomposition, hindcasts) on
+factors with and without a main block, each at a small shape and each twice; then the sampler, the
+targets, the path scores and the long-horizon calls with invalid arguments, one line
+`call, fault: status` each; then the long-horizon calls on mock devices so small that the particles
+go through in two or three chunks, where the driver also checks that every output element is
+written and nothing around the outputs is.  Every
 copy (kind, bytes, stream), kernel launch (mangled name, grid, block, LDS bytes, stream, integer
 arguments) and event record of a call goes into one line, the number of records and their hash.
-The output must equal tests/golden/oneshot_trace_v2.txt byte for byte: the host code around these
+The output must equal tests/golden/oneshot_trace_v3.txt byte for byte: the host code around these
 calls may be rearranged, what it asks of the runtime on a successful call may not change.  To see
 WHAT moved, run the driver of two builds with --full and diff.  The golden file is regenerated only
 by a change that means to move a copy or a launch.  No GPU is involved."""
@@ -19,7 +23,7 @@ import pytest
 
 from tests.test_host_sanitizers import HIPCC, ROOT, build
 
-GOLDEN = os.path.join(ROOT, "tests", "golden", "oneshot_trace_v2.txt")
+GOLDEN = os.path.join(ROOT, "tests", "golden", "oneshot_trace_v3.txt")
 
 
 @pytest.mark.skipif(HIPCC is None, reason="no hipcc")
