@@ -1,12 +1,23 @@
 """numpy model of the DEVICE algorithm (not the oracle): same block decomposition, the same
 augmented-row trick and the same epilogue algebra the HIP kernels implement
-(nowcastautogp_amd/csrc/ngp_chol.hip, ngp_epilogue.hip).  Used by CPU tests to pin the
-algebra independently of GPU availability, and as executable documentation.
+(nowcastautogp_amd/csrc/ngp_col_kernels.h: chol_diag_kernel and the column steps; epilogue_kernel
+in ngp_kernels.hip).  Used by CPU tests to pin the algebra independently
+of GPU availability, and as executable documentation.
 
   main block   n0 = 64*floor(n/64) training points, factored left-looking by 64-wide block
                columns; the 64x64 diagonal solve uses 16x16 diagonal-block inverses only.
   aux rows     [tail+appended points | forecast points | y] ride along as extra rows:
                W = X L^-T, then everything else is small Schur-complement algebra on G = W W'.
+
+``nowcast_model(..., hooks=...)`` can make the model WRONG on purpose, in the ways a column kernel
+can be wrong about its geometry (tests/test_geometry_cases_cpu.py: the judge of the geometry grid
+must fail such a model):
+  aux_groups(naux, tile) -> g   16-row groups of aux tile ``tile`` (64 aux rows) a column step works
+                                on; rows from 16 g on stay the zeros the tile was filled with
+                                (right: every group that holds a real row)
+  k_omit(nb0, jj) -> (lo, hi)   columns k in [lo, hi) that the step of block column jj leaves out of
+                                its update of the rows below the diagonal tile and of the aux rows
+                                (right: None)
 """
 import math
 
@@ -36,8 +47,9 @@ def block_trsm(C, Ljj, dinv):
     return X
 
 
-def nowcast_model(program, t, y, t_add, y_add, t_new, noise_on_new=True, spec=None):
+def nowcast_model(program, t, y, t_add, y_add, t_new, noise_on_new=True, spec=None, hooks=None):
     sp = oracle_np._spec(spec)
+    hooks = hooks or {}
     ops, params, noise = program
     t, y = np.asarray(t, float), np.asarray(y, float)
     t_add, t_new = np.asarray(t_add, float), np.asarray(t_new, float)
@@ -54,8 +66,17 @@ def nowcast_model(program, t, y, t_add, y_add, t_new, noise_on_new=True, spec=No
     L = np.zeros((n0, n0))
     W = np.zeros_like(X)
     logdet0 = 0.0
+    naux = X.shape[0]
+    live = np.ones(naux, bool)           # aux rows a column step works on
+    if "aux_groups" in hooks:
+        for tile in range((naux + NB - 1) // NB):
+            live[tile * NB + TB * hooks["aux_groups"](naux, tile):(tile + 1) * NB] = False
     for j in range(n0 // NB):
         c0, c1 = j * NB, (j + 1) * NB
+        kk = np.ones(c0, bool)           # columns the step accumulates
+        omit = hooks["k_omit"](n0 // NB, j) if "k_omit" in hooks else None
+        if omit:
+            kk[omit[0]:omit[1]] = False
         Kjj = k(t0[c0:c1], t0[c0:c1]) + nz * np.eye(NB)
         Cjj = Kjj - L[c0:c1, :c0] @ L[c0:c1, :c0].T
         Ljj, dinv = diag_block_factor(Cjj)
@@ -63,13 +84,13 @@ def nowcast_model(program, t, y, t_add, y_add, t_new, noise_on_new=True, spec=No
         logdet0 += np.log(np.diag(Ljj)).sum()
         for r in range(j + 1, n0 // NB):
             r0, r1 = r * NB, (r + 1) * NB
-            C = k(t0[r0:r1], t0[c0:c1]) - L[r0:r1, :c0] @ L[c0:c1, :c0].T
+            C = k(t0[r0:r1], t0[c0:c1]) - L[r0:r1, :c0][:, kk] @ L[c0:c1, :c0][:, kk].T
             L[r0:r1, c0:c1] = block_trsm(C, Ljj, dinv)
-        C = X[:, c0:c1] - W[:, :c0] @ L[c0:c1, :c0].T
-        W[:, c0:c1] = block_trsm(C, Ljj, dinv)
+        C = X[:, c0:c1] - W[:, :c0][:, kk] @ L[c0:c1, :c0][:, kk].T
+        W[live, c0:c1] = block_trsm(C, Ljj, dinv)[live]
     G = W @ W.T
     A, T, Y = slice(0, da), slice(da, da + m), da + m
-    # ---- epilogue (device: ngp_epilogue kernel) ---------------------------------------
+    # ---- epilogue (device: epilogue_kernel) ---------------------------------------
     S_AA = k(ta, ta) + nz * np.eye(da) - G[A, A]
     L_A = np.linalg.cholesky(S_AA) if da else np.zeros((0, 0))
     S_TA = k(t_new, ta) - G[T, A]
