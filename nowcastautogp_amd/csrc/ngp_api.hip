@@ -10,7 +10,10 @@
 //                        (FillLists, ngp_job, factor_chunk, stage_general, refinement, ngp_job_*, the
 //                        *_stage calls, *_direct, ngp_nowcast_batch); the resident factor with its
 //                        long-horizon and component queries, ngp_kernel_components / _terms,
-//                        ngp_cov_batch; gradient jobs and the HMC trajectory
+//                        ngp_cov_batch
+//   ngp_host_grad.h      gradient jobs: GradLeaf, LeafRun and its working blocks, the pair run, the
+//                        HMC trajectory, ngp_grad_job and its entry points, logml_grad_direct — on
+//                        the context, DevCall and the value jobs' sweep (factor_chunk, FillLists)
 //   ngp_host_mixture.h   the forecast mixture: weight normalisation, MixInput, sampler, summaries,
 //                        mapped CRPS, trajectory targets, ensemble and path scores — on the context
 //                        and DevCall alone: no job, factor or gradient code
@@ -158,8 +161,6 @@ struct ScopedEvent {   // a timing event of a microbenchmark
 }  // namespace
 
 namespace {
-
-constexpr int k_nparams[10] = {0, 1, 3, 2, 3, 3, 0, 0, 2, 2};
 
 // ---------------------------------------------------------------------------------------
 // program validation + flattening for the device
@@ -2644,980 +2645,7 @@ extern "C" ngp_status ngp_cov_batch(ngp_ctx *c, int32_t B, const ngp_kernel *ker
     return call.sync();
 }
 
-// ---------------------------------------------------------------------------------------
-// gradient jobs: the inputs of ngp_logml_grad_batch kept on the device across calls
-// ---------------------------------------------------------------------------------------
-struct GradLeaf {
-    bool toep_path = false;                // the Toeplitz gradient path
-    ngp_ctx *ctx = nullptr;
-    JobGeom g{};
-    int B = 0, n = 0;
-    PinVec<DevProgram> hp;                 // compiled programs (device parameter order), page-locked: they go up on every run
-    std::vector<std::vector<int>> perm;    // device parameter k of item i = the caller's perm[i][k]
-    std::vector<int32_t> n_ops, n_params;
-    // ONE device arena for everything that crosses the bus:
-    //   [programs | t | y | lattice indices | info | logdet | gradient | logml]
-    unsigned char *io = nullptr;
-    size_t o_t = 0, o_y = 0, o_q = 0, o_info = 0, o_logdet = 0, o_grad = 0, o_logml = 0, io_bytes = 0;
-    // lattice jobs: the items by the shape of their reduced program, as in a staged value job
-    // (ascending leaf indices; the fill of the main tiles runs on the value jobs' kernels)
-    FillLists fill;
-    PinVec<unsigned char> h_in, h_out;        // staging copy of a small job's inputs; results
-    bool fresh = false;                    // info / logdet still hold the zeros they were staged with
-    bool progs_dirty = false;              // set_params since the last upload
-    ngp_spec spec{};
-    int last_chunk = 0;                    // items per memory-driven chunk of the last run (ngp_grad_job_info)
-    // trajectories (ngp_grad_job_hmc): the leaf's latents in the caller's order, on the device from
-    // the first trajectory to the job's end
-    //   [off | slot || kind | frozen | z | pm || theta | U0 K0 U1 K1 logml1 | info1 || trace rows]
-    // kind .. pm go up in one copy per call, z .. info1 come back in one
-    unsigned char *hmc = nullptr;
-    size_t t_off = 0, t_slot = 0, t_kind = 0, t_frozen = 0, t_z = 0, t_pm = 0, t_theta = 0, t_sc = 0,
-           t_info = 0, t_trace = 0, t_rows = 0;
-    std::vector<int32_t> loff;             // [B + 1] first latent of every item
-    PinVec<unsigned char> t_up, t_down;
-    // The one place the outcome of a run or a trajectory reaches the leaf, after its scope has
-    // synchronised: the staging copy has left h_in, and after a failure the device holds neither the
-    // host's programs nor clean info / logdet — the next run sends and clears them.
-    void run_ended(ngp_status st) {
-        if (!h_in.empty()) PinVec<unsigned char>().swap(h_in);
-        if (st) {
-            progs_dirty = true;
-            fresh = false;
-        }
-    }
-};
-
-// What a gradient evaluation is staged under: the context's spec and the switches that pick its
-// routes.  A job keeps the one it was staged with; a combined group of gradient requests is staged
-// under its members' common one, which need not be the context's current one (ngp_grad_job_run).
-struct GradRoute {
-    ngp_spec spec{};
-    bool toeplitz = true, invariant = false, short_series = true;
-};
-
-static GradRoute grad_route_of(ngp_ctx *c) {   // c->mu held by the caller
-    GradRoute r;
-    r.spec = c->spec;
-    r.toeplitz = c->toeplitz;
-    r.invariant = c->invariant;
-    r.short_series = c->short_series;
-    return r;
-}
-
-static bool grad_route_same(const GradRoute &a, const GradRoute &b) {
-    const ngp_spec &x = a.spec, &y = b.spec;
-    return x.se_form == y.se_form && x.periodic_form == y.periodic_form && x.cp_form == y.cp_form &&
-           x.precision == y.precision && x.jitter == y.jitter && x.mixed_tau == y.mixed_tau &&
-           x.refine_tol == y.refine_tol && x.refine_max == y.refine_max && a.toeplitz == b.toeplitz &&
-           a.invariant == b.invariant && a.short_series == b.short_series;
-}
-
-namespace {
-
-void grad_leaf_destroy(GradLeaf *j);
-
-// toep_path: the items are stationary trees on a regular series — aux rows [y' ; e_1'] instead of
-// [I ; y'] (the caller, ngp_grad_stage, has checked both)
-// yrows: item b's observations are yrows[b][0..n) (y / ldy are then not read) — a subset of a
-// caller's batch, or the rows of several callers' arrays in a combined call
-ngp_status grad_leaf_stage(ngp_ctx *c, int32_t B, const ngp_kernel *kernels, int32_t n,
-                           const double *t, const double *y, int64_t ldy, bool toep_path,
-                           GradLeaf **out, const double *const *yrows, const GradRoute &route) {
-    if (!c || !out || !kernels || !t || (!y && !yrows) || B <= 0 || n <= 0) return NGP_ERR_ARG;
-    *out = nullptr;
-    GradLeaf *j = new (std::nothrow) GradLeaf();
-    if (!j) return NGP_ERR_TOO_LARGE;
-    j->ctx = c;
-    // (the leaf before the scope: on a failure the scope ends, synchronised, before the leaf is destroyed)
-    std::unique_ptr<GradLeaf, void (*)(GradLeaf *)> guard(j, grad_leaf_destroy);
-    j->toep_path = toep_path;
-    j->B = B;
-    j->n = n;
-    j->hp.resize((size_t)B);
-    j->perm.resize((size_t)B);
-    j->n_ops.resize((size_t)B);
-    j->n_params.resize((size_t)B);
-    int maxstat = 0, maxcp = 0, maxops = 0, maxtab = 0;
-    for (int i = 0; i < B; ++i) {
-        int ns = 0, nc = 0, nt = 0;
-        ngp_status st = compile_program(&kernels[i], &j->hp[(size_t)i], &j->perm[(size_t)i], &ns, &nc, &nt);
-        if (st) return st;
-        maxstat = std::max(maxstat, ns);
-        maxtab = std::max(maxtab, nt);
-        maxcp = std::max(maxcp, nc);
-        maxops = std::max(maxops, (int)kernels[i].n_ops);
-        j->n_ops[(size_t)i] = kernels[i].n_ops;
-        j->n_params[(size_t)i] = kernels[i].n_params;
-    }
-    // Geometry: the matrix is padded to a multiple of 64 with identity rows/cols (log 1 = 0, a
-    // zero in y), and the aux block is [I ; y'] so that the factorisation leaves W = [L^-T ; z'].
-    JobGeom &g = j->g;
-    g.B = B;
-    g.n0 = (n + NB - 1) / NB * NB;
-    g.nb0 = g.n0 / NB;
-    g.n_real = n;
-    g.aux_identity = toep_path ? 0 : 1;
-    g.aux_e1 = toep_path ? 1 : 0;
-    g.maxops = maxops;
-    g.naux = toep_path ? 2 : g.n0 + 1;
-    g.naux_pad = toep_path ? NB : g.n0 + NB;
-    g.D = 1;
-    g.y_shared = (ldy == 0 && !yrows) ? 1 : 0;
-    g.ld = g.n0;
-    g.item_stride = (int64_t)(g.n0 + g.naux_pad) * g.n0;
-    if (item_too_large(g.item_stride)) return NGP_ERR_TOO_LARGE;
-    g.npts = g.n0;
-    g.maxstat = std::max(maxstat, 1);
-    g.maxcp = std::max(maxcp, 1);
-    std::vector<int32_t> h_q;
-    {
-        std::vector<double> real(t, t + n);
-        double hh = 0.0;
-        int R = 0;
-        if (detect_lattice(real, &hh, &h_q, &R)) {
-            g.lattice = 1;
-            g.h = hh;
-            g.R = R;
-            h_q.resize((size_t)g.n0, 0);
-            // the subtree tables of the reduced programs behind the per-leaf tables (tables_kernel),
-            // and the items sorted by the kernel that fills their main tiles (launch_fill)
-            g.tab_sub = g.maxstat;
-            g.maxstat += maxtab;
-            j->fill.sort_items(j->hp.data(), B);
-        }
-    }
-    const int ny = g.y_shared ? 1 : B;
-    const int GP = NGP_MAX_PARAMS + 1;
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    j->o_t = al(sizeof(DevProgram) * (size_t)B);
-    j->o_y = j->o_t + al(8 * (size_t)g.n0);
-    j->o_q = j->o_y + al(8 * (size_t)ny * g.n0);
-    size_t off = j->o_q + (g.lattice ? al(4 * (size_t)g.n0) : 0);
-    j->fill.layout([&](size_t bytes) { const size_t o = off; off += al(bytes); return o; });
-    j->o_info = off;
-    j->o_logdet = j->o_info + al(4 * (size_t)B);
-    j->o_grad = j->o_logdet + al(8 * (size_t)B);
-    j->o_logml = j->o_grad + al(8 * (size_t)B * GP);
-    j->io_bytes = j->o_logml + al(8 * (size_t)B);
-    j->h_in.assign(j->o_grad, 0);
-    j->h_out.resize(j->io_bytes - j->o_info);
-    std::memcpy(j->h_in.data(), j->hp.data(), sizeof(DevProgram) * (size_t)B);
-    {
-        double *ht = (double *)(j->h_in.data() + j->o_t), *hy = (double *)(j->h_in.data() + j->o_y);
-        for (int i = 0; i < g.n0; ++i) ht[i] = t[std::min(i, n - 1)];
-        for (int b = 0; b < ny; ++b)
-            std::memcpy(hy + (size_t)b * g.n0, yrows ? yrows[b] : y + (int64_t)b * ldy, 8 * (size_t)n);
-        if (g.lattice) std::memcpy(j->h_in.data() + j->o_q, h_q.data(), 4 * (size_t)g.n0);
-        j->fill.copy_to(j->h_in.data());
-    }
-    DevCall call(c);
-    j->spec = route.spec;
-    g.invariant = route.invariant ? 1 : 0;
-    g.short_series = route.short_series ? 1 : 0;
-    // (gradient jobs store every tile: their tables are per leaf, and on a regular series the
-    // stationary trees — the ones structured storage could serve — are on the Toeplitz path)
-    if (call.keep(&j->io, j->io_bytes).status()) return call.status();   // nothing is queued yet
-    // the front part goes up in one copy (info and logdet arrive as the zeros the factorisation
-    // expects): a 24-particle call of a fit on a short series is a chain of dependent launches a
-    // few microseconds long, and each separate copy or memset was one more of them
-    const ngp_status st = stage_up(call, c->stream, j->io, j->h_in, j->h_in.size());
-    if (st) return st;
-    j->fresh = true;
-    *out = guard.release();
-    return NGP_OK;
-}
-
-ngp_status grad_leaf_set_params(GradLeaf *j, const double *params, const double *noise) {
-    if (!j || !params || !noise) return NGP_ERR_ARG;
-    size_t off = 0;
-    for (int i = 0; i < j->B; ++i) {
-        DevProgram &P = j->hp[(size_t)i];
-        const int np = j->n_params[(size_t)i];
-        // values are taken as ngp_logml_grad_batch takes them: a parameter the kernels cannot use
-        // shows in the item's info, not here
-        for (int q = 0; q < np; ++q) P.params[q] = params[off + (size_t)j->perm[(size_t)i][(size_t)q]];
-        P.noise = noise[i];
-        off += (size_t)np;
-    }
-    j->progs_dirty = true;
-    return NGP_OK;
-}
-
-// One evaluation of a leaf in three steps, so that two leaves of a small batch can be in flight side
-// by side (grad_pair_run): lay the working storage out in the context's workspace, enqueue
-// everything on a lane's streams (upload of new parameters ... results on their way back), and,
-// after the lane has been synchronised, unpack.
-struct LeafRun {
-    GradLeaf *j = nullptr;
-    int Bc = 0;
-    void *d_L = nullptr, *d_dinv = nullptr, *d_tab = nullptr, *d_sig = nullptr, *d_dtab = nullptr,
-         *d_kinv = nullptr, *d_alpha = nullptr, *d_quad = nullptr, *d_part = nullptr, *d_items = nullptr;
-    std::vector<int32_t> h_items;   // read by a queued copy: a LeafRun is declared before its run's scope
-    bool items_ready = false;       // a later evaluation of a trajectory: d_items holds the sorted items
-    double *splitk = nullptr;       // pair runs: the context's split-k buffer for this leaf's value kernels
-
-    size_t item_bytes() const {
-        const JobGeom &g = j->g;
-        const int GP = NGP_MAX_PARAMS + 1, ntri = g.nb0 * (g.nb0 + 1) / 2, nd = (g.n_real + 255) / 256;
-        const size_t l_bytes = (size_t)g.item_stride * 8;
-        const size_t tab_bytes = g.lattice ? 8 * (size_t)g.maxstat * g.R : 0;
-        const size_t sig_bytes = g.lattice ? 8 * (size_t)g.maxcp * g.npts : 0;
-        const size_t aux_bytes = 8 * (size_t)g.naux_pad * g.n0;
-        return j->toep_path ? l_bytes + 4 * tab_bytes + sig_bytes + 8 * (size_t)NB * NB * g.nb0 + aux_bytes +
-                                  8 * (size_t)g.n0 + 8 * (size_t)nd * GP
-                            : l_bytes + 4 * tab_bytes + sig_bytes + 8 * (size_t)g.n0 * g.n0 +
-                                  8 * (size_t)g.n0 + 8 * (size_t)ntri * GP;
-    }
-    // the working buffers of a chunk of Bc items, requested from `dalloc` (measured, then taken)
-    ngp_status layout(WsPlan &dalloc) {
-        const JobGeom &g = j->g;
-        const bool tp = j->toep_path;
-        const int GP = NGP_MAX_PARAMS + 1, ntri = g.nb0 * (g.nb0 + 1) / 2, nd = (g.n_real + 255) / 256;
-        const size_t l_bytes = (size_t)g.item_stride * 8;
-        const size_t tab_bytes = g.lattice ? 8 * (size_t)g.maxstat * g.R : 0;
-        const size_t sig_bytes = g.lattice ? 8 * (size_t)g.maxcp * g.npts : 0;
-        const size_t aux_bytes = 8 * (size_t)g.naux_pad * g.n0;
-        ngp_status r;
-        (void)((r = dalloc(&d_L, l_bytes * (size_t)Bc)) ||
-               // the Toeplitz path keeps every block inverse M_j for its backward sweep
-               (r = dalloc(&d_dinv, 8 * (size_t)Bc * NB * NB * (tp ? g.nb0 : 1))) ||
-               (g.lattice && ((r = dalloc(&d_tab, tab_bytes * (size_t)Bc)) ||
-                              (r = dalloc(&d_sig, sig_bytes * (size_t)Bc)) ||
-                              (r = dalloc(&d_dtab, 3 * tab_bytes * (size_t)Bc)))) ||
-               // general path: K^-1 [n0 x n0]; Toeplitz path: A = [a' ; x'] (one aux tile)
-               (r = dalloc(&d_kinv, tp ? aux_bytes * (size_t)Bc : 8 * (size_t)Bc * g.n0 * g.n0)) ||
-               (r = dalloc(&d_alpha, 8 * (size_t)Bc * g.n0)) ||      // Toeplitz path: w per distance
-               (r = dalloc(&d_quad, 8 * (size_t)Bc)) ||
-               // a chunk that is cut finer (split 2 or 4) writes at most 4096 partial rows; a coarse one Bc ntri
-               (r = dalloc(&d_part,
-                           tp ? 8 * (size_t)Bc * nd * GP
-                              : 8 * std::max<size_t>((size_t)Bc * ntri * grad_contract_split(ntri, Bc, g.invariant != 0),
-                                                     4096) * GP)) ||
-               (r = dalloc(&d_items, 4 * (size_t)j->B)));
-        return r;
-    }
-
-    // everything of the evaluation on the lane's streams, as steps of the run's scope, which waits for
-    // the lane; tm: the scope's timer of that lane
-    // copy_out: the results follow the last kernel into h_out (a trajectory reads them on the device)
-    void launch(DevCall &call, const Lane &ln, EventTimer &tm, bool no_lane_split, bool copy_out = true) {
-        ngp_ctx *c = j->ctx;
-        const JobGeom &g = j->g;
-        const int B = j->B;
-        const bool tp = j->toep_path;
-        const int GP = NGP_MAX_PARAMS + 1;
-        hipStream_t s = ln.main;
-        const DevSpec sp = dev_spec(j->spec);
-        if (!items_ready) h_items.assign((size_t)B, 0);
-        unsigned char *const io = j->io;
-        void *const d_prog = io, *const d_t = io + j->o_t, *const d_y = io + j->o_y,
-                    *const d_q = g.lattice ? io + j->o_q : nullptr, *const d_info = io + j->o_info,
-                    *const d_logdet = io + j->o_logdet, *const d_grad = io + j->o_grad,
-                    *const d_logml = io + j->o_logml;
-        // new parameters for the same trees: the programs go up again, nothing else.  On a lattice the
-        // first kernel of the chain (tables_kernel) fetches them from the page-locked host copy itself
-        // and leaves the device copy for the rest — a copy ahead of the chain cost 20 us of a 24-item
-        // call's 110.
-        const bool fetch_in_kernel = j->progs_dirty && g.lattice && g.n0 > 0 &&
-                                     pinned_pool().is_pinned(j->hp.data());
-        if (j->progs_dirty && !fetch_in_kernel) call.up(d_prog, j->hp.data(), sizeof(DevProgram) * (size_t)B, s);
-        // a re-run: info | logdet are contiguous in the arena (short jobs: written outright)
-        if (!j->fresh && !small_job(g, Bc)) call.zero(d_info, j->o_grad - j->o_info, s);
-        // (for the evaluations that follow in this scope; a failure takes both back: GradLeaf::run_ended)
-        j->progs_dirty = false;
-        j->fresh = false;
-        for (int b0 = 0; b0 < B; b0 += Bc) {
-            const int bc = std::min(Bc, B - b0);
-            ChunkPtrs p{};
-            p.L = (double *)d_L;
-            p.dinv = (double *)d_dinv;
-            p.progs = (const DevProgram *)d_prog + b0;
-            p.progs_src = fetch_in_kernel ? j->hp.data() + b0 : nullptr;
-            p.t0 = (const double *)d_t;
-            p.taux = (const double *)d_t;
-            p.y0 = (const double *)d_y + (g.y_shared ? 0 : (int64_t)b0 * g.n0);
-            p.logdet = (double *)d_logdet + b0;
-            p.info = (int32_t *)d_info + b0;
-            p.tab = (double *)d_tab;
-            p.sig = (double *)d_sig;
-            p.qpts = (const int32_t *)d_q;
-            p.dtab = (double *)d_dtab;
-            p.splitk_part = splitk;
-            if (g.lattice) j->fill.share_of(io, b0, bc, &p);
-            if (g.lattice) call.timed(tm, 4, 0.0, 0.0, [&] { launch_tables(g, p, bc, sp, s); });
-            call.timed(tm, cost_fill_grad(g, bc, tp), [&] { launch_fill(g, p, bc, sp, s); });
-            const size_t mstep = tp ? (size_t)bc * NB * NB : 0;
-            call.run([&] { factor_chunk(ln, g, p, bc, tm, mstep, nullptr, nullptr, nullptr, no_lane_split); });
-            if (tp) {
-                // z'z, then A = X K^-1 by one backward sweep of the two aux rows
-                call.timed(tm, cost_toep_quad(g, bc),
-                       [&] { launch_toep_quad(g, (const double *)d_L, (double *)d_quad, bc, s); });
-                for (int cc = g.nb0 - 1; cc >= 0; --cc)
-                    call.timed(tm, cost_toep_back(bc, cc), [&] {
-                        launch_aux_back(g, p, p.dinv, mstep, (double *)d_kinv, 0, bc, cc, s);
-                    });
-            } else {
-                const bool kinv_small = kinv_route(g, bc) == KINV_SMALL;
-                call.timed(tm, cost_kinv(g, bc), [&] {
-                    if (kinv_small)
-                        launch_grad_kinv_small(g, (const double *)d_L, (double *)d_kinv, (double *)d_alpha,
-                                               (double *)d_quad, bc, s);
-                    else
-                        launch_grad_kinv(g, (const double *)d_L, (double *)d_kinv, (double *)d_alpha,
-                                         (double *)d_quad, bc, s, ln.side, ln.fork, ln.join);
-                });
-            }
-            // the chunk's items sorted by tree size: every size class runs on the contraction kernel
-            // sized for it
-            const bool by_size = contract_by_size(g, tp, bc);
-            int32_t counts[GRAD_BUCKETS] = {};
-            if (by_size) for (int i = 0; i < bc; ++i) ++counts[grad_bucket(j->n_ops[(size_t)(b0 + i)])];
-            if (by_size && !items_ready) {
-                int32_t pos[GRAD_BUCKETS], acc = 0;
-                for (int k = 0; k < GRAD_BUCKETS; ++k) { pos[k] = acc; acc += counts[k]; }
-                for (int i = 0; i < bc; ++i)
-                    h_items[(size_t)b0 + (size_t)pos[grad_bucket(j->n_ops[(size_t)(b0 + i)])]++] = i;
-                call.up((int32_t *)d_items + b0, h_items.data() + b0, 4 * (size_t)bc, s);
-            }
-            if (tp) {
-                call.timed(tm, cost_toep_grad(g, bc), [&] {
-                    launch_toep_grad(g, p, (const double *)d_kinv, (double *)d_alpha,
-                                     (const double *)d_quad, (double *)d_part,
-                                     (double *)d_grad + (int64_t)b0 * GP, (double *)d_logml + b0, bc, sp,
-                                     s, by_size ? (const int32_t *)d_items + b0 : nullptr, counts);
-                });
-            } else {
-                call.timed(tm, cost_contract(g, bc), [&] {
-                    launch_grad_contract(g, p, (const double *)d_kinv, (const double *)d_alpha,
-                                         (const double *)d_quad, (double *)d_part,
-                                         (double *)d_grad + (int64_t)b0 * GP, (double *)d_logml + b0,
-                                         bc, sp, s, by_size ? (const int32_t *)d_items + b0 : nullptr,
-                                         counts, ln.side, ln.fork, ln.join);
-                });
-            }
-        }
-        if (copy_out) call.down(j->h_out.data(), d_info, j->h_out.size(), s);
-    }
-
-    // after the lane is synchronised: device parameter order -> caller's order; d/d noise last
-    void unpack(double *logml, double *grad, int32_t *info) {
-        const int GP = NGP_MAX_PARAMS + 1;
-        const int32_t *h_info = (const int32_t *)j->h_out.data();
-        const double *h_grad = (const double *)(j->h_out.data() + (j->o_grad - j->o_info)),
-                     *h_lm = (const double *)(j->h_out.data() + (j->o_logml - j->o_info));
-        size_t off = 0;
-        for (int i = 0; i < j->B; ++i) {
-            const int np = j->n_params[(size_t)i];
-            for (int k = 0; k < np; ++k)
-                grad[off + (size_t)j->perm[(size_t)i][(size_t)k]] = h_grad[(size_t)i * GP + (size_t)k];
-            grad[off + (size_t)np] = h_grad[(size_t)i * GP + (size_t)np];
-            off += (size_t)np + 1;
-            if (logml) logml[i] = h_lm[(size_t)i];
-            if (info) info[i] = h_info[(size_t)i];
-        }
-    }
-};
-
-// The memory-driven chunk of a leaf's run, laid out in the context's workspace (r.Bc and the d_*
-// pointers): as many items as the memory figure allows, halved when the device cannot hold that
-// after all (other handles, rounding).
-ngp_status chunk_for(ngp_ctx *c, LeafRun &r) {
-    const size_t B = (size_t)r.j->B, item_bytes = r.item_bytes();
-    if (B * item_bytes > c->mem_cap) c->refresh_mem_cap();   // large job: today's figure
-    r.Bc = (int)std::min<size_t>(std::min<size_t>(B, MAX_CHUNK_ITEMS), std::max<size_t>(1, c->mem_cap / item_bytes));
-    for (;; r.Bc = (r.Bc + 1) / 2) {
-        const ngp_status st = ws_layout(c, [&](WsPlan &w) { return r.layout(w); });
-        if (!st) r.j->last_chunk = r.Bc;
-        if (st != NGP_ERR_TOO_LARGE || r.Bc <= 1) return st;
-    }
-}
-
-ngp_status grad_leaf_run(GradLeaf *j, double *logml, double *grad, int32_t *info) {
-    if (!j || !grad) return NGP_ERR_ARG;
-    ngp_ctx *c = j->ctx;
-    LeafRun r;
-    r.j = j;
-    DevCall call(c);
-    if (call.status()) return call.status();
-    const ngp_status fit = chunk_for(c, r);
-    if (fit) return fit;   // nothing is queued yet
-    r.launch(call, lane_of(c), call.tm, false);
-    const ngp_status st = call.sync();
-    j->run_ended(st);
-    if (!st) r.unpack(logml, grad, info);
-    return st;
-}
-
-// The two leaves of a SMALL mixed batch side by side, each on its own pair of streams (the lanes of
-// the two-lane sweep): one after the other they are two chains of dependent launches where the
-// unsplit batch is one (64 items at n = 2048: 16.3 ms against 15.3).  Both as single chunks in one
-// workspace reservation; NGP_ERR_TOO_LARGE if that does not fit (the caller then runs them in turn).
-ngp_status grad_pair_run(GradLeaf *a, double *lm_a, double *g_a, int32_t *info_a, GradLeaf *b,
-                         double *lm_b, double *g_b, int32_t *info_b) {
-    ngp_ctx *c = a->ctx;
-    LeafRun ra, rb;
-    ra.j = a;
-    rb.j = b;
-    DevCall call(c);
-    if (call.status()) return call.status();
-    if (!c->make_lanes(2)) return NGP_ERR_TOO_LARGE;
-    ra.Bc = a->last_chunk = a->B;
-    rb.Bc = b->last_chunk = b->B;
-    WsPlan measure{c, true}, take{c, false};
-    (void)ra.layout(measure);
-    (void)rb.layout(measure);
-    if (measure.total > c->mem_cap) c->refresh_mem_cap();
-    if (measure.total > c->mem_cap) return NGP_ERR_TOO_LARGE;
-    ngp_status st = c->ws_reserve(measure.total);
-    if (st) return st;
-    if ((st = ra.layout(take)) || (st = rb.layout(take))) return st;   // nothing is queued yet
-    // the Toeplitz leaf runs on the value kernels: their split-k fat steps of late columns (small
-    // chunks) need the context's buffer, which factor_chunk only reserves for a chunk it owns whole
-    if (b->toep_path && splitk_eligible(b->g, b->B, false, false) && c->splitk_reserve(b->B) == NGP_OK)
-        rb.splitk = c->splitk_part;
-    const Lane l0 = lane_of(c);
-    const Lane l1 = lane_of(c, 1);
-    EventTimer &tm1 = call.second_lane();
-    // what the context's stream holds (the staging copies of both leaves) comes first on lane 1 too
-    call.run([&] {
-        (void)hipEventRecord(c->ev_lane_go, c->stream);
-        (void)hipStreamWaitEvent(l1.main, c->ev_lane_go, 0);
-    });
-    ra.launch(call, l0, call.tm, true);
-    rb.launch(call, l1, tm1, true);
-    st = call.sync();
-    a->run_ended(st);
-    b->run_ended(st);
-    if (st) return st;
-    ra.unpack(lm_a, g_a, info_a);
-    rb.unpack(lm_b, g_b, info_b);
-    return NGP_OK;
-}
-
-// One trajectory of a leaf (ngp_grad_job_hmc): kind / frozen / z0 / mom and the outputs are the
-// leaf's latents back to back in the caller's order.  The working storage is laid out once, the
-// n_leapfrog + 1 evaluations are LeafRun::launch as ngp_grad_job_run enqueues it, the step kernel
-// between them writes the next parameters into the device programs; one copy back, one
-// synchronisation.  z_trace: null or [n_leapfrog + 1][latents of the leaf].
-struct HmcOut {
-    double *z1, *mom1, *theta1, *U0, *K0, *U1, *K1, *lm1;
-    int32_t *info1;
-    double *trace;
-};
-
-ngp_status grad_leaf_hmc(GradLeaf *j, const ngp_hmc_config *cfg, const uint8_t *kind,
-                         const uint8_t *frozen, const double *z0, const double *mom, const HmcOut &o) {
-    ngp_ctx *c = j->ctx;
-    const int B = j->B, L = cfg->n_leapfrog;
-    // read by queued copies: before the scope
-    PinVec<unsigned char> maps;
-    LeafRun r;
-    r.j = j;
-    DevCall call(c);
-    if (call.status()) return call.status();
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    const size_t rows = o.trace ? (size_t)L + 1 : 0;
-    if (!j->hmc || rows > j->t_rows) {
-        // first trajectory of the job (or the first that asks for a longer trace): the arena, and
-        // the maps that do not change — item offsets, and the inverse of GradLeaf::perm
-        j->loff.assign((size_t)B + 1, 0);
-        for (int i = 0; i < B; ++i) j->loff[(size_t)i + 1] = j->loff[(size_t)i] + j->n_params[(size_t)i] + 1;
-        const size_t NL = (size_t)j->loff[(size_t)B];
-        j->t_off = 0;
-        j->t_slot = al(4 * ((size_t)B + 1));
-        j->t_kind = j->t_slot + al(NL);
-        j->t_frozen = j->t_kind + al(NL);
-        j->t_z = j->t_frozen + al(NL);
-        j->t_pm = j->t_z + al(8 * NL);
-        j->t_theta = j->t_pm + al(8 * NL);
-        j->t_sc = j->t_theta + al(8 * NL);
-        j->t_info = j->t_sc + 5 * al(8 * (size_t)B);
-        j->t_trace = j->t_info + al(4 * (size_t)B);
-        unsigned char *q = nullptr;
-        if (call.keep(&q, j->t_trace + 8 * NL * rows).status()) return call.status();   // nothing is queued yet
-        c->release(j->hmc);
-        j->hmc = q;
-        j->t_rows = rows;
-        j->t_up.assign(j->t_theta - j->t_kind, 0);
-        j->t_down.assign(j->t_trace - j->t_z, 0);
-        maps.assign(j->t_kind, 0);
-        std::memcpy(maps.data(), j->loff.data(), 4 * ((size_t)B + 1));
-        for (int i = 0; i < B; ++i) {
-            unsigned char *sl = maps.data() + j->t_slot + j->loff[(size_t)i];
-            const int np = j->n_params[(size_t)i];
-            for (int k = 0; k < np; ++k) sl[j->perm[(size_t)i][(size_t)k]] = (unsigned char)k;
-            sl[np] = (unsigned char)np;
-        }
-        // the arena is the job's only with its maps in it: a round trip of its own, once per job
-        if (call.up(j->hmc, maps.data(), maps.size()).wait()) {
-            c->release(j->hmc);
-            j->hmc = nullptr;
-            j->t_rows = 0;
-            return call.status();   // synchronised
-        }
-    }
-    const size_t NL = (size_t)j->loff[(size_t)B];
-    {
-        unsigned char *up = j->t_up.data();
-        std::memcpy(up, kind, NL);
-        if (frozen) std::memcpy(up + (j->t_frozen - j->t_kind), frozen, NL);
-        else std::memset(up + (j->t_frozen - j->t_kind), 0, NL);
-        std::memcpy(up + (j->t_z - j->t_kind), z0, 8 * NL);
-        std::memcpy(up + (j->t_pm - j->t_kind), mom, 8 * NL);
-    }
-    const ngp_status fit = chunk_for(c, r);
-    if (fit) return fit;   // nothing is queued
-    hipStream_t s = c->stream;
-    unsigned char *const h = j->hmc;
-    HmcDev a{};
-    a.progs = (DevProgram *)j->io;
-    a.grad = (const double *)(j->io + j->o_grad);
-    a.logml = (const double *)(j->io + j->o_logml);
-    a.info = (const int32_t *)(j->io + j->o_info);
-    a.off = (const int32_t *)(h + j->t_off);
-    a.slot = h + j->t_slot;
-    a.kind = h + j->t_kind;
-    a.frozen = h + j->t_frozen;
-    a.z = (double *)(h + j->t_z);
-    a.pm = (double *)(h + j->t_pm);
-    a.theta = (double *)(h + j->t_theta);
-    const size_t scb = al(8 * (size_t)B);
-    a.U0 = (double *)(h + j->t_sc);
-    a.K0 = (double *)(h + j->t_sc + scb);
-    a.U1 = (double *)(h + j->t_sc + 2 * scb);
-    a.K1 = (double *)(h + j->t_sc + 3 * scb);
-    a.lm1 = (double *)(h + j->t_sc + 4 * scb);
-    a.info1 = (int32_t *)(h + j->t_info);
-    a.eps = cfg->eps;
-    for (int k = 0; k < 5; ++k) {
-        a.mu[k] = k >= 2 ? cfg->prior_mu[k] : 0.0;
-        a.sigma[k] = k >= 2 ? cfg->prior_sigma[k] : 1.0;
-    }
-    a.B = B;
-    double *const trace = o.trace ? (double *)(h + j->t_trace) : nullptr;
-    // the device writes its own parameters from here on: whatever set_params left is superseded
-    j->progs_dirty = false;
-    call.up(h + j->t_kind, j->t_up.data(), j->t_up.size());
-    auto step = [&](int phase, int row) {
-        a.phase = phase;
-        a.trace = trace && row >= 0 ? trace + (size_t)row * NL : nullptr;
-        call.timed(call.tm, 4, 0.0, 0.0, [&] { launch_hmc_step(a, s); });
-    };
-    step(HMC_INIT, 0);
-    for (int ev = 0; ev <= L && !call.status(); ++ev) {
-        r.launch(call, lane_of(c), call.tm, false, false);
-        r.items_ready = true;
-        step(ev == L ? HMC_LAST : ev == 0 ? HMC_FIRST : HMC_MIDDLE, ev == L ? -1 : ev + 1);
-    }
-    call.down(j->t_down.data(), h + j->t_z, j->t_down.size());
-    if (trace) call.down(o.trace, trace, 8 * NL * ((size_t)L + 1));
-    const ngp_status st = call.sync();
-    j->run_ended(st);   // (after a failure the device programs are not the host's: the next run sends them)
-    if (st) return st;
-    const unsigned char *dn = j->t_down.data();
-    auto at = [&](size_t t_x) { return dn + (t_x - j->t_z); };
-    std::memcpy(o.z1, at(j->t_z), 8 * NL);
-    std::memcpy(o.mom1, at(j->t_pm), 8 * NL);
-    std::memcpy(o.theta1, at(j->t_theta), 8 * NL);
-    std::memcpy(o.U0, at(j->t_sc), 8 * (size_t)B);
-    std::memcpy(o.K0, at(j->t_sc + scb), 8 * (size_t)B);
-    std::memcpy(o.U1, at(j->t_sc + 2 * scb), 8 * (size_t)B);
-    std::memcpy(o.K1, at(j->t_sc + 3 * scb), 8 * (size_t)B);
-    std::memcpy(o.lm1, at(j->t_sc + 4 * scb), 8 * (size_t)B);
-    std::memcpy(o.info1, at(j->t_info), 4 * (size_t)B);
-    // the host copy of the programs follows the device's: the parameters of the last evaluation
-    for (int i = 0; i < B; ++i) {
-        DevProgram &P = j->hp[(size_t)i];
-        const double *th = o.theta1 + j->loff[(size_t)i];
-        const int np = j->n_params[(size_t)i];
-        for (int q = 0; q < np; ++q) P.params[q] = th[j->perm[(size_t)i][(size_t)q]];
-        P.noise = th[np];
-    }
-    return NGP_OK;
-}
-
-void grad_leaf_destroy(GradLeaf *j) {
-    if (!j) return;
-    {
-        DevCall call(j->ctx);
-        // a staging buffer that was kept must outlive its copy
-        if (!j->h_in.empty()) call.pending();
-        (void)call.sync();
-        j->ctx->release(j->io);
-        j->ctx->release(j->hmc);
-    }
-    delete j;
-}
-
-}  // namespace
-
-// The public handle: the batch as the caller sees it, carried by up to two leaves — the items that
-// are stationary trees, when the series is regular, on the Toeplitz path, the others on the general
-// one — with the index maps that scatter results and parameters.
-struct ngp_grad_job {
-    ngp_ctx *ctx = nullptr;
-    int B = 0;
-    GradLeaf *gen = nullptr, *toep = nullptr;
-    std::vector<int32_t> idx_gen, idx_toep;     // leaf item -> caller's item
-    std::vector<size_t> poff, goff;             // [B + 1] offsets of an item's parameters / gradient
-    std::vector<double> buf_p, buf_n, buf_lm, buf_g, buf_lm2, buf_g2;
-    std::vector<int32_t> buf_info, buf_info2;
-    bool side_by_side = false;                  // a small split batch: both leaves in flight together
-    // Small jobs keep a host copy of what a ONE-SHOT call over their items would take (trees and
-    // current parameters in the caller's order, dates, observation rows): when several tasks run
-    // their jobs at the same moment — the leapfrog steps of the per-scenario HMC moves of
-    // forecast_with_nowcasts, src/forecasting.jl:145-148 — the runs are combined into one call
-    // over all their items ("combining" section); alone, a run uses the resident inputs as before.
-    std::vector<int32_t> h_ops;
-    std::vector<double> h_params, h_t, h_y;
-    std::vector<ngp_kernel> h_k;
-    int32_t n = 0;
-    int64_t h_ldy = 0;
-    GradRoute route;                            // what the job was staged under
-};
-// host copies up to this size (64 particles x 2,049 points = 1 MB; a lockstep job of 12,800 items
-// is 210 MB and has no use for company)
-static constexpr size_t GRAD_JOB_HOST_COPY_BYTES = (size_t)16 << 20;
-
-static ngp_status grad_stage_impl(ngp_ctx *c, int32_t B, const ngp_kernel *kernels, int32_t n,
-                                  const double *t, const double *y, int64_t ldy,
-                                  const double *const *yrows, ngp_grad_job **out,
-                                  bool keep_host = false, const GradRoute *route_in = nullptr) {
-    if (!c || !out || !kernels || !t || (!y && !yrows) || B <= 0 || n <= 0) return NGP_ERR_ARG;
-    *out = nullptr;
-    for (int i = 0; i < B; ++i) {
-        ngp_status st = check_program(&kernels[i]);
-        if (st) return st;
-    }
-    std::unique_ptr<ngp_grad_job> j(new (std::nothrow) ngp_grad_job());
-    if (!j) return NGP_ERR_TOO_LARGE;
-    j->ctx = c;
-    j->B = B;
-    j->poff.assign((size_t)B + 1, 0);
-    j->goff.assign((size_t)B + 1, 0);
-    for (int i = 0; i < B; ++i) {
-        j->poff[(size_t)i + 1] = j->poff[(size_t)i] + (size_t)kernels[i].n_params;
-        j->goff[(size_t)i + 1] = j->goff[(size_t)i] + (size_t)kernels[i].n_params + 1;
-    }
-    // the Toeplitz path: a regular series (constant lattice stride over all n points), at least two
-    // blocks, short enough for the weights kernel's LDS image, and a tree without Linear or
-    // ChangePoint nodes
-    bool regular = false;
-    GradRoute route;
-    if (route_in) {
-        route = *route_in;
-    } else {
-        std::lock_guard<std::mutex> lk(c->mu);
-        route = grad_route_of(c);
-    }
-    const bool on = route.toeplitz, invariant = route.invariant, short_series = route.short_series;
-    const double jitter = route.spec.jitter;
-    if (toep_grad_series(n, B, on, short_series, invariant)) {
-        std::vector<double> real(t, t + n);
-        std::vector<int32_t> q;
-        double hh = 0.0;
-        int R = 0;
-        if (detect_lattice(real, &hh, &q, &R)) {
-            const long st0 = (long)q[1] - (long)q[0];
-            regular = st0 != 0;
-            for (int i = 2; i < n && regular; ++i) regular = (long)q[(size_t)i] - (long)q[(size_t)i - 1] == st0;
-        }
-    }
-    for (int i = 0; i < B; ++i) {
-        // (trees of more than 16 leaves stay on the general path: the 1-D contraction runs on the
-        // register-accumulator kernels, which end there)
-        bool stationary = regular && kernels[i].n_ops <= 31;
-        for (int k = 0; stationary && k < kernels[i].n_ops; ++k)
-            stationary = kernels[i].ops[k] != NGP_OP_LINEAR && kernels[i].ops[k] != NGP_OP_CHANGEPOINT;
-        if (stationary) {
-            // The Gohberg-Semencul sums divide by x_0 = (K^-1)_11 and lose about eps cond(K) of their
-            // digits; cond(K) <= n k(0) / (noise + jitter).  A matrix whose diagonal shift is below
-            // 1e-9 of its diagonal k(0) (reachable only with a jitter far below the default 1e-5: HMC
-            // clamps the noise at 1e-12) is not trusted to that formula and takes the general leaf.
-            double st[NGP_MAX_STACK];
-            int sp_ = 0, pi = 0;
-            for (int k = 0; k < kernels[i].n_ops; ++k) {
-                const int op = kernels[i].ops[k];
-                if (op == NGP_OP_PLUS || op == NGP_OP_TIMES) {
-                    const double b = st[--sp_], a = st[--sp_];
-                    st[sp_++] = op == NGP_OP_PLUS ? a + b : a * b;
-                } else {   // value at distance zero: the constant, or the leaf's amplitude (its last parameter)
-                    const int np = k_nparams[op];
-                    st[sp_++] = std::fabs(kernels[i].params[pi + np - 1]);
-                    pi += np;
-                }
-            }
-            const double k0 = st[0];
-            if (!(kernels[i].noise + jitter >= 1e-9 * k0)) stationary = false;
-        }
-        (stationary ? j->idx_toep : j->idx_gen).push_back(i);
-    }
-    // a mixed batch: both leaves in turn, side by side, or everything on the general leaf
-    if (!j->idx_gen.empty() && !j->idx_toep.empty()) {
-        const GradBatchRoute br = grad_batch_route(B, n, invariant);
-        if (br == GRAD_PAIR) {
-            j->side_by_side = true;
-        } else if (br == GRAD_UNSPLIT) {
-            j->idx_toep.clear();
-            j->idx_gen.resize((size_t)B);
-            for (int i = 0; i < B; ++i) j->idx_gen[(size_t)i] = i;
-        }
-    }
-    auto stage_leaf = [&](const std::vector<int32_t> &idx, bool toep_path, GradLeaf **leaf) -> ngp_status {
-        if (idx.empty()) return NGP_OK;
-        if ((int)idx.size() == B)   // the whole batch: the caller's arrays as they are
-            return grad_leaf_stage(c, B, kernels, n, t, y, ldy, toep_path, leaf, yrows, route);
-        std::vector<ngp_kernel> ks(idx.size());
-        for (size_t a = 0; a < idx.size(); ++a) ks[a] = kernels[idx[a]];
-        if (!yrows && ldy == 0)
-            return grad_leaf_stage(c, (int32_t)idx.size(), ks.data(), n, t, y, 0, toep_path, leaf,
-                                   nullptr, route);
-        std::vector<const double *> rows(idx.size());   // the leaf's rows where they lie
-        for (size_t a = 0; a < idx.size(); ++a)
-            rows[a] = yrows ? yrows[idx[a]] : y + (int64_t)idx[a] * ldy;
-        return grad_leaf_stage(c, (int32_t)idx.size(), ks.data(), n, t, nullptr, 0, toep_path, leaf,
-                               rows.data(), route);
-    };
-    ngp_status st = stage_leaf(j->idx_gen, false, &j->gen);
-    if (!st) st = stage_leaf(j->idx_toep, true, &j->toep);
-    if (st) {
-        grad_leaf_destroy(j->gen);
-        grad_leaf_destroy(j->toep);
-        return st;
-    }
-    j->n = n;
-    j->route = route;
-    const bool shared = !yrows && ldy == 0;
-    if (keep_host && (size_t)(shared ? 1 : B) * (size_t)n * 8 <= GRAD_JOB_HOST_COPY_BYTES) {
-        j->h_t.assign(t, t + n);
-        j->h_ldy = shared ? 0 : n;
-        j->h_y.resize((size_t)(shared ? 1 : B) * (size_t)n);
-        for (int b = 0; b < (shared ? 1 : B); ++b)
-            std::memcpy(j->h_y.data() + (size_t)b * n, yrows ? yrows[b] : y + (int64_t)b * ldy, 8 * (size_t)n);
-        size_t nops = 0;
-        for (int i = 0; i < B; ++i) nops += (size_t)kernels[i].n_ops;
-        j->h_ops.reserve(nops);
-        j->h_params.resize(std::max<size_t>(j->poff[(size_t)B], 1));
-        j->h_k.resize((size_t)B);
-        for (int i = 0; i < B; ++i) {
-            j->h_ops.insert(j->h_ops.end(), kernels[i].ops, kernels[i].ops + kernels[i].n_ops);
-            if (kernels[i].n_params > 0)
-                std::memcpy(j->h_params.data() + j->poff[(size_t)i], kernels[i].params,
-                            8 * (size_t)kernels[i].n_params);
-        }
-        size_t o = 0;
-        for (int i = 0; i < B; ++i) {
-            j->h_k[(size_t)i] = ngp_kernel{kernels[i].n_ops, kernels[i].n_params, j->h_ops.data() + o,
-                                           j->h_params.data() + j->poff[(size_t)i], kernels[i].noise};
-            o += (size_t)kernels[i].n_ops;
-        }
-    }
-    *out = j.release();
-    return NGP_OK;
-}
-
-extern "C" ngp_status ngp_grad_stage(ngp_ctx *c, int32_t B, const ngp_kernel *kernels, int32_t n,
-                                     const double *t, const double *y, int64_t ldy,
-                                     ngp_grad_job **out) {
-    if (!y) return NGP_ERR_ARG;
-    return grad_stage_impl(c, B, kernels, n, t, y, ldy, nullptr, out, true);
-}
-
-extern "C" ngp_status ngp_grad_job_set_params(ngp_grad_job *j, const double *params,
-                                              const double *noise) {
-    if (!j || !params || !noise) return NGP_ERR_ARG;
-    auto set_leaf = [&](GradLeaf *leaf, const std::vector<int32_t> &idx) -> ngp_status {
-        if (!leaf) return NGP_OK;
-        if ((int)idx.size() == j->B) return grad_leaf_set_params(leaf, params, noise);
-        j->buf_p.clear();
-        j->buf_n.clear();
-        for (int32_t i : idx) {
-            j->buf_p.insert(j->buf_p.end(), params + j->poff[(size_t)i], params + j->poff[(size_t)i + 1]);
-            j->buf_n.push_back(noise[i]);
-        }
-        if (j->buf_p.empty()) j->buf_p.push_back(0.0);
-        return grad_leaf_set_params(leaf, j->buf_p.data(), j->buf_n.data());
-    };
-    ngp_status st = set_leaf(j->gen, j->idx_gen);
-    if (!st) st = set_leaf(j->toep, j->idx_toep);
-    if (!st && !j->h_k.empty()) {   // the one-shot form of the job follows
-        if (j->poff[(size_t)j->B] > 0) std::memcpy(j->h_params.data(), params, 8 * j->poff[(size_t)j->B]);
-        for (int i = 0; i < j->B; ++i) j->h_k[(size_t)i].noise = noise[i];
-    }
-    return st;
-}
-
-// the run on the job's resident inputs (ngp_grad_job_run, defined in the "combining" section, comes
-// here when the job is alone)
-static ngp_status grad_job_run_resident(ngp_grad_job *j, double *logml, double *grad, int32_t *info) {
-    if (!j || !grad) return NGP_ERR_ARG;
-    auto scatter = [&](const std::vector<int32_t> &idx, const std::vector<double> &lm,
-                       const std::vector<double> &g, const std::vector<int32_t> &inf) {
-        size_t off = 0;
-        for (size_t a = 0; a < idx.size(); ++a) {
-            const size_t i = (size_t)idx[a], len = j->goff[i + 1] - j->goff[i];
-            std::memcpy(grad + j->goff[i], g.data() + off, 8 * len);
-            off += len;
-            if (logml) logml[i] = lm[a];
-            if (info) info[i] = inf[a];
-        }
-    };
-    if (j->side_by_side && j->gen && j->toep) {
-        auto size_bufs = [&](const std::vector<int32_t> &idx, std::vector<double> &lm,
-                             std::vector<double> &g, std::vector<int32_t> &inf) {
-            size_t ng = 0;
-            for (int32_t i : idx) ng += j->goff[(size_t)i + 1] - j->goff[(size_t)i];
-            lm.resize(idx.size());
-            inf.resize(idx.size());
-            g.resize(ng);
-        };
-        size_bufs(j->idx_gen, j->buf_lm, j->buf_g, j->buf_info);
-        size_bufs(j->idx_toep, j->buf_lm2, j->buf_g2, j->buf_info2);
-        const ngp_status st = grad_pair_run(j->gen, j->buf_lm.data(), j->buf_g.data(), j->buf_info.data(),
-                                            j->toep, j->buf_lm2.data(), j->buf_g2.data(),
-                                            j->buf_info2.data());
-        if (st == NGP_OK) {
-            scatter(j->idx_gen, j->buf_lm, j->buf_g, j->buf_info);
-            scatter(j->idx_toep, j->buf_lm2, j->buf_g2, j->buf_info2);
-            return NGP_OK;
-        }
-        if (st != NGP_ERR_TOO_LARGE) return st;   // no room for both at once: one after the other
-    }
-    auto run_leaf = [&](GradLeaf *leaf, const std::vector<int32_t> &idx) -> ngp_status {
-        if (!leaf) return NGP_OK;
-        if ((int)idx.size() == j->B) return grad_leaf_run(leaf, logml, grad, info);
-        size_t ng = 0;
-        for (int32_t i : idx) ng += j->goff[(size_t)i + 1] - j->goff[(size_t)i];
-        j->buf_lm.resize(idx.size());
-        j->buf_info.resize(idx.size());
-        j->buf_g.resize(ng);
-        ngp_status st = grad_leaf_run(leaf, j->buf_lm.data(), j->buf_g.data(), j->buf_info.data());
-        if (st) return st;
-        size_t off = 0;
-        for (size_t a = 0; a < idx.size(); ++a) {
-            const size_t i = (size_t)idx[a], len = j->goff[i + 1] - j->goff[i];
-            std::memcpy(grad + j->goff[i], j->buf_g.data() + off, 8 * len);
-            off += len;
-            if (logml) logml[i] = j->buf_lm[a];
-            if (info) info[i] = j->buf_info[a];
-        }
-        return NGP_OK;
-    };
-    ngp_status st = run_leaf(j->gen, j->idx_gen);
-    if (!st) st = run_leaf(j->toep, j->idx_toep);
-    return st;
-}
-
-extern "C" ngp_status ngp_grad_job_hmc(ngp_grad_job *j, const void *cfg_, const void *kind_,
-                                       const void *frozen_, const double *z0, const double *mom,
-                                       double *z1, double *mom1, double *theta1, double *U0, double *K0,
-                                       double *U1, double *K1, double *logml1, int32_t *info1,
-                                       double *z_trace) {
-    const ngp_hmc_config *cfg = (const ngp_hmc_config *)cfg_;
-    const uint8_t *kind = (const uint8_t *)kind_, *frozen = (const uint8_t *)frozen_;
-    if (!j || !cfg || !kind || !z0 || !mom || !z1 || !mom1 || !theta1 || !U0 || !K0 || !U1 || !K1 ||
-        !logml1 || !info1)
-        return NGP_ERR_ARG;
-    if (cfg->n_leapfrog < 1 || !std::isfinite(cfg->eps)) return NGP_ERR_ARG;
-    if (cfg->n_leapfrog > 65536) return NGP_ERR_TOO_LARGE;   // the limit include/ngp.h states
-    const int B = j->B;
-    const size_t NL = j->goff[(size_t)B];
-    for (size_t q = 0; q < NL; ++q) {
-        const int kd = kind[q];
-        if (kd > 4) return NGP_ERR_ARG;
-        if (kd >= 2 && !(cfg->prior_sigma[kd] > 0.0 && std::isfinite(cfg->prior_sigma[kd]) &&
-                         std::isfinite(cfg->prior_mu[kd])))
-            return NGP_ERR_ARG;
-    }
-    const int L = cfg->n_leapfrog;
-    auto run_leaf = [&](GradLeaf *leaf, const std::vector<int32_t> &idx) -> ngp_status {
-        if (!leaf) return NGP_OK;
-        if ((int)idx.size() == B)
-            return grad_leaf_hmc(leaf, cfg, kind, frozen, z0, mom,
-                                 HmcOut{z1, mom1, theta1, U0, K0, U1, K1, logml1, info1, z_trace});
-        // a leaf of some of the items: their latents gathered, the outputs scattered back
-        size_t nl = 0;
-        for (int32_t i : idx) nl += j->goff[(size_t)i + 1] - j->goff[(size_t)i];
-        const size_t nb = idx.size();
-        std::vector<uint8_t> kd(nl), fr(frozen ? nl : 0);
-        std::vector<double> in(2 * nl), out(3 * nl + 5 * nb), tr(z_trace ? nl * ((size_t)L + 1) : 0);
-        std::vector<int32_t> inf(nb);
-        size_t off = 0;
-        for (int32_t i : idx) {
-            const size_t g0 = j->goff[(size_t)i], len = j->goff[(size_t)i + 1] - g0;
-            std::memcpy(kd.data() + off, kind + g0, len);
-            if (frozen) std::memcpy(fr.data() + off, frozen + g0, len);
-            std::memcpy(in.data() + off, z0 + g0, 8 * len);
-            std::memcpy(in.data() + nl + off, mom + g0, 8 * len);
-            off += len;
-        }
-        double *sc = out.data() + 3 * nl;
-        const ngp_status st = grad_leaf_hmc(
-            leaf, cfg, kd.data(), frozen ? fr.data() : nullptr, in.data(), in.data() + nl,
-            HmcOut{out.data(), out.data() + nl, out.data() + 2 * nl, sc, sc + nb, sc + 2 * nb, sc + 3 * nb,
-                   sc + 4 * nb, inf.data(), z_trace ? tr.data() : nullptr});
-        if (st) return st;
-        off = 0;
-        for (size_t a = 0; a < nb; ++a) {
-            const size_t i = (size_t)idx[a], g0 = j->goff[i], len = j->goff[i + 1] - g0;
-            std::memcpy(z1 + g0, out.data() + off, 8 * len);
-            std::memcpy(mom1 + g0, out.data() + nl + off, 8 * len);
-            std::memcpy(theta1 + g0, out.data() + 2 * nl + off, 8 * len);
-            for (int r = 0; z_trace && r <= L; ++r)
-                std::memcpy(z_trace + (size_t)r * NL + g0, tr.data() + (size_t)r * nl + off, 8 * len);
-            U0[i] = sc[a]; K0[i] = sc[nb + a]; U1[i] = sc[2 * nb + a]; K1[i] = sc[3 * nb + a];
-            logml1[i] = sc[4 * nb + a];
-            info1[i] = inf[a];
-            off += len;
-        }
-        return NGP_OK;
-    };
-    // items are independent: the whole trajectory of the general leaf, then that of the Toeplitz leaf
-    // (each under the context's lock; a failure of the second leaves the job as include/ngp.h says)
-    ngp_status st = run_leaf(j->gen, j->idx_gen);
-    if (!st) st = run_leaf(j->toep, j->idx_toep);
-    if (!st && !j->h_k.empty()) {   // the one-shot form of the job follows (a combined run reads it)
-        for (int i = 0; i < B; ++i) {
-            const size_t g0 = j->goff[(size_t)i], np = j->poff[(size_t)i + 1] - j->poff[(size_t)i];
-            if (np) std::memcpy(j->h_params.data() + j->poff[(size_t)i], theta1 + g0, 8 * np);
-            j->h_k[(size_t)i].noise = theta1[g0 + np];
-        }
-    }
-    return st;
-}
-
-extern "C" ngp_status ngp_grad_job_info(const ngp_grad_job *j, int32_t *out5) {
-    if (!j || !out5) return NGP_ERR_ARG;
-    out5[0] = j->gen ? j->gen->B : 0;
-    out5[1] = j->gen ? j->gen->last_chunk : 0;
-    out5[2] = j->toep ? j->toep->B : 0;
-    out5[3] = j->toep ? j->toep->last_chunk : 0;
-    out5[4] = j->side_by_side ? 1 : 0;
-    return NGP_OK;
-}
-
-extern "C" void ngp_grad_job_destroy(ngp_grad_job *j) {
-    if (!j) return;
-    grad_leaf_destroy(j->gen);
-    grad_leaf_destroy(j->toep);
-    delete j;
-}
-
-// route: stage under this spec and these switches instead of the context's current ones
-static ngp_status logml_grad_direct(ngp_ctx *c, int32_t B, const ngp_kernel *kernels, int32_t n,
-                                    const double *t, const double *y, int64_t ldy,
-                                    const double *const *yrows, double *logml, double *grad,
-                                    int32_t *info, const GradRoute *route = nullptr) {
-    if (!grad) return NGP_ERR_ARG;
-    ngp_grad_job *j = nullptr;
-    ngp_status st = grad_stage_impl(c, B, kernels, n, t, y, ldy, yrows, &j, false, route);
-    if (st) return st;
-    st = grad_job_run_resident(j, logml, grad, info);
-    ngp_grad_job_destroy(j);
-    return st;
-}
-
+#include "ngp_host_grad.h"
 #include "ngp_host_mixture.h"
 #include "ngp_host_combine.h"
 #include "ngp_host_comm.h"

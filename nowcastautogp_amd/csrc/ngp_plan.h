@@ -63,6 +63,11 @@ constexpr long BY_SIZE_MIN_WGS = 4096, BY_SIZE_MIN_WGS_TOEP = 512;
 constexpr int SPLIT_MIN_ITEMS = 256, PAIR_MIN_ITEMS = 128, PAIR_MIN_N = 1024;
 // the Toeplitz gradient leaf: at least two blocks, short enough for the weights kernel's LDS image
 constexpr int TOEP_GRAD_MIN_N = 2 * NB, TOEP_GRAD_MAX_N = 8192;
+// ... and of such a series the items it takes (toep_leaf_item): trees of at most 16 leaves, i.e. 31
+// operators (the 1-D contraction runs on the register-accumulator kernels, which end there), whose
+// diagonal shift noise + jitter is at least this fraction of the diagonal k(0)
+constexpr int TOEP_LEAF_MAX_OPS = 31;
+constexpr double TOEP_LEAF_MIN_SHIFT = 1e-9;
 // stage_general / grad_leaf_stage keep a staging buffer up to this size with the job instead of
 // waiting for the copy; ngp_job_fetch brings a result region up to FETCH_PACKED_BYTES back in one copy
 constexpr size_t STAGE_KEEP_BYTES = (size_t)4 << 20, FETCH_PACKED_BYTES = (size_t)1 << 20;
@@ -346,6 +351,47 @@ inline bool toep_grad_series(int n, int B, bool option_on, bool short_series, bo
     return option_on && n >= TOEP_GRAD_MIN_N && n <= TOEP_GRAD_MAX_N &&
            !(short_series && n <= SM_MAX_NB * NB && (B <= SM_MAX_ITEMS || invariant));
 }
+// A regular series: a constant non-zero lattice stride over all n points (q: detect_lattice's indices).
+inline bool series_regular(const int32_t *q, int n) {
+    if (n < 2) return false;
+    const long st0 = (long)q[1] - (long)q[0];
+    bool regular = st0 != 0;
+    for (int i = 2; i < n && regular; ++i) regular = (long)q[i] - (long)q[i - 1] == st0;
+    return regular;
+}
+// parameters of a node, by ngp_op
+constexpr int k_nparams[10] = {0, 1, 3, 2, 3, 3, 0, 0, 2, 2};
+// k(0) of a tree of Plus, Times and stationary leaves: a leaf's value at distance zero is the
+// constant, or the leaf's amplitude (its last parameter)
+inline double kernel_k0(const ngp_kernel &k) {
+    double st[NGP_MAX_STACK];
+    int sp = 0, pi = 0;
+    for (int i = 0; i < k.n_ops; ++i) {
+        const int op = k.ops[i];
+        if (op == NGP_OP_PLUS || op == NGP_OP_TIMES) {
+            const double b = st[--sp], a = st[--sp];
+            st[sp++] = op == NGP_OP_PLUS ? a + b : a * b;
+        } else {
+            const int np = k_nparams[op];
+            st[sp++] = std::fabs(k.params[pi + np - 1]);
+            pi += np;
+        }
+    }
+    return st[0];
+}
+// Does an item of a regular series (series_regular, on a series toep_grad_series admits) take the
+// Toeplitz leaf?  A tree without Linear or ChangePoint nodes, of at most TOEP_LEAF_MAX_OPS operators.
+// And: the Gohberg-Semencul sums divide by x_0 = (K^-1)_11 and lose about eps cond(K) of their
+// digits; cond(K) <= n k(0) / (noise + jitter).  A matrix whose diagonal shift is below
+// TOEP_LEAF_MIN_SHIFT = 1e-9 of its diagonal k(0) (reachable only with a jitter far below the default
+// 1e-5: HMC clamps the noise at 1e-12) is not trusted to that formula and takes the general leaf.
+// (A checked program, check_program: the evaluator's stack holds it.)
+inline bool toep_leaf_item(const ngp_kernel &k, double jitter) {
+    if (k.n_ops > TOEP_LEAF_MAX_OPS) return false;
+    for (int i = 0; i < k.n_ops; ++i)
+        if (k.ops[i] == NGP_OP_LINEAR || k.ops[i] == NGP_OP_CHANGEPOINT) return false;
+    return k.noise + jitter >= TOEP_LEAF_MIN_SHIFT * kernel_k0(k);
+}
 // a batch with items for both leaves (see SPLIT_MIN_ITEMS).  Batch-invariant contexts route by the
 // item alone: a stationary tree on a regular series always takes the Toeplitz leaf, whatever travels
 // with it
@@ -353,6 +399,62 @@ enum GradBatchRoute { GRAD_UNSPLIT, GRAD_PAIR, GRAD_SPLIT };
 inline GradBatchRoute grad_batch_route(int B, int n, bool invariant) {
     if (B >= SPLIT_MIN_ITEMS) return GRAD_SPLIT;
     return (invariant || (n >= PAIR_MIN_N && B >= PAIR_MIN_ITEMS)) ? GRAD_PAIR : GRAD_UNSPLIT;
+}
+
+// ---- working storage of a gradient leaf's run --------------------------------------------------------
+// The blocks a LeafRun asks of the context's workspace, in request order, each once: the request for
+// a chunk of Bc items, and what the chunk-size estimate (chunk_for) counts for it per item.  Where the
+// two differ the estimate is the smaller one: the halving loop of chunk_for takes up what it leaves
+// out, and the chunk sizes (hence the launch grids) of every geometry are pinned to it
+// (tests/sanitize/plan_check.cpp restates both).
+enum LeafBlockId {
+    LEAF_L,       // the padded matrix and its aux rows
+    LEAF_DINV,    // block inverses M_j: the Toeplitz path keeps every one for its backward sweep, the general path one
+    LEAF_TAB,     // lattice: the tables of the stationary subtrees
+    LEAF_SIG,     // lattice: the ChangePoint sigmoids
+    LEAF_DTAB,    // lattice: the tables' derivatives
+    LEAF_KINV,    // general path: K^-1 [n0 x n0]; Toeplitz path: A = [a' ; x'] (one aux tile)
+    LEAF_ALPHA,   // alpha; Toeplitz path: w per distance
+    LEAF_QUAD,    // y' K^-1 y
+    LEAF_PART,    // partial sums of the contraction
+    LEAF_ITEMS,   // the leaf's items sorted by tree size
+    LEAF_N_BLOCKS
+};
+struct LeafBlock {
+    bool asked;         // false: never requested (the tables of a job off the lattice)
+    size_t bytes;       // the request for a chunk of Bc items
+    size_t est_item;    // bytes per item in the chunk-size estimate
+};
+inline void leaf_run_blocks(const JobGeom &g, bool toep_path, int Bc, LeafBlock (&b)[LEAF_N_BLOCKS]) {
+    const size_t GP = NGP_MAX_PARAMS + 1, ntri = (size_t)(g.nb0 * (g.nb0 + 1) / 2), nd = (size_t)((g.n_real + 255) / 256);
+    const size_t n0 = (size_t)g.n0, bc = (size_t)Bc, lat = g.lattice ? 1 : 0;
+    const size_t tab = lat * 8 * (size_t)g.maxstat * g.R, sig = lat * 8 * (size_t)g.maxcp * g.npts;
+    const size_t l = (size_t)g.item_stride * 8, aux = 8 * (size_t)g.naux_pad * n0, blk = 8 * (size_t)NB * NB;
+    const size_t kinv = toep_path ? aux : 8 * n0 * n0, part_rows = toep_path ? nd : ntri;
+    b[LEAF_L] = {true, l * bc, l};
+    // estimate: the general path's single block per item is an omission kept for behaviour's sake
+    b[LEAF_DINV] = {true, blk * bc * (toep_path ? (size_t)g.nb0 : 1), toep_path ? blk * g.nb0 : 0};
+    b[LEAF_TAB] = {lat != 0, tab * bc, tab};
+    b[LEAF_SIG] = {lat != 0, sig * bc, sig};
+    b[LEAF_DTAB] = {lat != 0, 3 * tab * bc, 3 * tab};
+    b[LEAF_KINV] = {true, kinv * bc, kinv};
+    b[LEAF_ALPHA] = {true, 8 * n0 * bc, 8 * n0};
+    b[LEAF_QUAD] = {true, 8 * bc, 0};   // estimate: 8 bytes per item, an omission kept for behaviour's sake
+    // A chunk of the general path that is cut finer (split 2 or 4) writes at most 4096 partial rows; a
+    // coarse one Bc ntri.  Estimate: the coarse figure — the split and the floor depend on Bc, which
+    // the estimate is there to choose (kept for behaviour's sake: at most 4096 GP 8 bytes = 3 MB a chunk)
+    b[LEAF_PART] = {true,
+                    8 * GP * (toep_path ? bc * nd
+                                        : std::max<size_t>(bc * ntri * (size_t)grad_contract_split((long)ntri, Bc, g.invariant != 0), 4096)),
+                    8 * part_rows * GP};
+    b[LEAF_ITEMS] = {true, 4 * (size_t)g.B, 0};   // of the whole leaf, not of a chunk: not an item's cost
+}
+inline size_t leaf_item_estimate(const JobGeom &g, bool toep_path) {
+    LeafBlock b[LEAF_N_BLOCKS];
+    leaf_run_blocks(g, toep_path, 1, b);
+    size_t n = 0;
+    for (const LeafBlock &k : b) n += k.est_item;
+    return n;
 }
 
 }  // namespace ngp

@@ -4,8 +4,9 @@
 // at most SM_MAX_SWEEPS sweeps — and must carry every aux row-block exactly once; the inverse phase of
 // a gradient job must give every block column to one wave.  Then the other route rules of
 // csrc/ngp_plan.h over their whole domain, for the relations the host layer relies on
-// (check_routes), and the acceptance rule of lattice dates (check_lattice).  Host code only (hipcc
-// --cuda-host-only).
+// (check_routes), the acceptance rule of lattice dates (check_lattice), the working blocks of a
+// gradient leaf's run against the formulas they replaced (check_leaf_blocks) and the rule that sends
+// an item to the Toeplitz leaf (check_leaf_rule).  Host code only (hipcc --cuda-host-only).
 #include <cstddef>
 #include <cstdio>
 #include <random>
@@ -239,9 +240,137 @@ static void check_lattice() {
            total, worst_unit, worst_any, accepted[0], accepted[1], accepted[2], accepted[3], accepted[4], accepted[5]);
 }
 
+// ---- the working blocks of a gradient leaf's run (leaf_run_blocks) ----------------------------------------
+// The list against the two formulas it replaced, written out as they stood: the per-item estimate of
+// the chunk size (it fixes the chunk, hence the launch grids, of every geometry) and the requests of
+// a chunk of Bc items, in their order.  This is the one place where the old expressions survive.
+static void check_leaf_blocks() {
+    long points = 0;
+    for (int nb0 = 1; nb0 <= 40; ++nb0)
+        for (int n_real : {64 * nb0 - 63, 64 * nb0 - 1, 64 * nb0})
+            for (int lat = 0; lat < 9; ++lat)          // 0: off the lattice; 1 .. 8: maxstat, maxcp, R
+                for (int flags = 0; flags < 4; ++flags)
+                    for (int Bc : {1, 3, 24, 64, 513, 5000, 65535}) {
+                        const bool tp = flags & 1;
+                        JobGeom g{};
+                        g.B = Bc + 3;
+                        g.n0 = nb0 * NB;
+                        g.nb0 = nb0;
+                        g.n_real = n_real;
+                        g.naux_pad = tp ? NB : g.n0 + NB;
+                        g.item_stride = (int64_t)(g.n0 + g.naux_pad) * g.n0;
+                        g.npts = g.n0;
+                        g.invariant = (flags >> 1) & 1;
+                        g.lattice = lat ? 1 : 0;
+                        g.maxstat = (lat - 1) & 1 ? 5 : 1;
+                        g.maxcp = (lat - 1) & 2 ? 5 : 1;
+                        g.R = lat ? ((lat - 1) & 4 ? 300 : 1) : 0;
+                        ++points;
+                        // the formulas of the code this list replaced
+                        const int GP = NGP_MAX_PARAMS + 1, ntri = g.nb0 * (g.nb0 + 1) / 2, nd = (g.n_real + 255) / 256;
+                        const size_t l_bytes = (size_t)g.item_stride * 8;
+                        const size_t tab_bytes = g.lattice ? 8 * (size_t)g.maxstat * g.R : 0;
+                        const size_t sig_bytes = g.lattice ? 8 * (size_t)g.maxcp * g.npts : 0;
+                        const size_t aux_bytes = 8 * (size_t)g.naux_pad * g.n0;
+                        const size_t item_bytes =
+                            tp ? l_bytes + 4 * tab_bytes + sig_bytes + 8 * (size_t)NB * NB * g.nb0 + aux_bytes +
+                                     8 * (size_t)g.n0 + 8 * (size_t)nd * GP
+                               : l_bytes + 4 * tab_bytes + sig_bytes + 8 * (size_t)g.n0 * g.n0 +
+                                     8 * (size_t)g.n0 + 8 * (size_t)ntri * GP;
+                        std::vector<size_t> asked;
+                        asked.push_back(l_bytes * (size_t)Bc);
+                        asked.push_back(8 * (size_t)Bc * NB * NB * (tp ? g.nb0 : 1));
+                        if (g.lattice) {
+                            asked.push_back(tab_bytes * (size_t)Bc);
+                            asked.push_back(sig_bytes * (size_t)Bc);
+                            asked.push_back(3 * tab_bytes * (size_t)Bc);
+                        }
+                        asked.push_back(tp ? aux_bytes * (size_t)Bc : 8 * (size_t)Bc * g.n0 * g.n0);
+                        asked.push_back(8 * (size_t)Bc * g.n0);
+                        asked.push_back(8 * (size_t)Bc);
+                        asked.push_back(tp ? 8 * (size_t)Bc * nd * GP
+                                           : 8 * std::max<size_t>((size_t)Bc * ntri * grad_contract_split(ntri, Bc, g.invariant != 0),
+                                                                  4096) * GP);
+                        asked.push_back(4 * (size_t)g.B);
+                        // ... and the list
+                        CHECK(leaf_item_estimate(g, tp) == item_bytes, "nb0 %d n %d lat %d flags %d: estimate %zu, was %zu",
+                              nb0, n_real, lat, flags, leaf_item_estimate(g, tp), item_bytes);
+                        LeafBlock b[LEAF_N_BLOCKS];
+                        leaf_run_blocks(g, tp, Bc, b);
+                        size_t k = 0, est = 0;
+                        for (int id = 0; id < LEAF_N_BLOCKS; ++id) {
+                            est += b[id].est_item;
+                            if (!b[id].asked) continue;
+                            CHECK(k < asked.size() && b[id].bytes == asked[k], "nb0 %d n %d lat %d flags %d Bc %d: block %d asks %zu, was %zu",
+                                  nb0, n_real, lat, flags, Bc, id, b[id].bytes, k < asked.size() ? asked[k] : (size_t)0);
+                            ++k;
+                        }
+                        CHECK(k == asked.size(), "nb0 %d lat %d: %zu requests, were %zu", nb0, lat, k, asked.size());
+                        CHECK(est == item_bytes, "the estimate is not the sum of the list's per-item figures");
+                    }
+    printf("leaf blocks: %ld points\n", points);
+}
+
+// ---- which items take the Toeplitz leaf (toep_leaf_item, kernel_k0, series_regular) ----------------------
+static void check_leaf_rule() {
+    // a sum of L SqExp leaves in postfix form: 2 L - 1 operators, 2 L parameters
+    auto sum_of = [](int leaves, std::vector<int32_t> *ops, std::vector<double> *par) {
+        ops->clear();
+        par->clear();
+        for (int l = 0; l < leaves; ++l) {
+            ops->push_back(NGP_OP_SQEXP);
+            par->push_back(0.5);
+            par->push_back(1.0);
+            if (l) ops->push_back(NGP_OP_PLUS);
+        }
+    };
+    std::vector<int32_t> ops;
+    std::vector<double> par;
+    auto kernel = [&](double noise) { return ngp_kernel{(int32_t)ops.size(), (int32_t)par.size(), ops.data(), par.data(), noise}; };
+    sum_of(16, &ops, &par);
+    CHECK(ops.size() == 31 && toep_leaf_item(kernel(0.1), 1e-5), "a stationary tree of 31 operators is refused");
+    sum_of(17, &ops, &par);
+    CHECK(ops.size() == 33 && !toep_leaf_item(kernel(0.1), 1e-5), "a tree of 33 operators is taken");
+    static_assert(TOEP_LEAF_MAX_OPS == 31 && TOEP_LEAF_MIN_SHIFT == 1e-9, "the thresholds of the Toeplitz leaf's items");
+    // Linear or ChangePoint anywhere: the general leaf
+    ops = {NGP_OP_SQEXP, NGP_OP_LINEAR, NGP_OP_PLUS};
+    par = {0.5, 1.0, 0.0, 0.1, 1.0};
+    CHECK(!toep_leaf_item(kernel(0.1), 1e-5), "a tree with a Linear node is taken");
+    ops = {NGP_OP_SQEXP, NGP_OP_SQEXP, NGP_OP_CHANGEPOINT};
+    par = {0.5, 1.0, 0.5, 1.0, 0.3, 0.1};
+    CHECK(!toep_leaf_item(kernel(0.1), 1e-5), "a tree with a ChangePoint node is taken");
+    // the diagonal shift against k(0) = 1: exactly 1e-9 passes, the next double below does not, nor a NaN
+    ops = {NGP_OP_SQEXP};
+    par = {0.5, 1.0};
+    CHECK(kernel_k0(kernel(0.0)) == 1.0, "k(0) of a leaf of amplitude 1");
+    CHECK(toep_leaf_item(kernel(1e-9), 0.0) && toep_leaf_item(kernel(0.0), 1e-9), "a shift of exactly 1e-9 k(0) is refused");
+    CHECK(!toep_leaf_item(kernel(std::nextafter(1e-9, 0.0)), 0.0), "a shift just below 1e-9 k(0) is taken");
+    CHECK(!toep_leaf_item(kernel(std::nan("")), 1e-5), "a NaN noise is taken");
+    // k(0) of Plus(Times(a, b), c) = |a| |b| + |c|, from the leaves' amplitudes (the last parameter of
+    // each: Periodic has three, a Constant is its value), signs dropped
+    ops = {NGP_OP_PERIODIC, NGP_OP_GAMMAEXP, NGP_OP_TIMES, NGP_OP_CONSTANT, NGP_OP_PLUS};
+    par = {0.7, 0.25, -3.0, 0.4, 1.5, 0.5, -0.125};
+    CHECK(kernel_k0(kernel(0.1)) == 3.0 * 0.5 + 0.125, "k(0) of Plus(Times(a, b), c) is %.17g", kernel_k0(kernel(0.1)));
+    // a regular series: one non-zero stride over all points
+    std::vector<int32_t> q(70);
+    for (int i = 0; i < 70; ++i) q[(size_t)i] = 3 * i;
+    CHECK(series_regular(q.data(), 70), "a stride of 3 is not regular");
+    for (int i = 0; i < 70; ++i) q[(size_t)i] = 210 - 3 * i;
+    CHECK(series_regular(q.data(), 70), "a descending stride is not regular");
+    q[69] -= 3;
+    CHECK(!series_regular(q.data(), 70), "a gap at the end is regular");
+    q[69] += 3;
+    q[35] += 1;
+    CHECK(!series_regular(q.data(), 70), "one irregular gap is regular");
+    std::fill(q.begin(), q.end(), 4);
+    CHECK(!series_regular(q.data(), 70), "a stride of 0 is regular");
+}
+
 int main() {
     check_routes();
     check_lattice();
+    check_leaf_blocks();
+    check_leaf_rule();
     int accepted = 0, refused = 0;
     for (int grad = 0; grad < 2; ++grad)
         for (int n0 = 64; n0 <= 320; n0 += 64)

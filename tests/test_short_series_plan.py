@@ -1,7 +1,9 @@
 """The planner of the short-series launch (``small_plan``, csrc/ngp_plan.h) checked on the host
 over every geometry it can be asked about (tests/sanitize/plan_check.cpp): what it accepts fits the
 kernel's registers, LDS and sweep count and carries every aux row-block exactly once; and ``detect_lattice`` over the date families of
-tests/date_cases.py: what it accepts fits its lattice to a measured multiple of eps span.  No GPU."""
+tests/date_cases.py: what it accepts fits its lattice to a measured multiple of eps span; and the
+working blocks of a gradient leaf's run (``leaf_run_blocks``) against the two formulas they replaced,
+with the rule that sends an item to the Toeplitz leaf (``toep_leaf_item``).  No GPU."""
 import os
 import shutil
 import subprocess
@@ -22,3 +24,6 @@ def test_every_accepted_geometry_fits_the_kernel(tmp_path):
     assert "0 failures" in out.stdout and "1024 geometries accepted" in out.stdout, out.stdout[-500:]
     # the acceptance rule of lattice dates (detect_lattice), swept over n = 2 .. 4096 in the same program
     assert "lattice sweep: 4095 lengths" in out.stdout, out.stdout[-800:]
+    # the sizes of a gradient leaf's working blocks: 40 block counts x 3 lengths x 9 lattice settings x
+    # 2 paths x invariant on / off x 7 chunk sizes
+    assert "leaf blocks: 30240 points" in out.stdout, out.stdout[-800:]
