@@ -423,7 +423,8 @@ __device__ __forceinline__ void small_sweep(const JobGeom &g, const ChunkPtrs &p
 // block goes out as one 32-byte store per lane.  The permutation costs nothing: the product
 // M_i (sum) delivers its rows in the order the A operand's lanes ask for M_i's rows, so lane m
 // reads row 4 (m & 3) + (m >> 2) of M_i from LDS.
-// L comes back from the slab (L2) through a ring of eight blocks requested eight products ahead.
+// L comes back from the slab (L2) through a ring of SM_RING = 6 blocks, each requested six products
+// ahead: product P reads slot P % SM_RING and, once it has, asks for the block of product P + SM_RING.
 constexpr int SM_RING = 6;
 constexpr int sm_tri_row(int p) {   // stage ii >= 1 of product p: ii (ii - 1) / 2 <= p < ii (ii + 1) / 2
     int ii = 1;

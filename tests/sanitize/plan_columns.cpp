@@ -5,8 +5,12 @@
 //   step   nb0 jj mode k0_col k0_diag ahead join
 //   waves  jj w
 //   route  nb0 invariant splitk diag_wave kinv        (kinv: of a gradient job of that many blocks)
+// With the argument "small" it prints instead, for tests/test_small_grad_cases_cpu.py, the small_plan
+// of a gradient job of n = 1 .. 256 points (refused: nbe = 0 and nothing after it):
+//   small  n nbe ident nsweeps kind[nsweeps] colwave[nbe]
 // Host code only (hipcc --cuda-host-only), the geometries set up as in plan_check.cpp.
 #include <cstdio>
+#include <cstring>
 
 #include "../../nowcastautogp_amd/csrc/ngp_internal.h"
 
@@ -32,7 +36,27 @@ static JobGeom grad_geom(int nb0, int invariant) {
     return g;
 }
 
-int main() {
+static void small_plans() {
+    for (int n = 1; n <= SM_MAX_NB * NB; ++n) {
+        JobGeom g = grad_geom((n + NB - 1) / NB, 0);
+        g.n_real = n;
+        SmallPlan pl{};
+        if (!small_plan(g, &pl)) {
+            printf("small %d 0\n", n);
+            continue;
+        }
+        printf("small %d %d %d %d", n, pl.nbe, pl.ident, pl.nsweeps);
+        for (int si = 0; si < pl.nsweeps; ++si) printf(" %d", pl.sw[si].main);
+        for (int j = 0; j < pl.nbe; ++j) printf(" %d", (int)((pl.colwave >> (4 * j)) & 15));
+        printf("\n");
+    }
+}
+
+int main(int argc, char **argv) {
+    if (argc > 1 && !strcmp(argv[1], "small")) {
+        small_plans();
+        return 0;
+    }
     const int B = 9, NB_MAX = 12;
     printf("constants %d %d %d %d %d %d\n", NB, COL_FULL, COL_FAT, COL_THIN, DIAG_AHEAD_SPLIT_K, B);
     for (int nb0 = 1; nb0 <= NB_MAX; ++nb0) {

@@ -9,7 +9,9 @@ sweep (option off) â€” other summation order, so to rounding, not bit for bit â€
 plan distinguishes: 1-4 block columns of 64, data rows that end inside a 16-block (gradient jobs
 pad with identity), aux rows that ride along / need a second and third sweep, the gradient job's
 identity rows in one sweep and (n0 = 256) with y' in a sweep of its own, per-item y rows, an
-indefinite matrix (info), batch-invariance of an item's bits, and re-runs of a staged job."""
+indefinite matrix (info), batch-invariance of an item's bits, and re-runs of a staged job.
+The componentwise judgement of the gradient job against long double, on every 16-row geometry, is
+tests/test_small_grad_gpu.py."""
 import numpy as np
 import pytest
 
