@@ -875,6 +875,46 @@ ngp_status ngp_factor_sample_long(ngp_factor *f, int32_t d, const double *t_add,
                                   double *out, int32_t *comp, double *mu, double *var,
                                   int32_t *info, int32_t *chol_info);
 
+/* ---- paths of a long horizon from independent mixtures ------------------------------
+ * ngp_factor_sample_long_indep is ngp_factor_sample_long for S mixtures that share no component
+ * (refined scenario clones: every clone's particles have parameters, and data, of their own): the
+ * factor's P items are S mixtures of P' = P / S components each, mixture-major — item s P' + k is
+ * component k of mixture s.  There are no appended points: a clone holds its nowcast points as
+ * data (ngp_factor_create with per-item y rows).  It is to ngp_factor_sample_long what
+ * ngp_mixture_sample_indep is to ngp_mixture_sample.
+ *   w         [S][P']         rows sum to 1
+ *   seeds     [S]
+ *   out       [S][draws][m]
+ *   comp      [S][draws]      the component within the mixture, 0 .. P' - 1; may be NULL
+ *   mu        [P][m]          may be NULL; the bits ngp_factor_predict_long returns for the same
+ *                             factor and dates (d = 0)
+ *   var       [P][m]          may be NULL; likewise
+ *   info      [P]             may be NULL; as ngp_factor_predict_long
+ *   chol_info [P]             may be NULL; as ngp_factor_sample_long.  An item with w = 0 is not
+ *                             factorised and reports 0.
+ * Same paths as the shared form, one mixture at a time: mixture s is keyed by seeds[s] with
+ * scenario counter 0 — counter (draw, 0, block, 0) — and draws what ngp_factor_sample_long draws on
+ * a factor created from that mixture's P' items alone with d = 0, w[s], `draws` and seed =
+ * seeds[s], bit for bit; to rounding, what ngp_mixture_sample_indep draws from the long query's
+ * moments.  One call replaces S factors and S calls.  The counters, the pick (fp64 running sum
+ * over the mixture's own P' weights, strict <, fallback P' - 1) and the Box-Muller pairing are
+ * those of ngp_mixture_sample.
+ * A path's bits depend on (seeds[s], draw, its item) alone: not on `draws`, not on S, not on the
+ * mixture's place in the call, not on the paths it shares a tile with, not on how the memory
+ * chunks the items or the paths.  Fixed summation orders, no floating-point atomics, bitwise
+ * reproducible from call to call.  A path picked from an item with info > 0 or chol_info > 0 is
+ * NaN in every date; other paths, those of the same mixture included, are not affected.
+ * NGP_ERR_ARG: null f, t_new, w, seeds or out; m < 1; draws < 1; S < 1; P not a multiple of S.
+ * NGP_ERR_TOO_LARGE: m > NGP_MAX_LONG_HORIZON, (n mod 64) + 1 > NGP_MAX_AUX, S draws > INT32_MAX
+ * — all before anything touches a device —, then what the device memory holds for the paths and
+ * ONE item; a large P is never refused.  Runs under the factor's spec and the context's lock; not
+ * combined with concurrent callers.  Profile classes: those of ngp_factor_sample_long.        */
+ngp_status ngp_factor_sample_long_indep(ngp_factor *f, int32_t S,
+                                        int32_t m, const double *t_new, int32_t noise_on_new,
+                                        const double *w, int32_t draws, const uint64_t *seeds,
+                                        double *out, int32_t *comp, double *mu, double *var,
+                                        int32_t *info, int32_t *chol_info);
+
 /* ---- the decomposition over a long horizon ------------------------------------------
  * ngp_factor_components_nowcast carries its C_p m component rows as aux rows, so (n mod 64) + d +
  * 1 + C_p m <= NGP_MAX_AUX: 42 dates per call at C_p = 3 with a tail of 63.

@@ -404,6 +404,33 @@ function sample_long(f::Factor, t_new::Vector{Float64}, w::Matrix{Float64}, draw
 end
 
 """
+Paths of a long horizon from independent mixtures (include/ngp.h `ngp_factor_sample_long_indep`):
+the factor's P items are S mixtures of P' = P / S components each, mixture-major (item s P' + k is
+component k of mixture s; a refined scenario clone holds its nowcast points as data).  `w` is
+P' x S, `seeds` has one key per mixture; mixture s draws what `sample_long` draws on a factor of its
+own items with `seeds[s]`.  Returns `out` (m x draws x S), `comp` (draws x S, 0-based within the
+mixture), `info` and `chol_info` (P); a path picked from an item with `info > 0` or `chol_info > 0`
+is NaN.
+"""
+function sample_long_indep(f::Factor, t_new::Vector{Float64}, w::Matrix{Float64}, draws::Integer,
+                           seeds::Vector{UInt64}; noise_on_new::Bool = true)
+    P, S, m = f.P, length(seeds), length(t_new)
+    (S >= 1 && P % S == 0) || throw(ArgumentError("the factor's items must be S mixtures of equal size"))
+    size(w) == (P ÷ S, S) || throw(ArgumentError("w must be P' x S"))
+    out = Array{Float64}(undef, m, draws, S)
+    comp = Matrix{Int32}(undef, draws, S)
+    info = zeros(Int32, P)
+    chol_info = zeros(Int32, P)
+    check(ccall((:ngp_factor_sample_long_indep, LIBNGP), Int32,
+                (Ptr{Cvoid}, Int32, Int32, Ptr{Float64}, Int32, Ptr{Float64}, Int32, Ptr{UInt64},
+                 Ptr{Float64}, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}, Ptr{Int32}),
+                f.h, S, m, t_new, noise_on_new, w, draws, seeds, out, comp,
+                Ptr{Float64}(C_NULL), Ptr{Float64}(C_NULL), info, chol_info),
+          "ngp_factor_sample_long_indep")
+    return (out = out, comp = comp, info = info, chol_info = chol_info)
+end
+
+"""
 The additive components of a program (include/ngp.h `ngp_kernel_components`): the maximal non-Plus
 subtrees under the root's Plus nodes, left to right, each a `Program` of its own.
 """

@@ -46,6 +46,7 @@ SYMBOLS = (
     "ngp_ensemble_scores", "ngp_mixture_path_scores",
     "ngp_factor_predict_long",
     "ngp_factor_sample_long",
+    "ngp_factor_sample_long_indep",
     "ngp_factor_components_long",
     "ngp_factor_predict_origins",
 )
@@ -132,6 +133,9 @@ def load():
                                           i32p]),
         "ngp_factor_sample_long": (i32, [vp, i32, f64p, i32, f64p, i32, f64p, i32, f64p, i32,
                                          C.c_uint64, f64p, i32p, f64p, f64p, i32p, i32p]),
+        "ngp_factor_sample_long_indep": (i32, [vp, i32, i32, f64p, i32, f64p, i32,
+                                               C.POINTER(C.c_uint64), f64p, i32p, f64p, f64p, i32p,
+                                               i32p]),
         "ngp_kernel_components": (i32, [KP, i32p, i32p, i32p, i32p, i32p]),
         "ngp_factor_components": (i32, [vp, i32p, KP, i32, f64p, f64p, f64p, f64p, i32p]),
         "ngp_kernel_terms": (i32, [KP, i32, i32, i32p, i32p, i32p, i32p, i32p, i32p, i32, f64p, i32]),
@@ -570,6 +574,37 @@ class Factor(_Handle):
                                            C.c_uint64(int(seed) & (2**64 - 1)), dptr(out),
                                            iptr(comp), _nullable(mu), _nullable(var), iptr(info),
                                            iptr(cinfo)), "ngp_factor_sample_long")
+        return (out, comp, info, cinfo, mu, var) if want_moments else (out, comp, info, cinfo)
+
+    def sample_long_indep(self, t_new, w, draws, seeds, noise_on_new=True, want_moments=False):
+        """``sample_long`` for S mixtures that share no component
+        (``ngp_factor_sample_long_indep``): the factor's P items are S = len(seeds) mixtures of
+        P' = P / S components each, mixture-major (item s P' + k is component k of mixture s), with
+        weights ``w`` [S, P'] and no appended points.  Mixture s is keyed by ``seeds[s]`` and draws
+        what ``sample_long`` draws on a factor of its own items alone.  Returns ``(out [S, draws,
+        m], comp [S, draws], info [P], chol_info [P])``, with ``want_moments`` also ``mu [P, m]``
+        and ``var [P, m]`` (``predict_long``'s bits).  A path picked from an item with ``info > 0``
+        or ``chol_info > 0`` is NaN."""
+        t_new = as_f64(t_new)
+        m, P = t_new.size, self.P
+        seeds = np.ascontiguousarray(np.asarray([int(s) & (2**64 - 1) for s in np.asarray(seeds, dtype=object).reshape(-1)],
+                                                dtype=np.uint64))
+        S = seeds.size
+        if S < 1 or P % S:
+            raise ValueError(f"sample_long_indep: {P} items are not {S} mixtures of equal size")
+        w = np.ascontiguousarray(np.asarray(w, dtype=np.float64))
+        if w.size != P:
+            raise ValueError(f"sample_long_indep: {w.size} weights for {P} items")
+        draws = int(draws)
+        out = np.empty((S, max(draws, 0), m))
+        comp = np.zeros((S, max(draws, 0)), dtype=np.int32)
+        info, cinfo = np.zeros(P, dtype=np.int32), np.zeros(P, dtype=np.int32)
+        mu = np.empty((P, m)) if want_moments else None
+        var = np.empty((P, m)) if want_moments else None
+        _chk(load().ngp_factor_sample_long_indep(
+            self._h, S, m, dptr(t_new) if m else None, int(noise_on_new), dptr(w), draws,
+            seeds.ctypes.data_as(C.POINTER(C.c_uint64)), dptr(out), iptr(comp), _nullable(mu),
+            _nullable(var), iptr(info), iptr(cinfo)), "ngp_factor_sample_long_indep")
         return (out, comp, info, cinfo, mu, var) if want_moments else (out, comp, info, cinfo)
 
     def components(self, comps, t_new, want_sigma=True):

@@ -1520,6 +1520,111 @@ def rand_lockstep(mixes: Sequence[MixtureMVN], draws: int, engine=None) -> List[
     return [np.ascontiguousarray(out[j].T) for j in range(len(mixes))]
 
 
+def _over_scenario_factors(models: Sequence[GPModel], needs: str, query):
+    """Resident factors over whole scenarios of D lockstep models — items mixture-major (model
+    after model, every model's particles together), per-item ``y`` rows — with as many scenarios
+    per factor as the device holds: all of them first; when the factor's creation or
+    ``query(factor, j0, j1)`` (the models j0 .. j1 - 1) is refused with ``NGP_ERR_TOO_LARGE`` the
+    factor is closed, the count halved and the work goes on from the same scenario.  One scenario
+    that does not fit is the error.  Every factor is closed behind its one query.  Returns the
+    queries' results in scenario order, or None (nothing queried) where the engine has no resident
+    factor with the method ``needs``."""
+    D = len(models)
+    P1 = len(models[0].particles)
+    if any(len(mm.particles) != P1 for mm in models):
+        raise ValueError("scenario factors: the models must hold equally many particles")
+    t, ys = _group_obs(models)
+    eng = models[0]._eng()
+    if getattr(eng, "factor", None) is None:
+        return None
+    out, j0, per = [], 0, D
+    while j0 < D:
+        k = min(per, D - j0)
+        sub = models[j0:j0 + k]
+        fac = None
+        try:
+            fac = eng.factor([p for mm in sub for p in mm.programs()], t,
+                             _item_y(ys[j0:j0 + k], np.repeat(np.arange(k), P1)))
+            if not hasattr(fac, needs):
+                return None
+            out.append(query(fac, j0, j0 + k))
+        except Exception as e:      # the engine's own error type: its status says what it is
+            if getattr(e, "status", None) != _NGP_ERR_TOO_LARGE or k == 1:
+                raise
+            per = max(1, k // 2)
+            continue
+        finally:
+            if fac is not None:
+                fac.close()
+        j0 += k
+    return out
+
+
+_NGP_ERR_TOO_LARGE = -3     # include/ngp.h
+
+
+def _lockstep_weights(models: Sequence[GPModel]) -> np.ndarray:
+    """[P_local, D]: every model's normalised weights, as ``predict_mvn_lockstep`` forms them"""
+    logw = np.stack([mm.log_weights for mm in models], axis=1)
+    return distributed.normalize_log_weights(logw, P_total=models[0].n_particles_total)[0]
+
+
+def sample_long_lockstep(models: Sequence[GPModel], ds, draws: int) -> Optional[List[np.ndarray]]:
+    """``rand_lockstep(predict_mvn_lockstep(models, ds), draws)`` on a horizon beyond one aux query
+    without a covariance leaving the device: factors over whole scenarios
+    (``_over_scenario_factors``), ONE ``Factor.sample_long_indep`` call per factor.  Mixture j is
+    keyed by one ``integers(0, 2**63 - 1)`` draw of model j's shared stream, taken in model order
+    where ``rand_lockstep`` takes the seeds of the device's independent form, so the streams end
+    where that form leaves them.  Returns a list of [m, draws] arrays on the models' scale — or
+    None, with no stream touched, where the engine's factor has no ``sample_long_indep``."""
+    k = int(draws)
+    t_new = models[0].ds_transform.apply(to_days(list(ds)))
+    w = _lockstep_weights(models)
+    seeds = []
+
+    def query(fac, j0, j1):
+        if not seeds:       # the first factor stands: only now are the streams touched
+            seeds.extend(int(mm.rng_shared.integers(0, 2**63 - 1)) for mm in models)
+        out, _, info, cinfo = fac.sample_long_indep(t_new, np.ascontiguousarray(w[:, j0:j1].T), k,
+                                                    seeds[j0:j1])
+        _raise_if_failed(info)
+        _raise_if_failed(cinfo)
+        return out
+
+    parts = _over_scenario_factors(models, "sample_long_indep", query)
+    if parts is None:
+        return None
+    out = np.concatenate(parts, axis=0)                                        # [D, draws, m]
+    return [np.ascontiguousarray(((out[j] - mm.y_transform.intercept) / mm.y_transform.slope).T)
+            for j, mm in enumerate(models)]
+
+
+def predict_marginals_lockstep(models: Sequence[GPModel], ds,
+                               noise_on_new: bool = True) -> Optional[List["MixtureMarginals"]]:
+    """``[mx.marginals() for mx in predict_mvn_lockstep(models, ds)]`` without the covariances:
+    ``Factor.predict_long(want_sigma=False)`` on the factors of ``sample_long_lockstep`` — no
+    m x m array is formed anywhere.  None where the engine's factor has no ``predict_long``."""
+    t_new = models[0].ds_transform.apply(to_days(list(ds)))
+    w = _lockstep_weights(models)
+
+    def query(fac, j0, j1):
+        mu, var, _, info = fac.predict_long(t_new, noise_on_new=noise_on_new, want_sigma=False)
+        _raise_if_failed(info)
+        return mu[:, 0], var
+
+    parts = _over_scenario_factors(models, "predict_long", query)
+    if parts is None:
+        return None
+    mu = np.concatenate([p[0] for p in parts], axis=0)
+    var = np.concatenate([p[1] for p in parts], axis=0)
+    P1, eng, res = len(models[0].particles), models[0]._eng(), []
+    for j, mm in enumerate(models):
+        sl_, rows = mm.y_transform.slope, slice(j * P1, (j + 1) * P1)
+        res.append(MixtureMarginals((mu[rows] - mm.y_transform.intercept) / sl_, var[rows] / (sl_ * sl_),
+                                    w[:, j], engine=eng))
+    return res
+
+
 def takes_independent_form(engine, mixes: Sequence[MixtureMVN], draws: int) -> bool:
     """Whether ``draws`` draws from each of ``mixes`` are ONE call of the device's independent form
     (``ngp_mixture_sample_indep`` and the targets / scores over it): the engine has it, there are

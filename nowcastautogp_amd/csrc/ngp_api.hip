@@ -2049,38 +2049,47 @@ extern "C" ngp_status ngp_factor_predict_long(ngp_factor *f, int32_t d, const do
     return run.call.sync();
 }
 
-// ---- paths of a long horizon ---------------------------------------
+// ---- paths of a long horizon (DESIGN.md sections 4.27, 4.30) --------------------------------
 // sigma of the long query stays on the device, [mpad x mpad] per particle with a unit diagonal in
 // the padding: factorised in place 64 columns at a time, then X = mu + L Z for the paths that
 // picked the particle, their normals staged once per path.  Particles go through in chunks sized
 // to the memory, and a chunk's paths in slices of the rows the staged normals have room for.
-extern "C" ngp_status ngp_factor_sample_long(ngp_factor *f, int32_t d, const double *t_add, int32_t D,
-                                             const double *y_add, int32_t m, const double *t_new,
-                                             int32_t noise_on_new, const double *w, int32_t draws,
-                                             uint64_t seed, double *out, int32_t *comp, double *mu,
-                                             double *var, int32_t *info, int32_t *chol_info) {
-    if (!w || !out || draws < 1) return NGP_ERR_ARG;
-    if (ngp_status e = long_check(f, d, t_add, D, y_add, m, t_new)) return e;
-    const int mpad = (m + NB - 1) / NB * NB;
-    LongStage st;
-    if (ngp_status e = long_stage(f, d, t_add, D, y_add, m, t_new, noise_on_new, 0, mpad, true, st)) return e;
-    const int S = st.g.D;                          // 1 without appended points
-    if ((int64_t)S * draws > INT32_MAX) return NGP_ERR_TOO_LARGE;
-    const size_t P = (size_t)f->P, N = (size_t)S * draws, um = (size_t)m, n_mu = (size_t)S * um;
+//
+// The two forms — ngp_factor_sample_long (S mixtures over the same P items) and
+// ngp_factor_sample_long_indep (S mixtures of P' items of their own) — differ in their checks, in
+// the blocks of the pick and in two launches, the pick and the normals; everything behind the picks
+// is long_sample_run.
+struct LongSampleDev {     // the sampler's device blocks beside the long query's
+    double *w = nullptr, *out = nullptr, *Z = nullptr, *dinv = nullptr, *logdet = nullptr;
+    int32_t *comp = nullptr, *item = nullptr, *order = nullptr, *cinfo = nullptr;
+    uint32_t *cnt = nullptr, *off = nullptr;
+    uint64_t *seeds = nullptr;
+};
+
+static LongSampleGeom long_sample_geom(size_t P, int S, int draws, int m, int mu_rows, int mu_own) {
     LongSampleGeom sg{};
     sg.P = (int32_t)P, sg.S = S, sg.draws = draws, sg.m = m;
-    sg.mpad = mpad, sg.nb = mpad / NB;
-    sg.N = (int64_t)N, sg.stride = (int64_t)mpad * mpad;
-    // weights, picks, grouping, every path (and the four bytes by which the chunk's size has always
-    // overcounted them); per item also sigma, block inverse, an unread log determinant, pivot report
+    sg.mpad = (m + NB - 1) / NB * NB, sg.nb = sg.mpad / NB;
+    sg.mu_rows = mu_rows, sg.mu_own = mu_own;
+    sg.N = (int64_t)S * draws, sg.stride = (int64_t)sg.mpad * sg.mpad;
+    return sg;
+}
+
+// A staged long query (d_in first) with the sampler's blocks declared in `dv`: the room of the
+// staged normals, the takes, the picks with the count round trip, the offsets and the grouping, the
+// runs of active items, the chunk loop with the slices of Z, the downloads.
+//   key        the block the paths are counted and grouped by: the item every path picked
+//   pick_cost  of the launch `pick(stream)` makes, the count behind it included
+//   normals    (first sorted position, rows, stream): Z of that slice
+//   weighted   (item): whether its own mixture gives it weight
+template <class Pick, class Normals, class Weighted>
+static ngp_status long_sample_run(ngp_factor *f, LongStage &st, const LongSampleGeom &sg, LongSampleDev &dv,
+                                  int32_t *LongSampleDev::*key, Cost pick_cost, Pick pick, Normals normals,
+                                  Weighted weighted, double *out, int32_t *comp, double *mu, double *var,
+                                  int32_t *info, int32_t *chol_info) {
     const LongPtrs &p = st.p;
-    double *d_w = nullptr, *d_out = nullptr, *d_Z = nullptr, *d_dinv = nullptr, *d_logdet = nullptr;
-    int32_t *d_comp = nullptr, *d_order = nullptr, *d_cinfo = nullptr;
-    uint32_t *d_cnt = nullptr, *d_off = nullptr;
-    st.work_blocks().per_item(&st.p.mu, n_mu).per_item(&st.p.var, um).per_item(&st.p.info, 1);
-    st.per_item(&st.p.sigma, (size_t)sg.stride).per_call(&d_w, (size_t)S * P, w).per_call(&d_comp, N);
-    st.per_call(&d_order, N).per_call(&d_cnt, P).per_call((uint32_t **)nullptr, 1).per_call(&d_off, P + 1);
-    st.per_call(&d_out, N * um).per_item(&d_dinv, (size_t)(NB * NB)).per_item(&d_logdet, 1).per_item(&d_cinfo, 1);
+    const int m = sg.m, mpad = sg.mpad;
+    const size_t P = (size_t)f->P, N = (size_t)sg.N, um = (size_t)m, n_mu = (size_t)sg.mu_rows * um;
     LongRun run(f, st);
     DevCall &call = run.call;
     if (call.status()) return call.status();
@@ -2094,59 +2103,56 @@ extern "C" ngp_status ngp_factor_sample_long(ngp_factor *f, int32_t d, const dou
     const size_t z_bytes = std::min(room - item_bytes, std::max(z_least, room / 4));
     const size_t zcap = std::min(std::min(N, Z_MAX_ROWS), z_bytes / row_bytes - NB);
     if (ngp_status e = run.open(row_bytes * (zcap + NB))) return e;
-    call.take(&d_Z, (size_t)mpad * (zcap + NB));
+    call.take(&dv.Z, (size_t)mpad * (zcap + NB));
     hipStream_t s = run.s;
     EventTimer &tm = call.tm;
-    // the picks and how many paths each particle got: one round trip, the offsets are the host's
+    // the picks and how many paths each item got: one round trip, the offsets are the host's
     std::vector<uint32_t> cnt(P, 0u), off(P + 1, 0u);
     std::vector<int32_t> hinfo(P, 0), hcinfo(P, 0);
-    call.timed(tm, 4, 0.0, 8.0 * (double)N + 4.0 * (double)N * (double)P, [&] {
-        launch_ls_pick(sg, d_w, seed, d_comp, s);
-        launch_ls_count(sg, d_comp, d_cnt, s);
+    call.timed(tm, pick_cost, [&] {
+        pick(s);
+        launch_ls_count(sg, dv.*key, dv.cnt, s);
     });
-    call.down(cnt.data(), d_cnt, 4 * P);
-    if (comp) call.down(comp, d_comp, 4 * N);
+    call.down(cnt.data(), dv.cnt, 4 * P);
+    if (comp) call.down(comp, dv.comp, 4 * N);
     if (call.wait()) return call.sync();
     for (size_t k = 0; k < P; ++k) off[k + 1] = off[k] + (uint32_t)std::min<size_t>(cnt[k], N - off[k]);
-    call.up(d_off, off.data(), 4 * (P + 1));
+    call.up(dv.off, off.data(), 4 * (P + 1));
     call.timed(tm, 4, 0.0, 4.0 * (double)N * (double)P + 4.0 * (double)N,
-               [&] { launch_ls_group(sg, d_comp, d_off, d_order, s); });
-    // a particle is factorised when a scenario gives it weight (or, rows that do not sum to 1, the
+               [&] { launch_ls_group(sg, dv.*key, dv.off, dv.order, s); });
+    // an item is factorised when a mixture gives it weight (or, rows that do not sum to 1, the
     // fallback of the pick fell on it)
     std::vector<char> active(P, 0);
-    for (size_t k = 0; k < P; ++k) {
-        active[k] = off[k + 1] > off[k];
-        for (int sc = 0; sc < S && !active[k]; ++sc) active[k] = w[(size_t)sc * P + k] > 0.0;
-    }
+    for (size_t k = 0; k < P; ++k) active[k] = off[k + 1] > off[k] || weighted(k);
     for (size_t b0 = 0, bc; (bc = run.next(b0)); b0 += bc) {
         run.launch(long_plain, run.small_bytes());
         if (mu) call.down(mu + b0 * n_mu, p.mu, 8 * bc * n_mu);
         if (var) call.down(var + b0 * um, p.var, 8 * bc * um);
         run.info_down(hinfo.data(), b0);
         // the chunk's sigma padded and factorised, then its paths drawn
-        call.zero(d_cinfo, 4 * bc).zero(d_logdet, 8 * bc);
+        call.zero(dv.cinfo, 4 * bc).zero(dv.logdet, 8 * bc);
         call.timed(tm, 4, 0.0, 8.0 * (double)bc * (double)(mpad - m) * (double)(m + mpad),
                    [&] { launch_ls_pad(sg, p.sigma, (int)bc, s); });
         LongSamplePtrs q{};
-        q.info = p.info, q.mu = p.mu, q.order = d_order, q.Z = d_Z, q.out = d_out;
-        // the factorisation, one launch sequence per run of active particles
+        q.info = p.info, q.mu = p.mu, q.order = dv.order, q.Z = dv.Z, q.out = dv.out;
+        // the factorisation, one launch sequence per run of active items
         for (size_t r0 = 0; r0 < bc;) {
             if (!active[b0 + r0]) { ++r0; continue; }
             size_t r1 = r0;
             while (r1 < bc && active[b0 + r1]) ++r1;
             const int B = (int)(r1 - r0);
             q.sigma = p.sigma + r0 * (size_t)sg.stride;
-            q.dinv = d_dinv + r0 * (size_t)(NB * NB);
-            q.logdet = d_logdet + r0;
-            q.cinfo = d_cinfo + r0;
+            q.dinv = dv.dinv + r0 * (size_t)(NB * NB);
+            q.logdet = dv.logdet + r0;
+            q.cinfo = dv.cinfo + r0;
             for (int j = 0; j < sg.nb; ++j) {
                 call.timed(tm, cost_diag(B, j, 0), [&] { launch_ls_diag(sg, q, B, j, s); });
                 if (j + 1 < sg.nb) call.timed(tm, cost_ls_panel(sg, B, j), [&] { launch_ls_panel(sg, q, B, j, s); });
             }
             r0 = r1;
         }
-        q.sigma = p.sigma, q.dinv = d_dinv, q.logdet = d_logdet, q.cinfo = d_cinfo;
-        q.off = d_off + b0;
+        q.sigma = p.sigma, q.dinv = dv.dinv, q.logdet = dv.logdet, q.cinfo = dv.cinfo;
+        q.off = dv.off + b0;
         // the chunk's paths, a slice of sorted positions at a time
         for (size_t z0 = off[b0]; z0 < off[b0 + bc] && !call.status(); z0 += zcap) {
             const size_t zr = std::min(zcap, (size_t)off[b0 + bc] - z0);
@@ -2158,14 +2164,14 @@ extern "C" ngp_status ngp_factor_sample_long(ngp_factor *f, int32_t d, const dou
                 waves += (have + NB - 1) / NB;
                 wgs += (have + LS_WG_PATHS - 1) / LS_WG_PATHS;
             }
-            call.timed(tm, 4, 0.0, row_bytes * (double)zr, [&] { launch_ls_normals(sg, seed, d_order, (int64_t)z0, (int64_t)zr, d_Z, s); });
+            call.timed(tm, cost_ls_normals(sg, (double)zr), [&] { normals((int64_t)z0, (int64_t)zr, s); });
             call.timed(tm, cost_ls_draw(sg, (double)zr, (double)waves, (double)wgs), [&] {
                 launch_ls_draw(sg, q, (int)bc, (int64_t)z0, (int64_t)zr, (int)((most + LS_WG_PATHS - 1) / LS_WG_PATHS), s);
             });
         }
-        call.down(hcinfo.data() + b0, d_cinfo, 4 * bc);
+        call.down(hcinfo.data() + b0, dv.cinfo, 4 * bc);
     }
-    call.down(out, d_out, 8 * N * um);
+    call.down(out, dv.out, 8 * N * um);
     const ngp_status e = call.sync();
     if (e) return e;
     for (size_t k = 0; k < P; ++k) {
@@ -2174,6 +2180,70 @@ extern "C" ngp_status ngp_factor_sample_long(ngp_factor *f, int32_t d, const dou
         if (chol_info) chol_info[k] = hinfo[k] > 0 ? 0 : hcinfo[k];
     }
     return NGP_OK;
+}
+
+extern "C" ngp_status ngp_factor_sample_long(ngp_factor *f, int32_t d, const double *t_add, int32_t D,
+                                             const double *y_add, int32_t m, const double *t_new,
+                                             int32_t noise_on_new, const double *w, int32_t draws,
+                                             uint64_t seed, double *out, int32_t *comp, double *mu,
+                                             double *var, int32_t *info, int32_t *chol_info) {
+    if (!w || !out || draws < 1) return NGP_ERR_ARG;
+    if (ngp_status e = long_check(f, d, t_add, D, y_add, m, t_new)) return e;
+    const int mpad = (m + NB - 1) / NB * NB;
+    LongStage st;
+    if (ngp_status e = long_stage(f, d, t_add, D, y_add, m, t_new, noise_on_new, 0, mpad, true, st)) return e;
+    const int S = st.g.D;                          // 1 without appended points
+    if ((int64_t)S * draws > INT32_MAX) return NGP_ERR_TOO_LARGE;
+    const size_t P = (size_t)f->P, N = (size_t)S * draws, um = (size_t)m, n_mu = (size_t)S * um;
+    const LongSampleGeom sg = long_sample_geom(P, S, draws, m, S, 1);
+    // weights, picks, grouping, every path (and the four bytes by which the chunk's size has always
+    // overcounted them); per item also sigma, block inverse, an unread log determinant, pivot report
+    LongSampleDev dv;
+    st.work_blocks().per_item(&st.p.mu, n_mu).per_item(&st.p.var, um).per_item(&st.p.info, 1);
+    st.per_item(&st.p.sigma, (size_t)sg.stride).per_call(&dv.w, (size_t)S * P, w).per_call(&dv.comp, N);
+    st.per_call(&dv.order, N).per_call(&dv.cnt, P).per_call((uint32_t **)nullptr, 1).per_call(&dv.off, P + 1);
+    st.per_call(&dv.out, N * um).per_item(&dv.dinv, (size_t)(NB * NB)).per_item(&dv.logdet, 1).per_item(&dv.cinfo, 1);
+    return long_sample_run(
+        f, st, sg, dv, &LongSampleDev::comp, Cost{4, 0.0, 8.0 * (double)N + 4.0 * (double)N * (double)P},
+        [&](hipStream_t s) { launch_ls_pick(sg, dv.w, seed, dv.comp, s); },
+        [&](int64_t z0, int64_t zr, hipStream_t s) { launch_ls_normals(sg, seed, dv.order, z0, zr, dv.Z, s); },
+        [&](size_t k) {
+            for (int sc = 0; sc < S; ++sc)
+                if (w[(size_t)sc * P + k] > 0.0) return true;
+            return false;
+        },
+        out, comp, mu, var, info, chol_info);
+}
+
+// The independent form: the factor's items are S mixtures of P' = P / S
+// components, mixture-major, without appended points; mixture s is keyed by seeds[s].
+extern "C" ngp_status ngp_factor_sample_long_indep(ngp_factor *f, int32_t S, int32_t m, const double *t_new,
+                                                   int32_t noise_on_new, const double *w, int32_t draws,
+                                                   const uint64_t *seeds, double *out, int32_t *comp,
+                                                   double *mu, double *var, int32_t *info,
+                                                   int32_t *chol_info) {
+    if (!w || !seeds || !out || draws < 1 || S < 1) return NGP_ERR_ARG;
+    if (ngp_status e = long_check(f, 0, nullptr, 1, nullptr, m, t_new)) return e;
+    if (f->P % S != 0) return NGP_ERR_ARG;
+    if ((int64_t)S * draws > INT32_MAX) return NGP_ERR_TOO_LARGE;
+    const int mpad = (m + NB - 1) / NB * NB;
+    LongStage st;
+    if (ngp_status e = long_stage(f, 0, nullptr, 1, nullptr, m, t_new, noise_on_new, 0, mpad, true, st)) return e;
+    const size_t P = (size_t)f->P, N = (size_t)S * draws, um = (size_t)m;
+    const int Pm = (int)(P / (size_t)S);
+    const LongSampleGeom sg = long_sample_geom(P, S, draws, m, 1, 0);
+    // as the shared form, with one weight per item, the mixtures' seeds and the picked item beside
+    // the component the caller gets
+    LongSampleDev dv;
+    st.work_blocks().per_item(&st.p.mu, um).per_item(&st.p.var, um).per_item(&st.p.info, 1);
+    st.per_item(&st.p.sigma, (size_t)sg.stride).per_call(&dv.w, P, w).per_call(&dv.seeds, (size_t)S, seeds);
+    st.per_call(&dv.comp, N).per_call(&dv.item, N).per_call(&dv.order, N).per_call(&dv.cnt, P).per_call(&dv.off, P + 1);
+    st.per_call(&dv.out, N * um).per_item(&dv.dinv, (size_t)(NB * NB)).per_item(&dv.logdet, 1).per_item(&dv.cinfo, 1);
+    return long_sample_run(
+        f, st, sg, dv, &LongSampleDev::item, cost_lsi_pick(sg, Pm),
+        [&](hipStream_t s) { launch_lsi_pick(sg, Pm, dv.w, dv.seeds, dv.item, dv.comp, s); },
+        [&](int64_t z0, int64_t zr, hipStream_t s) { launch_lsi_normals(sg, dv.seeds, dv.order, z0, zr, dv.Z, s); },
+        [&](size_t k) { return w[k] > 0.0; }, out, comp, mu, var, info, chol_info);
 }
 
 // ---- additive decomposition ---------------------------------------

@@ -123,5 +123,12 @@ inline Cost cost_ls_draw(const LongSampleGeom &g, double paths, double waves, do
     const double K = (double)g.mpad * ((double)g.mpad + NB) / (2.0 * NB);
     return {2, 2.0 * waves * NB * NB * K, 8.0 * (wgs * NB * K + waves * NB * K + paths * (2.0 * g.m))};
 }
+// ngp_factor_sample_long_indep.  The pick of S mixtures of Pm components: a path writes its item
+// and its component and walks its own mixture's weights alone
+inline Cost cost_lsi_pick(const LongSampleGeom &g, int Pm) {
+    return {4, 0.0, 8.0 * (double)g.N + 4.0 * (double)g.N * (double)Pm};
+}
+// the staged normals of `paths` paths (both forms): full rows of mpad doubles, written once
+inline Cost cost_ls_normals(const LongSampleGeom &g, double paths) { return {4, 0.0, 8.0 * g.mpad * paths}; }
 
 }  // namespace ngp

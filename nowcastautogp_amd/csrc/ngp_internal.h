@@ -279,6 +279,8 @@ constexpr int LS_WG_PATHS = 256;       // paths of a workgroup of the product: f
 struct LongSampleGeom {
     int32_t P, S, draws, m;
     int32_t mpad, nb;      // m rounded up to NB; mpad / NB
+    int32_t mu_rows;       // rows of mu per item: S, or 1 where every item has its own mean alone
+    int32_t mu_own;        // 1: a path adds row s of its item's means; 0: the item's one row
     int64_t N;             // S draws
     int64_t stride;        // elements per item in sigma: mpad mpad
 };
@@ -288,7 +290,7 @@ struct LongSamplePtrs {
     double *logdet;            // [B] scratch of the diagonal step
     int32_t *cinfo;            // [B] first non-positive pivot, 1-based; 0: none
     const int32_t *info;       // [B] the long query's status
-    const double *mu;          // [B][S][m]
+    const double *mu;          // [B][mu_rows][m]
     const uint32_t *off;       // [B + 1] first sorted position of each item's paths
     const int32_t *order;      // [N] path (s draws + d) at each sorted position
     const double *Z;           // [zrows + NB][mpad] normals of sorted positions zfirst ..
@@ -309,6 +311,13 @@ void launch_ls_panel(const LongSampleGeom &g, const LongSamplePtrs &p, int B, in
 // largest number of LS_WG_PATHS groups any of them needs
 void launch_ls_draw(const LongSampleGeom &g, const LongSamplePtrs &p, int B, int64_t zfirst, int64_t zrows,
                     int tiles, hipStream_t s);
+// ngp_factor_sample_long_indep (ngp_long_sample_indep_kernels.h): the geometry's P items are S
+// mixtures of Pm components each, mixture-major, mixture s keyed by seeds[s].  pick: item [N] (the
+// item s Pm + k, what count and group sort by) and comp [N] (k).  normals: as launch_ls_normals
+void launch_lsi_pick(const LongSampleGeom &g, int Pm, const double *w, const uint64_t *seeds, int32_t *item,
+                     int32_t *comp, hipStream_t s);
+void launch_lsi_normals(const LongSampleGeom &g, const uint64_t *seeds, const int32_t *order, int64_t zfirst,
+                        int64_t zrows, double *Z, hipStream_t s);
 
 // ---- short series in one launch (ngp_small_kernels.h) ------------------------------------
 constexpr int SM_WAVES = 8, SM_THREADS = 64 * SM_WAVES;   // two waves per SIMD: 256 VGPRs each

@@ -18,6 +18,7 @@
 //                         ngp_component_kernels.h: fill and epilogue of ngp_factor_components;
 //                         ngp_long_kernels.h: ngp_factor_predict_long (the dates as a solve's panel);
 //                         ngp_long_sample_kernels.h: ngp_factor_sample_long (paths from its sigma);
+//                         ngp_long_sample_indep_kernels.h: ngp_factor_sample_long_indep (its pick and normals);
 //                         ngp_long_component_kernels.h: ngp_factor_components_long (component rows in its panel);
 //                         ngp_long_origin_kernels.h: ngp_factor_predict_origins (prefixes of its solved rows);
 //                         ngp_path_kernels.h: functionals of whole sample paths
@@ -704,6 +705,7 @@ void launch_mixture_sample(int P, int S, int m, const double *w, const double *m
 }  // namespace ngp
 #include "ngp_path_kernels.h"   // uses philox4x32_10, u01 and small_chol_kernel above
 #include "ngp_long_sample_kernels.h"   // uses philox4x32_10 and u01 above, chol_diag_kernel and the column kernels' tile code
+#include "ngp_long_sample_indep_kernels.h"   // pick and normals of independent mixtures, behind the shared form's kernels
 #include "ngp_mixture_mapped_kernels.h"   // uses path_inv and the block reductions of ngp_mixture_kernels.h
 #include "ngp_score_kernels.h"   // uses path_inv and mix_block_sum
 namespace ngp {

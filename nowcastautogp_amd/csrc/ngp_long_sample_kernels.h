@@ -147,8 +147,9 @@ __global__ __launch_bounds__(256, 1) void ls_panel_kernel(LongSampleGeom g, Long
 // A wave owns 64 rows of L (block i) and 64 paths of one particle: acc = L_i,[0, 64 (i + 1)) Z', the
 // k-steps ascending whatever tile a path sits in, so a path's bits do not depend on its neighbours.
 // The tile goes through the wave's LDS rows 16 paths at a time and out as 512-byte rows of `out`,
-// the mean of the path's own scenario added on the way.  Paths of a particle whose long query or
-// factorisation failed are NaN.
+// the mean of the path's own scenario added on the way (row s of the item's mu_rows rows; the
+// item's one row where mu_own is 0).  Paths of a particle whose long query or factorisation failed
+// are NaN.
 __global__ __launch_bounds__(256, 1) void ls_draw_kernel(LongSampleGeom g, LongSamplePtrs p, long zfirst,
                                                          long zrows) {
     __shared__ __attribute__((aligned(16))) double tile[4][16 * EPI_PITCH];
@@ -173,7 +174,7 @@ __global__ __launch_bounds__(256, 1) void ls_draw_kernel(LongSampleGeom g, LongS
     gemm_rows<4>(acc4, L + ((long)i * NB + r16) * ld + 2 * q, Zr + (long)r16 * ld + 2 * q, ld, 0, (i + 1) * NB);
     const bool tainted = p.info[item] > 0 || p.cinfo[item] > 0;
     const double nan = __longlong_as_double(0x7ff8000000000000LL);
-    const double *mu = p.mu + (long)item * g.S * g.m;
+    const double *mu = p.mu + (long)item * g.mu_rows * g.m;
     double *buf = tile[wave];
     const int n16 = lane & 15, isub = lane >> 4;
     const int jj0 = 4 * (n16 >> 2) + isub;         // acc4[jt][it][r]: row 16 jt + jj0 of L, path 16 it + ((n16 + 4 r) & 15)
@@ -188,7 +189,7 @@ __global__ __launch_bounds__(256, 1) void ls_draw_kernel(LongSampleGeom g, LongS
         __builtin_amdgcn_wave_barrier();
         for (int row = 0; row < 16 && 16 * it + row < cntw; ++row) {
             const long idx = p.order[pos0 + 16 * it + row];
-            const int s = (int)(idx / g.draws);
+            const int s = g.mu_own ? (int)(idx / g.draws) : 0;
             if (col < g.m)
                 p.out[idx * g.m + col] = tainted ? nan : mu[(long)s * g.m + col] + buf[row * EPI_PITCH + lane];
         }

@@ -331,7 +331,8 @@ def forecast_with_nowcasts(base_model: GPModel, nowcasts: Sequence[TData], forec
                            n_hmc: int = 0, ess_threshold: float = 0.0,
                            forecast_n_hmc: Optional[int] = None, verbose: bool = False,
                            lockstep: bool = True, hmc_config: Optional[dict] = None,
-                           threads: Optional[int] = None, device_paths: bool = False) -> np.ndarray:
+                           threads: Optional[int] = None, device_paths: bool = False,
+                           refined_device_paths: bool = False) -> np.ndarray:
     """reference src/forecasting.jl:117-167.  Three keywords are this module's own: ``lockstep``
     (False: the reference's per-scenario loop), ``threads`` (with ``lockstep=False``: the loop's
     scenarios as concurrent tasks on that many threads — the reference's ``Threads.@spawn`` per
@@ -342,10 +343,15 @@ def forecast_with_nowcasts(base_model: GPModel, nowcasts: Sequence[TData], forec
     ``device_paths``: a horizon beyond what one aux query carries is drawn on the device in one
     ``Factor.sample_long`` call (``_Scenarios``, "device paths"); on a short horizon, in the
     refinement modes, without a resident factor that has ``sample_long`` or with
-    ``lockstep=False`` the existing path runs, as with the default."""
+    ``lockstep=False`` the existing path runs, as with the default.
+    ``refined_device_paths``: the same for the refined ensemble (mode "lockstep" of ``_Scenarios``,
+    "refined device paths"): every clone's paths of a long horizon come from
+    ``Factor.sample_long_indep`` on factors over whole scenarios; where its conditions do not hold
+    the existing path runs."""
     sc = _Scenarios(base_model, nowcasts, forecast_dates, n_mcmc=n_mcmc, n_hmc=n_hmc,
                     ess_threshold=ess_threshold, lockstep=lockstep, hmc_config=hmc_config,
-                    forecast_n_hmc=forecast_n_hmc, device_paths=device_paths)
+                    forecast_n_hmc=forecast_n_hmc, device_paths=device_paths,
+                    refined_device_paths=refined_device_paths)
     dates, draws, D = sc.dates, int(forecast_draws_per_nowcast), len(nowcasts)
     sc.run()
     if sc.mode == "shared":
@@ -356,6 +362,9 @@ def forecast_with_nowcasts(base_model: GPModel, nowcasts: Sequence[TData], forec
         autogp._raise_if_failed(info)
         return _apply(inv_transformation, np.ascontiguousarray(smp.reshape(D * draws, len(dates)).T))
     if sc.mode == "lockstep":
+        paths = sc.refined_paths(draws)
+        if paths is not None:
+            return np.hstack([_apply(inv_transformation, o) for o in paths])
         results = forecast_lockstep(sc.models, dates, draws, inv_transformation=inv_transformation,
                                     forecast_n_hmc=forecast_n_hmc, hmc_config=hmc_config)
         if verbose:
@@ -426,6 +435,13 @@ class _Scenarios:
     ``"lockstep"`` (refinement, shared dates, ``lockstep``): ``run`` leaves the D refined clones in
     ``models``, the reference's D tasks as ONE ensemble of P x D items (src/forecasting.jl:131-149).
 
+    Refined device paths (``refined_device_paths=True``, mode "lockstep" without
+    ``forecast_n_hmc``, a horizon beyond what one aux query carries, a single rank, an engine whose
+    resident factor has ``sample_long_indep``): ``refined_paths`` draws every clone's paths with
+    ``autogp.sample_long_lockstep`` — factors over whole scenarios, no covariance on the bus, each
+    clone keyed from its own stream as the device's independent form is; ``host_matrix`` and
+    ``device_input`` take the paths from it.  Otherwise it is None and today's route runs.
+
     ``"loop"``: the reference's per-scenario loop.  Nothing happens in ``run``; ``mixtures`` clones,
     refines and predicts scenario by scenario as it is consumed, so scenario s takes its root from
     the base model's shared stream only after scenario s - 1 has drawn."""
@@ -433,7 +449,7 @@ class _Scenarios:
     def __init__(self, base_model: GPModel, nowcasts: Sequence[TData], forecast_dates, *,
                  n_mcmc: int = 0, n_hmc: int = 0, ess_threshold: float = 0.0, lockstep: bool = True,
                  hmc_config: Optional[dict] = None, forecast_n_hmc: Optional[int] = None,
-                 device_paths: bool = False):
+                 device_paths: bool = False, refined_device_paths: bool = False):
         assert len(nowcasts) > 0, "nowcasts vector must not be empty"
         assert not (n_mcmc > 0 and n_hmc == 0), \
             "If n_mcmc > 0, n_hmc must also be > 0 for MCMC refinement"
@@ -451,6 +467,8 @@ class _Scenarios:
             self.mode = "lockstep"
         self._mixes = None
         self.device_paths, self.long_sampler = bool(device_paths), None
+        self.refined_device_paths = bool(refined_device_paths) and forecast_n_hmc is None
+        self._refined = None
 
     def run(self, want_sigma: bool = True) -> None:
         if self.mode == "shared":
@@ -482,6 +500,22 @@ class _Scenarios:
             autogp.mcmc_structure(m, self.n_mcmc, self.n_hmc, self.hmc_config)
         elif self.n_mcmc == 0 and self.n_hmc > 0:
             autogp.mcmc_parameters(m, self.n_hmc, self.hmc_config)
+
+    # -- mode "lockstep": refined device paths ------------------------------------------------------
+    def refined_on_device(self) -> bool:
+        """What of the refined device route is known before a factor is made: the keyword, the mode,
+        a horizon beyond one aux query, a single rank (call it after ``run``)."""
+        if not (self.refined_device_paths and self.mode == "lockstep") or autogp.distributed.world()[1] > 1:
+            return False
+        t, _ = self.models[0]._obs()
+        return autogp.horizon_blocks(t.size, 0, len(self.dates)) is not None
+
+    def refined_paths(self, draws: int):
+        """The clones' paths, a list of [m, draws] on the models' scale, from
+        ``autogp.sample_long_lockstep`` (drawn once) — or None: today's route."""
+        if self._refined is None and self.refined_on_device():
+            self._refined = autogp.sample_long_lockstep(self.models, self.dates, draws)
+        return self._refined
 
     def mixtures(self):
         """The scenarios' ``MixtureMVN``: a list from one ``predict_mvn_lockstep`` (made once) in
@@ -605,6 +639,9 @@ class _Scenarios:
         scenario, each resampled just before its own draws; "lockstep": ``rand_lockstep``;
         "loop": ``rand`` of each scenario's mixture as it is made."""
         if self.mode == "lockstep":
+            paths = self.refined_paths(draws)
+            if paths is not None:
+                return np.hstack(paths)
             return np.hstack(autogp.rand_lockstep(self.mixtures(), draws, self.base._eng()))
         if self.mode == "loop":
             return np.hstack([mx.rand(draws) for mx in self.mixtures()])
@@ -627,7 +664,10 @@ class _Scenarios:
         """``(mixes_or_arrays, seed)`` for ``autogp.path_targets`` / ``path_scores`` where
         ``forecast_with_nowcasts`` draws in one device call — "shared" with a sampler: the arrays
         and the seed after resampling; "lockstep" clones that take the independent form: their
-        mixtures, each keyed from its own stream — else None: ``host_matrix`` has the paths."""
+        mixtures, each keyed from its own stream — else None: ``host_matrix`` has the paths (also on
+        the refined device route, whose paths are drawn here)."""
+        if self.mode == "lockstep" and self.refined_paths(draws) is not None:
+            return None
         if self.mode == "shared" and self.sampler is not None:
             seed = self.resample_for_device()
             return (self.w, self.means, self.covs), seed
@@ -731,8 +771,8 @@ def hindcast(model: GPModel, report_dates, horizons, *, inv_transformation: Opti
 
 def forecast_mixture_with_nowcasts(base_model: GPModel, nowcasts: Sequence[TData], forecast_dates, *,
                                    n_mcmc: int = 0, n_hmc: int = 0, ess_threshold: float = 0.0,
-                                   lockstep: bool = True,
-                                   hmc_config: Optional[dict] = None) -> "autogp.MixtureMarginals":
+                                   lockstep: bool = True, hmc_config: Optional[dict] = None,
+                                   refined_device_paths: bool = False) -> "autogp.MixtureMarginals":
     """The mixture ``forecast_with_nowcasts`` draws from, pooled over the scenarios (every scenario
     weighs 1 / D, as its equal share of the draws does), as an ``autogp.MixtureMarginals``.
 
@@ -742,10 +782,18 @@ def forecast_mixture_with_nowcasts(base_model: GPModel, nowcasts: Sequence[TData
     no device sampler (or more forecast dates than it takes), ``forecast_with_nowcasts`` resamples
     a scenario AFTER it has drawn for the scenarios before it, so with ``ess_threshold > 0`` only
     the scenarios up to the first resampled one are the same there.  ``forecast_n_hmc`` (a new
-    mixture before every draw) has no single mixture and is not taken."""
+    mixture before every draw) has no single mixture and is not taken.
+    ``refined_device_paths``: on the conditions of ``forecast_with_nowcasts``' keyword the refined
+    clones' marginals come from ``autogp.predict_marginals_lockstep`` (means and variances of the
+    long query alone; no covariance is formed anywhere)."""
     sc = _Scenarios(base_model, nowcasts, forecast_dates, n_mcmc=n_mcmc, n_hmc=n_hmc,
-                    ess_threshold=ess_threshold, lockstep=lockstep, hmc_config=hmc_config)
+                    ess_threshold=ess_threshold, lockstep=lockstep, hmc_config=hmc_config,
+                    refined_device_paths=refined_device_paths)
     sc.run(want_sigma=False)
+    if sc.refined_on_device():
+        parts = autogp.predict_marginals_lockstep(sc.models, sc.dates)
+        if parts is not None:
+            return autogp.MixtureMarginals.pool(parts)
     if sc.mode != "shared":
         mixes = list(sc.mixtures())
         return autogp.MixtureMarginals.pool([mx.marginals(engine=base_model._eng()) for mx in mixes])
@@ -894,8 +942,8 @@ def forecast_targets_with_nowcasts(base_model: GPModel, nowcasts: Sequence[TData
                                    inv_transformation: Optional[Callable] = None, n_mcmc: int = 0,
                                    n_hmc: int = 0, ess_threshold: float = 0.0, lockstep: bool = True,
                                    hmc_config: Optional[dict] = None,
-                                   want_values: bool = False,
-                                   device_paths: bool = False) -> "autogp.PathTargets":
+                                   want_values: bool = False, device_paths: bool = False,
+                                   refined_device_paths: bool = False) -> "autogp.PathTargets":
     """``autogp.path_targets`` of the paths ``forecast_with_nowcasts`` returns.
 
     The scenario pipeline (``_Scenarios``) with the sampler seed ``forecast_with_nowcasts`` takes,
@@ -906,10 +954,11 @@ def forecast_targets_with_nowcasts(base_model: GPModel, nowcasts: Sequence[TData
     before every draw) is not taken; sharded runs raise ``NotImplementedError``.
     ``device_paths``: as ``forecast_with_nowcasts`` — the paths of a long horizon are drawn in one
     ``Factor.sample_long`` call and summarised by ``autogp.path_functionals``; where the conditions
-    do not hold the existing path runs."""
+    do not hold the existing path runs.  ``refined_device_paths``: likewise for the refined
+    ensemble (``Factor.sample_long_indep``)."""
     sc = _Scenarios(base_model, nowcasts, forecast_dates, n_mcmc=n_mcmc, n_hmc=n_hmc,
                     ess_threshold=ess_threshold, lockstep=lockstep, hmc_config=hmc_config,
-                    device_paths=device_paths)
+                    device_paths=device_paths, refined_device_paths=refined_device_paths)
     if autogp.distributed.world()[1] > 1:
         raise NotImplementedError("forecast_targets_with_nowcasts: single-rank runs only")
     draws = int(forecast_draws_per_nowcast)
@@ -946,8 +995,8 @@ def forecast_scores_with_nowcasts(base_model: GPModel, nowcasts: Sequence[TData]
                                   shift: float = 0.0, fair: bool = True,
                                   inv_transformation: Optional[Callable] = None, n_mcmc: int = 0,
                                   n_hmc: int = 0, ess_threshold: float = 0.0, lockstep: bool = True,
-                                  hmc_config: Optional[dict] = None,
-                                  device_paths: bool = False) -> "autogp.EnsembleScores":
+                                  hmc_config: Optional[dict] = None, device_paths: bool = False,
+                                  refined_device_paths: bool = False) -> "autogp.EnsembleScores":
     """``autogp.ensemble_scores`` of the paths ``forecast_with_nowcasts`` returns against ``y``
     [dates] (original scale): the sample CRPS per date and the energy score of the horizon
     (``windows`` None), or of the given windows of dates.
@@ -959,10 +1008,11 @@ def forecast_scores_with_nowcasts(base_model: GPModel, nowcasts: Sequence[TData]
     ``score_forecast``.  Sharded runs raise ``NotImplementedError``.
     ``device_paths``: as ``forecast_with_nowcasts`` — the paths of a long horizon are drawn in one
     ``Factor.sample_long`` call and scored by ``autogp.ensemble_scores``; where the conditions do
-    not hold the existing path runs."""
+    not hold the existing path runs.  ``refined_device_paths``: likewise for the refined ensemble
+    (``Factor.sample_long_indep``)."""
     sc = _Scenarios(base_model, nowcasts, forecast_dates, n_mcmc=n_mcmc, n_hmc=n_hmc,
                     ess_threshold=ess_threshold, lockstep=lockstep, hmc_config=hmc_config,
-                    device_paths=device_paths)
+                    device_paths=device_paths, refined_device_paths=refined_device_paths)
     if autogp.distributed.world()[1] > 1:
         raise NotImplementedError("forecast_scores_with_nowcasts: single-rank runs only")
     draws = int(forecast_draws_per_nowcast)
