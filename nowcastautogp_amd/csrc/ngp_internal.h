@@ -501,6 +501,7 @@ constexpr int SCORE_TILE = 128;        // paths per tile side: a thread owns 8 x
 constexpr int SCORE_DCHUNK = 16;       // dates of both tiles staged in LDS at a time (32 KiB)
 constexpr int SCORE_FOLD = 2048;       // dates after which a squared distance moves to a second accumulator
 constexpr int SCORE_REDUCE = 2048;     // rows of a slab one workgroup folds
+constexpr int SCORE_GRID_X = 1 << 23;    // workgroups per row of the pair kernel's grid: 2^31 threads, below the launch limit of 2^32
 constexpr int SCORE_MAX_PATHS = 1 << 20, SCORE_MAX_WINDOWS = 4096, SCORE_MAX_DATES = 65535;
 static_assert(SCORE_FOLD % SCORE_DCHUNK == 0, "a fold falls on a chunk boundary");
 inline int64_t score_tiles(int64_t N) { return (N + SCORE_TILE - 1) / SCORE_TILE; }

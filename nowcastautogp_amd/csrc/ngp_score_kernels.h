@@ -15,9 +15,12 @@
 //                         v = s(y) by the same device function
 //   score_obs_kernel      one thread per path: |u_i - v| per window; a slice's total in a fixed
 //                         order (wave shuffles, waves in order) into obs [slice][W]
-//   score_pairs_kernel    one workgroup per tile pair (ti <= tk) of SCORE_TILE paths — a 1-D grid of
-//                         exactly the nt (nt + 1) / 2 pairs, (ti, tk) decoded from the block index,
-//                         which is the pair's slot in the slab; a thread owns
+//   score_pairs_kernel    one workgroup per tile pair (ti <= tk) of SCORE_TILE paths — a grid of the
+//                         nt (nt + 1) / 2 pairs, in rows of at most SCORE_GRID_X workgroups (one row
+//                         up to N = 524,160; a launch takes fewer than 2^32 threads per dimension,
+//                         2^24 workgroups of 256, and N = 2^20 has 2^25 + 2^12 pairs), (ti, tk)
+//                         decoded from the block index, which is the pair's slot in the slab; a
+//                         thread owns
 //                         8 x 8 pairs in registers: rows tr + 16 r, columns tc + 16 c, so a wave
 //                         reads 4 row values (a broadcast each) and 16 consecutive column values
 //                         per date and register step — no bank conflicts.  A window's dates are
@@ -98,13 +101,15 @@ __global__ __launch_bounds__(SCORE_THREADS) void score_obs_kernel(int N, int W, 
 // row ti of the upper triangle of nt x nt tiles starts at slot ti nt - ti (ti - 1) / 2
 __host__ __device__ inline long score_row_start(long ti, long nt) { return ti * nt - ti * (ti - 1) / 2; }
 
-// grid (nt (nt + 1) / 2): the block index is the slot, in (ti, tk >= ti) order; part [slots][W].
+// grid score_pairs_grid(N): the block index, row-major, is the slot, in (ti, tk >= ti) order; a block
+// past the last slot (the grid's last row may be ragged) has nothing to do; part [slots][W].
 // LONG: some window of the call is longer than SCORE_FOLD dates (the second accumulator is
 // compiled in; a window up to SCORE_FOLD dates gets the same bits either way)
 template <bool LONG>
 __global__ __launch_bounds__(SCORE_THREADS) void score_pairs_kernel(int N, int W, const int32_t *win,
                                                                      const double *u, double *part) {
-    const long slot = blockIdx.x, nt = (N + SCORE_TILE - 1) / SCORE_TILE;
+    const long slot = (long)blockIdx.y * gridDim.x + blockIdx.x, nt = (N + SCORE_TILE - 1) / SCORE_TILE;
+    if (slot >= nt * (nt + 1) / 2) return;     // the whole workgroup, before its first barrier
     // the row of the slot: the root of the row-start quadratic (exact in fp64: nt <= 8,192), then settled
     const double b2 = (double)(2 * nt + 1);
     long row = (long)(0.5 * (b2 - sqrt(b2 * b2 - 8.0 * (double)slot)));
@@ -193,6 +198,13 @@ __global__ __launch_bounds__(SCORE_THREADS) void score_reduce_kernel(long rows, 
     if (threadIdx.x == 0) out[(long)blockIdx.x * W + w] = t;
 }
 
+// the pair kernel's grid: gridDim.x * SCORE_THREADS must stay below 2^32, so beyond SCORE_GRID_X slots
+// the slots are laid out in the fewest rows that hold them, of equal length (at most y - 1 idle blocks)
+static dim3 score_pairs_grid(int N) {
+    const long slots = score_tile_pairs(N), y = (slots + SCORE_GRID_X - 1) / SCORE_GRID_X;
+    return dim3((unsigned)((slots + y - 1) / y), (unsigned)y);
+}
+
 // folds slab[0] ([rows][W]) down to one row, ping-pong with slab[1]; returns where it is
 static const double *score_fold(long rows, int W, double *const slab[2], hipStream_t s) {
     int cur = 0;
@@ -216,12 +228,12 @@ hipError_t launch_scores(int N, int m, int W, bool long_windows, const ngp_inv_t
                        inv ? 1 : 0, scale, shift, b.u, b.v, b.flag);
     hipLaunchKernelGGL(score_obs_kernel, dim3((unsigned)score_slices(N)), dim3(SCORE_THREADS), 0, s, N,
                        W, b.win, (const double *)b.u, (const double *)b.v, b.obs[0]);
-    const unsigned slots = (unsigned)score_tile_pairs(N);      // <= 2^25 + 2^12 at N = 2^20
+    const dim3 slots = score_pairs_grid(N);                    // 2^25 + 2^12 slots at N = 2^20: 5 rows
     if (long_windows)
-        hipLaunchKernelGGL(score_pairs_kernel<true>, dim3(slots), dim3(SCORE_THREADS), 0, s, N, W,
+        hipLaunchKernelGGL(score_pairs_kernel<true>, slots, dim3(SCORE_THREADS), 0, s, N, W,
                            b.win, (const double *)b.u, b.pair[0]);
     else
-        hipLaunchKernelGGL(score_pairs_kernel<false>, dim3(slots), dim3(SCORE_THREADS), 0, s, N, W,
+        hipLaunchKernelGGL(score_pairs_kernel<false>, slots, dim3(SCORE_THREADS), 0, s, N, W,
                            b.win, (const double *)b.u, b.pair[0]);
     *obs_sum = score_fold(score_slices(N), W, b.obs, s);
     *pair_sum = score_fold(score_tile_pairs(N), W, b.pair, s);

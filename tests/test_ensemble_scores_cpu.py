@@ -1,7 +1,11 @@
 """Energy score and sample CRPS of forecast paths without a device: the numpy fallback of
 ``autogp.ensemble_scores`` against the long double restatement (tests/ensemble_scores_reference.py),
 the identities of the estimator, the vignette's ``crps`` transcribed literally, and the argument
-checks of the two C entry points through the real library (they return before a device is needed)."""
+checks of the two C entry points through the real library (they return before a device is needed).
+Also what the GPU tests at large N stand on: the sorted closed form of a one-date pair sum against
+the restatement's pair loop, the exact "lattice line" ensembles against the restatement (equal after
+conversion) and against the fallback (bit for bit, N = 1,000), and the exactness condition of every
+(N, direction, codes) row the GPU file scores."""
 import ctypes as C
 import os
 
@@ -10,6 +14,7 @@ import pytest
 
 from nowcastautogp_amd import _lib, autogp, nowcast
 from nowcastautogp_amd._abi import NgpInvTransform, dptr, iptr
+from tests import ensemble_scores_reference as E
 from tests.ensemble_scores_reference import CASES, RTOL, make_paths, scores_ld, windows_for
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -32,6 +37,75 @@ def test_fallback_matches_long_double(case):
     assert close(got["es"], es, to + 0.5 * tp)
     # the same window given twice: the same bits
     assert got["es"][2] == got["es"][5]
+
+
+@pytest.mark.parametrize("case", [c for c in CASES if c[1] >= 2] + [("lognormal", 1000, 3, 0, 0.0, True),
+                                                                  ("lognormal", 1000, 3, 1, 0.5, True)],
+                         ids=lambda c: f"{c[0]}-N{c[1]}-m{c[2]}-s{c[3]}")
+def test_sorted_closed_form_matches_the_long_double_pairs_on_one_date_windows(case):
+    """pair_sum_sorted is what judges one-date windows where the O(N^2) restatement cannot follow:
+    long double against long double, so far inside RTOL (measured: at most 1e-18 relative)"""
+    kind, N, m, scale, shift, _ = case
+    x, y = make_paths(kind, N, m, seed=N * 100 + m)
+    dates = sorted({0, m // 2, m - 1})
+    obs, pair = E.sums_ld(x, y, [(j, j) for j in dates], scale, shift)
+    obs2, pair2 = E.sums_one_date_ld(x, y, dates, scale, shift)
+    assert obs2.dtype == E.LD and pair2.dtype == E.LD
+    err = float(np.max(np.abs(pair2 - pair) / pair))
+    print(f"{kind} N={N} scale={scale}: sorted form against the pair loop {err:.1e}")
+    assert np.all(np.abs(pair2 - pair) <= 1e-17 * pair) and np.all(np.abs(obs2 - obs) <= 1e-17 * obs)
+
+
+@pytest.mark.parametrize("codes", ["index", "range"])
+@pytest.mark.parametrize("d", ["d34", "d4", "pm33"])
+@pytest.mark.parametrize("N", [129, 300])
+def test_line_ensembles_are_exact_in_the_long_double_restatement(N, d, codes):
+    """the integer reference and the restatement that judges everything else agree to the bit: the
+    sums of ``sums_ld``, converted, ARE the integer totals"""
+    x, y, k, ky = E.make_line_paths(N, d, codes)
+    win = E.LINE_WINDOWS[d]
+    obs_q, pair_q = E.line_totals(k, ky, E.line_norms(E.LINE_D[d], win))
+    obs, pair = E.sums_ld(x, y, win)
+    assert obs.astype(np.float64).tolist() == [q / 4.0 for q in obs_q]
+    assert pair.astype(np.float64).tolist() == [q / 4.0 for q in pair_q]
+    if codes == "index":
+        assert len(set(k.tolist())) == N          # no two paths tie
+    # a pair dropped or counted twice moves the total by at least a quarter
+    assert all(q > 0 for q in pair_q)
+
+
+@pytest.mark.parametrize("row", E.LINE_GPU_ROWS + E.LINE_GRID_ROWS, ids=lambda r: f"N{r[0]}-{r[1]}-{r[2]}")
+def test_every_exact_row_of_the_gpu_tests_keeps_the_exactness_condition(row):
+    """make_line_paths and line_totals assert it in integer arithmetic; here it is seen to hold for
+    each row, and the codes to be as large as it allows"""
+    N, d, codes = row
+    x, y, k, ky = E.make_line_paths(N, d, codes)
+    norms = E.line_norms(E.LINE_D[d], E.LINE_WINDOWS[d])
+    obs_q, pair_q = E.line_totals(k, ky, norms)
+    span = int(k.max() - k.min())
+    assert (span * max(norms)) ** 2 < 2 ** 53 and max(pair_q) < 2 ** 53 and max(obs_q) < 2 ** 53
+    assert x.shape == (N, len(E.LINE_D[d])) and np.all(x > 0.0)
+    if codes == "index":
+        assert N <= E.LINE_INDEX_MAX_N and np.array_equal(np.sort(k), np.arange(N))
+    else:
+        K = E.line_K(N, max(norms))
+        assert K & (K - 1) == 0 and not E.line_exact(N, 4 * K, max(norms)) and np.max(np.abs(k)) <= K
+    if N == 1 << 20:
+        assert E.line_K(N, 5) == 1024
+
+
+@pytest.mark.parametrize("fair", [True, False])
+@pytest.mark.parametrize("d,codes", [("d34", "index"), ("pm33", "index"), ("d34", "range")])
+def test_fallback_is_exact_on_a_line_ensemble(d, codes, fair):
+    """the numpy fallback is bound by the same argument as the device: bit for bit the integers"""
+    x, y, k, ky = E.make_line_paths(1000, d, codes)
+    win = E.LINE_WINDOWS[d]
+    es, to, tp = E.line_scores(k, ky, E.line_norms(E.LINE_D[d], win), fair)
+    got = autogp.host_ensemble_scores(x, y, win, 0, 0.0, fair)
+    assert not got["info"].any()
+    np.testing.assert_array_equal(got["term_obs"], to)
+    np.testing.assert_array_equal(got["term_pair"], tp)
+    np.testing.assert_array_equal(got["es"], es)
 
 
 def vignette_crps(y, X):

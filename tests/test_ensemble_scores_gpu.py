@@ -12,14 +12,43 @@ paths (1e6 + 1e-3 z) are judged on the natural scale only: on the log scale thei
 1e-9 of log(1e6), so ONE ulp between the device's log and numpy's moves a pair by 1e-6 of itself —
 that would judge the log, not the score.
 
+Edges: N in {127, 128, 129, 255, 256, 383, 384, 385} x m in {15, 16, 17, 32} with the windows
+(0, m-1), (1, 16), (5, 20), (5, 21) where they fit (both sides of the 128-path tile and of the
+16-date chunk, windows that do not start at date 0); m = 4,200 with windows of 2,047 | 2,048 | 2,049
+and 4,095 | 4,096 | 4,097 dates (two moves to the second accumulator).
+
+At scale, where the O(N^2 m) restatement cannot follow, two judgements:
+  * exact — "lattice line" ensembles (tests/ensemble_scores_reference.py: x = a + (k / 4) d with
+    integers k, d and integer window norms), on which every difference, square, square root and
+    partial sum of the device is exactly representable, so every order of summation gives the
+    same bits and the outputs must EQUAL what the host forms from the integer totals: tobytes(),
+    no tolerance.  A tolerance cannot see one dropped or doubled pair at these sizes (2 / N^2 of the
+    term); this sees a quarter of a unit in a total below 2^53 quarters.  N = 8,065 (64 tiles, 2,080
+    slab rows: a second fold level with a ragged block of 32 rows), 20,000 (the workload: 12,403 rows,
+    also every window alone, W = 1, against the call with all of them), 131,073 (1,025 tiles, the
+    last of one path), 524,160 | 524,161 (the pair kernel's grid gets a second row), 524,289 (the obs
+    slab folds twice, the pair slab three times, ragged at each) and 2^20 (the limit); fair and not,
+    paths as drawn, sorted and permuted.  The 2^20 row found the pair kernel's launch asking for
+    2^25 + 2^12 workgroups of 256 threads in one grid dimension — more than 2^32 threads, which a
+    launch does not take: term_pair came back as 0.1036 for 853.6, with status 0.  The grid is cut
+    into rows since.  A fold that rounds its block count down (tried once on a scratch build) fails
+    every exact and long double test from 8,065 up and no test at N <= 1,000.
+  * long double — lognormal paths at N = 8,065 (window (0, 1) by the restatement, 1.4 s on the
+    CPU), 20,000 and 131,073 (one-date windows by the sorted closed form), both scales, at RTOL.
+Measured on an MI355X, wall time of one exact call (upload, kernels, download), d = (3, 4) with
+three windows / the 33-date vector with seven: N = 8,065: 0.3 / 1.1 ms; 20,000: 0.8 / 3.2 ms;
+131,073: 24 / 105 ms; 524,289: 377 ms; 2^20 (one window of two dates): 628 ms.  Largest error of a
+term against long double at the new sizes: 2.2e-16 (edges), 2.1e-16 (at scale), 1.9e-16 (m = 4,200).
+
 Mixture form: ngp_mixture_path_scores against ngp_ensemble_scores of the numpy-transformed output of
 ngp_mixture_sample / _indep for the same seeds, largest relative deviation of a term over the
 windows; it may be 8 x BASELINE, BASELINE being the same deviation between the scores of that
 sampler output and of the ``oracle_np`` restatement's paths through the same numpy transformation,
 measured over the same cases in the same session.
 Measured on an MI355X: BASELINE = 4.08e-16 (tolerance 3.26e-15); the new call's largest deviation
-over the cases = 4.08e-16, over the mirror tests = 4.07e-16; the largest error of a term against
-long double over all shapes = 1.9e-16."""
+over the cases = 4.08e-16, over the mirror tests = 4.07e-16, on ``indep_s5`` with 1,613 draws per
+scenario (N = 8,065: the pair slab folds twice) = 1.3e-16; the largest error of a term against
+long double over the shapes of the first paragraph = 2.4e-16."""
 import numpy as np
 import pytest
 
@@ -89,6 +118,140 @@ def test_near_identical_and_clamped_paths_keep_their_distances(ctx, kind, N, m, 
     if kind == "clamped":
         assert 0.25 < np.mean(x == 0.0) < 0.45
     check(ctx.ensemble_scores(x, y, win, scale, shift, True), want, f"{kind} N={N} m={m} scale={scale}")
+
+
+# ---- edges of the tile (128 paths) and of the staged chunk (16 dates) -------------------------------
+_edge_sums = {}
+
+
+def edge_windows(m):
+    return [w for w in [(0, m - 1), (1, 16), (5, 20), (5, 21)] if w[1] < m]
+
+
+@pytest.mark.parametrize("scale,shift", [(0, 0.0), (1, 0.5)])
+@pytest.mark.parametrize("m", [15, 16, 17, 32])
+@pytest.mark.parametrize("N", [127, 128, 129, 255, 256, 383, 384, 385])
+def test_terms_match_long_double_on_both_sides_of_the_tile_and_chunk_edges(ctx, N, m, scale, shift):
+    """one path short of a tile, a full one, one path into the next; windows of 15 | 16 | 17 dates
+    from date 0 and of 16 | 17 dates that do not start there"""
+    key = (N, m, scale)
+    if key not in _edge_sums:
+        x, y = E.make_paths("lognormal", N, m, seed=1000 * N + m)
+        win = edge_windows(m)
+        _edge_sums[key] = (x, y, win, E.sums_ld(x, y, win, scale, shift))
+    x, y, win, (obs, pair) = _edge_sums[key]
+    for fair in (False, True):
+        got = ctx.ensemble_scores(x, y, win, scale, shift, fair)
+        check(got, E.scores_from_sums(obs, pair, N, fair), f"edges N={N} m={m} scale={scale} fair={int(fair)}")
+
+
+# ---- exact at scale: line ensembles against integers ------------------------------------------------
+_line = {}
+
+
+def line_case(N, d, codes):
+    """(x, y, windows, k, k_y, norms), made once; the tests leave it unchanged"""
+    key = (N, d, codes)
+    if key not in _line:
+        x, y, k, ky = E.make_line_paths(N, d, codes)
+        win = E.LINE_WINDOWS[d]
+        _line[key] = (x, y, win, k, ky, E.line_norms(E.LINE_D[d], win))
+    return _line[key]
+
+
+def assert_same_bits(got, want, what):
+    es, to, tp = want
+    assert not got["info"].any(), what
+    for name, w in (("term_obs", to), ("term_pair", tp), ("es", es)):
+        assert got[name].tobytes() == np.asarray(w).tobytes(), (what, name, got[name], w)
+        np.testing.assert_array_equal(got[name], w)
+
+
+@pytest.mark.parametrize("order", ["drawn", "sorted", "permuted"])
+@pytest.mark.parametrize("row", E.LINE_GPU_ROWS, ids=lambda r: f"N{r[0]}-{r[1]}-{r[2]}")
+def test_line_ensembles_are_scored_exactly_at_scale(ctx, row, order):
+    """every pair counted once, no rounding anywhere: the integer reference bit for bit, whatever
+    tile a path falls in.  8,065: a second fold level with a ragged block of 32 rows; 20,000: the
+    workload; 131,073: 1,025 tiles, the last of one path; 524,289: two levels of the obs fold, three
+    of the pair fold, ragged at each; 2^20: the limit (one window there: the structure is the point)"""
+    import time
+    N, d, codes = row
+    x, y, win, k, ky, norms = line_case(*row)
+    if N == 1 << 20:
+        win, norms = win[2:], norms[2:]
+    if order == "sorted":
+        x = np.ascontiguousarray(x[np.argsort(k, kind="stable")])
+    elif order == "permuted":
+        x = np.ascontiguousarray(x[np.random.default_rng(N).permutation(N)])
+    for fair in (True, False):
+        t0 = time.perf_counter()
+        got = ctx.ensemble_scores(x, y, win, 0, 0.0, fair)
+        print(f"exact N={N} {d} {codes} {order} fair={int(fair)} W={len(win)}: {(time.perf_counter() - t0) * 1e3:.1f} ms")
+        assert_same_bits(got, E.line_scores(k, ky, norms, fair), f"N={N} {d} {codes} {order} fair={int(fair)}")
+
+
+@pytest.mark.parametrize("row", E.LINE_GRID_ROWS, ids=lambda r: f"N{r[0]}")
+def test_line_ensembles_on_both_sides_of_the_pair_grids_second_row(ctx, row):
+    """a launch takes fewer than 2^32 threads per dimension, so the pair kernel's grid is cut into
+    rows: 524,160 paths are the last size with one row, 524,161 the first with two (the 2^20 row
+    above has five, 524,289 two with an idle block at the end)"""
+    x, y, win, k, ky, norms = line_case(*row)
+    got = ctx.ensemble_scores(x, y, win, 0, 0.0, True)
+    assert_same_bits(got, E.line_scores(k, ky, norms, True), f"N={row[0]} grid split")
+
+
+@pytest.mark.parametrize("d,codes", [("d34", "index"), ("pm33", "index"), ("d34", "range")])
+def test_a_window_alone_has_the_bits_it_has_among_others_at_the_workload_size(ctx, d, codes):
+    """12,403 slab rows fold to 7 and then to 1: [row][W] indexing with W = 1 and with W > 1"""
+    N = 20000
+    x, y, win, k, ky, norms = line_case(N, d, codes)
+    together = ctx.ensemble_scores(x, y, win, 0, 0.0, True)
+    want = E.line_scores(k, ky, norms, True)
+    assert_same_bits(together, want, f"N={N} {d} {codes} together")
+    for i, w in enumerate(win):
+        alone = ctx.ensemble_scores(x, y, [w], 0, 0.0, True)
+        for name in ("es", "term_obs", "term_pair"):
+            assert alone[name][0].tobytes() == together[name][i].tobytes(), (w, name)
+
+
+# ---- long double at scale ---------------------------------------------------------------------------
+_big = {}
+
+
+@pytest.mark.parametrize("scale,shift", [(0, 0.0), (1, 0.5)])
+@pytest.mark.parametrize("N", [8065, 20000, 131073])
+def test_general_position_paths_match_long_double_at_multi_level_sizes(ctx, N, scale, shift):
+    """lognormal paths, m = 2: the one-date windows against the sorted closed form in long double
+    at every N, the window (0, 1) against the O(N^2) restatement where it can follow (8,065)"""
+    key = (N, scale)
+    if key not in _big:
+        x, y = E.make_paths("lognormal", N, 2, seed=1000 * N + 2)
+        obs, pair = E.sums_one_date_ld(x, y, [0, 1], scale, shift)
+        win = [(0, 0), (1, 1)]
+        if N == 8065:
+            o2, p2 = E.sums_ld(x, y, [(0, 1)], scale, shift)
+            obs, pair, win = np.concatenate([obs, o2]), np.concatenate([pair, p2]), win + [(0, 1)]
+        _big[key] = (x, y, win, obs, pair)
+    x, y, win, obs, pair = _big[key]
+    for fair in (True, False):
+        got = ctx.ensemble_scores(x, y, win, scale, shift, fair)
+        check(got, E.scores_from_sums(obs, pair, N, fair), f"at scale N={N} scale={scale} fair={int(fair)}")
+
+
+def test_a_horizon_beyond_4096_dates(ctx):
+    """two moves to the second accumulator, and windows on both sides of one move and of two; the
+    2,048-date window runs the short kernel alone and the LONG one beside a longer window: same bits"""
+    N, m = 65, 4200
+    x = np.exp(5.0 + 0.3 * np.random.default_rng(11).standard_normal((N, m)))
+    y = np.full(m, np.exp(5.0))
+    win = [(0, 2046), (0, 2047), (7, 2055), (0, 4094), (100, 4195), (3, 4099), (0, m - 1), (2100, 4147)]
+    assert [b - a + 1 for a, b in win] == [2047, 2048, 2049, 4095, 4096, 4097, 4200, 2048]
+    got = ctx.ensemble_scores(x, y, win, 1, 0.0, True)
+    check(got, E.scores_ld(x, y, win, 1, 0.0, True), "m=4200")
+    for i in (0, 1, 7):
+        alone = ctx.ensemble_scores(x, y, [win[i]], 1, 0.0, True)
+        for k in ("es", "term_obs", "term_pair"):
+            assert alone[k][0].tobytes() == got[k][i].tobytes(), (i, k)
 
 
 def test_a_horizon_beyond_2048_dates(ctx):
@@ -175,11 +338,14 @@ MIX_CASES = ["n63_exp", "n257_boxcox_neg", "shared_s5", "indep_s5", "indep_s2_m3
 _mix = {}
 
 
-def mix_case(ctx, name):
+def mix_case(ctx, name, draws=None):
     """(case, y, windows, scores of the sampler's transformed output, scores of the restatement's
-    paths, the new call's result) — each computed once per session"""
+    paths, the new call's result) — each computed once per session; ``draws``: the case with that
+    many draws per scenario instead of its own"""
+    if draws is not None:
+        name = (name, draws)
     if name not in _mix:
-        c = R.make_case(name)
+        c = R.make_case(name) if draws is None else dict(R.make_case(name[0]), draws=draws)
         g = R.inv_numpy(c["inv"])
         v_ref = g(R.sample_paths(c["w"], c["mu"], c["sigma"], c["draws"], c["seed"]))
         if np.isscalar(c["seed"]):
@@ -220,6 +386,18 @@ def test_mixture_form_scores_the_samplers_paths(ctx, baseline, name):
     assert o["chol_info"].shape == (np.shape(c["w"]) if not np.isscalar(c["seed"]) else (c["w"].shape[1],))
     dev = term_deviation(o, a)
     print(f"{name}: deviation {dev:.3e}, baseline {baseline:.3e}, tolerance {8 * baseline:.3e}")
+    assert dev <= 8.0 * baseline, (dev, baseline)
+    assert np.all(np.abs(o["es"] - a["es"]) <= 8.0 * baseline * (a["term_obs"] + 0.5 * a["term_pair"]))
+
+
+def test_mixture_form_at_a_size_whose_pair_slab_folds_twice(ctx, baseline):
+    """``indep_s5`` with 1,613 draws per scenario: N = 8,065, the smallest N with a second fold
+    level; judged as the cases above are, by the same BASELINE"""
+    c, y, win, a, _, o = mix_case(ctx, "indep_s5", draws=1613)
+    assert c["w"].shape[0] * c["draws"] == 8065
+    assert not o["info"].any() and not o["chol_info"].any()
+    dev = term_deviation(o, a)
+    print(f"indep_s5 x 1613 draws: deviation {dev:.3e}, baseline {baseline:.3e}, tolerance {8 * baseline:.3e}")
     assert dev <= 8.0 * baseline, (dev, baseline)
     assert np.all(np.abs(o["es"] - a["es"]) <= 8.0 * baseline * (a["term_obs"] + 0.5 * a["term_pair"]))
 
